@@ -303,6 +303,63 @@ def step_stats(reports, n):
             "terminated_by_tolerance": int((term == 1).sum()), "failed": int((term == 2).sum())}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, windows, priors, reports, first_id):
+    """--dump-outputs: what vpl_ba_download handed back after the last timed step, one DIR/<name>.npy per array, float64,
+    one row per window.  Per-window lists of different lengths are padded with zeros to the longest; their lengths are
+    dumped too.  `window` holds the batch ids of the rows; above DUMP_LIMIT_BYTES the rows are a fixed, seeded sample."""
+    import numpy as np
+    n = len(windows)
+    pri = [priors[i] for i in range(n)]
+    rep = [reports[i] for i in range(n)]
+
+    def rows(values):
+        return np.asarray(list(values), dtype=np.float64)
+
+    def padded(values, width=()):
+        values = list(values)
+        out = np.zeros((len(values), max([len(x) for x in values] + [0])) + width)
+        for i, x in enumerate(values):
+            out[i, :len(x)] = x
+        return out
+
+    pn = max([p.n for p in pri] + [0])
+    prior_J = np.zeros((n, pn, pn))
+    for i, p in enumerate(pri):
+        prior_J[i, :p.n, :p.n] = p.J()
+    nb = max([p.n_blocks for p in pri] + [0])
+    arrays = {
+        "window": rows(range(first_id, first_id + n)),
+        "pose": rows(w.pose for w in windows),
+        "speed_bias": rows(w.speed_bias for w in windows),
+        "ex_pose": rows(w.ex_pose for w in windows),
+        "n_points": rows(len(w.point_start) for w in windows),
+        "inv_depth": padded(w.inv_depth for w in windows),
+        "n_lines": rows(len(w.line_start) for w in windows),
+        "line_plk": padded((w.line_plk for w in windows), (6,)),
+        "line_removed": padded(w.line_removed[:len(w.line_start)] for w in windows),
+        "prior_n": rows(p.n for p in pri),
+        "prior_J": prior_J,
+        "prior_r": padded(p.r() for p in pri),
+        "prior_n_blocks": rows(p.n_blocks for p in pri),
+        "prior_block_kind": rows(p.block_kind[:nb] for p in pri),
+        "prior_block_frame": rows(p.block_frame[:nb] for p in pri),
+        "prior_block_idx": rows(p.block_idx[:nb] for p in pri),
+        "prior_x0": rows([list(x) for x in p.x0[:nb]] for p in pri).reshape(n, nb, 9),
+    }
+    for name, _ in reports._type_._fields_:
+        arrays["report_" + name] = rows(getattr(r, name) for r in rep)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(n, max(1, n * DUMP_LIMIT_BYTES // total), replace=False))
+        arrays = {k: a[keep] for k, a in arrays.items()}
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+
+
 def frontend_config4(torch, v, dev, steps=5, warm=2, n=64, imgs=None):
     """BASELINE config 4 as an extra key: EDLines + KLT matching of the 64-frame 752x480 stream, frames resident in HBM.
     n = 256 (the stream four times over) is the second operating point: the routing stage runs one wave per frame, so a
@@ -411,6 +468,8 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the config-2 / config-4 / weak-scaling extra keys")
     ap.add_argument("--streams", type=int, default=1, help="experiment: cut the rank's block into this many blocks on streams of their own")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed (rank 0's block: states, "
+                    "priors, reports) as DIR/<name>.npy")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -473,8 +532,10 @@ def main():
         mb.close()
 
     # results: one all-gather of the per-window states, parity of the gathered set against the oracle on rank 0
-    _, reports = ctx.download()
+    priors, reports = ctx.download()
     n_local = hi - lo
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, strong.B, priors, reports, lo)
     # the block's states are packed on the device and gathered device to device (RCCL); only the sampled rows come to the host
     gathered_dev = v.shard.gather_states_device(dist, ctx, n_local, total, dev)
     gathered = gathered_dev.cpu().numpy()

@@ -58,6 +58,32 @@ def test_bench_prints_one_contract_line():
     assert d["parity"]["max_dp_m"] < 1e-4 and d["parity"]["max_dr_rad"] < 1e-6
 
 
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs DIR: the arrays of the last timed step, float, at most 64 MB, the same whatever the number of steps
+    (every step solves the same resident inputs); --steps is the number of timed steps the line reports."""
+    import numpy as np
+    dumps = {}
+    for steps in (2, 4):
+        d = tmp_path / ("s%d" % steps)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "1",
+                              "--no-extras", "--no-cpu-baseline", "--dump-outputs", str(d)],
+                             cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        line = json.loads([ln for ln in out.stdout.strip().splitlines() if ln.startswith("{")][0])
+        assert line["steps"] == steps and line["ms_per_step"] > 0
+        dumps[steps] = {f.stem: np.load(f) for f in sorted(d.glob("*.npy"))}
+    a, b = dumps[2], dumps[4]
+    assert sorted(a) == sorted(b) and {"pose", "speed_bias", "ex_pose", "inv_depth", "line_plk", "prior_J", "prior_r",
+                                        "report_iterations", "report_final_cost", "window"} <= set(a)
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64), k
+        assert np.array_equal(a[k], b[k]), k
+    assert np.array_equal(a["window"], np.arange(512)) and a["pose"].shape == (512, 11, 7)
+    assert np.all(a["report_iterations"] >= 1) and np.all(np.isfinite(a["pose"]))
+    assert np.all(a["prior_n"] == a["report_prior_n"]) and np.all(a["prior_n"] > 0)
+
+
 def test_bench_single_rank_rccl_path():
     """VPL_FORCE_DIST=1: one rank, but through torch.distributed (backend nccl = RCCL): the block's states are packed on the
     device and all-gathered device to device, the timing / parity summaries all-reduced -- the code the N > 1 launches run."""
