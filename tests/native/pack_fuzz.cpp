@@ -1,6 +1,6 @@
 // Host-only sweep of the layout packers of csrc/ba_pack.h under the address sanitizer (tests/test_point_units.py builds and
 // runs it with g++ -fsanitize=address,undefined): random track layouts, every output table allocated at exactly the size the
-// library gives it (vplines_ba.hip: maxPR, maxKS), so that a write or read past a table is an error here and not a silent
+// library gives it (ba_pack.h: max_point_unit_rounds, max_schur_ksteps), so that a write or read past a table is an error here and not a silent
 // corruption of the neighbouring table in the staging arena.  Also replays the commit-ticket chains of every layout.
 #include <cstdio>
 #include <cstdlib>
@@ -22,8 +22,8 @@ int main(int argc, char** argv) {
     const int caps[4] = {16, 64, 256, 200};
     const int maxP = caps[U(0, 3)], maxL = U(0, 1) ? 128 : 16;
     const int maxPO = maxP * U(2, NF);
-    const int maxPR = std::min((maxP / 16 + NF) * (NF - 1), maxPO / 16 + NF * (NF - 1) / 2) / 32 + 2;
-    const int maxKS = maxP / 4 + maxL + NF + 2;
+    const int maxPR = max_point_unit_rounds(maxP, maxPO);
+    const int maxKS = max_schur_ksteps(maxP, maxL);
     const int nP = U(0, maxP), nL = U(0, maxL);
     const int shape = U(0, 3);    // 0 uniform length, 1 ragged, 2 everything starts in frame 0, 3 long tracks
     std::vector<int> start(nP), nobs(nP), off(nP);
@@ -37,16 +37,9 @@ int main(int argc, char** argv) {
       total += nobs[p];
     }
     if (total > maxPO) continue;   // (the library refuses such a window before it packs)
-    int cnt[NF + 1] = {0};
-    for (int p = 0; p < nP; ++p) cnt[start[p] + 1]++;
-    for (int f = 0; f < NF; ++f) cnt[f + 1] += cnt[f];
+    int cnt[NF + 1];
     std::vector<int> ps(nP);
-    {
-      int pos[NF + 1];
-      for (int f = 0; f <= NF; ++f) pos[f] = cnt[f];
-      for (int p = 0; p < nP; ++p) ps[pos[start[p]]++] = p;
-      for (int f = 0; f < NF; ++f) std::stable_sort(ps.begin() + cnt[f], ps.begin() + cnt[f + 1], [&](int a, int b) { return nobs[a] > nobs[b]; });
-    }
+    sort_points_by_start(nP, start.data(), nobs.data(), ps.data(), cnt);
     int* lt = new int[(size_t)maxPR * 1024];
     int* st = new int[(size_t)maxPR * 512];
     PointUnitLayout PL;

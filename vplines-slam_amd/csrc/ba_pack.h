@@ -301,4 +301,29 @@ inline int pack_schur_ksteps(int nP, const int* ps_list, const int* cnt, int nL,
   return nks;
 }
 
+// ---- shared by the upload (vplines_ba.hip) and tests/native/pack_fuzz.cpp ----------------------------------------------------
+
+// Capacities of the per-window layout tables; vpl_ctx_create sizes the device arrays with them.
+// Point work units of k_lin: (start frame, chunk of <= 16 tracks, observation); a unit needs at most one quarter-wave slot;
+// slots <= factor lanes / 16 + one partial unit per (start, k) pair; the halves of the work-group differ by less than one chunk.
+inline int max_point_unit_rounds(int maxP, int maxPO) {
+  return std::min((maxP / 16 + NF) * (NF - 1), maxPO / 16 + NF * (NF - 1) / 2) / 32 + 2;
+}
+// K-steps of the landmark elimination (pack_schur_ksteps)
+inline int max_schur_ksteps(int maxP, int maxL) { return maxP / 4 + maxL + NF + 2; }
+// lane slots of the line phase; worst case: 11-frame tracks, 5 lines per wave
+inline int line_lane_slots(int maxL) { return 512 * ((maxL + 8 * (64 / NF) - 1) / (8 * (64 / NF))); }
+
+// Counting sort of a window's point tracks by start frame: list[cnt[f] .. cnt[f + 1]) are the tracks that start in f (cnt has
+// NF + 1 entries); inside a start frame the longer tracks come first, so the tracks observed at index k are a prefix of it.
+inline void sort_points_by_start(int n, const int* start, const int* nobs, int* list, int* cnt) {
+  for (int f = 0; f <= NF; ++f) cnt[f] = 0;
+  for (int p = 0; p < n; ++p) cnt[start[p] + 1]++;
+  for (int f = 0; f < NF; ++f) cnt[f + 1] += cnt[f];
+  int pos[NF + 1];
+  for (int f = 0; f <= NF; ++f) pos[f] = cnt[f];
+  for (int p = 0; p < n; ++p) list[pos[start[p]]++] = p;
+  for (int f = 0; f < NF; ++f) std::stable_sort(list + cnt[f], list + cnt[f + 1], [&](int a, int b) { return nobs[a] > nobs[b]; });
+}
+
 }  // namespace vpl

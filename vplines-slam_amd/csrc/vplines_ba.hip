@@ -26,6 +26,7 @@
 #include "ba_marg.h"
 #include "ba_lineopt.h"
 #include "ba_factors.h"
+#include "host_common.h"
 
 using namespace vpl;
 
@@ -82,6 +83,9 @@ struct Span {   // a piece of the pinned arena with the few std::vector members 
   T* end() const { return p + n; }
 };
 
+// The arena's bound is never written down: a call runs its takes and segments once on a DRY stage, which only counts them,
+// and reserves what that run used (stage_plan; the upload: upload_bound).  A take past the bound hands out host scratch and
+// flags `overflow`, which stage_run refuses, so a wrong bound is an error and never a write past the arena.
 struct Stage {
   char* h = nullptr;   // hipHostMalloc
   char* d = nullptr;   // hipMalloc
@@ -89,13 +93,13 @@ struct Stage {
   std::vector<CopySeg> segs;
   unsigned units = 0;
   bool overflow = false;
+  bool dry = false;                                  // sizing run: takes are empty pieces, nothing is allocated or written
+  std::vector<std::unique_ptr<char[]>> spill;        // pieces taken past the bound
 
   hipError_t reserve(size_t need) {
-    used = 0; segs.clear(); units = 0; overflow = false;
+    used = 0; segs.clear(); units = 0; overflow = false; spill.clear();
     if (need <= cap) return hipSuccess;
-    if (h) hipHostFree(h);
-    if (d) hipFree(d);
-    h = d = nullptr; cap = 0;
+    release();
     const size_t want = need + need / 4 + (1u << 16);
     hipError_t e = hipHostMalloc((void**)&h, want, hipHostMallocDefault);
     if (e != hipSuccess) return e;
@@ -105,24 +109,26 @@ struct Stage {
     return hipSuccess;
   }
   void release() {
-    if (h) hipHostFree(h);
-    if (d) hipFree(d);
+    if (h) (void)hipHostFree(h);   // (the old arena is dropped either way)
+    if (d) (void)hipFree(d);
     h = d = nullptr; cap = 0;
   }
+  // what a reserve must cover for the takes and segments so far: the data, and the segment table stage_run appends
+  size_t bound() const { return ((used + 63) & ~(size_t)63) + segs.size() * sizeof(CopySeg); }
   template <typename T>
   Span<T> take(size_t n) {   // uninitialised
     used = (used + 63) & ~(size_t)63;
     Span<T> sp;
-    if (used + n * sizeof(T) > cap) { overflow = true; static T dummy; sp.p = &dummy; sp.n = 0; return sp; }
-    sp.p = reinterpret_cast<T*>(h + used);
     sp.n = n;
+    if (!dry && used + n * sizeof(T) <= cap) sp.p = reinterpret_cast<T*>(h + used);
+    else if (!dry) { overflow = true; spill.emplace_back(new char[n * sizeof(T) + 1]); sp.p = reinterpret_cast<T*>(spill.back().get()); }
     used += n * sizeof(T);
     return sp;
   }
   template <typename T>
   Span<T> take(size_t n, T fill) {
     Span<T> sp = take<T>(n);
-    std::fill(sp.begin(), sp.end(), fill);
+    if (!dry) std::fill(sp.begin(), sp.end(), fill);
     return sp;
   }
   char* dev_of(const void* host_ptr) const { return d + (reinterpret_cast<const char*>(host_ptr) - h); }
@@ -138,7 +144,20 @@ struct Stage {
   // download: a device array to a piece of the arena (host address)
   template <typename T>
   void from_device(T* host_dst, const T* dev_src, size_t n) { seg(dev_src, dev_of(host_dst), n * sizeof(T)); }
+  template <typename T>
+  void put(T* dev_dst, const Span<T>& src) { to_device(dev_dst, src.p, src.n); }
 };
+
+// sizes the arena by a dry run of `plan` (its takes and segments), reserves that, and runs `plan` on the arena
+template <typename Plan>
+static hipError_t stage_plan(Stage& S, const Plan& plan) {
+  Stage dry;
+  dry.dry = true;
+  plan(dry);
+  const hipError_t e = S.reserve(dry.bound());
+  if (e == hipSuccess) plan(S);
+  return e;
+}
 
 struct vpl_ctx {
   int device = 0;
@@ -220,12 +239,7 @@ static hipError_t stage_run(vpl_ctx* c, bool upload) {
 }
 
 static void drop_graph(vpl_ctx* c) {
-  if (c->graph_exec) { hipGraphExecDestroy(c->graph_exec); c->graph_exec = nullptr; }
-}
-
-static int fail(vpl_ctx* c, int code, const std::string& msg) {
-  if (c) c->err = msg;
-  return code;
+  if (c->graph_exec) { (void)hipGraphExecDestroy(c->graph_exec); c->graph_exec = nullptr; }
 }
 
 // completes the asynchronous call that is still pending on this context, if any
@@ -240,28 +254,6 @@ static int finish_or_defer(vpl_ctx* c, bool async, std::function<int()> fin) {
   if (!async) return fin();
   c->pending = std::move(fin);
   return VPL_OK;
-}
-#define HIPCHK(ctx, call)                                                                         \
-  do {                                                                                            \
-    hipError_t e__ = (call);                                                                      \
-    if (e__ != hipSuccess) return fail(ctx, VPL_E_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
-  } while (0)
-
-// One hipMalloc per array.  (Measured alternative, round 2: all ~90 arrays out of one arena, with and without skewed
-// offsets -- k_cost, the kernel closest to the bandwidth roof, then runs at 0.30 ms per step in EVERY process, whereas with
-// separate allocations it is 0.24 ms in most processes and 0.30 ms in some: the difference is where the driver places the
-// buffers, not the code.  DESIGN.md section 8.)
-template <typename T>
-static hipError_t dalloc(vpl_ctx* c, T** p, size_t n) {
-  void* q = nullptr;
-  hipError_t e = hipMalloc(&q, n * sizeof(T) + 64);
-  if (e != hipSuccess) return e;
-  e = hipMemset(q, 0, n * sizeof(T) + 64);
-  if (e == hipSuccess && c->guards) e = hipMemset((char*)q + n * sizeof(T), 0xA5, 64);
-  c->allocs.push_back(q);
-  c->alloc_bytes.push_back(n * sizeof(T));
-  *p = (T*)q;
-  return e;
 }
 
 // ---- helpers -----------------------------------------------------------------------------------
@@ -278,43 +270,33 @@ static void to_dev_preint(const vpl_preintegration& p, DevPreint& d) {
   std::memset(d.sqrt_info, 0, sizeof(d.sqrt_info));
 }
 
-template <typename T>
-static hipError_t up(vpl_ctx* c, T* dst, const Span<T>& src) {   // a piece of the pinned arena: joins the upload's one copy
-  c->stage.to_device(dst, src.p, src.n);
-  return hipSuccess;
-}
-template <typename T>
-static hipError_t up(vpl_ctx* c, T* dst, const std::vector<T>& src) {
-  if (src.empty()) return hipSuccess;
-  return hipMemcpyAsync(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, c->stream);
-}
-
 struct KTimer {
   vpl_ctx* c;
   const char* name;
   hipEvent_t a = nullptr, b = nullptr;
   KTimer(vpl_ctx* c_, const char* n) : c(c_), name(n) {
-    if (c->timing) { hipEventCreate(&a); hipEventCreate(&b); hipEventRecord(a, c->stream); }
+    // (a timing aid: a failed event call leaves a time of 0 and nothing else)
+    if (c->timing) { (void)hipEventCreate(&a); (void)hipEventCreate(&b); (void)hipEventRecord(a, c->stream); }
   }
   ~KTimer() {
     if (c->timing) {
-      hipEventRecord(b, c->stream);
-      hipEventSynchronize(b);
+      (void)hipEventRecord(b, c->stream);
+      (void)hipEventSynchronize(b);
       float ms = 0;
-      hipEventElapsedTime(&ms, a, b);
+      (void)hipEventElapsedTime(&ms, a, b);
       auto& e = c->ktimes[name];
       e.first += ms;
       e.second += 1;
       c->ltimes.emplace_back(name, (double)ms);
-      hipEventDestroy(a);
-      hipEventDestroy(b);
+      (void)hipEventDestroy(a);
+      (void)hipEventDestroy(b);
     }
   }
 };
 
 struct DevBuf {
   void* p = nullptr;
-  ~DevBuf() { if (p) hipFree(p); }
+  ~DevBuf() { if (p) (void)hipFree(p); }
   hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 8); }
   double* d() { return (double*)p; }
 };
@@ -340,6 +322,36 @@ static int eval_generic(vpl_ctx* c, int n, const double* params, int psz, const 
   return VPL_OK;
 }
 
+// ---- pieces shared by the entry points ----------------------------------------------------------------
+// device line dl of window w is the caller's line h_lmap[w][dl]: the Pluecker vectors (plk: the window's [maxL][6]) go back for
+// the lines keep(dl, l) selects
+template <typename Keep>
+static void scatter_lines(const vpl_ctx* c, size_t w, vpl_window& v, const double* plk, Keep keep) {
+  const std::vector<int>& lmap = c->h_lmap[w];
+  for (size_t dl = 0; dl < lmap.size(); ++dl)
+    if (keep((int)dl, lmap[dl])) std::memcpy(v.line_plk + (size_t)lmap[dl] * 6, plk + dl * 6, 6 * 8);
+}
+// ... after a solve: the lines k_gauge erased (removeLineOutlier) keep the caller's value and are flagged in line_removed;
+// returns how many were erased
+static int scatter_solved_lines(const vpl_ctx* c, size_t w, vpl_window& v, const double* plk, const int* removed) {
+  if (v.line_removed) std::fill(v.line_removed, v.line_removed + v.n_lines, 0);
+  int n = 0;
+  scatter_lines(c, w, v, plk, [&](int dl, int l) {
+    if (v.line_removed) v.line_removed[l] = removed[dl] ? 1 : 0;
+    n += removed[dl] ? 1 : 0;
+    return !removed[dl];
+  });
+  return n;
+}
+static void fill_report(vpl_solve_report& r, const TrState& t) {
+  std::memset(&r, 0, sizeof(r));
+  r.iterations = t.iter;
+  r.num_successful_steps = t.num_successful;
+  r.termination = t.status == 1 ? 1 : t.status == 2 ? 2 : 0;
+  r.initial_cost = t.initial_cost;
+  r.final_cost = t.x_cost;
+}
+
 extern "C" {
 
 void vpl_ba_default_options(vpl_ba_options* o) {
@@ -355,25 +367,20 @@ void vpl_ba_default_options(vpl_ba_options* o) {
   o->huber_delta = 1.0;
 }
 
-int vpl_ctx_create(vpl_ctx** out, int device, int max_windows, int max_points, int max_point_obs, int max_lines,
-                   int max_line_obs) {
-  if (!out || max_windows < 1 || max_points < 0 || max_lines < 0) return VPL_E_INVALID;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0 || device >= ndev) return VPL_E_NODEVICE;
-  vpl_ctx* c = new vpl_ctx();
+// everything vpl_ctx_create does after the device checks; on failure vpl_ctx_create frees what was allocated
+static int ctx_init(vpl_ctx* c, int device, int max_windows, int max_points, int max_point_obs, int max_lines, int max_line_obs) {
   { const char* g = getenv("VPL_DEBUG_GUARDS"); c->guards = g && g[0] == '1'; }
   c->device = device;
-  if (hipSetDevice(device) != hipSuccess) { delete c; return VPL_E_NODEVICE; }
   c->maxW = max_windows;
   c->maxP = max_points > 0 ? (max_points + 1) & ~1 : 2;   // even: k_solve streams the gradient entries in 16-byte units
   c->maxPO = max_point_obs > 0 ? max_point_obs : 1;
   c->maxL = max_lines > 0 ? max_lines : 1;
   c->maxLO = max_line_obs > 0 ? max_line_obs : 1;
   // k_solve keeps 2 doubles per point and 18 per line in the LDS space behind its two staging buffers
-  if (2 * c->maxP + 18 * c->maxL > NAP - 2 * CROWS * CW) { delete c; return VPL_E_CAPACITY; }
+  if (2 * c->maxP + 18 * c->maxL > NAP - 2 * CROWS * CW) return VPL_E_CAPACITY;
   // ... and 4 doubles per point and 28 per line in the staging buffers' space between the scaling and the first chunk
-  if (4 * c->maxP + 28 * c->maxL > 2 * CROWS * CW) { delete c; return VPL_E_CAPACITY; }
-  if (solve_smem(c->maxP, c->maxL) > 159 * 1024) { delete c; return VPL_E_CAPACITY; }
+  if (4 * c->maxP + 28 * c->maxL > 2 * CROWS * CW) return VPL_E_CAPACITY;
+  if (solve_smem(c->maxP, c->maxL) > 159 * 1024) return VPL_E_CAPACITY;
   DevBatch& B = c->B;
   std::memset(&B, 0, sizeof(B));
   B.maxP = c->maxP; B.maxPO = c->maxPO; B.maxL = c->maxL; B.maxLO = c->maxLO;
@@ -384,13 +391,16 @@ int vpl_ctx_create(vpl_ctx** out, int device, int max_windows, int max_points, i
     if (const char* sv = std::getenv("VPL_BA_LIN_SPLIT")) ncu = std::atoi(sv) ? 1 << 30 : 0;   // 1: always two work-groups per window, 0: never (A/B runs, tests)
     B.ncu = ncu;
   }
-  // point work units of k_lin: (start frame, chunk of <= 16 tracks, observation); a unit needs at most one quarter-wave slot
-  // slots <= factor lanes / 16 + one partial unit per (start, k) pair; the halves of the work-group differ by less than one chunk
-  B.maxPR = std::min((B.maxP / 16 + NF) * (NF - 1), B.maxPO / 16 + NF * (NF - 1) / 2) / 32 + 2;
+  B.maxPR = max_point_unit_rounds(B.maxP, B.maxPO);
+  B.maxKS = max_schur_ksteps(B.maxP, B.maxL);
+  B.llSlots = line_lane_slots(B.maxL);
+  // One hipMalloc per array, in this order (vpl_ba_debug_guards names an array by its index).  (Measured alternative, round 2:
+  // all ~90 arrays out of one arena, with and without skewed offsets -- k_cost, the kernel closest to the bandwidth roof, then
+  // runs at 0.30 ms per step in EVERY process, whereas with separate allocations it is 0.24 ms in most processes and 0.30 ms in
+  // some: the difference is where the driver places the buffers, not the code.  DESIGN.md section 8.)
   const size_t W = max_windows;
   hipError_t e = hipSuccess;
 #define AL(ptr, n) if (e == hipSuccess) e = dalloc(c, &B.ptr, (size_t)(n))
-#define AL2(ptr, n) if (e == hipSuccess) e = dalloc(c, &B.ptr, (size_t)(n))
   AL(pose, W * 77); AL(sb, W * 99); AL(ex, W * 7); AL(invd, W * B.maxP); AL(orth, W * B.maxL * 4);
   AL(pose_c, W * 77); AL(sb_c, W * 99); AL(ex_c, W * 7); AL(invd_c, W * B.maxP); AL(orth_c, W * B.maxL * 4); AL(lw, W * B.maxL * 6); AL(lw_c, W * B.maxL * 6);
   AL(lin_part, W * LIN_PART); AL(lin_pcost, W); AL(lin_flag, W);
@@ -401,7 +411,6 @@ int vpl_ctx_create(vpl_ctx** out, int device, int max_windows, int max_points, i
   AL(ps_list, W * B.maxP); AL(ps_cnt, W * (NF + 1)); AL(pu_lane, W * B.maxPR * 1024); AL(pu_sub, W * B.maxPR * 512); AL(pu_cnt, W); AL(pu_cnt0, W);
   AL(ln_start, W * B.maxL); AL(ln_nobs, W * B.maxL); AL(ln_off, W * B.maxL); AL(ln_obs, W * B.maxLO * 8);
   AL(nLO, W); AL(lo_ln, W * B.maxLO);
-  B.llSlots = 512 * ((B.maxL + 8 * (64 / NF) - 1) / (8 * (64 / NF)));   // worst case: 11-frame tracks, 5 lines per wave
   AL(ll_tab, W * B.llSlots * 2); AL(ll_np, W);
   AL(pre, W * NF);
   AL(pr_n, W); AL(pr_nb, W); AL(pr_kind, W * MAXPB); AL(pr_frame, W * MAXPB); AL(pr_idx, W * MAXPB);
@@ -414,27 +423,18 @@ int vpl_ctx_create(vpl_ctx** out, int device, int max_windows, int max_points, i
   AL(mg_n, W); AL(mg_nb, W); AL(mg_kind, W * MAXPB); AL(mg_frame, W * MAXPB); AL(mg_idx, W * MAXPB);
   AL(mg_cam, W * MAXPB); AL(mg_x0, W * MAXPB * 9); AL(mg_J0, W * MAXKEEP * MAXKEEP); AL(mg_r0, W * MAXKEEP);
   AL(mg_A, W * MAXKEEP * MAXKEEP); AL(mg_b, W * MAXKEEP); AL(mg_m, W); AL(dbg, W * 64); AL(ln_removed, W * B.maxL); AL(ln_tri, W * B.maxL);
-#undef AL
   if (e == hipSuccess) e = dalloc(c, &c->d_act, (size_t)ACT_SLOTS * 4);
-  AL2(order, 2 * W); AL2(ord_cnt, 4);
-  B.maxKS = B.maxP / 4 + B.maxL + NF + 2;
-  AL2(sk_tab, W * B.maxKS * 4); AL2(sk_wave, W * 8 * SK_WSTRIDE); AL2(sacc, W * SACC_N); AL2(nz_tab, NZ_N); AL2(ycs, W * 176); AL2(sx, W * 8); AL2(path, W);
-  if (e != hipSuccess) {
-    for (void* p : c->allocs) hipFree(p);
-    delete c;
-    return VPL_E_HIP;
-  }
-  if (lin_smem_base(c->maxP, c->maxL) > LIN_LDS_BUDGET) { for (void* p : c->allocs) hipFree(p); delete c; return VPL_E_CAPACITY; }
+  AL(order, 2 * W); AL(ord_cnt, 4);
+  AL(sk_tab, W * B.maxKS * 4); AL(sk_wave, W * 8 * SK_WSTRIDE); AL(sacc, W * SACC_N); AL(nz_tab, NZ_N); AL(ycs, W * 176); AL(sx, W * 8); AL(path, W);
+#undef AL
+  if (e != hipSuccess) return VPL_E_HIP;
+  if (lin_smem_base(c->maxP, c->maxL) > LIN_LDS_BUDGET) return VPL_E_CAPACITY;
   B.prhN = lin_prh_n(c->maxP, c->maxL);
   {   // static table of the assembly pass of k_lin
     std::vector<int> tab(2 * NCP);
     for (int r = 0, e2 = 0; r < NC; ++r)
       for (int cc = 0; cc <= r; ++cc, ++e2) lin_asm_entry(r, cc, &tab[2 * e2]);
-    if (hipMemcpy(B.asm_tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
-      for (void* p : c->allocs) hipFree(p);
-      delete c;
-      return VPL_E_HIP;
-    }
+    if (hipMemcpy(B.asm_tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return VPL_E_HIP;
   }
   {   // non-zero pattern of the packed cam Hessian of a fast-path window (ba_types.h)
     std::vector<int> nz;
@@ -446,49 +446,55 @@ int vpl_ctx_create(vpl_ctx** out, int device, int max_windows, int max_points, i
         const bool sb0 = cc >= 6 && cc < 15 && cam2vis(r) >= 0;
         if (vis || band || sb0) nz.push_back(tri(r, cc) | r << 14 | cc << 22);
       }
-    if ((int)nz.size() != NZ_N || hipMemcpy(B.nz_tab, nz.data(), nz.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
-      for (void* p : c->allocs) hipFree(p);
-      delete c;
-      return VPL_E_HIP;
-    }
+    if ((int)nz.size() != NZ_N || hipMemcpy(B.nz_tab, nz.data(), nz.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return VPL_E_HIP;
   }
   // the attribute is per kernel, not per context: never lower what a larger context of this process has asked for
-  static size_t lin_max = 0, solve_max = 0;
+  static size_t lin_max = 0, solve_max = 0, schur_max = 0, back_max = 0;
   lin_max = std::max(lin_max, lin_smem(c->maxP, c->maxL));
   solve_max = std::max(solve_max, solve_smem(c->maxP, c->maxL));
-  hipFuncSetAttribute((const void*)k_lin2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lin_max);
-  hipFuncSetAttribute((const void*)k_lin<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lin_max);
-  hipFuncSetAttribute((const void*)k_lin<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lin_max);
-  hipFuncSetAttribute((const void*)k_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)solve_max);
-  static size_t schur_max = 0, back_max = 0;
   schur_max = std::max(schur_max, schur_smem(c->maxP, c->maxL));
   back_max = std::max(back_max, back_smem(c->maxP, c->maxL));
-  if (schur_max > 159 * 1024 || back_max > 159 * 1024) { for (void* p : c->allocs) hipFree(p); delete c; return VPL_E_CAPACITY; }
-  hipFuncSetAttribute((const void*)k_schur<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)schur_max);
-  hipFuncSetAttribute((const void*)k_schur<5>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)schur_max);
-  hipFuncSetAttribute((const void*)k_schur_mixed, hipFuncAttributeMaxDynamicSharedMemorySize, (int)schur_max);
-  hipFuncSetAttribute((const void*)k_chol, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CHOL_SMEM);
-  hipFuncSetAttribute((const void*)k_back, hipFuncAttributeMaxDynamicSharedMemorySize, (int)back_max);
-  hipFuncSetAttribute((const void*)k_prep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PREP_SMEM);
-  hipFuncSetAttribute((const void*)k_marg<MARG_THREADS>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
-  hipFuncSetAttribute((const void*)k_marg<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MARG_LDS_SMALL);
-  (void)hipGetLastError();
+  if (schur_max > 159 * 1024 || back_max > 159 * 1024) return VPL_E_CAPACITY;
+  const std::pair<const void*, size_t> lds[] = {
+      {(const void*)k_lin2, lin_max}, {(const void*)k_lin<1>, lin_max}, {(const void*)k_lin<2>, lin_max},
+      {(const void*)k_solve, solve_max}, {(const void*)k_schur<3>, schur_max}, {(const void*)k_schur<5>, schur_max},
+      {(const void*)k_schur_mixed, schur_max}, {(const void*)k_chol, CHOL_SMEM}, {(const void*)k_back, back_max},
+      {(const void*)k_prep, PREP_SMEM}, {(const void*)k_marg<MARG_THREADS>, 159 * 1024}, {(const void*)k_marg<256>, MARG_LDS_SMALL}};
+  for (const auto& k : lds)
+    if (hipFuncSetAttribute(k.first, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.second) != hipSuccess) return VPL_E_HIP;
   vpl_ba_default_options(&c->opt);
   if (const char* gv = std::getenv("VPL_BA_GRAPH")) c->use_graph = std::atoi(gv) != 0;
   if (const char* gv = std::getenv("VPL_BA_GENERAL")) c->force_general = std::atoi(gv) != 0;
   if (const char* gv = std::getenv("VPL_BA_SCHUR_WIDE")) { c->schur_wide_all = std::atoi(gv) > 0; c->schur_never_wide = std::atoi(gv) < 0; }
+  return VPL_OK;
+}
+
+int vpl_ctx_create(vpl_ctx** out, int device, int max_windows, int max_points, int max_point_obs, int max_lines,
+                   int max_line_obs) {
+  if (!out || max_windows < 1 || max_points < 0 || max_lines < 0) return VPL_E_INVALID;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0 || device >= ndev) return VPL_E_NODEVICE;
+  if (hipSetDevice(device) != hipSuccess) return VPL_E_NODEVICE;
+  vpl_ctx* c = new vpl_ctx();
+  const int rc = ctx_init(c, device, max_windows, max_points, max_point_obs, max_lines, max_line_obs);
+  if (rc != VPL_OK) {
+    free_arrays(c);
+    delete c;
+    return rc;
+  }
   *out = c;
   return VPL_OK;
 }
 
 void vpl_ctx_destroy(vpl_ctx* c) {
   if (!c) return;
-  hipSetDevice(c->device);
-  hipDeviceSynchronize();
+  // (teardown: a failure has nobody to be reported to)
+  (void)hipSetDevice(c->device);
+  (void)hipDeviceSynchronize();
   drop_graph(c);
-  for (void* p : c->allocs) hipFree(p);
+  free_arrays(c);
   c->stage.release();
-  for (hipEvent_t& e : c->leg_ev) if (e) hipEventDestroy(e);
+  for (hipEvent_t& e : c->leg_ev) if (e) (void)hipEventDestroy(e);
   delete c;
 }
 
@@ -550,31 +556,29 @@ int vpl_preintegrate_batch(vpl_ctx* c, int n, const int* offset, const int* nsam
   HIPCHK(c, hipSetDevice(c->device));
   size_t total = 0;
   for (int i = 0; i < n; ++i) total = std::max(total, (size_t)offset[i] + nsamples[i]);
-  int *d_off, *d_ns;
-  double *d_s, *d_a, *d_g, *d_ba, *d_bg;
-  DevPreint* d_out;
-  HIPCHK(c, hipMalloc(&d_off, n * sizeof(int)));
-  HIPCHK(c, hipMalloc(&d_ns, n * sizeof(int)));
-  HIPCHK(c, hipMalloc(&d_s, total * 7 * sizeof(double) + 8));
-  HIPCHK(c, hipMalloc(&d_a, n * 3 * sizeof(double)));
-  HIPCHK(c, hipMalloc(&d_g, n * 3 * sizeof(double)));
-  HIPCHK(c, hipMalloc(&d_ba, n * 3 * sizeof(double)));
-  HIPCHK(c, hipMalloc(&d_bg, n * 3 * sizeof(double)));
-  HIPCHK(c, hipMalloc(&d_out, n * sizeof(DevPreint)));
-  HIPCHK(c, hipMemcpyAsync(d_off, offset, n * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d_ns, nsamples, n * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d_s, samples, total * 7 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d_a, acc0, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d_g, gyr0, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d_ba, lin_ba, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d_bg, lin_bg, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  DevBuf d_off, d_ns, d_s, d_a, d_g, d_ba, d_bg, d_out;
+  HIPCHK(c, d_off.alloc(n * sizeof(int)));
+  HIPCHK(c, d_ns.alloc(n * sizeof(int)));
+  HIPCHK(c, d_s.alloc(total * 7 * sizeof(double) + 8));
+  HIPCHK(c, d_a.alloc(n * 3 * sizeof(double)));
+  HIPCHK(c, d_g.alloc(n * 3 * sizeof(double)));
+  HIPCHK(c, d_ba.alloc(n * 3 * sizeof(double)));
+  HIPCHK(c, d_bg.alloc(n * 3 * sizeof(double)));
+  HIPCHK(c, d_out.alloc(n * sizeof(DevPreint)));
+  HIPCHK(c, hipMemcpyAsync(d_off.p, offset, n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(d_ns.p, nsamples, n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(d_s.p, samples, total * 7 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(d_a.p, acc0, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(d_g.p, gyr0, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(d_ba.p, lin_ba, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(d_bg.p, lin_bg, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
   { KTimer t(c, "k_preintegrate");
-    hipLaunchKernelGGL(k_preintegrate, dim3((n + 3) / 4), dim3(64), 0, c->stream, n, d_off, d_ns, d_s, d_a, d_g, d_ba,
-                       d_bg, opt->acc_n * opt->acc_n, opt->gyr_n * opt->gyr_n, opt->acc_w * opt->acc_w,
-                       opt->gyr_w * opt->gyr_w, d_out); }
+    hipLaunchKernelGGL(k_preintegrate, dim3((n + 3) / 4), dim3(64), 0, c->stream, n, (const int*)d_off.p, (const int*)d_ns.p, d_s.d(),
+                       d_a.d(), d_g.d(), d_ba.d(), d_bg.d(), opt->acc_n * opt->acc_n, opt->gyr_n * opt->gyr_n,
+                       opt->acc_w * opt->acc_w, opt->gyr_w * opt->gyr_w, (DevPreint*)d_out.p); }
   HIPCHK(c, hipGetLastError());
   std::vector<DevPreint> h(n);
-  HIPCHK(c, hipMemcpyAsync(h.data(), d_out, n * sizeof(DevPreint), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(h.data(), d_out.p, n * sizeof(DevPreint), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   for (int i = 0; i < n; ++i) {
     vpl_preintegration& o = out[i];
@@ -584,7 +588,6 @@ int vpl_preintegrate_batch(vpl_ctx* c, int n, const int* offset, const int* nsam
     std::memcpy(o.jacobian, h[i].sqrt_info, sizeof(o.jacobian));   // k_preintegrate carries J out in this slot
     std::memcpy(o.covariance, h[i].cov, sizeof(o.covariance));
   }
-  hipFree(d_off); hipFree(d_ns); hipFree(d_s); hipFree(d_a); hipFree(d_g); hipFree(d_ba); hipFree(d_bg); hipFree(d_out);
   return VPL_OK;
 }
 
@@ -668,20 +671,99 @@ int vpl_line_orth_plus(vpl_ctx* c, int n, const double* x, const double* delta, 
 }
 
 // ---- window batch: upload / solve / download ------------------------------------------------------------
-static int upload_body(vpl_ctx* c, int nW, const vpl_window* win, const vpl_ba_options* opt, bool all_lines, bool chained);
-// An upload that is refused half way (a track outside the window in the third window, a prior of impossible size) has already
-// rewritten part of the batch's host tables and its size: the context then holds NO batch -- solve / download / reset return
-// VPL_E_INVALID until the next successful upload -- instead of running the new size on the old device data.  A refusal before
-// anything was touched (too many windows, unknown flag, no resident prior for a chained upload) leaves the previous batch as it was.
-static int upload_impl(vpl_ctx* c, int nW, const vpl_window* win, const vpl_ba_options* opt, bool all_lines, bool chained = false) {
-  const int rc = upload_body(c, nW, win, opt, all_lines, chained);
-  if (c) {
-    if (rc != VPL_OK && c->upload_open) { c->nW = 0; c->prior_resident = false; }
-    c->upload_open = false;
-  }
-  return rc;
+// The arrays one upload packs, pieces of the pinned arena (Stage).  take_upload and take_units are the one description of their
+// sizes and stage_upload the one list of where they go: upload_bound is a dry run of the three.
+struct UploadArena {
+  Span<double> pose, sb, ex, invd, plk, pt_obs, ln_obs, fail_ref, orth, pr_x0, pr_r0;
+  Span<int> nP, nL, pt_start, pt_nobs, pt_off, ln_start, ln_nobs, ln_off, ln_tri, pu_cnt, pu_cnt0, sk_tab, sk_wave, path, nLO, lo_ln,
+      ll_tab, ll_np, ps_list, ps_cnt, orth_in, pr_n, pr_nb, pr_kind, pr_frame, pr_idx, mg_n, mg_nb, mg_kind, mg_frame, mg_idx, mg_cam, mg_m;
+  Span<DevPreint> pre;
+  std::vector<Span<double>> J0;                  // per window: J0 of the incoming prior (empty: none, or a chained upload)
+  std::vector<Span<int>> pu_lane, pu_sub;        // per window: the first rounds of its point work units (same count for all)
+};
+
+// block table of a prior that stays on the device (chained upload)
+struct HostTab {
+  int n = 0, nb = 0, kind[MAXPB], frame[MAXPB], idx[MAXPB];
+  bool keep = false;                             // MARGIN_SECOND_NEW passed this window's prior through: pr_*, not mg_*
+};
+
+static void take_upload(Stage& S, UploadArena& A, const DevBatch& B, size_t W, const vpl_window* win, bool chained) {
+  A.pose = S.take<double>(W * 77); A.sb = S.take<double>(W * 99); A.ex = S.take<double>(W * 7); A.invd = S.take<double>(W * B.maxP, 1.0);
+  A.plk = S.take<double>(W * B.maxL * 6, 0.0);
+  A.nP = S.take<int>(W); A.nL = S.take<int>(W);
+  A.pt_start = S.take<int>(W * B.maxP, 0); A.pt_nobs = S.take<int>(W * B.maxP, 0); A.pt_off = S.take<int>(W * B.maxP, 0);
+  A.ln_start = S.take<int>(W * B.maxL, 0); A.ln_nobs = S.take<int>(W * B.maxL, 0); A.ln_off = S.take<int>(W * B.maxL, 0);
+  A.ln_tri = S.take<int>(W * B.maxL, 1);
+  A.pu_cnt = S.take<int>(W, 0); A.pu_cnt0 = S.take<int>(W, 0);
+  A.sk_tab = S.take<int>(W * B.maxKS * 4, 0); A.sk_wave = S.take<int>(W * 8 * SK_WSTRIDE, -1); A.path = S.take<int>(W, 0);
+  A.nLO = S.take<int>(W, 0); A.lo_ln = S.take<int>(W * B.maxLO, 0); A.ll_tab = S.take<int>(W * B.llSlots * 2, -1); A.ll_np = S.take<int>(W, 0);
+  A.ps_list = S.take<int>(W * B.maxP, 0); A.ps_cnt = S.take<int>(W * (NF + 1), 0);
+  A.pt_obs = S.take<double>(W * B.maxPO * 3, 0.0); A.ln_obs = S.take<double>(W * B.maxLO * 8, 0.0);
+  A.pre = S.take<DevPreint>(W * NF);
+  A.fail_ref = S.take<double>(W * 13, 0.0); A.orth = S.take<double>(W * B.maxL * 4, 0.0);
+  A.orth_in = S.take<int>(W, 0);
+  A.pr_n = S.take<int>(W, 0); A.pr_nb = S.take<int>(W, 0);
+  A.pr_kind = S.take<int>(W * MAXPB, 0); A.pr_frame = S.take<int>(W * MAXPB, 0); A.pr_idx = S.take<int>(W * MAXPB, 0);
+  A.pr_x0 = S.take<double>(W * MAXPB * 9, 0.0); A.pr_r0 = S.take<double>(W * MAXPN, 0.0);
+  A.mg_n = S.take<int>(W, 0); A.mg_nb = S.take<int>(W, 0); A.mg_kind = S.take<int>(W * MAXPB, 0); A.mg_frame = S.take<int>(W * MAXPB, 0);
+  A.mg_idx = S.take<int>(W * MAXPB, 0); A.mg_cam = S.take<int>(W * MAXPB, 0);
+  A.mg_m = S.take<int>(W);
+  A.J0.assign(W, Span<double>());
+  for (size_t w = 0; w < W; ++w)
+    if (!chained && win[w].has_prior && win[w].prior && win[w].prior->n > 0) A.J0[w] = S.take<double>((size_t)win[w].prior->n * win[w].prior->n);
 }
-static int upload_body(vpl_ctx* c, int nW, const vpl_window* win, const vpl_ba_options* opt, bool all_lines, bool chained) {
+static void take_units(Stage& S, UploadArena& A, size_t W, int rounds) {
+  A.pu_lane.clear();
+  A.pu_sub.clear();
+  if (rounds <= 0) return;
+  for (size_t w = 0; w < W; ++w) A.pu_lane.push_back(S.take<int>((size_t)rounds * 1024));
+  for (size_t w = 0; w < W; ++w) A.pu_sub.push_back(S.take<int>((size_t)rounds * 512));
+}
+// every piece to its device array(s): the segments of the upload's one copy
+static void stage_upload(Stage& S, const UploadArena& A, const DevBatch& B, size_t W, bool same_layout, bool chained) {
+  S.put(B.pose, A.pose); S.put(B.sb, A.sb); S.put(B.ex, A.ex); S.put(B.invd, A.invd);
+  S.put(B.plk, A.plk); S.put(B.fail_ref, A.fail_ref); S.put(B.orth_in, A.orth_in); S.put(B.orth, A.orth);
+  S.put(B.pose_0, A.pose); S.put(B.sb_0, A.sb); S.put(B.ex_0, A.ex); S.put(B.invd_0, A.invd); S.put(B.plk_0, A.plk);
+  S.put(B.pt_obs, A.pt_obs);
+  if (!same_layout) {
+    S.put(B.nP, A.nP); S.put(B.nL, A.nL);
+    S.put(B.pt_start, A.pt_start); S.put(B.pt_nobs, A.pt_nobs); S.put(B.pt_off, A.pt_off);
+    S.put(B.ps_list, A.ps_list); S.put(B.ps_cnt, A.ps_cnt);
+    for (size_t w = 0; w < A.pu_lane.size(); ++w) {
+      S.put(B.pu_lane + w * (size_t)B.maxPR * 1024, A.pu_lane[w]);
+      S.put(B.pu_sub + w * (size_t)B.maxPR * 512, A.pu_sub[w]);
+    }
+    S.put(B.pu_cnt, A.pu_cnt); S.put(B.pu_cnt0, A.pu_cnt0);
+    S.put(B.ln_start, A.ln_start); S.put(B.ln_nobs, A.ln_nobs); S.put(B.ln_off, A.ln_off);
+    S.put(B.nLO, A.nLO); S.put(B.lo_ln, A.lo_ln);
+    S.put(B.ll_tab, A.ll_tab); S.put(B.ll_np, A.ll_np);
+    S.put(B.sk_tab, A.sk_tab); S.put(B.sk_wave, A.sk_wave);
+  }
+  S.put(B.ln_obs, A.ln_obs); S.put(B.ln_tri, A.ln_tri);
+  S.put(B.pre, A.pre);
+  S.put(B.pr_n, A.pr_n); S.put(B.pr_nb, A.pr_nb); S.put(B.pr_kind, A.pr_kind); S.put(B.pr_frame, A.pr_frame); S.put(B.pr_idx, A.pr_idx);
+  if (!chained) {
+    S.put(B.pr_x0, A.pr_x0); S.put(B.pr_r0, A.pr_r0);
+    for (size_t w = 0; w < W; ++w) S.put(B.pr_J0 + w * (size_t)B.prS, A.J0[w]);
+  }
+  S.put(B.mg_n, A.mg_n); S.put(B.mg_nb, A.mg_nb); S.put(B.mg_kind, A.mg_kind);
+  S.put(B.mg_frame, A.mg_frame); S.put(B.mg_idx, A.mg_idx); S.put(B.mg_cam, A.mg_cam); S.put(B.mg_m, A.mg_m);
+  S.put(B.path, A.path);
+}
+// the arena an upload needs: its pieces, with every window's point work units at the capacity, and its segment table
+static size_t upload_bound(const DevBatch& B, size_t W, const vpl_window* win, bool same_layout, bool chained) {
+  Stage dry;
+  dry.dry = true;
+  UploadArena A;
+  take_upload(dry, A, B, W, win, chained);
+  take_units(dry, A, W, B.maxPR);
+  stage_upload(dry, A, B, W, same_layout, chained);
+  return dry.bound();
+}
+
+// 1. the refusals that leave the previous batch as it was
+static int upload_check(vpl_ctx* c, int nW, const vpl_window* win, const vpl_ba_options* opt, bool chained) {
   if (!c || !win || !opt || nW < 1) return VPL_E_INVALID;
   if (nW > c->maxW) return fail(c, VPL_E_CAPACITY, "more windows than max_windows");
   if (opt->marginalization_flag != VPL_MARGIN_OLD && opt->marginalization_flag != VPL_MARGIN_SECOND_NEW &&
@@ -693,11 +775,335 @@ static int upload_body(vpl_ctx* c, int nW, const vpl_window* win, const vpl_ba_o
   // marginalisation and nothing was uploaded since (any upload rewrites mg_n / mg_nb / mg_kind, the tables of the NEXT prior)
   if (chained && (!c->prior_resident || c->prior_resident_nW != nW))
     return fail(c, VPL_E_INVALID, "upload_chained: needs a previous solve of the same batch size with a marginalisation, and no upload since");
+  return VPL_OK;
+}
+
+// 2. chained upload: window w takes the prior the context's previous solve left for window w (device resident); only its
+// block table comes through the host -- the ten tables in one gather and one device-to-host copy of the arena
+static int read_resident_priors(vpl_ctx* c, size_t W, std::vector<HostTab>& tab) {
+  const DevBatch& B = c->B;
+  int* const src[10] = {B.mg_n, B.mg_nb, B.mg_kind, B.mg_frame, B.mg_idx, B.pr_n, B.pr_nb, B.pr_kind, B.pr_frame, B.pr_idx};
+  Span<int> t[10];   // [0, 5): mg_* (the next prior), [5, 10): pr_* (the prior a pass-through window keeps)
+  auto plan = [&](Stage& S) {
+    for (int k = 0; k < 10; ++k) {
+      t[k] = S.take<int>(k % 5 < 2 ? W : W * MAXPB);
+      S.from_device(t[k].p, src[k], t[k].n);
+    }
+  };
+  HIPCHK(c, stage_plan(c->stage, plan));
+  HIPCHK(c, stage_run(c, false));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  tab.resize(W);
+  for (size_t w = 0; w < W; ++w) {
+    HostTab& T = tab[w];
+    T.keep = c->h_passthrough[w] >= 0;      // MARGIN_SECOND_NEW left this window's prior as it was
+    const Span<int>* s = t + (T.keep ? 5 : 0);
+    T.n = s[0][w];
+    T.nb = s[1][w];
+    if (T.n < 0 || T.n > MAXPN || T.nb < 0 || T.nb > MAXPB) return fail(c, VPL_E_INVALID, "upload_chained: resident prior table out of range");
+    for (int b = 0; b < T.nb; ++b) {
+      T.kind[b] = s[2][w * MAXPB + b];
+      T.frame[b] = s[3][w * MAXPB + b];
+      T.idx[b] = s[4][w * MAXPB + b];
+    }
+  }
+  return VPL_OK;
+}
+
+// 3. batch strides: of the prior matrices (the largest prior) and of the compact W rows (the longest track); zero fill only where
+// some slot has no writer
+static int batch_strides(vpl_ctx* c, size_t W, const vpl_window* win, const vpl_ba_options* opt, const HostTab* ctab) {
+  DevBatch& B = c->B;
+  int nmax = 1;
+  for (size_t w = 0; w < W; ++w) {
+    if (ctab) nmax = std::max(nmax, ctab[w].n);
+    else if (win[w].has_prior && win[w].prior) nmax = std::max(nmax, win[w].prior->n);
+  }
+  if (nmax > MAXPN) return fail(c, VPL_E_CAPACITY, "prior larger than MAXPN");
+  B.prS = (nmax * nmax + 7) & ~7;
+  int maxTrack = 2, minTrack = NF;
+  for (size_t w = 0; w < W; ++w) {
+    for (int p = 0; p < win[w].n_points; ++p) { maxTrack = std::max(maxTrack, win[w].point_nobs[p]); minTrack = std::min(minTrack, win[w].point_nobs[p]); }
+    for (int l = 0; l < win[w].n_lines; ++l) { maxTrack = std::max(maxTrack, win[w].line_nobs[l]); minTrack = std::min(minTrack, win[w].line_nobs[l]); }
+  }
+  maxTrack = std::min(maxTrack, (int)NF);
+  B.WS = 6 * maxTrack + 6;
+  int maxLineTrack = 1;
+  for (size_t w = 0; w < W; ++w)
+    for (int l = 0; l < win[w].n_lines; ++l) maxLineTrack = std::max(maxLineTrack, std::min(win[w].line_nobs[l], (int)NF));
+  B.llK = maxLineTrack;
+  B.llNLW = 64 / maxLineTrack;
+  B.wfill = (minTrack != maxTrack || opt->remove_line_outliers) ? 1 : 0;
+  return VPL_OK;
+}
+
+// 4. signature of the track layout: when it is the last upload's, the lane / unit / K-step tables and the index arrays on the
+// device are the right ones.  The hash only finds the candidate; the decision is an exact comparison of the hashed integers
+// (a collision would reuse lane / unit / K-step tables of another track layout: out-of-range reads -- ADVICE r3).
+static bool layout_unchanged(vpl_ctx* c, size_t W, const vpl_window* win, bool all_lines) {
+  const DevBatch& B = c->B;
+  unsigned long long h = 1469598103934665603ull;
+  auto mix = [&](const void* p, size_t n) { const unsigned char* b = (const unsigned char*)p; for (size_t i = 0; i < n; ++i) { h ^= b[i]; h *= 1099511628211ull; } };
+  const int hdr[8] = {(int)W, B.WS, B.llK, B.llNLW, B.wfill, all_lines ? 1 : 0, B.maxP, B.maxL};
+  mix(hdr, sizeof(hdr));
+  std::vector<int> key;
+  key.reserve(16 + W * 8);
+  key.insert(key.end(), hdr, hdr + 8);
+  for (size_t w = 0; w < W; ++w) {
+    const vpl_window& v = win[w];
+    mix(&v.n_points, 4); mix(&v.n_lines, 4);
+    key.push_back(v.n_points); key.push_back(v.n_lines);
+    const bool hp = v.n_points > 0 && v.point_start && v.point_nobs, hl = v.n_lines > 0 && v.line_start && v.line_nobs;
+    const bool ht = v.n_lines > 0 && v.line_triangulated;
+    key.push_back((hp ? 1 : 0) | (hl ? 2 : 0) | (ht ? 4 : 0));   // which arrays follow
+    if (hp) {
+      mix(v.point_start, 4 * (size_t)v.n_points); mix(v.point_nobs, 4 * (size_t)v.n_points);
+      key.insert(key.end(), v.point_start, v.point_start + v.n_points); key.insert(key.end(), v.point_nobs, v.point_nobs + v.n_points);
+    }
+    if (hl) {
+      mix(v.line_start, 4 * (size_t)v.n_lines); mix(v.line_nobs, 4 * (size_t)v.n_lines);
+      key.insert(key.end(), v.line_start, v.line_start + v.n_lines); key.insert(key.end(), v.line_nobs, v.line_nobs + v.n_lines);
+    }
+    if (ht) {
+      mix(v.line_triangulated, 4 * (size_t)v.n_lines);
+      key.insert(key.end(), v.line_triangulated, v.line_triangulated + v.n_lines);
+    }
+  }
+  const bool same = c->layout_valid && h == c->layout_sig && key == c->layout_key && std::getenv("VPL_BA_NO_LAYOUT_CACHE") == nullptr;
+  c->layout_sig = h;
+  c->layout_key.swap(key);
+  c->layout_valid = false;       // becomes valid when this upload has gone through
+  return same;
+}
+
+// 5. states, tracks and observations of window w; h_lmap[w][dl] is the caller's index of device line dl
+static int pack_window(vpl_ctx* c, UploadArena& A, size_t w, const vpl_window& v, bool all_lines) {
+  const DevBatch& B = c->B;
+  if (v.n_points > B.maxP || v.n_lines > B.maxL) return fail(c, VPL_E_CAPACITY, "too many tracks for the context");
+  std::memcpy(&A.pose[w * 77], v.pose, 77 * 8);
+  std::memcpy(&A.sb[w * 99], v.speed_bias, 99 * 8);
+  std::memcpy(&A.ex[w * 7], v.ex_pose, 7 * 8);
+  if (v.failure_occur) {
+    A.fail_ref[w * 13] = 1.0;
+    std::memcpy(&A.fail_ref[w * 13 + 1], v.last_P0, 3 * 8);
+    std::memcpy(&A.fail_ref[w * 13 + 4], v.last_R0, 9 * 8);
+  }
+  A.nP[w] = v.n_points;
+  c->h_nP[w] = v.n_points;
+  int off = 0;
+  for (int p = 0; p < v.n_points; ++p) {
+    const int s = v.point_start[p], no = v.point_nobs[p];
+    if (s < 0 || no < 2 || s + no > NF) return fail(c, VPL_E_INVALID, "point track outside the window");
+    if (off + no > B.maxPO) return fail(c, VPL_E_CAPACITY, "too many point observations");
+    A.pt_start[w * B.maxP + p] = s; A.pt_nobs[w * B.maxP + p] = no; A.pt_off[w * B.maxP + p] = off;
+    std::memcpy(&A.pt_obs[(w * B.maxPO + off) * 3], v.point_obs + (size_t)off * 3, (size_t)no * 3 * 8);
+    A.invd[w * B.maxP + p] = v.inv_depth[p];
+    off += no;
+  }
+  off = 0;
+  int woff = 0, nl = 0;
+  std::vector<int>& lmap = c->h_lmap[w];
+  lmap.clear();
+  for (int l = 0; l < v.n_lines; ++l) {
+    const int s = v.line_start[l], no = v.line_nobs[l];
+    if (s < 0 || no < 1 || s + no > NF) return fail(c, VPL_E_INVALID, "line track outside the window");
+    const int tri_flag = (!v.line_triangulated || v.line_triangulated[l]) ? 1 : 0;
+    // lines that are not triangulated take no part in the solves (estimator.cpp:1133); they travel only for
+    // vpl_ba_triangulate_lines
+    if (all_lines || tri_flag) {
+      if (off + no > B.maxLO) return fail(c, VPL_E_CAPACITY, "too many line observations");
+      const size_t dl = w * B.maxL + nl;
+      A.ln_start[dl] = s; A.ln_nobs[dl] = no; A.ln_off[dl] = off; A.ln_tri[dl] = tri_flag;
+      std::memcpy(&A.ln_obs[(w * B.maxLO + off) * 8], v.line_obs + (size_t)woff * 8, (size_t)no * 8 * 8);
+      if (v.line_orth) std::memcpy(&A.orth[dl * 4], v.line_orth + (size_t)l * 4, 4 * 8);
+      else std::memcpy(&A.plk[dl * 6], v.line_plk + (size_t)l * 6, 6 * 8);
+      for (int k = 0; k < no; ++k) A.lo_ln[w * B.maxLO + off + k] = nl;
+      off += no;
+      lmap.push_back(l);
+      ++nl;
+    }
+    woff += no;
+  }
+  A.nL[w] = nl;
+  A.orth_in[w] = v.line_orth ? 1 : 0;
+  c->h_nL[w] = nl;
+  A.nLO[w] = off;
+  for (int j = 0; j < NF; ++j) to_dev_preint(v.preint[j], A.pre[w * NF + j]);
+  return VPL_OK;
+}
+
+// 6. layout tables of window w: the point work units of k_lin (into lane / sub, maxPR rounds), the K-steps of k_schur and the
+// lane layout of the line phase (ba_pack.h)
+static int build_layout(vpl_ctx* c, UploadArena& A, size_t w, const vpl_window& v, int* lane, int* sub, long* wide_w, long* total_w) {
+  const DevBatch& B = c->B;
+  int* list = &A.ps_list[w * B.maxP];
+  int* cnt = &A.ps_cnt[w * (NF + 1)];
+  sort_points_by_start(v.n_points, v.point_start, v.point_nobs, list, cnt);
+  PointUnitLayout PL;
+  if (!pack_point_units(v.point_nobs, &A.pt_off[w * B.maxP], list, cnt, B.maxPR, lane, sub, &PL))
+    return fail(c, VPL_E_CAPACITY, "point work-unit table too small");
+  A.pu_cnt[w] = PL.rounds;
+  A.pu_cnt0[w] = PL.rounds0;
+  // a pass that waited for a ticket owned by a unit it never runs would spin forever on the device: replay both chains
+  if (!point_unit_chains_finish(sub, PL, false) || !point_unit_chains_finish(sub, PL, true))
+    return fail(c, VPL_E_INVALID, "internal: commit-ticket order of the point work units is not executable");
+  // K-steps of k_schur: landmark rows by start frame, dealt to the waves, flush tickets; rows wider than the 6-frame view of
+  // k_schur<3>: entries with a longer track are flagged wide (k_schur_mixed)
+  const int nl = A.nL[w];
+  if (pack_schur_ksteps(v.n_points, list, cnt, nl, &A.ln_start[w * B.maxL], B.maxKS, &A.sk_tab[w * B.maxKS * 4],
+                        &A.sk_wave[w * 8 * SK_WSTRIDE], SCHUR_THREADS / 64, v.point_nobs, &A.ln_nobs[w * B.maxL],
+                        B.WS + 2 > 48 ? SCHUR_NARROW_FRAMES : 0, wide_w, total_w) < 0)
+    return fail(c, VPL_E_CAPACITY, "K-step table of the landmark elimination too small");
+  // lane layout of the line phase: llNLW whole tracks per wave, k-major; tracks in the caller's order (tracks that start in the
+  // same frame side by side would pile their LDS adds onto the same addresses)
+  const int NLW = B.llNLW, perPass = 8 * NLW;
+  A.ll_np[w] = (nl + perPass - 1) / perPass;
+  if (A.ll_np[w] * 512 > B.llSlots) return fail(c, VPL_E_CAPACITY, "line layout table too small");
+  for (int dl = 0; dl < nl; ++dl) {
+    const int pass = dl / perPass, wave = (dl % perPass) / NLW, i = dl % NLW;
+    const int no = std::min(A.ln_nobs[w * B.maxL + dl], (int)NF);
+    for (int k = 0; k < no; ++k) {      // (observation, line | k << 16 | start frame << 20): everything a lane's loads need
+      int* e = &A.ll_tab[2 * ((size_t)w * B.llSlots + pass * 512 + wave * 64 + k * NLW + i)];
+      e[0] = A.ln_off[w * B.maxL + dl] + k;
+      e[1] = dl | k << 16 | A.ln_start[w * B.maxL + dl] << 20;
+    }
+  }
+  return VPL_OK;
+}
+
+// 7. the incoming prior of window w: its block table (T: the resident one of a chained upload) or the caller's vpl_prior
+static int pack_prior(vpl_ctx* c, UploadArena& A, size_t w, const vpl_window& v, const HostTab* T) {
+  if (T) {
+    A.pr_n[w] = T->n; A.pr_nb[w] = T->nb;
+    c->maxPriorN = std::max(c->maxPriorN, T->n);
+    for (int b = 0; b < T->nb; ++b) {
+      A.pr_kind[w * MAXPB + b] = T->kind[b]; A.pr_frame[w * MAXPB + b] = T->frame[b]; A.pr_idx[w * MAXPB + b] = T->idx[b];
+      if (T->kind[b] == 1 && T->frame[b] != 0) A.path[w] = 1;
+    }
+    return VPL_OK;
+  }
+  if (!v.has_prior || !v.prior) return VPL_OK;
+  const vpl_prior& pr = *v.prior;
+  if (pr.n < 0 || pr.n > MAXPN || pr.n_blocks < 0 || pr.n_blocks > MAXPB) return fail(c, VPL_E_INVALID, "bad prior");
+  A.pr_n[w] = pr.n; A.pr_nb[w] = pr.n_blocks;
+  // k_chol's elimination order keeps speed/bias 0 in its dense part; a prior that ties another frame's speed/bias block
+  // (never produced by the reference's marginalisation) takes the general path
+  for (int b = 0; b < pr.n_blocks; ++b)
+    if (pr.block_kind[b] == 1 && pr.block_frame[b] != 0) A.path[w] = 1;
+  c->maxPriorN = std::max(c->maxPriorN, pr.n);
+  for (int b = 0; b < pr.n_blocks; ++b) {
+    A.pr_kind[w * MAXPB + b] = pr.block_kind[b];
+    A.pr_frame[w * MAXPB + b] = pr.block_frame[b];
+    A.pr_idx[w * MAXPB + b] = pr.block_idx[b];
+    std::memcpy(&A.pr_x0[(w * MAXPB + b) * 9], pr.x0[b], 9 * 8);
+    if (pr.block_kind[b] < 0 || pr.block_kind[b] > 2 || pr.block_frame[b] < 0 || pr.block_frame[b] >= NF)
+      return fail(c, VPL_E_INVALID, "bad prior block");
+  }
+  std::memcpy(&A.pr_r0[w * MAXPN], pr.r0, (size_t)pr.n * 8);
+  if (pr.n > 0) std::memcpy(A.J0[w].p, pr.J0, (size_t)pr.n * pr.n * 8);
+  return VPL_OK;
+}
+
+// 8. kept blocks of window w's next prior in the canonical (address) order of the reference's para_* layout
+static int keep_blocks(vpl_ctx* c, UploadArena& A, size_t w, const vpl_window& v, const HostTab* T) {
+  const DevBatch& B = c->B;
+  int* kd = &A.mg_kind[w * MAXPB]; int* fr = &A.mg_frame[w * MAXPB]; int* ix = &A.mg_idx[w * MAXPB]; int* cm = &A.mg_cam[w * MAXPB];
+  const int pnb = T ? T->nb : ((v.has_prior && v.prior) ? v.prior->n_blocks : 0);
+  const int* pk = pnb ? (T ? T->kind : v.prior->block_kind) : nullptr;
+  const int* pf = pnb ? (T ? T->frame : v.prior->block_frame) : nullptr;
+  c->h_passthrough[w] = -1;
+  if (c->opt.marginalization_flag == VPL_MARGIN_OLD) {
+    KeepSrc S;
+    S.nP = v.n_points; S.pt_start = v.point_start; S.pt_nobs = v.point_nobs;
+    S.nL = A.nL[w]; S.ln_start = &A.ln_start[w * B.maxL]; S.ln_nobs = &A.ln_nobs[w * B.maxL]; S.ln_removed = nullptr;
+    S.pr_nb = pnb; S.pr_kind = pk; S.pr_frame = pf;
+    S.imu01 = v.preint[1].sum_dt < 10.0;
+    int mm = 0;
+    keep_tables_old(S, kd, fr, ix, cm, &A.mg_n[w], &A.mg_nb[w], &mm);
+    c->h_mg_m[w] = mm;
+  } else if (c->opt.marginalization_flag == VPL_MARGIN_SECOND_NEW) {
+    const int rc = pnb ? keep_tables_second_new(pnb, pk, pf, kd, fr, ix, cm, &A.mg_n[w], &A.mg_nb[w]) : 0;
+    if (rc < 0) return fail(c, VPL_E_INVALID, "MARGIN_SECOND_NEW: the prior holds the speed/bias of frame WINDOW_SIZE-1");
+    if (rc == 1) { c->h_mg_m[w] = 6; c->any_second_new = true; }
+    else if (pnb) {   // the reference leaves last_marginalization_info as it is (estimator.cpp:1385)
+      c->h_passthrough[w] = (int)c->h_pass_priors.size();
+      if (T) {          // the prior lives on the device only: the pass-through entry carries its table (download refetches the rest)
+        vpl_prior hp;
+        std::memset(&hp, 0, sizeof(int) * (2 + 3 * VPL_MAX_PRIOR_BLOCKS));
+        hp.n = -1;      // marker: not available on the host
+        c->h_pass_priors.push_back(hp);
+      } else {
+        c->h_pass_priors.push_back(*v.prior);
+      }
+    }
+  }
+  if (A.mg_n[w] > MAXKEEP) return fail(c, VPL_E_CAPACITY, "marginalisation keeps more than MAXKEEP dims");
+  return VPL_OK;
+}
+
+// 9. the k_marg variant: kept blocks of up to 48 dims (the one-wave factorisations) whose workspace fits 79 KB take 256
+// threads, two work-groups per CU
+static int choose_marg(vpl_ctx* c, const Span<int>& mg_n, size_t W) {
+  const DevBatch& B = c->B;
+  int nmax = 0;
+  for (size_t w = 0; w < W; ++w) nmax = std::max(nmax, mg_n[w]);
+  c->marg_small = nmax <= 48 && B.maxP <= 256 && B.maxL <= 256 &&
+                  (size_t)marg_layout(nmax, true).total * sizeof(double) <= MARG_LDS_SMALL && std::getenv("VPL_BA_MARG_BIG") == nullptr;
+  c->marg_smem = (size_t)marg_layout(nmax, c->marg_small).total * sizeof(double);
+  if (c->marg_smem > 159 * 1024) return fail(c, VPL_E_CAPACITY, "marginalisation workspace exceeds LDS");
+  return VPL_OK;
+}
+
+// the first max-over-the-batch rounds of every window's point work units, packed into the arena (rounds a window does not use
+// travel too: idle lanes, empty slots)
+static void pack_units(Stage& S, UploadArena& A, size_t W, int maxPR, const int* lane, const int* sub) {
+  int rmax = 0;
+  for (size_t w = 0; w < W; ++w) rmax = std::max(rmax, A.pu_cnt[w]);
+  take_units(S, A, W, rmax);
+  for (size_t w = 0; w < A.pu_lane.size(); ++w) {
+    int* l = A.pu_lane[w].p;
+    int* u = A.pu_sub[w].p;
+    std::memcpy(l, lane + w * maxPR * 1024, (size_t)A.pu_cnt[w] * 4096);
+    std::memcpy(u, sub + w * maxPR * 512, (size_t)A.pu_cnt[w] * 2048);
+    std::fill(l + (size_t)A.pu_cnt[w] * 1024, l + (size_t)rmax * 1024, -1);
+    std::fill(u + (size_t)A.pu_cnt[w] * 512, u + (size_t)rmax * 512, 0);
+  }
+}
+
+// 10. chained upload: the values of the priors move device to device, before the upload's scatter overwrites mg_* with the
+// next solve's tables
+static int hand_over_priors(vpl_ctx* c, const std::vector<HostTab>& ctab, int prev_prS) {
+  const DevBatch& B = c->B;
+  const int nW = (int)ctab.size();
+  std::vector<int> keep(nW);
+  for (int w = 0; w < nW; ++w) keep[w] = ctab[w].keep ? 1 : 0;
+  DevBuf dkeep;
+  HIPCHK(c, dkeep.alloc(nW * 4));
+  HIPCHK(c, hipMemcpyAsync(dkeep.p, keep.data(), nW * 4, hipMemcpyHostToDevice, c->stream));
+  if (B.prS != prev_prS && std::any_of(keep.begin(), keep.end(), [](int k) { return k != 0; })) {
+    // windows that keep their prior (MARGIN_SECOND_NEW pass-through) have J0 at the PREVIOUS batch stride: move them through
+    // a scratch copy (old and new locations of different windows overlap) -- ADVICE r3
+    DevBuf tmp;
+    HIPCHK(c, tmp.alloc(nW * (size_t)MAXPN * MAXPN * 8));
+    hipLaunchKernelGGL(k_prior_restride, dim3(nW), dim3(256), 0, c->stream, B, (const int*)dkeep.p, prev_prS, tmp.d(), 0);
+    hipLaunchKernelGGL(k_prior_restride, dim3(nW), dim3(256), 0, c->stream, B, (const int*)dkeep.p, prev_prS, tmp.d(), 1);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  hipLaunchKernelGGL(k_prior_handoff, dim3(nW), dim3(256), 0, c->stream, B, (const int*)dkeep.p);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return VPL_OK;
+}
+
+static int upload_body(vpl_ctx* c, int nW, const vpl_window* win, const vpl_ba_options* opt, bool all_lines, bool chained) {
+  int rc = upload_check(c, nW, win, opt, chained);
+  if (rc) return rc;
   const int prev_prS = c->B.prS;
   c->prior_resident = false;
   if (c->leg_timing) HIPCHK(c, hipEventRecord(c->leg_ev[0], c->stream));
   drop_graph(c);
-  c->upload_open = true;
+  c->upload_open = true;   // from here on a refusal leaves the context with no batch (upload_impl)
   c->opt = *opt;
   c->nW = nW;
   DevBatch& B = c->B;
@@ -711,80 +1117,9 @@ static int upload_body(vpl_ctx* c, int nW, const vpl_window* win, const vpl_ba_o
   B.opt.sqrt_info_vp = opt->vp_factor;
   B.opt.g_norm = opt->g_norm;
   B.opt.huber_delta = opt->huber_delta;
-
   const size_t W = nW;
-  // Every array that travels is packed straight into the context's pinned arena (Stage); the bound below is the sum of the
-  // pieces taken from it (+ 64-byte alignment per piece, + the segment table).
-  Stage& SG = c->stage;
-  {
-    size_t j0 = 0;
-    if (!chained)
-      for (size_t w = 0; w < W; ++w)
-        if (win[w].has_prior && win[w].prior && win[w].prior->n > 0 && win[w].prior->n <= MAXPN) j0 += (size_t)win[w].prior->n * win[w].prior->n * 8 + 64;
-    const size_t dbl = 77 + 99 + 7 + B.maxP + 6 * B.maxL + 3 * B.maxPO + 8 * B.maxLO + 13 + 4 * B.maxL + 9 * MAXPB + MAXPN;
-    const size_t ints = 2 + 3 * B.maxP + 4 * B.maxL + 2 + 4 * B.maxKS + 8 * SK_WSTRIDE + 1 + 1 + B.maxLO + 2 * B.llSlots + 1 + B.maxP + (NF + 1) +
-                        1 + 2 + 3 * MAXPB + 2 + 4 * MAXPB + 1 + 1 + B.maxPR * 1536;
-    const size_t perW = dbl * 8 + ints * 4 + NF * sizeof(DevPreint);
-    const size_t need = W * perW + j0 + 96 * 64 + (96 + 4 * W) * sizeof(CopySeg) + 4096;
-    HIPCHK(c, SG.reserve(need));
-  }
-  Span<double> pose = SG.take<double>(W * 77), sb = SG.take<double>(W * 99), ex = SG.take<double>(W * 7), invd = SG.take<double>(W * B.maxP, 1.0),
-               plk = SG.take<double>(W * B.maxL * 6, 0.0);
-  Span<int> nP = SG.take<int>(W), nL = SG.take<int>(W), pt_start = SG.take<int>(W * B.maxP, 0), pt_nobs = SG.take<int>(W * B.maxP, 0),
-            pt_off = SG.take<int>(W * B.maxP, 0);
-  Span<int> ln_start = SG.take<int>(W * B.maxL, 0), ln_nobs = SG.take<int>(W * B.maxL, 0), ln_off = SG.take<int>(W * B.maxL, 0),
-            ln_tri = SG.take<int>(W * B.maxL, 1);
-  // (plain heap, no value-initialisation: only the rounds a window uses are filled; the used rounds are packed into the arena
-  // after the loop)
-  std::unique_ptr<int[]> pu_lane(new int[W * B.maxPR * 1024]), pu_sub(new int[W * B.maxPR * 512]);
-  Span<int> pu_cnt = SG.take<int>(W, 0), pu_cnt0 = SG.take<int>(W, 0);
-  Span<int> sk_tab = SG.take<int>(W * B.maxKS * 4, 0), sk_wave = SG.take<int>(W * 8 * SK_WSTRIDE, -1), path = SG.take<int>(W, 0);
-  Span<int> nLO = SG.take<int>(W, 0), lo_ln = SG.take<int>(W * B.maxLO, 0), ll_tab = SG.take<int>(W * B.llSlots * 2, -1), ll_np = SG.take<int>(W, 0);
-  Span<int> ps_list = SG.take<int>(W * B.maxP, 0), ps_cnt = SG.take<int>(W * (NF + 1), 0);
-  Span<double> pt_obs = SG.take<double>(W * B.maxPO * 3, 0.0), ln_obs = SG.take<double>(W * B.maxLO * 8, 0.0);
-  Span<DevPreint> pre = SG.take<DevPreint>(W * NF);
-  Span<double> fail_ref = SG.take<double>(W * 13, 0.0), orth = SG.take<double>(W * B.maxL * 4, 0.0);
-  Span<int> orth_in = SG.take<int>(W, 0);
-  Span<int> pr_n = SG.take<int>(W, 0), pr_nb = SG.take<int>(W, 0), pr_kind = SG.take<int>(W * MAXPB, 0), pr_frame = SG.take<int>(W * MAXPB, 0),
-            pr_idx = SG.take<int>(W * MAXPB, 0);
-  Span<double> pr_x0 = SG.take<double>(W * MAXPB * 9, 0.0), pr_r0 = SG.take<double>(W * MAXPN, 0.0);
-  Span<int> mg_n = SG.take<int>(W, 0), mg_nb = SG.take<int>(W, 0), mg_kind = SG.take<int>(W * MAXPB, 0), mg_frame = SG.take<int>(W * MAXPB, 0),
-            mg_idx = SG.take<int>(W * MAXPB, 0), mg_cam = SG.take<int>(W * MAXPB, 0);
-  if (SG.overflow) return fail(c, VPL_E_CAPACITY, "internal: staging arena bound too small");
-  // chained mode: window w takes the prior the context's previous solve left for window w (device resident); only its block
-  // table comes through the host
-  struct HostTab { int n = 0, nb = 0, kind[MAXPB], frame[MAXPB], idx[MAXPB]; };
   std::vector<HostTab> ctab;
-  std::vector<int> keep_prior(W, 0);
-  if (chained) {
-    ctab.resize(W);
-    std::vector<int> t_n(W), t_nb(W), t_kind(W * MAXPB), t_frame(W * MAXPB), t_idx(W * MAXPB), p_n(W), p_nb(W), p_kind(W * MAXPB),
-        p_frame(W * MAXPB), p_idx(W * MAXPB);
-    HIPCHK(c, hipMemcpyAsync(t_n.data(), B.mg_n, W * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(t_nb.data(), B.mg_nb, W * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(t_kind.data(), B.mg_kind, W * MAXPB * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(t_frame.data(), B.mg_frame, W * MAXPB * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(t_idx.data(), B.mg_idx, W * MAXPB * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(p_n.data(), B.pr_n, W * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(p_nb.data(), B.pr_nb, W * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(p_kind.data(), B.pr_kind, W * MAXPB * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(p_frame.data(), B.pr_frame, W * MAXPB * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(p_idx.data(), B.pr_idx, W * MAXPB * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (size_t w = 0; w < W; ++w) {
-      const bool keep = c->h_passthrough[w] >= 0;      // MARGIN_SECOND_NEW left this window's prior as it was
-      keep_prior[w] = keep ? 1 : 0;
-      HostTab& T = ctab[w];
-      T.n = keep ? p_n[w] : t_n[w];
-      T.nb = keep ? p_nb[w] : t_nb[w];
-      if (T.n < 0 || T.n > MAXPN || T.nb < 0 || T.nb > MAXPB) return fail(c, VPL_E_INVALID, "upload_chained: resident prior table out of range");
-      for (int b = 0; b < T.nb; ++b) {
-        T.kind[b] = (keep ? p_kind : t_kind)[w * MAXPB + b];
-        T.frame[b] = (keep ? p_frame : t_frame)[w * MAXPB + b];
-        T.idx[b] = (keep ? p_idx : t_idx)[w * MAXPB + b];
-      }
-    }
-  }
+  if (chained && (rc = read_resident_priors(c, W, ctab))) return rc;
   c->h_mg_m.assign(W, 0);
   c->maxPriorN = 0;
   c->h_passthrough.assign(W, -1);
@@ -793,315 +1128,36 @@ static int upload_body(vpl_ctx* c, int nW, const vpl_window* win, const vpl_ba_o
   c->h_nP.assign(W, 0);
   c->h_nL.assign(W, 0);
   c->h_lmap.resize(W);
-
-  {   // stride of the per-window prior matrices: the largest prior of the batch
-    int nmax = 1;
-    for (size_t w = 0; w < W; ++w) {
-      if (chained) nmax = std::max(nmax, ctab[w].n);
-      else if (win[w].has_prior && win[w].prior) nmax = std::max(nmax, win[w].prior->n);
-    }
-    if (nmax > MAXPN) return fail(c, VPL_E_CAPACITY, "prior larger than MAXPN");
-    B.prS = (nmax * nmax + 7) & ~7;
-  }
-  // compact W rows: stride from the longest track of the batch; zero fill only where some slot has no writer
-  {
-    int maxTrack = 2, minTrack = NF;
-    for (size_t w = 0; w < W; ++w) {
-      for (int p = 0; p < win[w].n_points; ++p) { maxTrack = std::max(maxTrack, win[w].point_nobs[p]); minTrack = std::min(minTrack, win[w].point_nobs[p]); }
-      for (int l = 0; l < win[w].n_lines; ++l) { maxTrack = std::max(maxTrack, win[w].line_nobs[l]); minTrack = std::min(minTrack, win[w].line_nobs[l]); }
-    }
-    maxTrack = std::min(maxTrack, (int)NF);
-    B.WS = 6 * maxTrack + 6;
-    int maxLineTrack = 1;
-    for (size_t w = 0; w < W; ++w)
-      for (int l = 0; l < win[w].n_lines; ++l) maxLineTrack = std::max(maxLineTrack, std::min(win[w].line_nobs[l], (int)NF));
-    B.llK = maxLineTrack;
-    B.llNLW = 64 / maxLineTrack;
-    B.wfill = (minTrack != maxTrack || opt->remove_line_outliers) ? 1 : 0;
-  }
-
+  if ((rc = batch_strides(c, W, win, opt, chained ? ctab.data() : nullptr))) return rc;
+  const bool same_layout = layout_unchanged(c, W, win, all_lines);
+  // every array that travels is packed straight into the context's pinned arena
+  Stage& SG = c->stage;
+  HIPCHK(c, SG.reserve(upload_bound(B, W, win, same_layout, chained)));
+  UploadArena A;
+  take_upload(SG, A, B, W, win, chained);
+  // (plain heap, no value-initialisation: only the rounds a window uses are filled and packed into the arena)
+  std::unique_ptr<int[]> lane(new int[W * B.maxPR * 1024]), sub(new int[W * B.maxPR * 512]);
   long schur_wide_w = 0, schur_total_w = 0;   // matrix-core weight of the wide entries / of all entries of k_schur's table
-  bool same_layout = false;
-  {
-    unsigned long long h = 1469598103934665603ull;
-    auto mix = [&](const void* p, size_t n) { const unsigned char* b = (const unsigned char*)p; for (size_t i = 0; i < n; ++i) { h ^= b[i]; h *= 1099511628211ull; } };
-    const int hdr[8] = {nW, B.WS, B.llK, B.llNLW, B.wfill, all_lines ? 1 : 0, B.maxP, B.maxL};
-    mix(hdr, sizeof(hdr));
-    for (size_t w = 0; w < W; ++w) {
-      const vpl_window& v = win[w];
-      mix(&v.n_points, 4); mix(&v.n_lines, 4);
-      if (v.n_points > 0 && v.point_start && v.point_nobs) { mix(v.point_start, 4 * (size_t)v.n_points); mix(v.point_nobs, 4 * (size_t)v.n_points); }
-      if (v.n_lines > 0 && v.line_start && v.line_nobs) { mix(v.line_start, 4 * (size_t)v.n_lines); mix(v.line_nobs, 4 * (size_t)v.n_lines); }
-      if (v.n_lines > 0 && v.line_triangulated) mix(v.line_triangulated, 4 * (size_t)v.n_lines);
-    }
-    // the hash only finds the candidate; the decision is an exact comparison of the hashed integers (a collision would reuse
-    // lane / unit / K-step tables of another track layout: out-of-range reads -- ADVICE r3)
-    std::vector<int> key;
-    key.reserve(16 + (size_t)W * 8);
-    key.insert(key.end(), hdr, hdr + 8);
-    for (size_t w = 0; w < W; ++w) {
-      const vpl_window& v = win[w];
-      key.push_back(v.n_points); key.push_back(v.n_lines);
-      const bool hp = v.n_points > 0 && v.point_start && v.point_nobs, hl = v.n_lines > 0 && v.line_start && v.line_nobs;
-      key.push_back((hp ? 1 : 0) | (hl ? 2 : 0) | ((v.n_lines > 0 && v.line_triangulated) ? 4 : 0));   // which arrays follow
-      if (hp) { key.insert(key.end(), v.point_start, v.point_start + v.n_points); key.insert(key.end(), v.point_nobs, v.point_nobs + v.n_points); }
-      if (hl) { key.insert(key.end(), v.line_start, v.line_start + v.n_lines); key.insert(key.end(), v.line_nobs, v.line_nobs + v.n_lines); }
-      if (v.n_lines > 0 && v.line_triangulated) key.insert(key.end(), v.line_triangulated, v.line_triangulated + v.n_lines);
-    }
-    same_layout = c->layout_valid && h == c->layout_sig && key == c->layout_key && std::getenv("VPL_BA_NO_LAYOUT_CACHE") == nullptr;
-    c->layout_sig = h;
-    c->layout_key.swap(key);
-    c->layout_valid = false;       // becomes valid when this upload has gone through
-  }
   for (size_t w = 0; w < W; ++w) {
-    const vpl_window& v = win[w];
-    if (v.n_points > B.maxP || v.n_lines > B.maxL) return fail(c, VPL_E_CAPACITY, "too many tracks for the context");
-    std::memcpy(&pose[w * 77], v.pose, 77 * 8);
-    std::memcpy(&sb[w * 99], v.speed_bias, 99 * 8);
-    std::memcpy(&ex[w * 7], v.ex_pose, 7 * 8);
-    if (v.failure_occur) {
-      fail_ref[w * 13] = 1.0;
-      std::memcpy(&fail_ref[w * 13 + 1], v.last_P0, 3 * 8);
-      std::memcpy(&fail_ref[w * 13 + 4], v.last_R0, 9 * 8);
-    }
-    nP[w] = v.n_points;
-    c->h_nP[w] = v.n_points;
-    int off = 0;
-    for (int p = 0; p < v.n_points; ++p) {
-      const int s = v.point_start[p], no = v.point_nobs[p];
-      if (s < 0 || no < 2 || s + no > NF) return fail(c, VPL_E_INVALID, "point track outside the window");
-      if (off + no > B.maxPO) return fail(c, VPL_E_CAPACITY, "too many point observations");
-      pt_start[w * B.maxP + p] = s; pt_nobs[w * B.maxP + p] = no; pt_off[w * B.maxP + p] = off;
-      std::memcpy(&pt_obs[(w * B.maxPO + off) * 3], v.point_obs + (size_t)off * 3, (size_t)no * 3 * 8);
-      invd[w * B.maxP + p] = v.inv_depth[p];
-      off += no;
-    }
-    if (!same_layout) {   // counting sort of the point tracks by start frame
-      int cnt[NF + 1] = {0};
-      for (int p = 0; p < v.n_points; ++p) cnt[v.point_start[p] + 1]++;
-      for (int f = 0; f < NF; ++f) cnt[f + 1] += cnt[f];
-      for (int f = 0; f <= NF; ++f) ps_cnt[w * (NF + 1) + f] = cnt[f];
-      int pos[NF + 1];
-      for (int f = 0; f <= NF; ++f) pos[f] = cnt[f];
-      for (int p = 0; p < v.n_points; ++p) ps_list[w * B.maxP + pos[v.point_start[p]]++] = p;
-      // inside a start frame the longer tracks come first: the tracks observed at index k are then a prefix of the list
-      for (int f = 0; f < NF; ++f)
-        std::stable_sort(&ps_list[w * B.maxP + cnt[f]], &ps_list[w * B.maxP + cnt[f + 1]],
-                         [&](int a, int b) { return v.point_nobs[a] > v.point_nobs[b]; });
-      // work units of the point phase of k_lin and their commit tickets (ba_pack.h)
-      PointUnitLayout PL;
-      if (!pack_point_units(v.point_nobs, &pt_off[w * B.maxP], &ps_list[w * B.maxP], cnt, B.maxPR, &pu_lane[w * B.maxPR * 1024],
-                            &pu_sub[w * B.maxPR * 512], &PL))
-        return fail(c, VPL_E_CAPACITY, "point work-unit table too small");
-      pu_cnt[w] = PL.rounds;
-      pu_cnt0[w] = PL.rounds0;
-      // a pass that waited for a ticket owned by a unit it never runs would spin forever on the device: replay both chains
-      if (!point_unit_chains_finish(&pu_sub[w * B.maxPR * 512], PL, false) || !point_unit_chains_finish(&pu_sub[w * B.maxPR * 512], PL, true))
-        return fail(c, VPL_E_INVALID, "internal: commit-ticket order of the point work units is not executable");
-    }
-    off = 0;
-    int woff = 0, nl = 0;
-    std::vector<int>& lmap = c->h_lmap[w];
-    lmap.clear();
-    for (int l = 0; l < v.n_lines; ++l) {
-      const int s = v.line_start[l], no = v.line_nobs[l];
-      if (s < 0 || no < 1 || s + no > NF) return fail(c, VPL_E_INVALID, "line track outside the window");
-      const int tri_flag = (!v.line_triangulated || v.line_triangulated[l]) ? 1 : 0;
-      // lines that are not triangulated take no part in the solves (estimator.cpp:1133); they travel only for
-      // vpl_ba_triangulate_lines
-      if (all_lines || tri_flag) {
-        if (off + no > B.maxLO) return fail(c, VPL_E_CAPACITY, "too many line observations");
-        const size_t dl = w * B.maxL + nl;
-        ln_start[dl] = s; ln_nobs[dl] = no; ln_off[dl] = off; ln_tri[dl] = tri_flag;
-        std::memcpy(&ln_obs[(w * B.maxLO + off) * 8], v.line_obs + (size_t)woff * 8, (size_t)no * 8 * 8);
-        if (v.line_orth) std::memcpy(&orth[dl * 4], v.line_orth + (size_t)l * 4, 4 * 8);
-        else std::memcpy(&plk[dl * 6], v.line_plk + (size_t)l * 6, 6 * 8);
-        for (int k = 0; k < no; ++k) lo_ln[w * B.maxLO + off + k] = nl;
-        off += no;
-        lmap.push_back(l);
-        ++nl;
-      }
-      woff += no;
-    }
-    nL[w] = nl;
-    if (!same_layout) {   // K-steps of k_schur: landmark rows by start frame, dealt to the waves, flush tickets (ba_pack.h)
-      int cnt[NF + 1];
-      for (int f = 0; f <= NF; ++f) cnt[f] = ps_cnt[w * (NF + 1) + f];
-      // rows wider than the 6-frame view of k_schur<3>: entries with a longer track are flagged wide (k_schur_mixed)
-      if (pack_schur_ksteps(v.n_points, &ps_list[w * B.maxP], cnt, nl, &ln_start[w * B.maxL], B.maxKS, &sk_tab[w * B.maxKS * 4],
-                            &sk_wave[w * 8 * SK_WSTRIDE], SCHUR_THREADS / 64, v.point_nobs, &ln_nobs[w * B.maxL],
-                            B.WS + 2 > 48 ? SCHUR_NARROW_FRAMES : 0, &schur_wide_w, &schur_total_w) < 0)
-        return fail(c, VPL_E_CAPACITY, "K-step table of the landmark elimination too small");
-    }
-    if (!same_layout) {   // lane layout of the line phase: llNLW whole tracks per wave, k-major; tracks in the caller's order (tracks that start
-        // in the same frame side by side would pile their LDS adds onto the same addresses)
-      std::vector<int> ord(nl);
-      for (int i = 0; i < nl; ++i) ord[i] = i;
-      const int NLW = B.llNLW, perPass = 8 * NLW;
-      ll_np[w] = (nl + perPass - 1) / perPass;
-      if (ll_np[w] * 512 > B.llSlots) return fail(c, VPL_E_CAPACITY, "line layout table too small");
-      for (int q = 0; q < nl; ++q) {
-        const int dl = ord[q], pass = q / perPass, wave = (q % perPass) / NLW, i = q % NLW;
-        const int no = std::min(ln_nobs[w * B.maxL + dl], (int)NF);
-        for (int k = 0; k < no; ++k) {      // (observation, line | k << 16 | start frame << 20): everything a lane's loads need
-          int* e = &ll_tab[2 * ((size_t)w * B.llSlots + pass * 512 + wave * 64 + k * NLW + i)];
-          e[0] = ln_off[w * B.maxL + dl] + k;
-          e[1] = dl | k << 16 | ln_start[w * B.maxL + dl] << 20;
-        }
-      }
-    }
-    orth_in[w] = v.line_orth ? 1 : 0;
-    c->h_nL[w] = nl;
-    nLO[w] = off;
-    for (int j = 0; j < NF; ++j) to_dev_preint(v.preint[j], pre[w * NF + j]);
-    if (chained) {
-      const HostTab& T = ctab[w];
-      pr_n[w] = T.n; pr_nb[w] = T.nb;
-      c->maxPriorN = std::max(c->maxPriorN, T.n);
-      for (int b = 0; b < T.nb; ++b) {
-        pr_kind[w * MAXPB + b] = T.kind[b]; pr_frame[w * MAXPB + b] = T.frame[b]; pr_idx[w * MAXPB + b] = T.idx[b];
-        if (T.kind[b] == 1 && T.frame[b] != 0) path[w] = 1;
-      }
-    } else if (v.has_prior && v.prior) {
-      const vpl_prior& pr = *v.prior;
-      if (pr.n < 0 || pr.n > MAXPN || pr.n_blocks < 0 || pr.n_blocks > MAXPB) return fail(c, VPL_E_INVALID, "bad prior");
-      pr_n[w] = pr.n; pr_nb[w] = pr.n_blocks;
-      // k_chol's elimination order keeps speed/bias 0 in its dense part; a prior that ties another frame's speed/bias block
-      // (never produced by the reference's marginalisation) takes the general path
-      for (int b = 0; b < pr.n_blocks; ++b)
-        if (pr.block_kind[b] == 1 && pr.block_frame[b] != 0) path[w] = 1;
-      c->maxPriorN = std::max(c->maxPriorN, pr.n);
-      for (int b = 0; b < pr.n_blocks; ++b) {
-        pr_kind[w * MAXPB + b] = pr.block_kind[b];
-        pr_frame[w * MAXPB + b] = pr.block_frame[b];
-        pr_idx[w * MAXPB + b] = pr.block_idx[b];
-        std::memcpy(&pr_x0[(w * MAXPB + b) * 9], pr.x0[b], 9 * 8);
-        if (pr.block_kind[b] < 0 || pr.block_kind[b] > 2 || pr.block_frame[b] < 0 || pr.block_frame[b] >= NF)
-          return fail(c, VPL_E_INVALID, "bad prior block");
-      }
-      std::memcpy(&pr_r0[w * MAXPN], pr.r0, (size_t)pr.n * 8);
-      if (pr.n > 0) {
-        Span<double> j0 = SG.take<double>((size_t)pr.n * pr.n);
-        if (SG.overflow) return fail(c, VPL_E_CAPACITY, "internal: staging arena bound too small");
-        std::memcpy(j0.p, pr.J0, (size_t)pr.n * pr.n * 8);
-        SG.to_device(B.pr_J0 + w * (size_t)B.prS, j0.p, j0.n);
-      }
-    }
-    // kept blocks of the next prior in the canonical (address) order of the reference's para_* layout
-    {
-      int* kd = &mg_kind[w * MAXPB]; int* fr = &mg_frame[w * MAXPB]; int* ix = &mg_idx[w * MAXPB]; int* cm = &mg_cam[w * MAXPB];
-      const int pnb = chained ? ctab[w].nb : ((v.has_prior && v.prior) ? v.prior->n_blocks : 0);
-      const int* pk = pnb ? (chained ? ctab[w].kind : v.prior->block_kind) : nullptr;
-      const int* pf = pnb ? (chained ? ctab[w].frame : v.prior->block_frame) : nullptr;
-      c->h_passthrough[w] = -1;
-      if (opt->marginalization_flag == VPL_MARGIN_OLD) {
-        KeepSrc S;
-        S.nP = v.n_points; S.pt_start = v.point_start; S.pt_nobs = v.point_nobs;
-        S.nL = nL[w]; S.ln_start = &ln_start[w * B.maxL]; S.ln_nobs = &ln_nobs[w * B.maxL]; S.ln_removed = nullptr;
-        S.pr_nb = pnb; S.pr_kind = pk; S.pr_frame = pf;
-        S.imu01 = v.preint[1].sum_dt < 10.0;
-        int mm = 0;
-        keep_tables_old(S, kd, fr, ix, cm, &mg_n[w], &mg_nb[w], &mm);
-        c->h_mg_m[w] = mm;
-      } else if (opt->marginalization_flag == VPL_MARGIN_SECOND_NEW) {
-        const int rc = pnb ? keep_tables_second_new(pnb, pk, pf, kd, fr, ix, cm, &mg_n[w], &mg_nb[w]) : 0;
-        if (rc < 0) return fail(c, VPL_E_INVALID, "MARGIN_SECOND_NEW: the prior holds the speed/bias of frame WINDOW_SIZE-1");
-        if (rc == 1) { c->h_mg_m[w] = 6; c->any_second_new = true; }
-        else if (pnb) {   // the reference leaves last_marginalization_info as it is (estimator.cpp:1385)
-          c->h_passthrough[w] = (int)c->h_pass_priors.size();
-          if (chained) {    // the prior lives on the device only: the pass-through entry carries its table (download refetches the rest)
-            vpl_prior hp;
-            std::memset(&hp, 0, sizeof(int) * (2 + 3 * VPL_MAX_PRIOR_BLOCKS));
-            hp.n = -1;      // marker: not available on the host
-            c->h_pass_priors.push_back(hp);
-          } else {
-            c->h_pass_priors.push_back(*v.prior);
-          }
-        }
-      }
-      if (mg_n[w] > MAXKEEP) return fail(c, VPL_E_CAPACITY, "marginalisation keeps more than MAXKEEP dims");
-    }
+    const HostTab* T = chained ? &ctab[w] : nullptr;
+    if ((rc = pack_window(c, A, w, win[w], all_lines))) return rc;
+    if (!same_layout &&
+        (rc = build_layout(c, A, w, win[w], &lane[w * B.maxPR * 1024], &sub[w * B.maxPR * 512], &schur_wide_w, &schur_total_w)))
+      return rc;
+    if ((rc = pack_prior(c, A, w, win[w], T))) return rc;
+    if ((rc = keep_blocks(c, A, w, win[w], T))) return rc;
   }
-  {
-    int nmax = 0;
-    for (size_t w = 0; w < W; ++w) nmax = std::max(nmax, mg_n[w]);
-    // kept blocks of up to 48 dims (the one-wave factorisations) whose workspace fits 79 KB: 256 threads, two work-groups per CU
-    c->marg_small = nmax <= 48 && B.maxP <= 256 && B.maxL <= 256 &&
-                    (size_t)marg_layout(nmax, true).total * sizeof(double) <= MARG_LDS_SMALL && std::getenv("VPL_BA_MARG_BIG") == nullptr;
-    c->marg_smem = (size_t)marg_layout(nmax, c->marg_small).total * sizeof(double);
-    if (c->marg_smem > 159 * 1024) return fail(c, VPL_E_CAPACITY, "marginalisation workspace exceeds LDS");
-  }
-  HIPCHK(c, up(c, B.pose, pose)); HIPCHK(c, up(c, B.sb, sb)); HIPCHK(c, up(c, B.ex, ex)); HIPCHK(c, up(c, B.invd, invd));
-  HIPCHK(c, up(c, B.plk, plk)); HIPCHK(c, up(c, B.fail_ref, fail_ref)); HIPCHK(c, up(c, B.orth_in, orth_in));
-  HIPCHK(c, up(c, B.orth, orth));
-  HIPCHK(c, up(c, B.pose_0, pose)); HIPCHK(c, up(c, B.sb_0, sb)); HIPCHK(c, up(c, B.ex_0, ex)); HIPCHK(c, up(c, B.invd_0, invd));
-  HIPCHK(c, up(c, B.plk_0, plk));
-  HIPCHK(c, up(c, B.pt_obs, pt_obs));
-  if (!same_layout) {
-  HIPCHK(c, up(c, B.nP, nP)); HIPCHK(c, up(c, B.nL, nL));
-  HIPCHK(c, up(c, B.pt_start, pt_start)); HIPCHK(c, up(c, B.pt_nobs, pt_nobs)); HIPCHK(c, up(c, B.pt_off, pt_off));
-  HIPCHK(c, up(c, B.ps_list, ps_list)); HIPCHK(c, up(c, B.ps_cnt, ps_cnt));
-  {   // the first max-over-the-batch rounds of every window, packed into the arena
-    int rmax = 0;
-    for (size_t q = 0; q < W; ++q) rmax = std::max(rmax, pu_cnt[q]);
-    if (rmax > 0) {
-      Span<int> pl = SG.take<int>(W * (size_t)rmax * 1024), psb = SG.take<int>(W * (size_t)rmax * 512);
-      if (SG.overflow) return fail(c, VPL_E_CAPACITY, "internal: staging arena bound too small");
-      for (size_t q = 0; q < W; ++q) {   // rounds a window does not use travel too: idle lanes, empty slots
-        int* l = pl.p + q * (size_t)rmax * 1024;
-        int* u = psb.p + q * (size_t)rmax * 512;
-        std::memcpy(l, &pu_lane[q * B.maxPR * 1024], (size_t)pu_cnt[q] * 4096);
-        std::memcpy(u, &pu_sub[q * B.maxPR * 512], (size_t)pu_cnt[q] * 2048);
-        std::fill(l + (size_t)pu_cnt[q] * 1024, l + (size_t)rmax * 1024, -1);
-        std::fill(u + (size_t)pu_cnt[q] * 512, u + (size_t)rmax * 512, 0);
-        SG.to_device(B.pu_lane + q * (size_t)B.maxPR * 1024, l, (size_t)rmax * 1024);
-        SG.to_device(B.pu_sub + q * (size_t)B.maxPR * 512, u, (size_t)rmax * 512);
-      }
-    }
-  } HIPCHK(c, up(c, B.pu_cnt, pu_cnt)); HIPCHK(c, up(c, B.pu_cnt0, pu_cnt0));
-  HIPCHK(c, up(c, B.ln_start, ln_start)); HIPCHK(c, up(c, B.ln_nobs, ln_nobs)); HIPCHK(c, up(c, B.ln_off, ln_off));
-  HIPCHK(c, up(c, B.nLO, nLO)); HIPCHK(c, up(c, B.lo_ln, lo_ln));
-  HIPCHK(c, up(c, B.ll_tab, ll_tab)); HIPCHK(c, up(c, B.ll_np, ll_np));
-  HIPCHK(c, up(c, B.sk_tab, sk_tab)); HIPCHK(c, up(c, B.sk_wave, sk_wave));
-  }
-  HIPCHK(c, up(c, B.ln_obs, ln_obs)); HIPCHK(c, up(c, B.ln_tri, ln_tri));
-  HIPCHK(c, up(c, B.pre, pre));
-  HIPCHK(c, up(c, B.pr_n, pr_n)); HIPCHK(c, up(c, B.pr_nb, pr_nb)); HIPCHK(c, up(c, B.pr_kind, pr_kind));
-  HIPCHK(c, up(c, B.pr_frame, pr_frame)); HIPCHK(c, up(c, B.pr_idx, pr_idx));
-  if (!chained) { HIPCHK(c, up(c, B.pr_x0, pr_x0)); HIPCHK(c, up(c, B.pr_r0, pr_r0)); }
-  else {
-    // values of the priors: device to device, before the scatter below overwrites mg_* with the next solve's tables
-    DevBuf dkeep;
-    HIPCHK(c, dkeep.alloc(W * 4));
-    HIPCHK(c, hipMemcpyAsync(dkeep.p, keep_prior.data(), W * 4, hipMemcpyHostToDevice, c->stream));
-    if (B.prS != prev_prS && std::any_of(keep_prior.begin(), keep_prior.end(), [](int k) { return k != 0; })) {
-      // windows that keep their prior (MARGIN_SECOND_NEW pass-through) have J0 at the PREVIOUS batch stride: move them through
-      // a scratch copy (old and new locations of different windows overlap) -- ADVICE r3
-      DevBuf tmp;
-      HIPCHK(c, tmp.alloc(W * (size_t)MAXPN * MAXPN * 8));
-      hipLaunchKernelGGL(k_prior_restride, dim3(nW), dim3(256), 0, c->stream, B, (const int*)dkeep.p, prev_prS, tmp.d(), 0);
-      hipLaunchKernelGGL(k_prior_restride, dim3(nW), dim3(256), 0, c->stream, B, (const int*)dkeep.p, prev_prS, tmp.d(), 1);
-      HIPCHK(c, hipGetLastError());
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    hipLaunchKernelGGL(k_prior_handoff, dim3(nW), dim3(256), 0, c->stream, B, (const int*)dkeep.p);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-  }
-  HIPCHK(c, up(c, B.mg_n, mg_n)); HIPCHK(c, up(c, B.mg_nb, mg_nb)); HIPCHK(c, up(c, B.mg_kind, mg_kind));
-  HIPCHK(c, up(c, B.mg_frame, mg_frame)); HIPCHK(c, up(c, B.mg_idx, mg_idx)); HIPCHK(c, up(c, B.mg_cam, mg_cam));
-  {
-    Span<int> mm = SG.take<int>(W);
-    if (SG.overflow) return fail(c, VPL_E_CAPACITY, "internal: staging arena bound too small");
-    std::memcpy(mm.p, c->h_mg_m.data(), W * 4);
-    HIPCHK(c, up(c, B.mg_m, mm));
-  }
-  c->h_mg_n.assign(mg_n.begin(), mg_n.end());
+  if ((rc = choose_marg(c, A.mg_n, W))) return rc;
+  if (!same_layout) pack_units(SG, A, W, B.maxPR, lane.get(), sub.get());
+  std::memcpy(A.mg_m.p, c->h_mg_m.data(), W * 4);
+  c->h_mg_n.assign(A.mg_n.begin(), A.mg_n.end());
   // k_schur_mixed pays five passes over the rows of a wide entry: measured (tools/bench_tracks.py, 512 windows) 0.52 ms per step
   // with a tenth of the point tracks long, 3.2 ms with every track long, against 1.5 - 1.65 ms of k_schur<5> either way
   if (!same_layout) c->schur_mostly_wide = schur_total_w > 0 && 20 * schur_wide_w > 7 * schur_total_w;
-  if (c->force_general) std::fill(path.begin(), path.end(), 1);
-  HIPCHK(c, up(c, B.path, path));
+  if (c->force_general) std::fill(A.path.begin(), A.path.end(), 1);
+  if (SG.overflow) return fail(c, VPL_E_CAPACITY, "internal: staging arena bound too small");
+  stage_upload(SG, A, B, W, same_layout, chained);
+  if (chained && (rc = hand_over_priors(c, ctab, prev_prS))) return rc;
   // ONE host-to-device copy of the arena, ONE kernel that scatters its pieces into the batch's arrays
   HIPCHK(c, stage_run(c, true));
   if (c->leg_timing) HIPCHK(c, hipEventRecord(c->leg_ev[1], c->stream));
@@ -1109,18 +1165,35 @@ static int upload_body(vpl_ctx* c, int nW, const vpl_window* win, const vpl_ba_o
   c->layout_valid = true;
   return VPL_OK;
 }
+// An upload that is refused half way (a track outside the window in the third window, a prior of impossible size) has already
+// rewritten part of the batch's host tables and its size: the context then holds NO batch -- solve / download / reset return
+// VPL_E_INVALID until the next successful upload -- instead of running the new size on the old device data.  A refusal before
+// anything was touched (too many windows, unknown flag, no resident prior for a chained upload) leaves the previous batch as it was.
+static int upload_impl(vpl_ctx* c, int nW, const vpl_window* win, const vpl_ba_options* opt, bool all_lines, bool chained = false) {
+  const int rc = upload_body(c, nW, win, opt, all_lines, chained);
+  if (c) {
+    if (rc != VPL_OK && c->upload_open) { c->nW = 0; c->prior_resident = false; }
+    c->upload_open = false;
+  }
+  return rc;
+}
 
-int vpl_ba_reset_state(vpl_ctx* c) {
-  if (c) { const int rs = settle(c); if (rs) return rs; }
-  if (!c || c->nW < 1) return VPL_E_INVALID;
-  DevBatch& B = c->B;
+// the states of the uploaded batch back to what the upload put there (pose, sb, ex, invd and, with `plk`, the lines)
+static int restore_states(vpl_ctx* c, bool plk) {
+  const DevBatch& B = c->B;
   const size_t W = c->nW;
   HIPCHK(c, hipMemcpyAsync(B.pose, B.pose_0, W * 77 * 8, hipMemcpyDeviceToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(B.sb, B.sb_0, W * 99 * 8, hipMemcpyDeviceToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(B.ex, B.ex_0, W * 7 * 8, hipMemcpyDeviceToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(B.invd, B.invd_0, W * B.maxP * 8, hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(B.plk, B.plk_0, W * B.maxL * 6 * 8, hipMemcpyDeviceToDevice, c->stream));
+  if (plk) HIPCHK(c, hipMemcpyAsync(B.plk, B.plk_0, W * B.maxL * 6 * 8, hipMemcpyDeviceToDevice, c->stream));
   return VPL_OK;
+}
+
+int vpl_ba_reset_state(vpl_ctx* c) {
+  if (c) { const int rs = settle(c); if (rs) return rs; }
+  if (!c || c->nW < 1) return VPL_E_INVALID;
+  return restore_states(c, true);
 }
 
 int vpl_ba_upload(vpl_ctx* c, int nW, const vpl_window* win, const vpl_ba_options* opt) {
@@ -1130,11 +1203,33 @@ int vpl_ba_upload_chained(vpl_ctx* c, int nW, const vpl_window* win, const vpl_b
   return upload_impl(c, nW, win, opt, false, true);
 }
 
-// FeatureManager::triangulateLine for a batch: upload (every line), k_triangulate, flags + Pluecker vectors back
-static int triangulate_lines_impl(vpl_ctx* c, int nW, vpl_window* win, bool async) {
-  if (!c || !win || nW < 1) return VPL_E_INVALID;
-  for (int w = 0; w < nW; ++w)
-    if (win[w].n_lines > 0 && !win[w].line_triangulated) return fail(c, VPL_E_INVALID, "line_triangulated is required");
+// k_prep: whitening matrices, q <- Quaterniond(R(q)), the world orth of the lines and J0^T J0 of the incoming prior
+static void launch_prep(vpl_ctx* c, const DevBatch& B, int nw, hipStream_t s) {
+  KTimer t(c, "k_prep");
+  hipLaunchKernelGGL(k_prep, dim3(nw), dim3(PREP_THREADS), prep_smem(c->maxPriorN), s, B, std::min(c->maxPriorN, PREP_NMAX));
+}
+// the marginalisation of the uploaded flag: k_lin<1|2> linearises its factor subset at the current states, k_marg eliminates
+// and factors the kept block.  Nothing runs for MARGIN_NONE, nor for MARGIN_SECOND_NEW when every window passes its prior through.
+static void launch_marg(vpl_ctx* c, DevBatch& B, int nw, hipStream_t s) {
+  const bool old = c->opt.marginalization_flag == VPL_MARGIN_OLD;
+  if (!old && !c->any_second_new) return;
+  const dim3 grid(nw);
+  { KTimer t(c, "k_lin_marg");
+    if (old) hipLaunchKernelGGL(k_lin<1>, grid, dim3(LIN_THREADS), lin_smem(c->maxP, c->maxL), s, B);
+    else hipLaunchKernelGGL(k_lin<2>, grid, dim3(LIN_THREADS), lin_smem(c->maxP, c->maxL), s, B); }
+  ++B.launch;
+  { KTimer t(c, "k_marg");
+    if (c->marg_small) hipLaunchKernelGGL(k_marg<256>, grid, dim3(256), c->marg_smem, s, B);
+    else hipLaunchKernelGGL(k_marg<MARG_THREADS>, grid, dim3(MARG_THREADS), c->marg_smem, s, B); }
+}
+// FeatureManager::triangulate (points: k_triangulate_points, inverse depths back) and / or ::triangulateLine (lines:
+// k_triangulate, flags + Pluecker vectors back) for a batch, on ONE upload with every line (the two touch different arrays:
+// what solveOdometry's two threads start with)
+static int triangulate_impl(vpl_ctx* c, int nW, vpl_window* win, bool points, bool lines, double init_depth, bool async) {
+  if (!c || !win || nW < 1 || (points && !(init_depth > 0.0))) return VPL_E_INVALID;
+  if (lines)
+    for (int w = 0; w < nW; ++w)
+      if (win[w].n_lines > 0 && !win[w].line_triangulated) return fail(c, VPL_E_INVALID, "line_triangulated is required");
   vpl_ba_options opt;
   vpl_ba_default_options(&opt);
   opt.marginalization_flag = VPL_MARGIN_NONE;
@@ -1142,32 +1237,49 @@ static int triangulate_lines_impl(vpl_ctx* c, int nW, vpl_window* win, bool asyn
   if (rc) return rc;
   DevBatch& B = c->B;
   hipStream_t s = c->stream;
-  { KTimer t(c, "k_triangulate"); hipLaunchKernelGGL(k_triangulate, dim3(nW), dim3(128), 0, s, B); }
+  if (points) { KTimer t(c, "k_triangulate_points"); hipLaunchKernelGGL(k_triangulate_points, dim3(nW), dim3(128), 0, s, B, init_depth); }
+  if (lines) { KTimer t(c, "k_triangulate"); hipLaunchKernelGGL(k_triangulate, dim3(nW), dim3(128), 0, s, B); }
   HIPCHK(c, hipGetLastError());
   const size_t W = nW;
-  auto plk = std::make_shared<std::vector<double>>(W * B.maxL * 6);
-  auto tri = std::make_shared<std::vector<int>>(W * B.maxL);
-  HIPCHK(c, hipMemcpyAsync(plk->data(), B.plk, plk->size() * 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(tri->data(), B.ln_tri, tri->size() * 4, hipMemcpyDeviceToHost, s));
-  const int maxL = B.maxL;
-  return finish_or_defer(c, async, [c, win, W, plk, tri, maxL, s]() -> int {
+  struct Out { std::vector<double> invd, plk; std::vector<int> tri; };
+  auto out = std::make_shared<Out>();
+  if (points) {
+    out->invd.resize(W * B.maxP);
+    HIPCHK(c, hipMemcpyAsync(out->invd.data(), B.invd, out->invd.size() * 8, hipMemcpyDeviceToHost, s));
+  }
+  if (lines) {
+    out->plk.resize(W * B.maxL * 6);
+    out->tri.resize(W * B.maxL);
+    HIPCHK(c, hipMemcpyAsync(out->plk.data(), B.plk, out->plk.size() * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(out->tri.data(), B.ln_tri, out->tri.size() * 4, hipMemcpyDeviceToHost, s));
+  }
+  const int maxP = B.maxP, maxL = B.maxL;
+  return finish_or_defer(c, async, [c, win, W, out, points, lines, maxP, maxL, s]() -> int {
     HIPCHK(c, hipStreamSynchronize(s));
     for (size_t w = 0; w < W; ++w) {
       vpl_window& v = win[w];
-      const std::vector<int>& lmap = c->h_lmap[w];
-      for (size_t dl = 0; dl < lmap.size(); ++dl) {
-        const int l = lmap[dl];
-        if (!v.line_triangulated[l] && (*tri)[w * maxL + dl]) {
-          std::memcpy(v.line_plk + (size_t)l * 6, &(*plk)[(w * maxL + dl) * 6], 6 * 8);
+      if (points)
+        for (int p = 0; p < v.n_points; ++p) v.inv_depth[p] = out->invd[w * maxP + p];
+      if (lines) {
+        const int* tri = &out->tri[w * maxL];
+        scatter_lines(c, w, v, &out->plk[w * maxL * 6], [&](int dl, int l) {
+          if (v.line_triangulated[l] || !tri[dl]) return false;
           v.line_triangulated[l] = 1;
-        }
+          return true;
+        });
       }
     }
     return VPL_OK;
   });
 }
-int vpl_ba_triangulate_lines(vpl_ctx* c, int nW, vpl_window* win) { return triangulate_lines_impl(c, nW, win, false); }
-int vpl_ba_triangulate_lines_async(vpl_ctx* c, int nW, vpl_window* win) { return triangulate_lines_impl(c, nW, win, true); }
+int vpl_ba_triangulate_lines(vpl_ctx* c, int nW, vpl_window* win) { return triangulate_impl(c, nW, win, false, true, 0.0, false); }
+int vpl_ba_triangulate_lines_async(vpl_ctx* c, int nW, vpl_window* win) { return triangulate_impl(c, nW, win, false, true, 0.0, true); }
+int vpl_ba_triangulate_points(vpl_ctx* c, int nW, vpl_window* win, double init_depth) {
+  return triangulate_impl(c, nW, win, true, false, init_depth, false);
+}
+int vpl_ba_triangulate_points_async(vpl_ctx* c, int nW, vpl_window* win, double init_depth) {
+  return triangulate_impl(c, nW, win, true, false, init_depth, true);
+}
 
 // Estimator::slideWindow for a batch.  The list bookkeeping (start frames, dropped observations, erased tracks) is integer
 // work on the caller's arrays and is done here on the host; the re-anchoring arithmetic of removeBackShiftDepth runs in
@@ -1285,32 +1397,6 @@ int vpl_ba_slide_window_async(vpl_ctx* c, int nW, vpl_window* win, int flag, dou
   return slide_window_impl(c, nW, win, flag, init_depth, out, true);
 }
 
-// FeatureManager::triangulate for a batch: upload, k_triangulate_points, inverse depths back
-static int triangulate_points_impl(vpl_ctx* c, int nW, vpl_window* win, double init_depth, bool async) {
-  if (!c || !win || nW < 1 || !(init_depth > 0.0)) return VPL_E_INVALID;
-  vpl_ba_options opt;
-  vpl_ba_default_options(&opt);
-  opt.marginalization_flag = VPL_MARGIN_NONE;
-  int rc = upload_impl(c, nW, win, &opt, true);
-  if (rc) return rc;
-  DevBatch& B = c->B;
-  hipStream_t s = c->stream;
-  { KTimer t(c, "k_triangulate_points"); hipLaunchKernelGGL(k_triangulate_points, dim3(nW), dim3(128), 0, s, B, init_depth); }
-  HIPCHK(c, hipGetLastError());
-  const size_t W = nW;
-  auto invd = std::make_shared<std::vector<double>>(W * B.maxP);
-  HIPCHK(c, hipMemcpyAsync(invd->data(), B.invd, invd->size() * 8, hipMemcpyDeviceToHost, s));
-  const int maxP = B.maxP;
-  return finish_or_defer(c, async, [c, win, W, invd, maxP, s]() -> int {
-    HIPCHK(c, hipStreamSynchronize(s));
-    for (size_t w = 0; w < W; ++w)
-      for (int p = 0; p < win[w].n_points; ++p) win[w].inv_depth[p] = (*invd)[w * maxP + p];
-    return VPL_OK;
-  });
-}
-int vpl_ba_triangulate_points(vpl_ctx* c, int nW, vpl_window* win, double init_depth) { return triangulate_points_impl(c, nW, win, init_depth, false); }
-int vpl_ba_triangulate_points_async(vpl_ctx* c, int nW, vpl_window* win, double init_depth) { return triangulate_points_impl(c, nW, win, init_depth, true); }
-
 // Estimator::onlyLineOpt for a batch: upload (triangulated lines), k_prep (world orth of the lines), k_line_opt (the LM
 // loop), k_gauge (setLineOrth + removeLineOutlier; the gauge transform is the identity, the poses did not move)
 // solve_opt != nullptr (vpl_ba_solve_odometry): the upload is made with the options of the solve that FOLLOWS, so that the
@@ -1330,7 +1416,7 @@ static int only_line_opt_impl(vpl_ctx* c, int nW, vpl_window* win, const vpl_ba_
   B.opt.remove_line_outliers = opt.remove_line_outliers;
   const dim3 grid(nW);
   hipStream_t s = c->stream;
-  { KTimer t(c, "k_prep"); hipLaunchKernelGGL(k_prep, grid, dim3(PREP_THREADS), prep_smem(c->maxPriorN), s, B, std::min(c->maxPriorN, PREP_NMAX)); }
+  launch_prep(c, B, nW, s);
   {
     KTimer t(c, "k_line_opt");
     if (4 * c->maxL <= LOPT_THREADS) hipLaunchKernelGGL(k_line_opt<4>, grid, dim3(LOPT_THREADS), 0, s, B);
@@ -1351,25 +1437,15 @@ static int only_line_opt_impl(vpl_ctx* c, int nW, vpl_window* win, const vpl_ba_
     HIPCHK(c, hipStreamSynchronize(s));
     for (size_t w = 0; w < W; ++w) {
       vpl_window& v = win[w];
-      const std::vector<int>& lmap = c->h_lmap[w];
-      if (v.line_removed)
-        for (int l = 0; l < v.n_lines; ++l) v.line_removed[l] = 0;
       if (reports) std::memset(&reports[w], 0, sizeof(reports[w]));
-      if (lmap.size() < 4) continue;       // "if (feature_index < 3) return;" -- nothing is touched
-      for (size_t dl = 0; dl < lmap.size(); ++dl) {
-        const bool rem = (*removed)[w * maxL + dl] != 0;
-        if (!rem) std::memcpy(v.line_plk + (size_t)lmap[dl] * 6, &(*plk)[(w * maxL + dl) * 6], 6 * 8);
-        if (v.line_removed) v.line_removed[lmap[dl]] = rem ? 1 : 0;
-        if (reports) reports[w].n_lines_removed += rem ? 1 : 0;
+      if (c->h_lmap[w].size() < 4) {       // "if (feature_index < 3) return;" -- nothing is touched
+        if (v.line_removed) std::fill(v.line_removed, v.line_removed + v.n_lines, 0);
+        continue;
       }
+      const int nrem = scatter_solved_lines(c, w, v, &(*plk)[w * maxL * 6], &(*removed)[w * maxL]);
       if (reports) {
-        vpl_solve_report& r = reports[w];
-        const TrState& t = (*tr)[w];
-        r.iterations = t.iter;
-        r.num_successful_steps = t.num_successful;
-        r.termination = t.status == 1 ? 1 : t.status == 2 ? 2 : 0;
-        r.initial_cost = t.initial_cost;
-        r.final_cost = t.x_cost;
+        fill_report(reports[w], (*tr)[w]);
+        reports[w].n_lines_removed = nrem;
       }
     }
     return VPL_OK;
@@ -1389,9 +1465,9 @@ static void launch_solve(vpl_ctx* c, int w0, int nw, hipStream_t s) {
   // with kernel timing on, every launch also counts the windows that did work in it (vpl_ba_launch_profile)
   B.act = c->timing ? c->d_act : nullptr;
   B.launch = 0;
-  if (c->timing) { c->ltimes.clear(); hipMemsetAsync(c->d_act, 0, sizeof(int) * ACT_SLOTS * 4, s); }
+  if (c->timing) { c->ltimes.clear(); (void)hipMemsetAsync(c->d_act, 0, sizeof(int) * ACT_SLOTS * 4, s); }   // (counts only)
   const dim3 grid(nw);
-  { KTimer t(c, "k_prep"); hipLaunchKernelGGL(k_prep, grid, dim3(PREP_THREADS), prep_smem(c->maxPriorN), s, B, std::min(c->maxPriorN, PREP_NMAX)); }
+  launch_prep(c, B, nw, s);
   ++B.launch;
   { KTimer t(c, "k_lin"); hipLaunchKernelGGL(k_lin2, dim3(16 * ((nw + 7) / 8)), dim3(LIN_THREADS), lin_smem(c->maxP, c->maxL), s, B); }
   ++B.launch;
@@ -1423,15 +1499,7 @@ static void launch_solve(vpl_ctx* c, int w0, int nw, hipStream_t s) {
   B.ord_it = 0;
   { KTimer t(c, "k_gauge"); hipLaunchKernelGGL(k_gauge, grid, dim3(128), 0, s, B); }
   ++B.launch;
-  if (c->opt.marginalization_flag == VPL_MARGIN_OLD) {
-    { KTimer t(c, "k_lin_marg"); hipLaunchKernelGGL(k_lin<1>, grid, dim3(LIN_THREADS), lin_smem(c->maxP, c->maxL), s, B); }
-    ++B.launch;
-    { KTimer t(c, "k_marg"); if (c->marg_small) hipLaunchKernelGGL(k_marg<256>, grid, dim3(256), c->marg_smem, s, B); else hipLaunchKernelGGL(k_marg<MARG_THREADS>, grid, dim3(MARG_THREADS), c->marg_smem, s, B); }
-  } else if (c->any_second_new) {
-    { KTimer t(c, "k_lin_marg"); hipLaunchKernelGGL(k_lin<2>, grid, dim3(LIN_THREADS), lin_smem(c->maxP, c->maxL), s, B); }
-    ++B.launch;
-    { KTimer t(c, "k_marg"); if (c->marg_small) hipLaunchKernelGGL(k_marg<256>, grid, dim3(256), c->marg_smem, s, B); else hipLaunchKernelGGL(k_marg<MARG_THREADS>, grid, dim3(MARG_THREADS), c->marg_smem, s, B); }
-  }
+  launch_marg(c, B, nw, s);
 }
 
 // vpl_ba_solve: the kernel-per-phase sequence over the whole batch, asynchronous on the context's stream.
@@ -1454,7 +1522,7 @@ int vpl_ba_solve(vpl_ctx* c) {
       launch_solve(c, 0, c->nW, c->stream);
       HIPCHK(c, hipStreamEndCapture(c->stream, &graph));
       hipError_t e = hipGraphInstantiate(&c->graph_exec, graph, nullptr, nullptr, 0);
-      hipGraphDestroy(graph);
+      (void)hipGraphDestroy(graph);   // (the instance does not need it)
       if (e != hipSuccess) { c->graph_exec = nullptr; return fail(c, VPL_E_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e)); }
     }
     HIPCHK(c, hipGraphLaunch(c->graph_exec, c->stream));
@@ -1466,24 +1534,15 @@ int vpl_ba_solve(vpl_ctx* c) {
 }
 
 // priors of the last marginalisation (k_marg) of the uploaded batch -> host; mn[2 w] = m, mn[2 w + 1] = n.
-// Two steps around ONE device-to-host copy of the staging arena: plan (pieces of the arena + gather segments), then -- after
-// stage_run(c, false) and a stream synchronisation -- finish (scatter into the caller's vpl_prior structs).
+// Two steps around ONE device-to-host copy of the staging arena: plan (pieces of the arena + gather segments, a stage_plan), then
+// -- after stage_run(c, false) and a stream synchronisation -- finish (scatter into the caller's vpl_prior structs).
 struct PriorFetch {
   Span<int> mg_n, mg_nb, mg_kind, mg_frame, mg_idx, mg_m;
   Span<double> mg_x0, mg_r0;
   std::vector<Span<double>> J0;   // per window: the host-side bound of the kept dims, squared
 };
-static size_t prior_fetch_bytes(vpl_ctx* c, int nW) {
-  size_t b = (size_t)nW * ((3 + 3 * MAXPB) * 4 + (9 * MAXPB + MAXKEEP) * 8 + 64 + sizeof(CopySeg)) + 16 * 64;
-  for (int w = 0; w < nW; ++w) {
-    const int n = (size_t)w < c->h_mg_n.size() ? std::min(std::max(c->h_mg_n[w], 0), (int)MAXKEEP) : (int)MAXKEEP;
-    b += (size_t)n * n * 8;
-  }
-  return b;
-}
-static int prior_fetch_plan(vpl_ctx* c, int nW, PriorFetch& F) {
-  DevBatch& B = c->B;
-  Stage& S = c->stage;
+static void prior_fetch_plan(vpl_ctx* c, int nW, PriorFetch& F, Stage& S) {
+  const DevBatch& B = c->B;
   const size_t W = nW;
   F.mg_m = S.take<int>(W); F.mg_n = S.take<int>(W); F.mg_nb = S.take<int>(W);
   F.mg_kind = S.take<int>(W * MAXPB); F.mg_frame = S.take<int>(W * MAXPB); F.mg_idx = S.take<int>(W * MAXPB);
@@ -1498,8 +1557,6 @@ static int prior_fetch_plan(vpl_ctx* c, int nW, PriorFetch& F) {
     F.J0[w] = S.take<double>((size_t)n * n);
     S.from_device(F.J0[w].p, B.mg_J0 + w * (size_t)MAXKEEP * MAXKEEP, (size_t)n * n);
   }
-  if (S.overflow) return fail(c, VPL_E_CAPACITY, "internal: staging arena bound too small");
-  return VPL_OK;
 }
 static int prior_fetch_finish(vpl_ctx* c, int nW, const PriorFetch& F, vpl_prior* priors, std::vector<int>& mn) {
   DevBatch& B = c->B;
@@ -1544,10 +1601,9 @@ static int prior_fetch_finish(vpl_ctx* c, int nW, const PriorFetch& F, vpl_prior
   return VPL_OK;
 }
 static int fetch_priors(vpl_ctx* c, int nW, vpl_prior* priors, std::vector<int>& mn) {
-  HIPCHK(c, c->stage.reserve(prior_fetch_bytes(c, nW) + 4096));
   PriorFetch F;
-  int rc = prior_fetch_plan(c, nW, F);
-  if (rc) return rc;
+  auto plan = [&](Stage& S) { prior_fetch_plan(c, nW, F, S); };
+  HIPCHK(c, stage_plan(c->stage, plan));
   HIPCHK(c, stage_run(c, false));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return prior_fetch_finish(c, nW, F, priors, mn);
@@ -1573,23 +1629,25 @@ int vpl_ba_download(vpl_ctx* c, int nW, vpl_window* win, vpl_prior* priors, vpl_
   hipStream_t s = c->stream;
   if (c->leg_timing) HIPCHK(c, hipEventRecord(c->leg_ev[4], s));
   // one gather kernel into the device arena, ONE device-to-host copy into the pinned arena
-  Stage& S = c->stage;
-  HIPCHK(c, S.reserve(W * ((77 + 99 + 7 + B.maxP + 6 * B.maxL) * 8 + sizeof(TrState) + 4 + B.maxL * 4) + 16 * 64 + 16 * sizeof(CopySeg) +
-                      (marg ? prior_fetch_bytes(c, nW) : 0) + 4096));
-  Span<double> pose = S.take<double>(W * 77), sb = S.take<double>(W * 99), ex = S.take<double>(W * 7), invd = S.take<double>(W * B.maxP),
-               plk = S.take<double>(W * B.maxL * 6);
-  Span<TrState> tr = S.take<TrState>(W);
-  Span<int> mg_m = S.take<int>(W), removed = S.take<int>(W * B.maxL);
-  std::vector<int> mn;
-  S.from_device(pose.p, B.pose, W * 77); S.from_device(sb.p, B.sb, W * 99); S.from_device(ex.p, B.ex, W * 7);
-  S.from_device(invd.p, B.invd, W * B.maxP); S.from_device(plk.p, B.plk, W * B.maxL * 6); S.from_device(tr.p, B.tr, W);
-  S.from_device(mg_m.p, B.mg_m, W); S.from_device(removed.p, B.ln_removed, W * B.maxL);
+  Span<double> pose, sb, ex, invd, plk;
+  Span<TrState> tr;
+  Span<int> mg_m, removed;
   PriorFetch F;
-  if (marg) { const int rc = prior_fetch_plan(c, nW, F); if (rc) return rc; }
-  if (S.overflow) return fail(c, VPL_E_CAPACITY, "internal: staging arena bound too small");
+  auto plan = [&](Stage& S) {
+    pose = S.take<double>(W * 77); sb = S.take<double>(W * 99); ex = S.take<double>(W * 7); invd = S.take<double>(W * B.maxP);
+    plk = S.take<double>(W * B.maxL * 6);
+    tr = S.take<TrState>(W);
+    mg_m = S.take<int>(W); removed = S.take<int>(W * B.maxL);
+    S.from_device(pose.p, B.pose, W * 77); S.from_device(sb.p, B.sb, W * 99); S.from_device(ex.p, B.ex, W * 7);
+    S.from_device(invd.p, B.invd, W * B.maxP); S.from_device(plk.p, B.plk, W * B.maxL * 6); S.from_device(tr.p, B.tr, W);
+    S.from_device(mg_m.p, B.mg_m, W); S.from_device(removed.p, B.ln_removed, W * B.maxL);
+    if (marg) prior_fetch_plan(c, nW, F, S);
+  };
+  HIPCHK(c, stage_plan(c->stage, plan));
   HIPCHK(c, stage_run(c, false));
   if (c->leg_timing) HIPCHK(c, hipEventRecord(c->leg_ev[5], s));
   HIPCHK(c, hipStreamSynchronize(s));
+  std::vector<int> mn;
   if (marg) {
     const int rc = prior_fetch_finish(c, nW, F, priors, mn);
     if (rc) return rc;
@@ -1600,24 +1658,14 @@ int vpl_ba_download(vpl_ctx* c, int nW, vpl_window* win, vpl_prior* priors, vpl_
     std::memcpy(v.speed_bias, &sb[w * 99], 99 * 8);
     std::memcpy(v.ex_pose, &ex[w * 7], 7 * 8);
     for (int p = 0; p < v.n_points; ++p) v.inv_depth[p] = invd[w * B.maxP + p];
-    const std::vector<int>& lmap = c->h_lmap[w];
-    for (size_t dl = 0; dl < lmap.size(); ++dl)   // erased tracks keep the caller's value (they are gone from f_manager)
-      if (!removed[w * B.maxL + dl]) std::memcpy(v.line_plk + (size_t)lmap[dl] * 6, &plk[(w * B.maxL + dl) * 6], 6 * 8);
+    // erased tracks keep the caller's value (they are gone from f_manager)
+    const int nrem = scatter_solved_lines(c, w, v, &plk[w * B.maxL * 6], &removed[w * B.maxL]);
     if (reports) {
       vpl_solve_report& r = reports[w];
-      std::memset(&r, 0, sizeof(r));
-      r.iterations = tr[w].iter;
-      r.num_successful_steps = tr[w].num_successful;
-      r.termination = tr[w].status == 1 ? 1 : tr[w].status == 2 ? 2 : 0;
-      r.initial_cost = tr[w].initial_cost;
-      r.final_cost = tr[w].x_cost;
+      fill_report(r, tr[w]);
       r.prior_m = mg_m[w];
       r.prior_n = marg ? mn[2 * w + 1] : 0;
-      for (size_t dl = 0; dl < lmap.size(); ++dl) r.n_lines_removed += removed[w * B.maxL + dl] ? 1 : 0;
-    }
-    if (v.line_removed) {
-      for (int l = 0; l < v.n_lines; ++l) v.line_removed[l] = 0;
-      for (size_t dl = 0; dl < lmap.size(); ++dl) v.line_removed[lmap[dl]] = removed[w * B.maxL + dl] ? 1 : 0;
+      r.n_lines_removed = nrem;
     }
   }
   return VPL_OK;
@@ -1639,24 +1687,14 @@ static int marginalize_impl(vpl_ctx* c, int nW, const vpl_window* win, const vpl
   if (rc) return rc;
   DevBatch B = c->B;
   B.ord_it = 0; B.act = nullptr; B.launch = 0;
-  const dim3 grid(nW);
   hipStream_t s = c->stream;
   // no line of this call is erased (remove_line_outliers = 0 above): the flags k_lin<MARG> and k_marg read are written by
   // k_gauge, which runs in a solve only -- without this they would be those of the batch the context solved before
   HIPCHK(c, hipMemsetAsync(B.ln_removed, 0, (size_t)nW * B.maxL * sizeof(int), s));
-  // k_prep: whitening matrices, q <- Quaterniond(R(q)) and the world orth of the lines (the vector2double() the reference
-  // runs before it marginalises, estimator.cpp:1233), J0^T J0 of the incoming prior
-  { KTimer t(c, "k_prep"); hipLaunchKernelGGL(k_prep, grid, dim3(PREP_THREADS), prep_smem(c->maxPriorN), s, B, std::min(c->maxPriorN, PREP_NMAX)); }
-  bool ran = false;
-  if (marginalization_flag == VPL_MARGIN_OLD) {
-    { KTimer t(c, "k_lin_marg"); hipLaunchKernelGGL(k_lin<1>, grid, dim3(LIN_THREADS), lin_smem(c->maxP, c->maxL), s, B); }
-    ran = true;
-  } else if (c->any_second_new) {
-    { KTimer t(c, "k_lin_marg"); hipLaunchKernelGGL(k_lin<2>, grid, dim3(LIN_THREADS), lin_smem(c->maxP, c->maxL), s, B); }
-    ran = true;
-  }
+  // k_prep runs the vector2double() the reference runs before it marginalises (estimator.cpp:1233)
+  launch_prep(c, B, nW, s);
+  launch_marg(c, B, nW, s);   // (B.act is null: the launch counter it steps is not read)
   c->prior_resident = true; c->prior_resident_nW = nW;
-  if (ran) { KTimer t(c, "k_marg"); if (c->marg_small) hipLaunchKernelGGL(k_marg<256>, grid, dim3(256), c->marg_smem, s, B); else hipLaunchKernelGGL(k_marg<MARG_THREADS>, grid, dim3(MARG_THREADS), c->marg_smem, s, B); }
   HIPCHK(c, hipGetLastError());
   // (the priors are fetched from the device when the call completes: any later call on the context completes this one first)
   return finish_or_defer(c, async, [c, nW, priors, m_out, n_out]() -> int {
@@ -1690,42 +1728,6 @@ int vpl_ba_solve_windows(vpl_ctx* c, int nW, vpl_window* win, const vpl_ba_optio
   return vpl_ba_download(c, nW, win, priors, reports);
 }
 
-// f_manager.triangulate and f_manager.triangulateLine on ONE upload (both work on the window with every line, and touch
-// different arrays): what solveOdometry's two threads start with
-static int triangulate_points_and_lines(vpl_ctx* c, int nW, vpl_window* win, double init_depth) {
-  if (!(init_depth > 0.0)) return VPL_E_INVALID;
-  vpl_ba_options opt;
-  vpl_ba_default_options(&opt);
-  opt.marginalization_flag = VPL_MARGIN_NONE;
-  int rc = upload_impl(c, nW, win, &opt, true);
-  if (rc) return rc;
-  DevBatch& B = c->B;
-  hipStream_t s = c->stream;
-  { KTimer t(c, "k_triangulate_points"); hipLaunchKernelGGL(k_triangulate_points, dim3(nW), dim3(128), 0, s, B, init_depth); }
-  { KTimer t(c, "k_triangulate"); hipLaunchKernelGGL(k_triangulate, dim3(nW), dim3(128), 0, s, B); }
-  HIPCHK(c, hipGetLastError());
-  const size_t W = nW;
-  std::vector<double> invd(W * B.maxP), plk(W * B.maxL * 6);
-  std::vector<int> tri(W * B.maxL);
-  HIPCHK(c, hipMemcpyAsync(invd.data(), B.invd, invd.size() * 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(plk.data(), B.plk, plk.size() * 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(tri.data(), B.ln_tri, tri.size() * 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  for (size_t w = 0; w < W; ++w) {
-    vpl_window& v = win[w];
-    for (int p = 0; p < v.n_points; ++p) v.inv_depth[p] = invd[w * B.maxP + p];
-    const std::vector<int>& lmap = c->h_lmap[w];
-    for (size_t dl = 0; dl < lmap.size(); ++dl) {
-      const int l = lmap[dl];
-      if (!v.line_triangulated[l] && tri[w * B.maxL + dl]) {
-        std::memcpy(v.line_plk + (size_t)l * 6, &plk[(w * B.maxL + dl) * 6], 6 * 8);
-        v.line_triangulated[l] = 1;
-      }
-    }
-  }
-  return VPL_OK;
-}
-
 // Estimator::solveOdometry (estimator.cpp:624-648) for a batch, in one call: triangulate || (triangulateLine -> onlyLineOpt)
 // -> optimizationwithLine.  The two line stages change WHICH lines take part (newly triangulated ones join, the ones
 // removeLineOutlier erases leave), and the lane / unit / K-step tables of the kernels are built on the host from that set: the
@@ -1742,7 +1744,7 @@ int vpl_ba_solve_odometry(vpl_ctx* c, int nW, vpl_window* win, const vpl_ba_opti
     }
   using oclk = std::chrono::steady_clock;
   const auto t0 = oclk::now();
-  int rc = any_lines ? triangulate_points_and_lines(c, nW, win, init_depth) : vpl_ba_triangulate_points(c, nW, win, init_depth);
+  int rc = triangulate_impl(c, nW, win, true, any_lines, init_depth, false);
   if (rc) return rc;
   const auto t1 = oclk::now();
   c->odo_ms[0] = std::chrono::duration<double, std::milli>(t1 - t0).count();
@@ -1769,13 +1771,8 @@ int vpl_ba_solve_odometry(vpl_ctx* c, int nW, vpl_window* win, const vpl_ba_opti
     // What a fresh upload of the caller's arrays would put on the device is there already: the layout tables, observations,
     // prior and kept-block tables of this very line set, the optimised Pluecker vectors (the caller's copy was downloaded
     // from B.plk), and -- after this restore -- the states k_prep re-normalised in place.  Same bits as the four-stage call.
-    DevBatch& B = c->B;
-    const size_t W = nW;
-    HIPCHK(c, hipMemcpyAsync(B.pose, B.pose_0, W * 77 * 8, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(B.sb, B.sb_0, W * 99 * 8, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(B.ex, B.ex_0, W * 7 * 8, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(B.invd, B.invd_0, W * B.maxP * 8, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(B.ln_removed, 0, W * B.maxL * 4, c->stream));
+    if ((rc = restore_states(c, false))) return rc;
+    HIPCHK(c, hipMemsetAsync(c->B.ln_removed, 0, (size_t)nW * c->B.maxL * 4, c->stream));
     rc = vpl_ba_solve(c);
     if (!rc) rc = vpl_ctx_synchronize(c);
     if (!rc) rc = vpl_ba_download(c, nW, win, priors, reports);
@@ -1807,21 +1804,7 @@ int vpl_ba_debug_marg_Ab(vpl_ctx* c, int w, double* A, double* b) {
 // Debug aid of the randomised sweeps (tools/fuzz_*.py with VPL_DEBUG_GUARDS=1 in the environment when the context is made): the
 // 64 bytes behind every device array then hold 0xA5; returns how many arrays have had theirs written to (a kernel ran past the
 // end of an array), the first one named in vpl_last_error by its allocation index and size.
-int vpl_ba_debug_guards(vpl_ctx* c) {
-  if (!c) return VPL_E_INVALID;
-  if (!c->guards) return 0;
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipDeviceSynchronize());
-  int bad = 0;
-  unsigned char pad[64];
-  for (size_t i = 0; i < c->allocs.size(); ++i) {
-    HIPCHK(c, hipMemcpy(pad, (char*)c->allocs[i] + c->alloc_bytes[i], 64, hipMemcpyDeviceToHost));
-    bool hit = false;
-    for (int k = 0; k < 64; ++k) hit |= pad[k] != 0xA5;
-    if (hit && !bad++) c->err = "guard behind device array #" + std::to_string(i) + " (" + std::to_string(c->alloc_bytes[i]) + " bytes) overwritten";
-  }
-  return bad;
-}
+int vpl_ba_debug_guards(vpl_ctx* c) { return debug_guards(c); }
 
 int vpl_ba_debug_stamps(vpl_ctx* c, int w, long long* out) {
   HIPCHK(c, hipMemcpy(out, c->B.dbg + (size_t)w * 64, 64 * 8, hipMemcpyDeviceToHost));
@@ -1833,19 +1816,13 @@ int vpl_ba_debug_point_units(int n_points, const int* point_start, const int* po
                              int* unit_table, int* rounds, int* rounds0) {
   if (n_points < 0 || !point_start || !point_nobs || !lane_table || !unit_table || !rounds || !rounds0 || max_rounds < 1) return VPL_E_INVALID;
   std::vector<int> off(n_points + 1, 0), list(n_points + 1, 0);
-  int cnt[NF + 1] = {0};
+  int cnt[NF + 1];
   int o = 0;
   for (int p = 0; p < n_points; ++p) {
     if (point_start[p] < 0 || point_nobs[p] < 2 || point_start[p] + point_nobs[p] > NF) return VPL_E_INVALID;
     off[p] = o; o += point_nobs[p];
-    cnt[point_start[p] + 1]++;
   }
-  for (int f = 0; f < NF; ++f) cnt[f + 1] += cnt[f];
-  int pos[NF + 1];
-  for (int f = 0; f <= NF; ++f) pos[f] = cnt[f];
-  for (int p = 0; p < n_points; ++p) list[pos[point_start[p]]++] = p;
-  for (int f = 0; f < NF; ++f)
-    std::stable_sort(&list[cnt[f]], &list[cnt[f + 1]], [&](int a, int b) { return point_nobs[a] > point_nobs[b]; });
+  sort_points_by_start(n_points, point_start, point_nobs, list.data(), cnt);
   PointUnitLayout PL;
   if (!pack_point_units(point_nobs, off.data(), list.data(), cnt, max_rounds, lane_table, unit_table, &PL)) return VPL_E_CAPACITY;
   *rounds = PL.rounds; *rounds0 = PL.rounds0;

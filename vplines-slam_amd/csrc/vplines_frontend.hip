@@ -10,6 +10,7 @@
 
 #include "vplines_ba.h"        // VPL_E_* codes
 #include "vplines_frontend.h"
+#include "host_common.h"
 #include "ed_kernels.h"
 #include "lm_kernels.h"
 #include "pre_kernels.h"
@@ -60,43 +61,21 @@ struct FeTimer {
   const char* name;
   hipEvent_t a = nullptr, b = nullptr;
   FeTimer(vpl_fe_ctx* c_, const char* n) : c(c_), name(n) {
-    if (c->timing) { hipEventCreate(&a); hipEventCreate(&b); hipEventRecord(a, c->stream); }
+    // (a timing aid: a failed event call leaves a time of 0 and nothing else)
+    if (c->timing) { (void)hipEventCreate(&a); (void)hipEventCreate(&b); (void)hipEventRecord(a, c->stream); }
   }
   ~FeTimer() {
     if (c->timing) {
-      hipEventRecord(b, c->stream);
-      hipEventSynchronize(b);
+      (void)hipEventRecord(b, c->stream);
+      (void)hipEventSynchronize(b);
       float ms = 0;
-      hipEventElapsedTime(&ms, a, b);
+      (void)hipEventElapsedTime(&ms, a, b);
       c->ktimes.emplace_back(name, (double)ms);
-      hipEventDestroy(a);
-      hipEventDestroy(b);
+      (void)hipEventDestroy(a);
+      (void)hipEventDestroy(b);
     }
   }
 };
-
-static int fe_fail(vpl_fe_ctx* c, int code, const std::string& m) {
-  if (c) c->err = m;
-  return code;
-}
-#define FECHK(ctx, call)                                                                                \
-  do {                                                                                                  \
-    hipError_t e__ = (call);                                                                            \
-    if (e__ != hipSuccess) return fe_fail(ctx, VPL_E_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
-  } while (0)
-
-template <typename T>
-static hipError_t fe_alloc(vpl_fe_ctx* c, T** p, size_t n) {
-  void* q = nullptr;
-  hipError_t e = hipMalloc(&q, n * sizeof(T) + 64);
-  if (e != hipSuccess) return e;
-  c->allocs.push_back(q);
-  c->alloc_bytes.push_back(n * sizeof(T));
-  *p = (T*)q;
-  e = hipMemset(q, 0, n * sizeof(T) + 64);
-  if (e == hipSuccess && c->guards) e = hipMemset((char*)q + n * sizeof(T), 0xA5, 64);
-  return e;
-}
 
 extern "C" {
 
@@ -155,7 +134,7 @@ int vpl_fe_create(vpl_fe_ctx** out, int device, int max_images, int width, int h
   const size_t N = max_images, PX = (size_t)width * height;
   hipError_t e = hipSuccess;
   uint8_t* img = nullptr;
-#define AL(ptr, n) if (e == hipSuccess) e = fe_alloc(c, &ptr, (size_t)(n))
+#define AL(ptr, n) if (e == hipSuccess) e = dalloc(c, &ptr, (size_t)(n))
   AL(img, N * PX); B.img = img;
   AL(B.dx, N * PX); AL(B.dy, N * PX); AL(B.g, N * PX); AL(B.dir, N * PX);
   B.Wc = (width + ED_TILE - 1) / ED_TILE * ED_TILE;
@@ -177,7 +156,7 @@ int vpl_fe_create(vpl_fe_ctx** out, int device, int max_images, int width, int h
     // walk is one wave; the strip then moves vertically as well, which the helper waves make cheap) -- measured below.
     {
       int ncu = 0;
-      hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device);
+      (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device);   // (unknown: 0, the default strip)
       const char* ev = std::getenv("VPL_FE_ROUTE_HS");
       int want = ev ? std::atoi(ev) : 0;
       if (!ev && ncu > 0 && max_images > ncu) {
@@ -198,7 +177,7 @@ int vpl_fe_create(vpl_fe_ctx** out, int device, int max_images, int width, int h
     if (e == hipSuccess) route_max = c->routeSmem;
   }
   if (e != hipSuccess) {
-    for (void* p : c->allocs) hipFree(p);
+    free_arrays(c);
     delete c;
     return e == hipErrorInvalidValue ? VPL_E_CAPACITY : VPL_E_HIP;
   }
@@ -208,15 +187,16 @@ int vpl_fe_create(vpl_fe_ctx** out, int device, int max_images, int width, int h
 
 void vpl_fe_destroy(vpl_fe_ctx* c) {
   if (!c) return;
-  hipSetDevice(c->device);
-  hipDeviceSynchronize();
-  for (void* p : c->allocs) hipFree(p);
+  // (teardown: a failure has nobody to be reported to)
+  (void)hipSetDevice(c->device);
+  (void)hipDeviceSynchronize();
+  free_arrays(c);
   delete c;
 }
 int vpl_fe_set_stream(vpl_fe_ctx* c, void* s) {
   if (!c) return VPL_E_INVALID;
   if (c->stream != (hipStream_t)s) {   // what was enqueued on the stream so far is completed first (downloads follow on the new one)
-    FECHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipSetDevice(c->device));
     (void)hipStreamSynchronize(c->stream);
     (void)hipGetLastError();
   }
@@ -236,31 +216,17 @@ int vpl_fe_kernel_times(vpl_fe_ctx* c, int* count, const char** names, double* m
   *count = n;
   return VPL_OK;
 }
-int vpl_fe_synchronize(vpl_fe_ctx* c) { if (!c) return VPL_E_INVALID; FECHK(c, hipStreamSynchronize(c->stream)); return VPL_OK; }
+int vpl_fe_synchronize(vpl_fe_ctx* c) { if (!c) return VPL_E_INVALID; HIPCHK(c, hipStreamSynchronize(c->stream)); return VPL_OK; }
 const char* vpl_fe_last_error(const vpl_fe_ctx* c) { return c ? c->err.c_str() : "null context"; }
 // Debug aid of the randomised sweeps (VPL_DEBUG_GUARDS=1 when the context is made: the 64 bytes behind every device array hold
 // 0xA5): how many arrays have had theirs written to; the first is named in vpl_fe_last_error.
-int vpl_fe_debug_guards(vpl_fe_ctx* c) {
-  if (!c) return VPL_E_INVALID;
-  if (!c->guards) return 0;
-  FECHK(c, hipSetDevice(c->device));
-  FECHK(c, hipDeviceSynchronize());
-  int bad = 0;
-  unsigned char pad[64];
-  for (size_t i = 0; i < c->allocs.size(); ++i) {
-    FECHK(c, hipMemcpy(pad, (char*)c->allocs[i] + c->alloc_bytes[i], 64, hipMemcpyDeviceToHost));
-    bool hit = false;
-    for (int k = 0; k < 64; ++k) hit |= pad[k] != 0xA5;
-    if (hit && !bad++) c->err = "guard behind device array #" + std::to_string(i) + " (" + std::to_string(c->alloc_bytes[i]) + " bytes) overwritten";
-  }
-  return bad;
-}
+int vpl_fe_debug_guards(vpl_fe_ctx* c) { return debug_guards(c); }
 
 int vpl_edlines_upload(vpl_fe_ctx* c, int n, const uint8_t* images) {
   if (!c || !images || n < 1) return VPL_E_INVALID;
-  if (n > c->maxN) return fe_fail(c, VPL_E_CAPACITY, "more images than max_images");
-  FECHK(c, hipSetDevice(c->device));
-  FECHK(c, hipMemcpyAsync((void*)c->B.img, images, (size_t)n * c->W * c->H, hipMemcpyHostToDevice, c->stream));
+  if (n > c->maxN) return fail(c, VPL_E_CAPACITY, "more images than max_images");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync((void*)c->B.img, images, (size_t)n * c->W * c->H, hipMemcpyHostToDevice, c->stream));
   c->n = n;
   c->B.N = n;
   return VPL_OK;
@@ -269,24 +235,24 @@ int vpl_edlines_upload(vpl_fe_ctx* c, int n, const uint8_t* images) {
 // ---- image preparation: cv::remap + CLAHE of LineFeatureTracker::readImage (line_feature_tracker.cpp:62-68) ----
 int vpl_pre_set_maps(vpl_fe_ctx* c, const float* map_x, const float* map_y) {
   if (!c || (map_x == nullptr) != (map_y == nullptr)) return VPL_E_INVALID;
-  FECHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipSetDevice(c->device));
   if (!map_x) { c->haveMaps = false; return VPL_OK; }
   const size_t PX = (size_t)c->W * c->H;
-  if (!c->d_mapx) { FECHK(c, fe_alloc(c, &c->d_mapx, PX)); FECHK(c, fe_alloc(c, &c->d_mapy, PX)); }
-  FECHK(c, hipMemcpyAsync(c->d_mapx, map_x, PX * 4, hipMemcpyHostToDevice, c->stream));
-  FECHK(c, hipMemcpyAsync(c->d_mapy, map_y, PX * 4, hipMemcpyHostToDevice, c->stream));
-  FECHK(c, hipStreamSynchronize(c->stream));   // the caller's maps may go away
+  if (!c->d_mapx) { HIPCHK(c, dalloc(c, &c->d_mapx, PX)); HIPCHK(c, dalloc(c, &c->d_mapy, PX)); }
+  HIPCHK(c, hipMemcpyAsync(c->d_mapx, map_x, PX * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->d_mapy, map_y, PX * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));   // the caller's maps may go away
   c->haveMaps = true;
   return VPL_OK;
 }
 
 int vpl_pre_upload(vpl_fe_ctx* c, int n, const uint8_t* raw) {
   if (!c || !raw || n < 1) return VPL_E_INVALID;
-  if (n > c->maxN) return fe_fail(c, VPL_E_CAPACITY, "more images than max_images");
-  FECHK(c, hipSetDevice(c->device));
+  if (n > c->maxN) return fail(c, VPL_E_CAPACITY, "more images than max_images");
+  HIPCHK(c, hipSetDevice(c->device));
   const size_t PX = (size_t)c->W * c->H;
-  if (!c->d_raw) { FECHK(c, fe_alloc(c, &c->d_raw, (size_t)c->maxN * PX)); FECHK(c, fe_alloc(c, &c->d_mid, (size_t)c->maxN * PX)); }
-  FECHK(c, hipMemcpyAsync(c->d_raw, raw, (size_t)n * PX, hipMemcpyHostToDevice, c->stream));
+  if (!c->d_raw) { HIPCHK(c, dalloc(c, &c->d_raw, (size_t)c->maxN * PX)); HIPCHK(c, dalloc(c, &c->d_mid, (size_t)c->maxN * PX)); }
+  HIPCHK(c, hipMemcpyAsync(c->d_raw, raw, (size_t)n * PX, hipMemcpyHostToDevice, c->stream));
   c->n = n;
   c->B.N = n;
   return VPL_OK;
@@ -294,8 +260,8 @@ int vpl_pre_upload(vpl_fe_ctx* c, int n, const uint8_t* raw) {
 
 int vpl_pre_run(vpl_fe_ctx* c, int equalize, double clip_limit, int tiles_x, int tiles_y) {
   if (!c || c->n < 1 || !c->d_raw) return VPL_E_INVALID;
-  if (equalize && (tiles_x < 1 || tiles_y < 1 || tiles_x > c->W || tiles_y > c->H)) return fe_fail(c, VPL_E_INVALID, "bad CLAHE grid");
-  FECHK(c, hipSetDevice(c->device));
+  if (equalize && (tiles_x < 1 || tiles_y < 1 || tiles_x > c->W || tiles_y > c->H)) return fail(c, VPL_E_INVALID, "bad CLAHE grid");
+  HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = c->stream;
   const size_t PX = (size_t)c->W * c->H;
   PreBatch P;
@@ -311,11 +277,11 @@ int vpl_pre_run(vpl_fe_ctx* c, int equalize, double clip_limit, int tiles_x, int
     hipLaunchKernelGGL(k_pre_remap, gpx, dim3(256), 0, s, P, dst);
     clahe_in = dst;
   } else if (!equalize) {
-    FECHK(c, hipMemcpyAsync(P.out, c->d_raw, (size_t)c->n * PX, hipMemcpyDeviceToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(P.out, c->d_raw, (size_t)c->n * PX, hipMemcpyDeviceToDevice, s));
   }
   if (equalize) {
     const int tiles = tiles_x * tiles_y;
-    if (tiles > c->lutTiles) { FECHK(c, fe_alloc(c, &c->d_lut, (size_t)c->maxN * tiles * 256)); c->lutTiles = tiles; }
+    if (tiles > c->lutTiles) { HIPCHK(c, dalloc(c, &c->d_lut, (size_t)c->maxN * tiles * 256)); c->lutTiles = tiles; }
     P.lut = c->d_lut;
     int extW = c->W, extH = c->H;
     if (c->W % tiles_x != 0 || c->H % tiles_y != 0) { extW += tiles_x - c->W % tiles_x; extH += tiles_y - c->H % tiles_y; }
@@ -327,15 +293,15 @@ int vpl_pre_run(vpl_fe_ctx* c, int equalize, double clip_limit, int tiles_x, int
     hipLaunchKernelGGL(k_pre_clahe_lut, dim3(tiles, c->n), dim3(256), 0, s, P, clahe_in);
     hipLaunchKernelGGL(k_pre_clahe_interp, gpx, dim3(256), 0, s, P, clahe_in);
   }
-  FECHK(c, hipGetLastError());
+  HIPCHK(c, hipGetLastError());
   return VPL_OK;
 }
 
 int vpl_pre_download(vpl_fe_ctx* c, int n, uint8_t* images) {
   if (!c || !images || n < 1 || n > c->n) return VPL_E_INVALID;
-  FECHK(c, hipSetDevice(c->device));
-  FECHK(c, hipMemcpyAsync(images, c->B.img, (size_t)n * c->W * c->H, hipMemcpyDeviceToHost, c->stream));
-  FECHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(images, c->B.img, (size_t)n * c->W * c->H, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return VPL_OK;
 }
 
@@ -397,8 +363,8 @@ int vpl_fe_set_blur_kernel(vpl_fe_ctx* c, int mode) {
 
 int vpl_fe_keep_blurred(vpl_fe_ctx* c, int enable) {
   if (!c) return VPL_E_INVALID;
-  FECHK(c, hipSetDevice(c->device));
-  if (enable && !c->d_blur) FECHK(c, fe_alloc(c, &c->d_blur, (size_t)c->maxN * c->W * c->H));
+  HIPCHK(c, hipSetDevice(c->device));
+  if (enable && !c->d_blur) HIPCHK(c, dalloc(c, &c->d_blur, (size_t)c->maxN * c->W * c->H));
   c->B.blurOut = enable ? c->d_blur : nullptr;
   return VPL_OK;
 }
@@ -406,8 +372,8 @@ int vpl_fe_keep_blurred(vpl_fe_ctx* c, int enable) {
 // EDLineDetector::EDline(image, lines, smoothed) for the uploaded batch (edline_detector.cpp:1176-1198 -> EdgeDrawing :81-710)
 int vpl_edlines_detect_ex(vpl_fe_ctx* c, const vpl_edline_param* p, int smoothed) {
   if (!c || !p || c->n < 1) return VPL_E_INVALID;
-  if (p->scanIntervals < 1 || p->minLineLen < 2) return fe_fail(c, VPL_E_INVALID, "bad EDLine parameters");
-  FECHK(c, hipSetDevice(c->device));
+  if (p->scanIntervals < 1 || p->minLineLen < 2) return fail(c, VPL_E_INVALID, "bad EDLine parameters");
+  HIPCHK(c, hipSetDevice(c->device));
   EdBatch& B = c->B;
   // member types of EDLineDetector: short gradienThreshold_, unsigned char anchorThreshold_ (edline_detector.h:113-117)
   B.gradTh = (int)(short)p->gradientThreshold;
@@ -417,18 +383,18 @@ int vpl_edlines_detect_ex(vpl_fe_ctx* c, const vpl_edline_param* p, int smoothed
   B.fitErr = p->lineFitErrThreshold;
   const int PX = c->W * c->H;
   hipStream_t s = c->stream;
-  FECHK(c, hipMemsetAsync(B.nLines, 0, c->n * sizeof(int), s));
+  HIPCHK(c, hipMemsetAsync(B.nLines, 0, c->n * sizeof(int), s));
   int ksz = 1;
   if (!smoothed) {   // cv::GaussianBlur(image, image_, cv::Size(ksize_, ksize_), sigma_), edline_detector.cpp:82-84
     ksz = gauss_kernel_q8(p->ksize, (double)p->sigma, c->blurMode, B.blurK, 2 * EDB_RMAX + 1);
-    if (ksz < 0) return fe_fail(c, VPL_E_INVALID, "Gaussian kernel size must be odd and at most 7");
-    if (c->W < 8 || c->H < 8) return fe_fail(c, VPL_E_INVALID, "frames smaller than 8 x 8 are not supported with smoothed = false");
+    if (ksz < 0) return fail(c, VPL_E_INVALID, "Gaussian kernel size must be odd and at most 7");
+    if (c->W < 8 || c->H < 8) return fail(c, VPL_E_INVALID, "frames smaller than 8 x 8 are not supported with smoothed = false");
     B.blurR = ksz / 2;
   }
   if (smoothed || ksz == 1) {   // a 1 x 1 kernel copies (GaussianBlur's early return)
     FeTimer t(c, "k_ed_grad");
     hipLaunchKernelGGL(k_ed_grad, dim3((PX + 255) / 256, c->n), dim3(256), 0, s, B);
-    if (!smoothed && B.blurOut) FECHK(c, hipMemcpyAsync(B.blurOut, B.img, (size_t)c->n * PX, hipMemcpyDeviceToDevice, s));
+    if (!smoothed && B.blurOut) HIPCHK(c, hipMemcpyAsync(B.blurOut, B.img, (size_t)c->n * PX, hipMemcpyDeviceToDevice, s));
   } else {
     FeTimer t(c, "k_ed_blur_grad");
     hipLaunchKernelGGL(k_ed_blur_grad, dim3((c->W + EDB_TW - 1) / EDB_TW, (c->H + EDB_TH - 1) / EDB_TH, c->n), dim3(256), 0, s, B);
@@ -437,14 +403,14 @@ int vpl_edlines_detect_ex(vpl_fe_ctx* c, const vpl_edline_param* p, int smoothed
     FeTimer t(c, "k_ed_anchor");
     const int nWs = (c->W - 2 + B.scan - 1) / B.scan, nHs = (c->H - 2 + B.scan - 1) / B.scan;
     const size_t abytes = (size_t)nWs * ((nHs + 31) / 32) * 4;
-    if (abytes > 60 * 1024) return fe_fail(c, VPL_E_CAPACITY, "anchor bitmask exceeds LDS (frame too large for this scanIntervals)");
+    if (abytes > 60 * 1024) return fail(c, VPL_E_CAPACITY, "anchor bitmask exceeds LDS (frame too large for this scanIntervals)");
     hipLaunchKernelGGL(k_ed_anchor, dim3(c->n), dim3(1024), abytes, s, B);
   }
   { FeTimer t(c, "k_ed_code"); hipLaunchKernelGGL(k_ed_code, dim3((PX + 255) / 256, c->n), dim3(256), 0, s, B); }
   { FeTimer t(c, "k_ed_route"); hipLaunchKernelGGL(k_ed_route, dim3(c->n), dim3(64 * ED_ROUTE_WAVES), c->routeSmem, s, B); }
   { FeTimer t(c, "k_ed_fit"); hipLaunchKernelGGL(k_ed_fit, dim3(ED_FIT_BLOCKS, c->n), dim3(64), 0, s, B); }
   { FeTimer t(c, "k_ed_sort_lines"); hipLaunchKernelGGL(k_ed_sort_lines, dim3(c->n), dim3(256), 0, s, B, c->d_sorted, c->d_sortedCnt, c->maxLines); }
-  FECHK(c, hipGetLastError());
+  HIPCHK(c, hipGetLastError());
   return VPL_OK;
 }
 
@@ -453,10 +419,10 @@ int vpl_edlines_detect(vpl_fe_ctx* c, const vpl_edline_param* p) { return vpl_ed
 
 int vpl_edlines_debug_blurred(vpl_fe_ctx* c, int img, uint8_t* out) {
   if (!c || !out || img < 0 || img >= c->n || !c->B.blurOut) return VPL_E_INVALID;
-  FECHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipSetDevice(c->device));
   const size_t PX = (size_t)c->W * c->H;
-  FECHK(c, hipMemcpyAsync(out, c->B.blurOut + img * PX, PX, hipMemcpyDeviceToHost, c->stream));
-  FECHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpyAsync(out, c->B.blurOut + img * PX, PX, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return VPL_OK;
 }
 
@@ -465,24 +431,24 @@ int vpl_edlines_debug_blurred(vpl_fe_ctx* c, int img, uint8_t* out) {
 // wherever it reaches the host: found[i] = lines the detector found in frame i.
 static int lines_overflow_check(vpl_fe_ctx* c, int n) {
   std::vector<int> found(n);
-  FECHK(c, hipMemcpyAsync(found.data(), c->B.nLines, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  FECHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpyAsync(found.data(), c->B.nLines, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   for (int i = 0; i < n; ++i)
     if (found[i] > c->maxLines)
-      return fe_fail(c, VPL_E_CAPACITY, "frame " + std::to_string(i) + ": " + std::to_string(found[i]) + " lines found, max_lines_per_image is " +
+      return fail(c, VPL_E_CAPACITY, "frame " + std::to_string(i) + ": " + std::to_string(found[i]) + " lines found, max_lines_per_image is " +
                                             std::to_string(c->maxLines));
   return VPL_OK;
 }
 
 int vpl_edlines_download(vpl_fe_ctx* c, int n, vpl_line* lines, int* counts) {
   if (!c || n != c->n || !lines || !counts) return VPL_E_INVALID;
-  FECHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipSetDevice(c->device));
   const size_t ML = c->maxLines;
   // (the deterministic order -- edge chain, ordinal inside the chain -- and the vpl_line layout are made on the device by
   // k_ed_sort_lines; rows beyond counts[i] are not defined)
-  FECHK(c, hipMemcpyAsync(counts, c->d_sortedCnt, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  FECHK(c, hipMemcpyAsync(lines, c->d_sorted, (size_t)n * ML * sizeof(vpl_line), hipMemcpyDeviceToHost, c->stream));
-  FECHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpyAsync(counts, c->d_sortedCnt, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(lines, c->d_sorted, (size_t)n * ML * sizeof(vpl_line), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return lines_overflow_check(c, n);
 }
 
@@ -505,62 +471,62 @@ int vpl_edlines_detect_batch(vpl_fe_ctx* c, int n, const uint8_t* images, const 
 // vpl_edlines_download and vpl_match_from_detected then see the filtered lists
 int vpl_line_filter_detected(vpl_fe_ctx* c, float distance_threshold, float parallel_threshold) {
   if (!c || c->n < 1) return VPL_E_INVALID;
-  if (c->maxLines > 8192) return fe_fail(c, VPL_E_INVALID, "LineFilter: max_lines_per_image above 8192");
-  FECHK(c, hipSetDevice(c->device));
+  if (c->maxLines > 8192) return fail(c, VPL_E_INVALID, "LineFilter: max_lines_per_image above 8192");
+  HIPCHK(c, hipSetDevice(c->device));
   FeTimer t(c, "k_lm_line_filter");
   hipLaunchKernelGGL(k_lm_line_filter, dim3(c->n), dim3(256), (size_t)c->maxLines * 8, c->stream, c->d_sorted, c->d_sortedCnt,
                      c->maxLines, distance_threshold, parallel_threshold);
-  FECHK(c, hipGetLastError());
+  HIPCHK(c, hipGetLastError());
   return VPL_OK;
 }
 
 // the same for caller-owned line lists [n][max_lines] (in / out), through the context's line table
 int vpl_line_filter_batch(vpl_fe_ctx* c, int n, vpl_line* lines, int* counts, float distance_threshold, float parallel_threshold) {
   if (!c || !lines || !counts || n < 1 || n > c->maxN) return VPL_E_INVALID;
-  if (c->maxLines > 8192) return fe_fail(c, VPL_E_INVALID, "LineFilter: max_lines_per_image above 8192");
+  if (c->maxLines > 8192) return fail(c, VPL_E_INVALID, "LineFilter: max_lines_per_image above 8192");
   for (int i = 0; i < n; ++i)
-    if (counts[i] < 0 || counts[i] > c->maxLines) return fe_fail(c, VPL_E_INVALID, "line count beyond max_lines_per_image");
-  FECHK(c, hipSetDevice(c->device));
+    if (counts[i] < 0 || counts[i] > c->maxLines) return fail(c, VPL_E_INVALID, "line count beyond max_lines_per_image");
+  HIPCHK(c, hipSetDevice(c->device));
   const size_t ML = c->maxLines;
-  FECHK(c, hipMemcpyAsync(c->d_sorted, lines, (size_t)n * ML * sizeof(vpl_line), hipMemcpyHostToDevice, c->stream));
-  FECHK(c, hipMemcpyAsync(c->d_sortedCnt, counts, n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->d_sorted, lines, (size_t)n * ML * sizeof(vpl_line), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->d_sortedCnt, counts, n * sizeof(int), hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(k_lm_line_filter, dim3(n), dim3(256), ML * 8, c->stream, c->d_sorted, c->d_sortedCnt, (int)ML,
                      distance_threshold, parallel_threshold);
-  FECHK(c, hipGetLastError());
-  FECHK(c, hipMemcpyAsync(counts, c->d_sortedCnt, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  FECHK(c, hipMemcpyAsync(lines, c->d_sorted, (size_t)n * ML * sizeof(vpl_line), hipMemcpyDeviceToHost, c->stream));
-  FECHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(counts, c->d_sortedCnt, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(lines, c->d_sorted, (size_t)n * ML * sizeof(vpl_line), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return VPL_OK;
 }
 
 int vpl_edlines_debug_stage(vpl_fe_ctx* c, int img, int16_t* dx, int16_t* dy, int16_t* g, uint8_t* dir, uint32_t* anchors,
                             int* n_anchors, uint32_t* chain_x, uint32_t* chain_y, uint32_t* sId, int* n_edges) {
   if (!c || img < 0 || img >= c->n) return VPL_E_INVALID;
-  FECHK(c, hipSetDevice(c->device));
-  FECHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   const EdBatch& B = c->B;
   const size_t PX = (size_t)c->W * c->H;
-  if (dx) FECHK(c, hipMemcpy(dx, B.dx + img * PX, PX * 2, hipMemcpyDeviceToHost));
-  if (dy) FECHK(c, hipMemcpy(dy, B.dy + img * PX, PX * 2, hipMemcpyDeviceToHost));
-  if (g) FECHK(c, hipMemcpy(g, B.g + img * PX, PX * 2, hipMemcpyDeviceToHost));
-  if (dir) FECHK(c, hipMemcpy(dir, B.dir + img * PX, PX, hipMemcpyDeviceToHost));
+  if (dx) HIPCHK(c, hipMemcpy(dx, B.dx + img * PX, PX * 2, hipMemcpyDeviceToHost));
+  if (dy) HIPCHK(c, hipMemcpy(dy, B.dy + img * PX, PX * 2, hipMemcpyDeviceToHost));
+  if (g) HIPCHK(c, hipMemcpy(g, B.g + img * PX, PX * 2, hipMemcpyDeviceToHost));
+  if (dir) HIPCHK(c, hipMemcpy(dir, B.dir + img * PX, PX, hipMemcpyDeviceToHost));
   int nA = 0, nE = 0;
-  FECHK(c, hipMemcpy(&nA, B.nAnch + img, 4, hipMemcpyDeviceToHost));
-  FECHK(c, hipMemcpy(&nE, B.nEdges + img, 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(&nA, B.nAnch + img, 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(&nE, B.nEdges + img, 4, hipMemcpyDeviceToHost));
   if (n_anchors) *n_anchors = nA;
   if (n_edges) *n_edges = nE;
   if (anchors) {
     std::vector<uint32_t> ax(nA), ay(nA);
-    FECHK(c, hipMemcpy(ax.data(), B.anchX + (size_t)img * B.cap, nA * 4, hipMemcpyDeviceToHost));
-    FECHK(c, hipMemcpy(ay.data(), B.anchY + (size_t)img * B.cap, nA * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(ax.data(), B.anchX + (size_t)img * B.cap, nA * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(ay.data(), B.anchY + (size_t)img * B.cap, nA * 4, hipMemcpyDeviceToHost));
     for (int i = 0; i < nA; ++i) { anchors[2 * i] = ax[i]; anchors[2 * i + 1] = ay[i]; }
   }
-  if (sId) FECHK(c, hipMemcpy(sId, B.sId + (size_t)img * (B.capEdges + 2), (nE + 1) * 4, hipMemcpyDeviceToHost));
+  if (sId) HIPCHK(c, hipMemcpy(sId, B.sId + (size_t)img * (B.capEdges + 2), (nE + 1) * 4, hipMemcpyDeviceToHost));
   if (chain_x && chain_y) {
     uint32_t npx = 0;
-    FECHK(c, hipMemcpy(&npx, B.sId + (size_t)img * (B.capEdges + 2) + nE, 4, hipMemcpyDeviceToHost));
-    FECHK(c, hipMemcpy(chain_x, B.cX + (size_t)img * 2 * B.cap, npx * 4, hipMemcpyDeviceToHost));
-    FECHK(c, hipMemcpy(chain_y, B.cY + (size_t)img * 2 * B.cap, npx * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&npx, B.sId + (size_t)img * (B.capEdges + 2) + nE, 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(chain_x, B.cX + (size_t)img * 2 * B.cap, npx * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(chain_y, B.cY + (size_t)img * 2 * B.cap, npx * 4, hipMemcpyDeviceToHost));
   }
   return VPL_OK;
 }
@@ -568,9 +534,9 @@ int vpl_edlines_debug_stage(vpl_fe_ctx* c, int img, int16_t* dx, int16_t* dy, in
 
 int vpl_edlines_debug_route_stats(vpl_fe_ctx* c, int img, unsigned long long* out4) {
   if (!c || img < 0 || img >= c->n || !out4) return VPL_E_INVALID;
-  FECHK(c, hipSetDevice(c->device));
-  FECHK(c, hipStreamSynchronize(c->stream));
-  FECHK(c, hipMemcpy(out4, c->B.rstats + (size_t)img * 4, 32, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(out4, c->B.rstats + (size_t)img * 4, 32, hipMemcpyDeviceToHost));
   return VPL_OK;
 }
 
@@ -585,9 +551,9 @@ void vpl_match_default_param(vpl_match_param* p) {
 
 int vpl_match_reserve(vpl_fe_ctx* c, int max_pairs, int max_kps) {
   if (!c || max_pairs < 1 || max_kps < 1) return VPL_E_INVALID;
-  if (c->lmReserved) return fe_fail(c, VPL_E_INVALID, "vpl_match_reserve called twice");
-  if (c->W <= LM_WIN || c->H <= LM_WIN) return fe_fail(c, VPL_E_INVALID, "image smaller than the KLT window");
-  FECHK(c, hipSetDevice(c->device));
+  if (c->lmReserved) return fail(c, VPL_E_INVALID, "vpl_match_reserve called twice");
+  if (c->W <= LM_WIN || c->H <= LM_WIN) return fail(c, VPL_E_INVALID, "image smaller than the KLT window");
+  HIPCHK(c, hipSetDevice(c->device));
   LmBatch& M = c->M;
   std::memset(&M, 0, sizeof(M));
   M.W = c->W; M.H = c->H; M.img = c->B.img;
@@ -609,7 +575,7 @@ int vpl_match_reserve(vpl_fe_ctx* c, int max_pairs, int max_kps) {
   c->maxPairs = max_pairs;
   const size_t N = c->maxN, P = max_pairs, ML = c->maxLines, MK = max_kps;
   hipError_t e = hipSuccess;
-#define AL(ptr, n) if (e == hipSuccess) e = fe_alloc(c, &ptr, (size_t)(n))
+#define AL(ptr, n) if (e == hipSuccess) e = dalloc(c, &ptr, (size_t)(n))
   AL(M.pyr, N * M.pyrSize); AL(M.der, N * M.pyrSize * 2);
   AL(c->d_refImg, P); AL(c->d_curImg, P); AL(c->d_nRef, P); AL(c->d_nCur, P);
   AL(c->d_linesRef, P * ML); AL(c->d_linesCur, P * ML);
@@ -617,7 +583,7 @@ int vpl_match_reserve(vpl_fe_ctx* c, int max_pairs, int max_kps) {
   AL(M.kpOff, P * ML); AL(M.kpNum, P * ML); AL(M.nK, P); AL(M.r2c, P * ML); AL(M.valid, P);
   AL(M.chunkOff, P + 1); AL(M.workCounter, 1); AL(M.winScratch, (size_t)LM_KLT_GRID * LM_NPX * 64);
 #undef AL
-  if (e != hipSuccess) return fe_fail(c, VPL_E_HIP, std::string("vpl_match_reserve: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return fail(c, VPL_E_HIP, std::string("vpl_match_reserve: ") + hipGetErrorString(e));
   M.refImg = c->d_refImg; M.curImg = c->d_curImg; M.nRef = c->d_nRef; M.nCur = c->d_nCur;
   M.linesRef = c->d_linesRef; M.linesCur = c->d_linesCur;
   c->lmReserved = true;
@@ -628,25 +594,25 @@ int vpl_match_upload(vpl_fe_ctx* c, int n_pairs, const int* ref_image, const int
                      const int* n_ref, const vpl_line* lines_cur, const int* n_cur) {
   if (!c || !c->lmReserved || n_pairs < 1 || !ref_image || !cur_image || !lines_ref || !n_ref || !lines_cur || !n_cur)
     return VPL_E_INVALID;
-  if (n_pairs > c->maxPairs) return fe_fail(c, VPL_E_CAPACITY, "more pairs than max_pairs");
-  if (c->n < 1) return fe_fail(c, VPL_E_INVALID, "no images uploaded");
+  if (n_pairs > c->maxPairs) return fail(c, VPL_E_CAPACITY, "more pairs than max_pairs");
+  if (c->n < 1) return fail(c, VPL_E_INVALID, "no images uploaded");
   c->matchFromDetected = false;
   for (int i = 0; i < n_pairs; ++i) {
     if (ref_image[i] < 0 || ref_image[i] >= c->n || cur_image[i] < 0 || cur_image[i] >= c->n)
-      return fe_fail(c, VPL_E_INVALID, "pair names an image that was not uploaded");
+      return fail(c, VPL_E_INVALID, "pair names an image that was not uploaded");
     if (n_ref[i] < 0 || n_ref[i] > c->maxLines || n_cur[i] < 0 || n_cur[i] > c->maxLines)
-      return fe_fail(c, VPL_E_CAPACITY, "more lines than max_lines_per_image");
+      return fail(c, VPL_E_CAPACITY, "more lines than max_lines_per_image");
   }
-  FECHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = c->stream;
   const size_t P = n_pairs, ML = c->maxLines;
-  FECHK(c, hipMemcpyAsync(c->d_refImg, ref_image, P * 4, hipMemcpyHostToDevice, s));
-  FECHK(c, hipMemcpyAsync(c->d_curImg, cur_image, P * 4, hipMemcpyHostToDevice, s));
-  FECHK(c, hipMemcpyAsync(c->d_nRef, n_ref, P * 4, hipMemcpyHostToDevice, s));
-  FECHK(c, hipMemcpyAsync(c->d_nCur, n_cur, P * 4, hipMemcpyHostToDevice, s));
-  FECHK(c, hipMemcpyAsync(c->d_linesRef, lines_ref, P * ML * sizeof(vpl_line), hipMemcpyHostToDevice, s));
-  FECHK(c, hipMemcpyAsync(c->d_linesCur, lines_cur, P * ML * sizeof(vpl_line), hipMemcpyHostToDevice, s));
-  FECHK(c, hipStreamSynchronize(s));   // the caller's buffers may be pageable and short-lived
+  HIPCHK(c, hipMemcpyAsync(c->d_refImg, ref_image, P * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(c->d_curImg, cur_image, P * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(c->d_nRef, n_ref, P * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(c->d_nCur, n_cur, P * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(c->d_linesRef, lines_ref, P * ML * sizeof(vpl_line), hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(c->d_linesCur, lines_cur, P * ML * sizeof(vpl_line), hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipStreamSynchronize(s));   // the caller's buffers may be pageable and short-lived
   c->nPairs = n_pairs;
   return VPL_OK;
 }
@@ -657,38 +623,38 @@ int vpl_match_upload(vpl_fe_ctx* c, int n_pairs, const int* ref_image, const int
 // detector's order).  Asynchronous on the context's stream.
 int vpl_match_from_detected(vpl_fe_ctx* c, int n_pairs, const int* ref_image, const int* cur_image, int max_lines) {
   if (!c || !c->lmReserved || n_pairs < 1 || !ref_image || !cur_image || max_lines < 1) return VPL_E_INVALID;
-  if (n_pairs > c->maxPairs) return fe_fail(c, VPL_E_CAPACITY, "more pairs than max_pairs");
-  if (c->n < 1) return fe_fail(c, VPL_E_INVALID, "no images uploaded");
+  if (n_pairs > c->maxPairs) return fail(c, VPL_E_CAPACITY, "more pairs than max_pairs");
+  if (c->n < 1) return fail(c, VPL_E_INVALID, "no images uploaded");
   for (int i = 0; i < n_pairs; ++i)
     if (ref_image[i] < 0 || ref_image[i] >= c->n || cur_image[i] < 0 || cur_image[i] >= c->n)
-      return fe_fail(c, VPL_E_INVALID, "pair names an image that was not uploaded");
+      return fail(c, VPL_E_INVALID, "pair names an image that was not uploaded");
   c->matchFromDetected = true;
-  FECHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = c->stream;
   const size_t P = n_pairs;
-  FECHK(c, hipMemcpyAsync(c->d_refImg, ref_image, P * 4, hipMemcpyHostToDevice, s));
-  FECHK(c, hipMemcpyAsync(c->d_curImg, cur_image, P * 4, hipMemcpyHostToDevice, s));
-  FECHK(c, hipStreamSynchronize(s));   // (two small index arrays; the caller's buffers may be short-lived)
+  HIPCHK(c, hipMemcpyAsync(c->d_refImg, ref_image, P * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(c->d_curImg, cur_image, P * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipStreamSynchronize(s));   // (two small index arrays; the caller's buffers may be short-lived)
   hipLaunchKernelGGL(k_lm_take_lines, dim3(n_pairs, 2), dim3(256), 0, s, c->d_sorted, c->d_sortedCnt, c->maxLines,
                      std::min(max_lines, c->maxLines), c->d_refImg, c->d_curImg, c->d_linesRef, c->d_linesCur, c->d_nRef, c->d_nCur);
-  FECHK(c, hipGetLastError());
+  HIPCHK(c, hipGetLastError());
   c->nPairs = n_pairs;
   return VPL_OK;
 }
 // number of lines of every pair's two frames that take part in the match (after vpl_match_upload / vpl_match_from_detected)
 int vpl_match_counts(vpl_fe_ctx* c, int n_pairs, int* n_ref, int* n_cur) {
   if (!c || !c->lmReserved || n_pairs != c->nPairs || !n_ref || !n_cur) return VPL_E_INVALID;
-  FECHK(c, hipSetDevice(c->device));
-  FECHK(c, hipMemcpyAsync(n_ref, c->d_nRef, n_pairs * 4, hipMemcpyDeviceToHost, c->stream));
-  FECHK(c, hipMemcpyAsync(n_cur, c->d_nCur, n_pairs * 4, hipMemcpyDeviceToHost, c->stream));
-  FECHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(n_ref, c->d_nRef, n_pairs * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(n_cur, c->d_nCur, n_pairs * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return VPL_OK;
 }
 
 int vpl_match_run(vpl_fe_ctx* c, const vpl_match_param* p) {
   if (!c || !p || !c->lmReserved || c->nPairs < 1) return VPL_E_INVALID;
-  if (p->step < 1) return fe_fail(c, VPL_E_INVALID, "bad LineMatching parameters");
-  FECHK(c, hipSetDevice(c->device));
+  if (p->step < 1) return fail(c, VPL_E_INVALID, "bad LineMatching parameters");
+  HIPCHK(c, hipSetDevice(c->device));
   LmBatch& M = c->M;
   M.N = c->n; M.nPairs = c->nPairs; M.prm = *p;
   double eps = std::min(std::max(0.001, 0.), 10.);   // TermCriteria(COUNT|EPS, 30, 0.001) through KLT::KLT, klt.cpp:28-33
@@ -703,22 +669,22 @@ int vpl_match_run(vpl_fe_ctx* c, const vpl_match_param* p) {
     hipLaunchKernelGGL(k_lm_plan, dim3(1), dim3(64), 0, s, M); }
   { FeTimer t(c, "k_lm_klt"); hipLaunchKernelGGL(k_lm_klt, dim3(LM_KLT_GRID), dim3(64), LM_KLT_SMEM, s, M); }
   { FeTimer t(c, "k_lm_vote"); hipLaunchKernelGGL(k_lm_vote, dim3(c->nPairs), dim3(256), (2 * M.maxLines + 1) * sizeof(int), s, M); }
-  FECHK(c, hipGetLastError());
+  HIPCHK(c, hipGetLastError());
   return VPL_OK;
 }
 
 int vpl_match_download(vpl_fe_ctx* c, int n_pairs, int* r2c, int* matched) {
   if (!c || !c->lmReserved || n_pairs != c->nPairs || !r2c || !matched) return VPL_E_INVALID;
-  FECHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipSetDevice(c->device));
   const size_t ML = c->maxLines;
   std::vector<int> valid(n_pairs), nref(n_pairs), buf((size_t)n_pairs * ML);
-  FECHK(c, hipMemcpyAsync(valid.data(), c->M.valid, n_pairs * 4, hipMemcpyDeviceToHost, c->stream));
-  FECHK(c, hipMemcpyAsync(nref.data(), c->d_nRef, n_pairs * 4, hipMemcpyDeviceToHost, c->stream));
-  FECHK(c, hipMemcpyAsync(buf.data(), c->M.r2c, buf.size() * 4, hipMemcpyDeviceToHost, c->stream));
-  FECHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpyAsync(valid.data(), c->M.valid, n_pairs * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(nref.data(), c->d_nRef, n_pairs * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(buf.data(), c->M.r2c, buf.size() * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   if (c->matchFromDetected) { const int ro = lines_overflow_check(c, c->n); if (ro) return ro; }
   for (int i = 0; i < n_pairs; ++i)
-    if (valid[i] < 0) return fe_fail(c, VPL_E_CAPACITY, "pair " + std::to_string(i) + ": more key points than max_kps");
+    if (valid[i] < 0) return fail(c, VPL_E_CAPACITY, "pair " + std::to_string(i) + ": more key points than max_kps");
   for (int i = 0; i < n_pairs; ++i) {
     matched[i] = valid[i];
     if (valid[i] == 1) std::memcpy(r2c + (size_t)i * ML, buf.data() + (size_t)i * ML, (size_t)nref[i] * 4);
@@ -743,50 +709,50 @@ int vpl_line_match_batch(vpl_fe_ctx* c, int n_images, const uint8_t* images, int
 int vpl_match_debug_kps(vpl_fe_ctx* c, int pair, int cap, float* kps_ref, float* kps_cur, uint8_t* status, float* err,
                         int* kp2line_cur, int* n_kps) {
   if (!c || !c->lmReserved || pair < 0 || pair >= c->nPairs) return VPL_E_INVALID;
-  FECHK(c, hipSetDevice(c->device));
-  FECHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   const LmBatch& M = c->M;
   int nk = 0;
-  FECHK(c, hipMemcpy(&nk, M.nK + pair, 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(&nk, M.nK + pair, 4, hipMemcpyDeviceToHost));
   if (n_kps) *n_kps = nk;
   const size_t m = (size_t)std::min(nk, cap), o = (size_t)pair * M.maxK;
   if (m == 0) return VPL_OK;
-  if (kps_ref) FECHK(c, hipMemcpy(kps_ref, M.kpsRef + o, m * 8, hipMemcpyDeviceToHost));
-  if (kps_cur) FECHK(c, hipMemcpy(kps_cur, M.kpsCur + o, m * 8, hipMemcpyDeviceToHost));
-  if (status) FECHK(c, hipMemcpy(status, M.status + o, m, hipMemcpyDeviceToHost));
-  if (err) FECHK(c, hipMemcpy(err, M.err + o, m * 4, hipMemcpyDeviceToHost));
-  if (kp2line_cur) FECHK(c, hipMemcpy(kp2line_cur, M.kp2lineCur + o, m * 4, hipMemcpyDeviceToHost));
+  if (kps_ref) HIPCHK(c, hipMemcpy(kps_ref, M.kpsRef + o, m * 8, hipMemcpyDeviceToHost));
+  if (kps_cur) HIPCHK(c, hipMemcpy(kps_cur, M.kpsCur + o, m * 8, hipMemcpyDeviceToHost));
+  if (status) HIPCHK(c, hipMemcpy(status, M.status + o, m, hipMemcpyDeviceToHost));
+  if (err) HIPCHK(c, hipMemcpy(err, M.err + o, m * 4, hipMemcpyDeviceToHost));
+  if (kp2line_cur) HIPCHK(c, hipMemcpy(kp2line_cur, M.kp2lineCur + o, m * 4, hipMemcpyDeviceToHost));
   return VPL_OK;
 }
 
 int vpl_match_debug_level(vpl_fe_ctx* c, int img, int level, uint8_t* pixels, int16_t* deriv, int* w, int* h) {
   if (!c || !c->lmReserved || img < 0 || img >= c->n || level < 0 || level >= c->M.nLevels) return VPL_E_INVALID;
-  FECHK(c, hipSetDevice(c->device));
-  FECHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   const LmBatch& M = c->M;
   const int lw = M.lw[level], lh = M.lh[level], S = M.ls[level];
   if (w) *w = lw;
   if (h) *h = lh;
   const size_t base = (size_t)img * M.pyrSize + M.loff[level] + (size_t)LM_WIN * S + LM_WIN;
-  if (pixels) FECHK(c, hipMemcpy2D(pixels, lw, M.pyr + base, S, lw, lh, hipMemcpyDeviceToHost));
-  if (deriv) FECHK(c, hipMemcpy2D(deriv, (size_t)lw * 4, M.der + base * 2, (size_t)S * 4, (size_t)lw * 4, lh, hipMemcpyDeviceToHost));
+  if (pixels) HIPCHK(c, hipMemcpy2D(pixels, lw, M.pyr + base, S, lw, lh, hipMemcpyDeviceToHost));
+  if (deriv) HIPCHK(c, hipMemcpy2D(deriv, (size_t)lw * 4, M.der + base * 2, (size_t)S * 4, (size_t)lw * 4, lh, hipMemcpyDeviceToHost));
   return VPL_OK;
 }
 
 // ---- vanishing points (vanishing_point_detection.cpp) ----
 static int vp_reserve(vpl_fe_ctx* c) {
   if (c->vpReserved) return VPL_OK;
-  if (c->maxLines > 1024) return fe_fail(c, VPL_E_CAPACITY, "vanishing points: max_lines_per_image above 1024");
+  if (c->maxLines > 1024) return fail(c, VPL_E_CAPACITY, "vanishing points: max_lines_per_image above 1024");
   const size_t N = c->maxN, ML = c->maxLines;
   VpBatch& V = c->V;
   std::memset(&V, 0, sizeof(V));
-  FECHK(c, fe_alloc(c, &c->d_vpHyp, N * ML * 4)); FECHK(c, fe_alloc(c, &c->d_vpAll, N * ML * 4));
-  FECHK(c, fe_alloc(c, &c->d_vpNHyp, N)); FECHK(c, fe_alloc(c, &c->d_vpNAll, N)); FECHK(c, fe_alloc(c, &c->d_vpFirst, N));
-  FECHK(c, fe_alloc(c, &c->d_vpSeed, N));
-  FECHK(c, fe_alloc(c, &V.g, N * VP_CELLS)); FECHK(c, fe_alloc(c, &V.grid, N * VP_CELLS));
-  FECHK(c, fe_alloc(c, &V.pairs, N * VP_IT * 2)); FECHK(c, fe_alloc(c, &V.rng, N * 36)); FECHK(c, fe_alloc(c, &V.status, N));
-  FECHK(c, fe_alloc(c, &V.partScore, N * VP_SCORE_BLOCKS)); FECHK(c, fe_alloc(c, &V.partIdx, N * VP_SCORE_BLOCKS));
-  FECHK(c, fe_alloc(c, &V.vps, N * 9)); FECHK(c, fe_alloc(c, &V.ids, N * ML)); FECHK(c, fe_alloc(c, &V.bestIdx, N));
+  HIPCHK(c, dalloc(c, &c->d_vpHyp, N * ML * 4)); HIPCHK(c, dalloc(c, &c->d_vpAll, N * ML * 4));
+  HIPCHK(c, dalloc(c, &c->d_vpNHyp, N)); HIPCHK(c, dalloc(c, &c->d_vpNAll, N)); HIPCHK(c, dalloc(c, &c->d_vpFirst, N));
+  HIPCHK(c, dalloc(c, &c->d_vpSeed, N));
+  HIPCHK(c, dalloc(c, &V.g, N * VP_CELLS)); HIPCHK(c, dalloc(c, &V.grid, N * VP_CELLS));
+  HIPCHK(c, dalloc(c, &V.pairs, N * VP_IT * 2)); HIPCHK(c, dalloc(c, &V.rng, N * 36)); HIPCHK(c, dalloc(c, &V.status, N));
+  HIPCHK(c, dalloc(c, &V.partScore, N * VP_SCORE_BLOCKS)); HIPCHK(c, dalloc(c, &V.partIdx, N * VP_SCORE_BLOCKS));
+  HIPCHK(c, dalloc(c, &V.vps, N * 9)); HIPCHK(c, dalloc(c, &V.ids, N * ML)); HIPCHK(c, dalloc(c, &V.bestIdx, N));
   V.maxL = (int)ML;
   V.hypEnds = c->d_vpHyp; V.allEnds = c->d_vpAll; V.nHyp = c->d_vpNHyp; V.nAll = c->d_vpNAll; V.seed = c->d_vpSeed;
   V.firstFrame = c->d_vpFirst;
@@ -799,13 +765,13 @@ int vpl_vp_detect_batch(vpl_fe_ctx* c, int n, const vpl_line* hyp_lines, const i
                         int* vp_ids, int* status) {
   if (!c || n < 1 || !hyp_lines || !n_hyp || !all_lines || !n_all || !seeds || !first_frame || !vps || !vp_ids || !status)
     return VPL_E_INVALID;
-  if (n > c->maxN) return fe_fail(c, VPL_E_CAPACITY, "more frames than max_images");
-  FECHK(c, hipSetDevice(c->device));
+  if (n > c->maxN) return fail(c, VPL_E_CAPACITY, "more frames than max_images");
+  HIPCHK(c, hipSetDevice(c->device));
   int rc = vp_reserve(c);
   if (rc) return rc;
   const size_t ML = c->maxLines;
   for (int i = 0; i < n; ++i)
-    if (n_hyp[i] < 0 || n_all[i] < 0 || n_hyp[i] > (int)ML || n_all[i] > (int)ML) return fe_fail(c, VPL_E_CAPACITY, "more lines than max_lines");
+    if (n_hyp[i] < 0 || n_all[i] < 0 || n_hyp[i] > (int)ML || n_all[i] > (int)ML) return fail(c, VPL_E_CAPACITY, "more lines than max_lines");
   std::vector<float> eh((size_t)n * ML * 4, 0.f), ea((size_t)n * ML * 4, 0.f);
   for (int i = 0; i < n; ++i) {
     for (int k = 0; k < n_hyp[i]; ++k) std::memcpy(&eh[((size_t)i * ML + k) * 4], hyp_lines[(size_t)i * ML + k].line_endpoint, 16);
@@ -814,24 +780,24 @@ int vpl_vp_detect_batch(vpl_fe_ctx* c, int n, const vpl_line* hyp_lines, const i
   hipStream_t s = c->stream;
   VpBatch& V = c->V;
   V.N = n; V.f = f; V.ppx = cx; V.ppy = cy;
-  FECHK(c, hipMemcpyAsync(c->d_vpHyp, eh.data(), eh.size() * 4, hipMemcpyHostToDevice, s));
-  FECHK(c, hipMemcpyAsync(c->d_vpAll, ea.data(), ea.size() * 4, hipMemcpyHostToDevice, s));
-  FECHK(c, hipMemcpyAsync(c->d_vpNHyp, n_hyp, (size_t)n * 4, hipMemcpyHostToDevice, s));
-  FECHK(c, hipMemcpyAsync(c->d_vpNAll, n_all, (size_t)n * 4, hipMemcpyHostToDevice, s));
-  FECHK(c, hipMemcpyAsync(c->d_vpSeed, seeds, (size_t)n * 4, hipMemcpyHostToDevice, s));
-  FECHK(c, hipMemcpyAsync(c->d_vpFirst, first_frame, (size_t)n * 4, hipMemcpyHostToDevice, s));
-  FECHK(c, hipMemsetAsync(V.g, 0, (size_t)n * VP_CELLS * 8, s));
+  HIPCHK(c, hipMemcpyAsync(c->d_vpHyp, eh.data(), eh.size() * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(c->d_vpAll, ea.data(), ea.size() * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(c->d_vpNHyp, n_hyp, (size_t)n * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(c->d_vpNAll, n_all, (size_t)n * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(c->d_vpSeed, seeds, (size_t)n * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(c->d_vpFirst, first_frame, (size_t)n * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemsetAsync(V.g, 0, (size_t)n * VP_CELLS * 8, s));
   hipLaunchKernelGGL(k_vp_grid, dim3(n, 2), dim3(64), 0, s, V);
   hipLaunchKernelGGL(k_vp_smooth, dim3((VP_CELLS + 255) / 256, n), dim3(256), 0, s, V);
   hipLaunchKernelGGL(k_vp_score, dim3(VP_SCORE_BLOCKS, n), dim3(256), 0, s, V);
   const size_t pickSmem = ML * (3 * 8 + 4 + 3 * 4);
   hipLaunchKernelGGL(k_vp_pick, dim3(n), dim3(64), pickSmem, s, V);
-  FECHK(c, hipGetLastError());
-  FECHK(c, hipMemcpyAsync(vps, V.vps, (size_t)n * 72, hipMemcpyDeviceToHost, s));
-  FECHK(c, hipMemcpyAsync(status, V.status, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(vps, V.vps, (size_t)n * 72, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(status, V.status, (size_t)n * 4, hipMemcpyDeviceToHost, s));
   std::vector<int> ids((size_t)n * ML);
-  FECHK(c, hipMemcpyAsync(ids.data(), V.ids, ids.size() * 4, hipMemcpyDeviceToHost, s));
-  FECHK(c, hipStreamSynchronize(s));
+  HIPCHK(c, hipMemcpyAsync(ids.data(), V.ids, ids.size() * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
   for (int i = 0; i < n; ++i) std::memcpy(vp_ids + (size_t)i * ML, &ids[(size_t)i * ML], (size_t)n_all[i] * 4);
   c->vpN = n;
   return VPL_OK;
@@ -839,13 +805,13 @@ int vpl_vp_detect_batch(vpl_fe_ctx* c, int n, const vpl_line* hyp_lines, const i
 
 int vpl_vp_debug(vpl_fe_ctx* c, int frame, double* grid, int* pairs, int* best_idx, int* drawn) {
   if (!c || !c->vpReserved || frame < 0 || frame >= c->vpN) return VPL_E_INVALID;
-  FECHK(c, hipSetDevice(c->device));
-  FECHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   const VpBatch& V = c->V;
-  if (grid) FECHK(c, hipMemcpy(grid, V.grid + (size_t)frame * VP_CELLS, VP_CELLS * 8, hipMemcpyDeviceToHost));
-  if (pairs) FECHK(c, hipMemcpy(pairs, V.pairs + (size_t)frame * VP_IT * 2, VP_IT * 2 * 4, hipMemcpyDeviceToHost));
-  if (best_idx) FECHK(c, hipMemcpy(best_idx, V.bestIdx + frame, 4, hipMemcpyDeviceToHost));
-  if (drawn) FECHK(c, hipMemcpy(drawn, V.rng + (size_t)frame * 36 + 35, 4, hipMemcpyDeviceToHost));
+  if (grid) HIPCHK(c, hipMemcpy(grid, V.grid + (size_t)frame * VP_CELLS, VP_CELLS * 8, hipMemcpyDeviceToHost));
+  if (pairs) HIPCHK(c, hipMemcpy(pairs, V.pairs + (size_t)frame * VP_IT * 2, VP_IT * 2 * 4, hipMemcpyDeviceToHost));
+  if (best_idx) HIPCHK(c, hipMemcpy(best_idx, V.bestIdx + frame, 4, hipMemcpyDeviceToHost));
+  if (drawn) HIPCHK(c, hipMemcpy(drawn, V.rng + (size_t)frame * 36 + 35, 4, hipMemcpyDeviceToHost));
   return VPL_OK;
 }
 
