@@ -5,7 +5,7 @@
 //            straight into the FP64 matrix cores -- the lane that supplies operand element (row, column) loads exactly that
 //            element -- in the COMPACT coordinates of the rows' start frame (WS + 2 columns instead of 80), every wave on its
 //            own span of rows.  No staging buffers, no work-group barriers in the product.
-//   k_chol   (256 threads, ~70 KB LDS, two work-groups per CU)  the reduced camera system.  The 99 speed/bias dims touch IMU
+//   k_chol   (256 threads, ~62 KB LDS, two work-groups per CU)  the reduced camera system.  The 99 speed/bias dims touch IMU
 //            factors and the prior only: the blocks of frames 1..4 and 10..6 are eliminated first as two block chains (one
 //            wave each, 9-row strips held in registers with the columns in the lanes), which leaves the DENSE system
 //            [72 pose / extrinsic dims | speed/bias 0 | speed/bias 5 | rhs] = 91 rows = 6 tile columns instead of 11.
@@ -667,14 +667,15 @@ inline size_t schur_smem(int maxP, int maxL, int ntc = 5) {
 constexpr int DN = 90;                       // dense dims (rhs row = DN)
 constexpr int DNT = 6;                       // 16x16 tiles per dimension of the dense system (96 >= 91)
 constexpr int DNAP = DNT * (DNT + 1) / 2 * 256;   // tile-major lower storage (5376 doubles)
-#ifdef VPL_CHOL_OCC3                         // A/B switch: three work-groups per CU (53 KB of LDS, 168 registers)
-constexpr int XLD = 66;
-constexpr int CHOL_MIN_WAVES = 3;
-#else
-constexpr int XLD = 72;                      // row stride of the chains' X rows in LDS (64 lanes + 8)
+// The chains' X rows are stored in DENSE coordinates, five tile columns per chain: chain A tile columns 0, 1, 2, 4, 5 (dense
+// 0..47, 64..95), chain B 1..5 (dense 16..95).  Columns a chain never writes stay zero.
+constexpr int XLD = 80;                      // row stride of the X rows: five tile columns
 constexpr int CHOL_MIN_WAVES = 2;
-#endif
 constexpr int XROWS_A = 36, XROWS_B = 48;    // 4 x 9 rows ; 5 x 9 rows padded to a multiple of 4
+// position in a chain's X row of dense tile column J (J = 3 is not in chain A's rows, J = 0 not in chain B's)
+__device__ __forceinline__ constexpr int xcol(int ch, int J) { return ch == 0 ? 16 * (J > 3 ? J - 1 : J) : 16 * (J - 1); }
+// row I of tile t of the tile-major lower storage (t = I (I + 1) / 2 + J)
+__device__ __forceinline__ constexpr int tile_row(int t) { return t < 1 ? 0 : t < 3 ? 1 : t < 6 ? 2 : t < 10 ? 3 : t < 15 ? 4 : 5; }
 
 __device__ __forceinline__ int chain_frame(int ch, int b) { return ch == 0 ? 1 + b : 10 - b; }
 // cam index of the column of `lane` in block b of chain ch; NC = rhs, -1 = none
@@ -726,7 +727,7 @@ __device__ __forceinline__ void chol_body(const DevBatch& B, const int w, double
   constexpr int REG = (XROWS_A + XROWS_B) * XLD > DNAP ? (XROWS_A + XROWS_B) * XLD : DNAP;
   double* XA = sm;                       // chain A's X rows (36 x XLD); chain B's behind them (48 x XLD)
   double* XBm = sm + XROWS_A * XLD;
-  double* S = sm;                        // the dense system, tile-major lower, once the chains' products are in registers
+  double* S = sm;                        // the dense system, tile-major lower, once the partner waves hold it in registers
   double* scv = sm + REG;                // 176 jacobi scale of the cam dims
   double* dgv = scv + 176;               // 176 dogleg diagonal
   double* ycam = dgv + 176;              // 176 solution, cam-indexed (scaled space)
@@ -735,8 +736,7 @@ __device__ __forceinline__ void chol_body(const DevBatch& B, const int w, double
   double* Linv = isd + 96;               // 256 inverse of the current diagonal tile's factor
   double* red = Linv + 256;              // 24
   int* flag = (int*)(red + 24);          // [0] failure, [1], [2] blocks finished by chain A / B
-  int* cdmap = flag + 8;                 // 2 x 64: dense index of the lanes of the chains' X rows
-  double* rsL = (double*)(cdmap + 128);  // 2 x 5 x 9: 1 / L_kk of the chains' pivot blocks (for the back-substitution)
+  double* rsL = (double*)(flag + 8);     // 2 x 5 x 9: 1 / L_kk of the chains' pivot blocks (for the back-substitution)
 
   const size_t fb = (size_t)w * B.nfull;
   const double* gscale = B.scale + fb;
@@ -749,14 +749,15 @@ __device__ __forceinline__ void chol_body(const DevBatch& B, const int w, double
   const double mu = tr->mu;
   for (int c = tid; c < 176; c += T) { scv[c] = c < NC ? gscale[c] : 0.0; dgv[c] = c < NC ? gdiag[c] : 1.0; ycam[c] = 0.0; }
   if (tid < 4) flag[tid] = 0;
-  if (tid < 128) cdmap[tid] = chain_dense(tid >> 6, tid & 63);
-  for (int i = tid; i < 3 * XLD; i += T) XBm[(XROWS_B - 3) * XLD + i] = 0.0;   // rows 45..47 of chain B: K padding
+  // the columns of the X rows no chain lane writes, and rows 45..47 of chain B (K padding)
+  for (int i = tid; i < (XROWS_A + XROWS_B) * XLD; i += T) sm[i] = 0.0;
   __syncthreads();
   VPL_STAMP(B, w, 8);
 
-  // ================= phase 1: the two chains (waves 0, 1) and their X^T X on the matrix cores (waves 2, 3) =============
+  // ================= phase 1: the two chains (waves 0, 1); the dense system assembled and the chains' X^T X taken off it
+  // on the matrix cores (waves 2, 3) =================================================================================
   // One register array, two tenants: the chain waves keep X of every block for the back-substitution (Xs(b, k) = U[9 b + k]),
-  // the partner waves the lower tiles of sum_b X_b^T X_b in lane coordinates (64 x 64: 10 tiles x 4 = U[0..39]).
+  // the partner waves their tiles of the dense system (11 or 10 tiles x 4 = U[0..43]).
   double U[45];
 #pragma unroll
   for (int i = 0; i < 45; ++i) U[i] = 0.0;
@@ -764,6 +765,8 @@ __device__ __forceinline__ void chol_body(const DevBatch& B, const int w, double
   if (wv < 2) {
     const int ch = wv, nblk = ch == 0 ? 4 : 5;
     double* Xout = ch == 0 ? XA : XBm;
+    const int xd = chain_dense(ch, lane);                 // the lane's X entries go to dense column xd (none: -1)
+    const int xp = xd < 0 ? -1 : xcol(ch, xd >> 4) + (xd & 15);
     bool bad = false;
     // original strip of block b: H~[pivot rows][lane's column]; nine independent loads per lane
     auto load_strip = [&](int b, double (&raw)[9]) {
@@ -831,7 +834,7 @@ __device__ __forceinline__ void chol_body(const DevBatch& B, const int w, double
           if (lane == 0) rsL[(5 * ch + b) * 9 + k] = rs;
           const double xv = R[k] * rs;
           Xs(b, k) = col >= 0 ? xv : 0.0;
-          Xout[(9 * b + k) * XLD + lane] = dcol ? xv : 0.0;
+          if (xp >= 0) Xout[(9 * b + k) * XLD + xp] = dcol ? xv : 0.0;
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         if (lane == 0) __hip_atomic_store(&flag[1 + ch], b + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -839,149 +842,107 @@ __device__ __forceinline__ void chol_body(const DevBatch& B, const int w, double
     }
     if (bad && lane == 0) flag[0] = 1;
   } else {
-    // partner of chain wv - 2: consumes the X rows K-step by K-step as the blocks are finished
-    const int ch = wv - 2, nblk = ch == 0 ? 4 : 5;
-    const double* Xin = ch == 0 ? XA : XBm;
+    // partner waves: the dense system in registers, tile t = (I, J) of the tile-major lower storage -- wave 2 the even
+    // tiles, wave 3 the odd ones.  Each chain's product is summed from zero on the matrix cores, K-step by K-step as its X
+    // rows are finished, and then subtracted: (H~ - P_A) - P_B.  The K-steps, the products and the roundings of every
+    // entry are those of the lane-coordinate products this replaced, whichever tile the entry lands in: the same bits.
+    // The entries of H~ are loaded once chain A is done, while chain B eliminates its last block (held from the start,
+    // they would not fit in the registers next to the accumulators).
     const int m = lane & 15, kk = lane >> 4;
-    const int nks = (ch == 0 ? XROWS_A : XROWS_B) / 4;
-    int have = 0;
-    v4d pacc[10];
+    // entry (r, c) of H~ before the chains: (Hcc - Schur) in the scaled space + mu D^2 (speed/bias rows: no Schur term),
+    // the rhs row (g - Schur) scaled; the rhs diagonal and the padding rows are an identity (never a pivot).  Diagonal
+    // tiles are full squares: (r, c) and (c, r) get the same bits.
+    auto h0 = [&](int r, int c) -> double {
+      if (r < c) { const int t = r; r = c; c = t; }
+      if (r > DN || c == DN) return r == c ? 1.0 : 0.0;
+      const int cc = dense2cam(c);
+      if (r == DN) return (gc[cc] - (c < NV ? sacc[tri(NV, c)] : 0.0)) * scv[cc];
+      const int cr = dense2cam(r);
+      double v = Hcc[cr >= cc ? tri(cr, cc) : tri(cc, cr)];
+      if (r < NV) v -= sacc[tri(r, c)];
+      v *= scv[cr] * scv[cc];
+      if (r == c) v += mu * dgv[cr] * dgv[cr];
+      return v;
+    };
+    const int p = __builtin_amdgcn_readfirstlane(wv - 2);
+    v4d hs[11], acc[11];
 #pragma unroll
-    for (int t = 0; t < 10; ++t) pacc[t] = v4d{0, 0, 0, 0};
-    for (int ks = 0; ks < nks; ++ks) {
-      const int need = min(nblk, (4 * ks + 3) / 9 + 1);
+    for (int i = 0; i < 11; ++i) acc[i] = v4d{0, 0, 0, 0};
+    int have = 0;
+#pragma unroll 1
+    for (int ks = 0; ks < XROWS_A / 4; ++ks) {          // chain A: dense tile columns 0, 1, 2, 4, 5
+      const int need = min(4, (4 * ks + 3) / 9 + 1);
       while (have < need) {
-        have = __hip_atomic_load(&flag[1 + ch], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        have = __hip_atomic_load(&flag[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         if (have >= need) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
       }
-      const double* row = Xin + (4 * ks + kk) * XLD + m;
-      const double x0 = row[0], x1 = row[16], x2 = row[32], x3 = row[48];
-      pacc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(x0, x0, pacc[0], 0, 0, 0);
-      pacc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(x1, x0, pacc[1], 0, 0, 0);
-      pacc[2] = __builtin_amdgcn_mfma_f64_16x16x4f64(x1, x1, pacc[2], 0, 0, 0);
-      pacc[3] = __builtin_amdgcn_mfma_f64_16x16x4f64(x2, x0, pacc[3], 0, 0, 0);
-      pacc[4] = __builtin_amdgcn_mfma_f64_16x16x4f64(x2, x1, pacc[4], 0, 0, 0);
-      pacc[5] = __builtin_amdgcn_mfma_f64_16x16x4f64(x2, x2, pacc[5], 0, 0, 0);
-      pacc[6] = __builtin_amdgcn_mfma_f64_16x16x4f64(x3, x0, pacc[6], 0, 0, 0);
-      pacc[7] = __builtin_amdgcn_mfma_f64_16x16x4f64(x3, x1, pacc[7], 0, 0, 0);
-      pacc[8] = __builtin_amdgcn_mfma_f64_16x16x4f64(x3, x2, pacc[8], 0, 0, 0);
-      pacc[9] = __builtin_amdgcn_mfma_f64_16x16x4f64(x3, x3, pacc[9], 0, 0, 0);
+      const double* row = XA + (4 * ks + kk) * XLD + m;
+      double x[6];
+#pragma unroll
+      for (int J = 0; J < 6; ++J) x[J] = J == 3 ? 0.0 : row[xcol(0, J)];
+#pragma unroll
+      for (int t = 0; t < 21; ++t) {
+        const int I = tile_row(t), J = t - I * (I + 1) / 2;
+        if ((t & 1) != p || I == 3 || J == 3) continue;
+        acc[t >> 1] = __builtin_amdgcn_mfma_f64_16x16x4f64(x[I], x[J], acc[t >> 1], 0, 0, 0);
+      }
+    }
+    // the assembled entries minus chain A's product
+#pragma unroll
+    for (int t = 0; t < 21; ++t) {
+      if ((t & 1) != p) continue;
+      const int I = tile_row(t), J = t - I * (I + 1) / 2;
+      const int r = 16 * I + kk, c = 16 * J + m;
+      const v4d h = v4d{h0(r, c), h0(r + 4, c), h0(r + 8, c), h0(r + 12, c)};
+      hs[t >> 1] = (I == 3 || J == 3) ? h : h - acc[t >> 1];
+      acc[t >> 1] = v4d{0, 0, 0, 0};
+    }
+    if (p) hs[10] = v4d{0, 0, 0, 0};
+    have = 0;
+#pragma unroll 1
+    for (int ks = 0; ks < XROWS_B / 4; ++ks) {          // chain B: dense tile columns 1..5
+      const int need = min(5, (4 * ks + 3) / 9 + 1);
+      while (have < need) {
+        have = __hip_atomic_load(&flag[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (have >= need) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+      }
+      const double* row = XBm + (4 * ks + kk) * XLD + m;
+      double x[6];
+#pragma unroll
+      for (int J = 0; J < 6; ++J) x[J] = J == 0 ? 0.0 : row[xcol(1, J)];
+#pragma unroll
+      for (int t = 0; t < 21; ++t) {
+        const int I = tile_row(t), J = t - I * (I + 1) / 2;
+        if ((t & 1) != p || J == 0) continue;
+        acc[t >> 1] = __builtin_amdgcn_mfma_f64_16x16x4f64(x[I], x[J], acc[t >> 1], 0, 0, 0);
+      }
     }
 #pragma unroll
-    for (int t = 0; t < 10; ++t) { U[4 * t] = pacc[t].x; U[4 * t + 1] = pacc[t].y; U[4 * t + 2] = pacc[t].z; U[4 * t + 3] = pacc[t].w; }
+    for (int i = 0; i < 11; ++i) {
+      const v4d h = hs[i] - acc[i];
+      U[4 * i] = h.x; U[4 * i + 1] = h.y; U[4 * i + 2] = h.z; U[4 * i + 3] = h.w;
+    }
   }
   __syncthreads();   // the X rows are dead: their space becomes the dense system
   VPL_STAMP(B, w, 9);
 
-  // ================= phase 2: the dense system in LDS ================================================================
-  // Every global operand of this thread is requested first (one batch: ~30 loads in flight), the LDS image is zeroed
-  // meanwhile, then the entries are scaled and stored.
-  auto put = [&](int r, int c, double v) {             // r >= c; diagonal tiles are kept as full squares
-    S[tix(r, c)] = v;
-    if ((r >> 4) == (c >> 4) && r != c) S[tix(c, r)] = v;
-  };
-  {
-    constexpr int NVP = NV * (NV + 1) / 2;
-    constexpr int NB1 = (NVP + CHOL_THREADS - 1) / CHOL_THREADS;          // 11 entries of the vis triangle per thread
-    constexpr int NB2 = (19 * 96 + CHOL_THREADS - 1) / CHOL_THREADS;      // 8 entries of the speed/bias rows + rhs row
-    double hh[NB1], ss[NB1], h2[NB2], s2[NB2];
-    int rc1[NB1], rc2[NB2];
+  // ================= phase 2: the dense system from the partner waves' registers into LDS ===========================
+  if (wv >= 2) {
+    const int p = __builtin_amdgcn_readfirstlane(wv - 2);
+    const int m = lane & 15, kk = lane >> 4;
 #pragma unroll
-    for (int u = 0; u < NB1; ++u) {
-      const int e = u * T + tid;
-      hh[u] = 0.0; ss[u] = 0.0; rc1[u] = -1;
-      if (e < NVP) {
-        int vr, vc;
-        tri_decode(e, vr, vc);
-        rc1[u] = vr | vc << 8;
-        hh[u] = Hcc[tri(vis2cam(vr), vis2cam(vc))];
-        ss[u] = sacc[e];
+    for (int t = 0; t < 21; ++t) {
+      if ((t & 1) != p) continue;
+      double* St = S + (t << 8);
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        const int r = kk + 4 * v;
+        // (rhs, rhs) is not part of the system: it keeps its unit diagonal
+        St[tsw(r, m)] = (t == 20 && r == DN - 80 && m == DN - 80) ? 1.0 : U[4 * (t >> 1) + v];
       }
     }
-#pragma unroll
-    for (int u = 0; u < NB2; ++u) {
-      const int idx = u * T + tid;
-      const int i = idx / 96, dc = idx - 96 * i;
-      const int dr = 72 + i;
-      h2[u] = 0.0; s2[u] = 0.0; rc2[u] = -1;
-      if (idx < 19 * 96 && dc <= dr && dc < DN) {
-        rc2[u] = dr | dc << 8;
-        const int c = dense2cam(dc);
-        if (dr < DN) {
-          const int r = dense2cam(dr);
-          h2[u] = Hcc[r >= c ? tri(r, c) : tri(c, r)];
-        } else {
-          h2[u] = gc[c];
-          if (dc < NV) s2[u] = sacc[tri(NV, dc)];
-        }
-      }
-    }
-    for (int i = tid; i < DNAP; i += T) S[i] = 0.0;
-    __syncthreads();
-    VPL_STAMP(B, w, 14);
-    // (i) pose / extrinsic block: (Hcc - Schur) in the scaled space + mu D^2; the packed index of the 72 x 72 vis triangle is
-    //     the index into the compact Schur product
-#pragma unroll
-    for (int u = 0; u < NB1; ++u)
-      if (rc1[u] >= 0) {
-        const int vr = rc1[u] & 255, vc = rc1[u] >> 8;
-        const int r = vis2cam(vr), c = vis2cam(vc);
-        double v = (hh[u] - ss[u]) * (scv[r] * scv[c]);
-        if (r == c) v += mu * dgv[r] * dgv[r];
-        put(vr, vc, v);
-      }
-    // (ii) rows of speed/bias 0 and 5, (iii) the rhs row
-#pragma unroll
-    for (int u = 0; u < NB2; ++u)
-      if (rc2[u] >= 0) {
-        const int dr = rc2[u] & 255, dc = rc2[u] >> 8;
-        const int c = dense2cam(dc);
-        if (dr < DN) {
-          const int r = dense2cam(dr);
-          double v = h2[u] * (scv[r] * scv[c]);
-          if (r == c) v += mu * dgv[r] * dgv[r];
-          put(dr, dc, v);
-        } else {
-          put(DN, dc, (h2[u] - s2[u]) * scv[c]);
-        }
-      }
-    if (tid < 6) S[tix(DN + tid, DN + tid)] = 1.0;      // rhs row and padding rows: unit diagonal, never a pivot
   }
   __syncthreads();
-  VPL_STAMP(B, w, 15);
-  // (iv) minus the chains' products.  An entry gets a term from both chains only when both of its dims are met by both:
-  // pose 5 (vis 30..35), speed/bias 5 (81..89), the rhs (90).  Pass 0: chain A's partner subtracts everything it has, chain B's
-  // partner everything outside that overlap -- side by side, on different entries; pass 1: chain B's partner subtracts its
-  // overlap entries.  Every entry sees its terms in the order A, B.
-  auto in_both = [](int d) { return (d >= 30 && d < 36) || d >= 81; };
-#pragma unroll 1
-  for (int pass = 0; pass < 2; ++pass) {
-    if ((wv == 2 && pass == 0) || wv == 3) {
-      const int ch = wv - 2;
-      const int m = lane & 15, kk = lane >> 4;
-      int t = 0;
-#pragma unroll
-      for (int ta = 0; ta < 4; ++ta)
-#pragma unroll
-        for (int tb = 0; tb <= ta; ++tb, ++t) {
-          const int j = 16 * tb + m, dj = cdmap[64 * ch + j];
-#pragma unroll
-          for (int v = 0; v < 4; ++v) {
-            const int i = 16 * ta + kk + 4 * v;
-            if (i < j) continue;
-            const int di = cdmap[64 * ch + i];
-            if (di < 0 || dj < 0) continue;
-            if (ch == 1 && (in_both(di) && in_both(dj)) != (pass == 1)) continue;
-            const int r = di > dj ? di : dj, c = di > dj ? dj : di;
-            if (c >= DN) continue;                       // (rhs, rhs) is not part of the system
-            const double val = U[4 * t + v];
-            S[tix(r, c)] -= val;
-            if ((r >> 4) == (c >> 4) && r != c) S[tix(c, r)] -= val;
-          }
-        }
-    }
-    __syncthreads();
-  }
   VPL_STAMP(B, w, 10);
 
   // ================= phase 3: left-looking tile Cholesky of the dense system (the scheme of ba_solve.h, 6 tile columns,
