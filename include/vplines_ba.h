@@ -273,6 +273,20 @@ int vpl_ba_solve_windows(vpl_ctx* ctx, int n_windows, vpl_window* windows, const
  * input prior back (estimator.cpp:1385).  Synchronous (upload, kernels, download). */
 int vpl_ba_marginalize(vpl_ctx* ctx, int n_windows, const vpl_window* windows, const vpl_ba_options* opt,
                        int marginalization_flag, vpl_prior* priors_out, int* m, int* n);
+/* How the kept block A (with b) becomes the next prior (J0, r0) -- marginalization_factor.cpp:349-357, selected per context:
+ *   VPL_PRIOR_PIVOTED_CHOLESKY (default): A's pivoted Cholesky factor, cut where a pivot drops below 1e-8.
+ *                               The same prior up to an orthogonal Q (J0' = Q J0, r0' = Q r0) where A is well determined;
+ *                               it keeps one to five directions fewer than the reference on weakly determined blocks.
+ *   VPL_PRIOR_EIGEN:            the reference's rule: SelfAdjointEigenSolver of A (its lower triangle) by a parallel Jacobi
+ *                               on the device, eigenvalues S > 1e-8 kept, J0 = sqrt(S) V^T, r0 = S^-1/2 V^T b -- rows in
+ *                               ascending eigenvalue order, dropped rows zero, each eigenvector's largest component positive.
+ *                               Costs a second kernel (k_prior_eigen) after the factorisation.
+ * The rule applies to every entry point that marginalises: vpl_ba_solve / _solve_windows, vpl_ba_marginalize(_async),
+ * vpl_ba_solve_odometry, and so the prior vpl_ba_upload_chained hands over.  A pending asynchronous call is collected first:
+ * a call runs under the rule that was in force when it was enqueued.  An unknown rule: VPL_E_INVALID. */
+#define VPL_PRIOR_PIVOTED_CHOLESKY 0
+#define VPL_PRIOR_EIGEN 1
+int vpl_ba_set_prior_rule(vpl_ctx* ctx, int rule);
 
 /* ---- line map maintenance that precedes the main solve (estimator.cpp:635-638) -------------------------------- */
 /* FeatureManager::triangulateLine (feature_manager.cpp:413-563): lines with line_triangulated[i] == 0 are triangulated

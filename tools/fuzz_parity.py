@@ -16,7 +16,7 @@ from the first answer.  The device differs from the oracle in the order of EVERY
 one: a window outside the bar counts as a MISS only if the device is more than ten times further from the oracle than the
 oracle is from itself; otherwise it is printed as `ill-posed`.  Exit status 1 if there is a MISS.
 
-    python tools/fuzz_parity.py [batches=12] [windows per batch=8] [seed=1]
+    python tools/fuzz_parity.py [batches=12] [windows per batch=8] [seed=1] [prior rule: 0 pivoted Cholesky (default), 1 eigen]
 """
 import os
 import sys
@@ -94,15 +94,18 @@ def draw_window(rng, idx, t):
 def main():
     nb = int(sys.argv[1]) if len(sys.argv) > 1 else 12
     per = int(sys.argv[2]) if len(sys.argv) > 2 else 8
-    res = run(nb, per, int(sys.argv[3]) if len(sys.argv) > 3 else 1)
+    res = run(nb, per, int(sys.argv[3]) if len(sys.argv) > 3 else 1, prior_rule=int(sys.argv[4]) if len(sys.argv) > 4 else None)
     return 1 if res["miss"] else 0
 
 
-def run(nb, per, seed, out=print):
+def run(nb, per, seed, out=print, prior_rule=None):
     """-> dict(total, miss, ill, miss_first, total_first, worst_dp, worst_dr); *_first count the windows solved without an
-    incoming prior (the chained ones depend on the marginalisation of the solve before)"""
+    incoming prior (the chained ones depend on the marginalisation of the solve before).  prior_rule: vpl_ba_set_prior_rule
+    on the device's context (None: the context's default)"""
     rng = np.random.default_rng(seed)
     ctx = make_ctx(per)
+    if prior_rule is not None:
+        ctx.set_prior_rule(prior_rule)
     bad = total = ill = bad0 = total0 = 0
     worst = [0.0, 0.0]                                # over the windows that determine their states
     for b in range(nb):

@@ -11,6 +11,7 @@ NF = 11
 MAX_PRIOR_BLOCKS = 23
 MAX_PRIOR_DIM = 171
 MARGIN_OLD, MARGIN_SECOND_NEW, MARGIN_NONE = 0, 1, -1
+PRIOR_PIVOTED_CHOLESKY, PRIOR_EIGEN = 0, 1   # vpl_ba_set_prior_rule
 BLOCK_POSE, BLOCK_SPEEDBIAS, BLOCK_EXPOSE = 0, 1, 2
 
 _dp = C.POINTER(C.c_double)
@@ -197,6 +198,7 @@ def load_hip_library():
     lib.vpl_ctx_destroy.argtypes = [vp]
     lib.vpl_ctx_destroy.restype = None
     lib.vpl_ctx_set_stream.argtypes = [vp, vp]
+    lib.vpl_ba_set_prior_rule.argtypes = [vp, C.c_int]
     lib.vpl_last_error.argtypes = [vp]
     lib.vpl_last_error.restype = C.c_char_p
     lib.vpl_preintegrate_batch.argtypes = [vp, C.c_int, _ip, _ip, _dp, _dp, _dp, _dp, _dp, C.POINTER(BaOptions),
@@ -283,6 +285,12 @@ class Context:
     def set_stream(self, stream_ptr):
         self._settle()
         self._check(self.lib.vpl_ctx_set_stream(self.h, C.c_void_p(stream_ptr)), "vpl_ctx_set_stream")
+
+    def set_prior_rule(self, rule):
+        """PRIOR_PIVOTED_CHOLESKY (default) or PRIOR_EIGEN (the reference's eigen-decomposed prior); an enqueued call is
+        collected first"""
+        self._settle()
+        self._check(self.lib.vpl_ba_set_prior_rule(self.h, int(rule)), "vpl_ba_set_prior_rule")
 
     def synchronize(self):
         self._check(self.lib.vpl_ctx_synchronize(self.h), "vpl_ctx_synchronize")

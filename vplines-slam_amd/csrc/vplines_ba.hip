@@ -24,6 +24,7 @@
 #include "ba_solve.h"
 #include "ba_step.h"
 #include "ba_marg.h"
+#include "ba_prior_eig.h"
 #include "ba_lineopt.h"
 #include "ba_factors.h"
 #include "host_common.h"
@@ -198,6 +199,8 @@ struct vpl_ctx {
   std::vector<int> h_nP, h_nL;
   std::vector<std::vector<int>> h_lmap;          // per window: device line index -> index in the vpl_window arrays
   size_t marg_smem = 0;
+  int marg_nmax = 0;                             // largest kept block of the uploaded batch (k_prior_eigen's LDS layout)
+  int prior_rule = VPL_PRIOR_PIVOTED_CHOLESKY;   // vpl_ba_set_prior_rule
   bool marg_small = false;                       // k_marg<256> (two work-groups per CU) instead of k_marg<512>
   int maxPriorN = 0;                             // largest prior of the uploaded batch (k_prep stages J0 in LDS)
   // asynchronous variants of the line-map entry points: the host-side completion (wait for the stream, scatter the staged
@@ -459,7 +462,8 @@ static int ctx_init(vpl_ctx* c, int device, int max_windows, int max_points, int
       {(const void*)k_lin2, lin_max}, {(const void*)k_lin<1>, lin_max}, {(const void*)k_lin<2>, lin_max},
       {(const void*)k_solve, solve_max}, {(const void*)k_schur<3>, schur_max}, {(const void*)k_schur<5>, schur_max},
       {(const void*)k_schur_mixed, schur_max}, {(const void*)k_chol, CHOL_SMEM}, {(const void*)k_back, back_max},
-      {(const void*)k_prep, PREP_SMEM}, {(const void*)k_marg<MARG_THREADS>, 159 * 1024}, {(const void*)k_marg<256>, MARG_LDS_SMALL}};
+      {(const void*)k_prep, PREP_SMEM}, {(const void*)k_marg<MARG_THREADS>, 159 * 1024}, {(const void*)k_marg<256>, MARG_LDS_SMALL},
+      {(const void*)k_prior_eigen, prior_eig_layout(MAXKEEP).bytes}};
   for (const auto& k : lds)
     if (hipFuncSetAttribute(k.first, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.second) != hipSuccess) return VPL_E_HIP;
   vpl_ba_default_options(&c->opt);
@@ -511,6 +515,16 @@ int vpl_ctx_set_stream(vpl_ctx* c, void* s) {
   }
   drop_graph(c);
   c->stream = (hipStream_t)s;
+  return VPL_OK;
+}
+// the rule that turns the kept block into the next prior (k_marg's pivoted Cholesky, or k_prior_eigen behind it); a call already
+// enqueued is collected first, so that every call runs under the rule in force when it was enqueued
+int vpl_ba_set_prior_rule(vpl_ctx* c, int rule) {
+  if (!c || (rule != VPL_PRIOR_PIVOTED_CHOLESKY && rule != VPL_PRIOR_EIGEN)) return VPL_E_INVALID;
+  const int rs = settle(c);
+  if (rs) return rs;
+  drop_graph(c);   // the launch sequence of a solve changes: the next vpl_ba_solve captures it again
+  c->prior_rule = rule;
   return VPL_OK;
 }
 const char* vpl_last_error(const vpl_ctx* c) { return c ? c->err.c_str() : "null context"; }
@@ -1047,6 +1061,7 @@ static int choose_marg(vpl_ctx* c, const Span<int>& mg_n, size_t W) {
   const DevBatch& B = c->B;
   int nmax = 0;
   for (size_t w = 0; w < W; ++w) nmax = std::max(nmax, mg_n[w]);
+  c->marg_nmax = nmax;
   c->marg_small = nmax <= 48 && B.maxP <= 256 && B.maxL <= 256 &&
                   (size_t)marg_layout(nmax, true).total * sizeof(double) <= MARG_LDS_SMALL && std::getenv("VPL_BA_MARG_BIG") == nullptr;
   c->marg_smem = (size_t)marg_layout(nmax, c->marg_small).total * sizeof(double);
@@ -1209,7 +1224,7 @@ static void launch_prep(vpl_ctx* c, const DevBatch& B, int nw, hipStream_t s) {
   hipLaunchKernelGGL(k_prep, dim3(nw), dim3(PREP_THREADS), prep_smem(c->maxPriorN), s, B, std::min(c->maxPriorN, PREP_NMAX));
 }
 // the marginalisation of the uploaded flag: k_lin<1|2> linearises its factor subset at the current states, k_marg eliminates
-// and factors the kept block.  Nothing runs for MARGIN_NONE, nor for MARGIN_SECOND_NEW when every window passes its prior through.
+// and factors the kept block (VPL_PRIOR_EIGEN: k_prior_eigen then replaces the factor by the reference's).  Nothing runs for MARGIN_NONE, nor for MARGIN_SECOND_NEW when every window passes its prior through.
 static void launch_marg(vpl_ctx* c, DevBatch& B, int nw, hipStream_t s) {
   const bool old = c->opt.marginalization_flag == VPL_MARGIN_OLD;
   if (!old && !c->any_second_new) return;
@@ -1221,6 +1236,10 @@ static void launch_marg(vpl_ctx* c, DevBatch& B, int nw, hipStream_t s) {
   { KTimer t(c, "k_marg");
     if (c->marg_small) hipLaunchKernelGGL(k_marg<256>, grid, dim3(256), c->marg_smem, s, B);
     else hipLaunchKernelGGL(k_marg<MARG_THREADS>, grid, dim3(MARG_THREADS), c->marg_smem, s, B); }
+  if (c->prior_rule == VPL_PRIOR_EIGEN) {   // the reference's factor of the kept block k_marg left in mg_A / mg_b
+    KTimer t(c, "k_prior_eigen");
+    hipLaunchKernelGGL(k_prior_eigen, grid, dim3(PRIOR_EIG_THREADS), prior_eig_layout(c->marg_nmax).bytes, s, B, c->marg_nmax);
+  }
 }
 // FeatureManager::triangulate (points: k_triangulate_points, inverse depths back) and / or ::triangulateLine (lines:
 // k_triangulate, flags + Pluecker vectors back) for a batch, on ONE upload with every line (the two touch different arrays:

@@ -337,6 +337,9 @@ class MarginalizationInfo {
   }
   // marginalization_factor.cpp:177-363
   void marginalize();
+  // how marginalize() turns the kept block into (J0, r0): vpl_ba_set_prior_rule on the context it creates (VPL_PRIOR_EIGEN: the
+  // reference's eigen-decomposed factor, :349-357)
+  int prior_rule = VPL_PRIOR_PIVOTED_CHOLESKY;
   // marginalization_factor.cpp:458-478: kept blocks in prior order, their addresses shifted by the caller's map
   std::vector<double*> getParameterBlocks(std::unordered_map<long, double*>& addr_shift) {
     std::vector<double*> keep_block_addr;
@@ -466,7 +469,8 @@ inline void MarginalizationInfo::marginalize() {
   const int npo = (int)(pobs.size() / 3), nlo = (int)(lobs.size() / 8);
   int rc = vpl_ctx_create(&ctx, 0, 1, std::max(1, w.n_points), std::max(1, npo), std::max(1, w.n_lines), std::max(1, nlo));
   if (rc != VPL_OK) throw std::runtime_error("MarginalizationInfo: vpl_ctx_create failed (" + std::to_string(rc) + "); there is no CPU fallback");
-  rc = vpl_ba_marginalize(ctx, 1, &w, &opt, flag, &prior, &m, &n);
+  rc = vpl_ba_set_prior_rule(ctx, prior_rule);
+  if (rc == VPL_OK) rc = vpl_ba_marginalize(ctx, 1, &w, &opt, flag, &prior, &m, &n);
   const std::string err = rc == VPL_OK ? "" : vpl_last_error(ctx);
   vpl_ctx_destroy(ctx);
   if (rc != VPL_OK) throw std::runtime_error("vpl_ba_marginalize failed: " + err);
