@@ -168,6 +168,17 @@ __device__ __forceinline__ void diag_tile_step(double (&d)[4], double (&m)[4], i
     }
   }
 }
+// the 16 column steps of the diagonal tile (columns ncol..15 are left untouched)
+__device__ __forceinline__ void diag_tile_factor(double (&d)[4], double (&m)[4], int r4, int cc, int ncol, double& pivc, bool& bad) {
+  diag_tile_step<0>(d, m, r4, cc, ncol, pivc, bad);  diag_tile_step<1>(d, m, r4, cc, ncol, pivc, bad);
+  diag_tile_step<2>(d, m, r4, cc, ncol, pivc, bad);  diag_tile_step<3>(d, m, r4, cc, ncol, pivc, bad);
+  diag_tile_step<4>(d, m, r4, cc, ncol, pivc, bad);  diag_tile_step<5>(d, m, r4, cc, ncol, pivc, bad);
+  diag_tile_step<6>(d, m, r4, cc, ncol, pivc, bad);  diag_tile_step<7>(d, m, r4, cc, ncol, pivc, bad);
+  diag_tile_step<8>(d, m, r4, cc, ncol, pivc, bad);  diag_tile_step<9>(d, m, r4, cc, ncol, pivc, bad);
+  diag_tile_step<10>(d, m, r4, cc, ncol, pivc, bad); diag_tile_step<11>(d, m, r4, cc, ncol, pivc, bad);
+  diag_tile_step<12>(d, m, r4, cc, ncol, pivc, bad); diag_tile_step<13>(d, m, r4, cc, ncol, pivc, bad);
+  diag_tile_step<14>(d, m, r4, cc, ncol, pivc, bad); diag_tile_step<15>(d, m, r4, cc, ncol, pivc, bad);
+}
 
 
 // Cholesky of a small SPD matrix (n <= 16, row-major, leading dimension ld, in LDS) by ONE wave with the register tile
@@ -184,10 +195,7 @@ __device__ __forceinline__ bool wave_chol16(double* A, int n, int ld, double* Xi
   }
   double pivc = 1.0;
   bool bad = false;
-#define VPL_DSTEP(J) diag_tile_step<J>(d, m, r4, cc, 16, pivc, bad);
-  VPL_DSTEP(0) VPL_DSTEP(1) VPL_DSTEP(2) VPL_DSTEP(3) VPL_DSTEP(4) VPL_DSTEP(5) VPL_DSTEP(6) VPL_DSTEP(7)
-  VPL_DSTEP(8) VPL_DSTEP(9) VPL_DSTEP(10) VPL_DSTEP(11) VPL_DSTEP(12) VPL_DSTEP(13) VPL_DSTEP(14) VPL_DSTEP(15)
-#undef VPL_DSTEP
+  diag_tile_factor(d, m, r4, cc, 16, pivc, bad);
   if (bad) return false;
   const double sq = sqrt(pivc), isq = 1.0 / sq;       // pivot of column cc
 #pragma unroll

@@ -40,6 +40,180 @@ __device__ __forceinline__ int tix(int r, int c) {
 }
 typedef double v4d __attribute__((ext_vector_type(4)));
 
+// Left-looking Cholesky of the tile-major lower system S (nt tile rows of 16x16 tiles; diagonal tiles kept as full squares)
+// by nwv waves.  Row n (inside the last tile row) is the rhs and rides along: forward substitution for free.  Per tile
+// column K:
+//   (a) C(I,K) -= sum_{J<K} L(I,J) L(K,J)^T  on the FP64 matrix cores, accumulator in registers
+//   (b) factor the diagonal tile (wave 0, 16 column steps in registers)
+//   (c) tiles below: X = A(I,K) L(K,K)^-T as one matrix-core product with L(K,K)^-1
+// Leaves L in S and 1 / L_jj in isd (16 nt); Linv (256) is the work tile of (c).  wv is the wave's role (0 .. nwv-1), not
+// necessarily its index in the work-group.  Every thread of the work-group calls it.  A non-positive pivot sets flag[0] and
+// makes it return false.  Diagnostic builds (VPL_STAMPS) store the cycles of (a), (b), (c) and of the 16 column steps alone
+// to stamps[0..3] unless stamps is nullptr.
+// The sizes are arguments, not template parameters: callers pass constants, which fold once the body is inlined.  As a
+// template the body was optimised on its own first, and k_solve came out with 13 more spilled VGPRs.
+__device__ __forceinline__ bool tile_cholesky(double* S, double* Linv, double* isd, int* flag, int nt, int n, int nwv, int lane, int wv,
+                                              long long* stamps) {
+  auto rank_update = [&](int col, int I, int J0, int J1) {
+    const int m = lane & 15, kk = lane >> 4;
+    double* Ct = S + ((I * (I + 1) / 2 + col) << 8);
+    v4d c;
+    c.x = Ct[tsw(kk, m)]; c.y = Ct[tsw(kk + 4, m)]; c.z = Ct[tsw(kk + 8, m)]; c.w = Ct[tsw(kk + 12, m)];
+    for (int J = J0; J < J1; ++J) {
+      const double* Ai = S + ((I * (I + 1) / 2 + J) << 8);
+      const double* Bk = S + ((col * (col + 1) / 2 + J) << 8);
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        const double av = -Ai[tsw(m, 4 * ks + kk)];
+        const double bv = Bk[tsw(m, 4 * ks + kk)];
+        c = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, c, 0, 0, 0);
+      }
+    }
+    Ct[tsw(kk, m)] = c.x; Ct[tsw(kk + 4, m)] = c.y; Ct[tsw(kk + 8, m)] = c.z; Ct[tsw(kk + 12, m)] = c.w;
+  };
+#ifdef VPL_STAMPS
+  long long ta = 0, tb = 0, tc = 0, td = 0, t0 = __builtin_readcyclecounter();
+#endif
+  for (int K = 0; K < nt; ++K) {
+    // C(I,K) -= sum_{J<K} L(I,J) L(K,J)^T is applied in parts: the terms J < K-1 by the idle waves while wave 0 factored
+    // the previous diagonal tile (look-ahead); the term J = K-1 of the diagonal tile by wave 0 at the end of the previous
+    // solve phase, of the tiles below it by the idle waves while wave 0 factors this diagonal tile.  Two barriers per
+    // tile column.  The order of the terms, and therefore every bit of the result, is the one of a single pass.
+#ifdef VPL_STAMPS
+    { const long long t1 = __builtin_readcyclecounter(); ta += t1 - t0; t0 = t1; }
+#endif
+    if (wv == 0) {
+      // Diagonal tile in registers: lane (r4, cc) holds rows r4, r4+4, r4+8, r4+12 of column cc of the (symmetric)
+      // tile.  Per column step the pivot comes by v_readlane, the pivot column of the lane's rows by ds_swizzle inside
+      // its 16-lane row group, the pivot row entry D[j][cc] (= D[cc][j]) by one ds_bpermute -- no LDS round trips.
+      double* D = S + ((K * (K + 1) / 2 + K) << 8);
+      const int r4 = lane >> 4, cc = lane & 15;
+      double d[4];
+#pragma unroll
+      for (int v = 0; v < 4; ++v) d[v] = D[tsw(r4 + 4 * v, cc)];
+      const int ncol = min(16, n - 16 * K);
+      double pivc = 1.0;
+      bool bad = false;
+      double m[4];
+#pragma unroll
+      for (int v = 0; v < 4; ++v) m[v] = (r4 + 4 * v == cc) ? 1.0 : 0.0;
+#ifdef VPL_STAMPS
+      const long long td0 = __builtin_readcyclecounter();
+#endif
+      diag_tile_factor(d, m, r4, cc, ncol, pivc, bad);
+#ifdef VPL_STAMPS
+      td += __builtin_readcyclecounter() - td0;
+#endif
+      if (bad) {
+        if (lane == 0) flag[0] = 1;
+      } else {
+        // scale columns: L_ij = a_ij / sqrt(a_jj); publish 1/L_jj
+        const double sq = sqrt(pivc);
+        if (cc < ncol) {
+#pragma unroll
+          for (int v = 0; v < 4; ++v) {
+            const int r = r4 + 4 * v;
+            if (r > cc) D[tsw(r, cc)] = d[v] / sq;
+            else if (r == cc) { const double id = 1.0 / sq; isd[16 * K + cc] = id; D[tsw(r, cc)] = 1.0 / id; }
+          }
+        }
+        if (K < nt - 1) {
+          // L^-1 = diag(1 / sqrt(pivot)) m for the tiles below (ncol == 16 here); 1/sqrt(pivot of row r) sits in lane r
+          const double isq = 1.0 / sq;
+#pragma unroll
+          for (int v = 0; v < 4; ++v) {
+            const int r = r4 + 4 * v;
+            const double ir = __shfl(isq, r, 64);
+            Linv[tsw(r, cc)] = cc <= r ? m[v] * ir : 0.0;
+          }
+        }
+      }
+    } else if (K >= 1) {
+      // Meanwhile the other waves (i) finish tile column K below the diagonal tile with its last term J = K-1 (the
+      // diagonal tile itself got that term from wave 0 in the previous solve phase, below) and (ii) look ahead: the
+      // finished columns J < K are subtracted from tile column K+1.
+      for (int I = K + 1 + (wv - 1); I < nt; I += nwv - 1) rank_update(K, I, K - 1, K);
+      if (K + 1 < nt)
+        for (int I = K + 1 + (wv - 1); I < nt; I += nwv - 1) rank_update(K + 1, I, 0, K);
+    }
+    __syncthreads();
+#ifdef VPL_STAMPS
+    { const long long t1 = __builtin_readcyclecounter(); tb += t1 - t0; t0 = t1; }
+#endif
+    if (flag[0]) break;
+    // tiles below the diagonal tile (the rhs row is in the last tile row): X = A(I,K) L(K,K)^-T = A(I,K) Linv^T on the
+    // matrix cores, X[m][n] = sum_k A[m][k] Linv[n][k]
+    for (int I = K + 1 + wv; I < nt; I += nwv) {
+      const int m = lane & 15, kk = lane >> 4;
+      double* At = S + ((I * (I + 1) / 2 + K) << 8);
+      v4d c = {0.0, 0.0, 0.0, 0.0};
+      double av[4], bv[4];
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) { av[ks] = At[tsw(m, 4 * ks + kk)]; bv[ks] = Linv[tsw(m, 4 * ks + kk)]; }
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) c = __builtin_amdgcn_mfma_f64_16x16x4f64(av[ks], bv[ks], c, 0, 0, 0);
+      At[tsw(kk, m)] = c.x; At[tsw(kk + 4, m)] = c.y; At[tsw(kk + 8, m)] = c.z; At[tsw(kk + 12, m)] = c.w;
+      if (I == K + 1) {
+        // wave 0 has just made L(K+1, K): it gives the next diagonal tile its last term right away, so that the
+        // factorisation of D(K+1) starts after this phase's barrier instead of after an update phase of its own
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        rank_update(K + 1, K + 1, K, K + 1);
+      }
+    }
+    __syncthreads();
+#ifdef VPL_STAMPS
+    { const long long t1 = __builtin_readcyclecounter(); tc += t1 - t0; t0 = t1; }
+#endif
+  }
+#ifdef VPL_STAMPS
+  if (stamps && wv == 0 && lane == 0) { stamps[0] = ta; stamps[1] = tb; stamps[2] = tc; stamps[3] = td; }
+#endif
+  __syncthreads();
+  return flag[0] == 0;
+}
+
+// Back substitution L^T y = z after tile_cholesky: z is the rhs row n of S (16 nt entries into yv, zero past n), y
+// overwrites it.  Tile by tile from the bottom: the diagonal tile is solved by wave 0 (16 dependent register steps), the
+// update z_J -= L(K,J)^T y_K is spread over the T threads of the work-group.
+__device__ __forceinline__ void tile_back_substitute(const double* S, const double* isd, double* yv, int nt, int n, int tid, int T, int lane,
+                                                     int wv) {
+  for (int c = tid; c < 16 * nt; c += T) yv[c] = c < n ? S[tix(n, c)] : 0.0;
+  __syncthreads();
+  for (int K = nt - 1; K >= 0; --K) {
+    const double* D = S + ((K * (K + 1) / 2 + K) << 8);
+    if (wv == 0) {
+      // diagonal tile: lane i keeps y_i in a register and has its column L[j][i] preloaded; the 16 dependent steps are
+      // a v_readlane + two multiplies each (no LDS round trip inside the chain)
+      const int ncol = min(16, n - 16 * K);
+      double yl = lane < 16 ? yv[16 * K + lane] : 0.0;
+      const double isdl = lane < ncol ? isd[16 * K + lane] : 0.0;
+      double Lcol[16];
+#pragma unroll
+      for (int j = 0; j < 16; ++j) Lcol[j] = (lane < j && j < ncol) ? D[tsw(j, lane & 15)] : 0.0;
+#pragma unroll
+      for (int j = 15; j >= 0; --j) {
+        if (j < ncol) {
+          const double yj = readlane_f64(yl, j) * readlane_f64(isdl, j);
+          if (lane < j) yl -= Lcol[j] * yj;
+          if (lane == j) yl = yj;
+        }
+      }
+      if (lane < ncol) yv[16 * K + lane] = yl;
+    }
+    __syncthreads();
+    for (int c = tid; c < 16 * K; c += T) {
+      const double* Lk = S + ((K * (K + 1) / 2 + (c >> 4)) << 8);
+      double s2 = 0.0;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) s2 += Lk[tsw(r, c & 15)] * yv[16 * K + r];
+      yv[c] -= s2;
+    }
+    __syncthreads();
+  }
+}
+
 // Compact "vis" system used by the Schur accumulation: 72 vis dims + rhs column (72) + Cauchy
 // column (73), padded to 80 = 5 tiles of 16.  15 lower tiles live in MFMA accumulators.
 constexpr int CW = 80;             // staged row width (doubles)
@@ -472,132 +646,9 @@ __device__ __forceinline__ void solve_body(const DevBatch& B, const int w, doubl
       alpha = a1 / (q + qq);   // DoglegStrategy::ComputeCauchyPoint
       __syncthreads();
       VPL_STAMP(B, w, 3);
-      // ---- left-looking tile Cholesky (16x16 tiles).  Per tile column K:
-      //   (a) C(I,K) -= sum_{J<K} L(I,J) L(K,J)^T  on the FP64 matrix cores, accumulator in registers
-      //   (b) factor the diagonal tile (one wave, 16 column steps)
-      //   (c) rows below: x = a L(K,K)^-T, one lane per row
-      // The rhs row (row NC, inside tile row 10) rides along: forward substitution for free.
-#ifdef VPL_STAMPS
-      long long ta = 0, tb = 0, tc = 0, td = 0, t0 = __builtin_readcyclecounter();
-#endif
-      for (int K = 0; K < NT16; ++K) {
-        // C(I,K) -= sum_{J<K} L(I,J) L(K,J)^T is applied in parts: the terms J < K-1 by the idle waves while wave 0 factored
-        // the previous diagonal tile (look-ahead); the term J = K-1 of the diagonal tile by wave 0 at the end of the previous
-        // solve phase, of the tiles below it by the idle waves while wave 0 factors this diagonal tile.  Two barriers per
-        // tile column.  The order of the terms, and therefore every bit of the result, is the one of a single pass.
-        auto rank_update = [&](int col, int I, int J0, int J1) {
-          const int m = lane & 15, kk = lane >> 4;
-          double* Ct = S + ((I * (I + 1) / 2 + col) << 8);
-          v4d c;
-          c.x = Ct[tsw(kk, m)]; c.y = Ct[tsw(kk + 4, m)]; c.z = Ct[tsw(kk + 8, m)]; c.w = Ct[tsw(kk + 12, m)];
-          for (int J = J0; J < J1; ++J) {
-            const double* Ai = S + ((I * (I + 1) / 2 + J) << 8);
-            const double* Bk = S + ((col * (col + 1) / 2 + J) << 8);
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-              const double av = -Ai[tsw(m, 4 * ks + kk)];
-              const double bv = Bk[tsw(m, 4 * ks + kk)];
-              c = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, c, 0, 0, 0);
-            }
-          }
-          Ct[tsw(kk, m)] = c.x; Ct[tsw(kk + 4, m)] = c.y; Ct[tsw(kk + 8, m)] = c.z; Ct[tsw(kk + 12, m)] = c.w;
-        };
-#ifdef VPL_STAMPS
-        { const long long t1 = __builtin_readcyclecounter(); ta += t1 - t0; t0 = t1; }
-#endif
-        if (wv == 0) {
-          // Diagonal tile in registers: lane (r4, cc) holds rows r4, r4+4, r4+8, r4+12 of column cc of the (symmetric)
-          // tile.  Per column step the pivot comes by v_readlane, the pivot column of the lane's rows by ds_swizzle inside
-          // its 16-lane row group, the pivot row entry D[j][cc] (= D[cc][j]) by one ds_bpermute -- no LDS round trips.
-          double* D = S + ((K * (K + 1) / 2 + K) << 8);
-          const int r4 = lane >> 4, cc = lane & 15;
-          double d[4];
-#pragma unroll
-          for (int v = 0; v < 4; ++v) d[v] = D[tsw(r4 + 4 * v, cc)];
-          const int ncol = min(16, NC - 16 * K);
-          double pivc = 1.0;
-          bool bad = false;
-          double m[4];
-#pragma unroll
-          for (int v = 0; v < 4; ++v) m[v] = (r4 + 4 * v == cc) ? 1.0 : 0.0;
-#ifdef VPL_STAMPS
-          const long long td0 = __builtin_readcyclecounter();
-#endif
-#define VPL_DSTEP(J) diag_tile_step<J>(d, m, r4, cc, ncol, pivc, bad);
-          VPL_DSTEP(0) VPL_DSTEP(1) VPL_DSTEP(2) VPL_DSTEP(3) VPL_DSTEP(4) VPL_DSTEP(5) VPL_DSTEP(6) VPL_DSTEP(7)
-          VPL_DSTEP(8) VPL_DSTEP(9) VPL_DSTEP(10) VPL_DSTEP(11) VPL_DSTEP(12) VPL_DSTEP(13) VPL_DSTEP(14) VPL_DSTEP(15)
-#undef VPL_DSTEP
-#ifdef VPL_STAMPS
-          td += __builtin_readcyclecounter() - td0;
-#endif
-          if (bad) {
-            if (lane == 0) flag[0] = 1;
-          } else {
-            // scale columns: L_ij = a_ij / sqrt(a_jj); publish 1/L_jj
-            const double sq = sqrt(pivc);
-            if (cc < ncol) {
-#pragma unroll
-              for (int v = 0; v < 4; ++v) {
-                const int r = r4 + 4 * v;
-                if (r > cc) D[tsw(r, cc)] = d[v] / sq;
-                else if (r == cc) { const double id = 1.0 / sq; isd[16 * K + cc] = id; D[tsw(r, cc)] = 1.0 / id; }
-              }
-            }
-            if (K < NT16 - 1) {
-              // L^-1 = diag(1 / sqrt(pivot)) m for the tiles below (ncol == 16 here); 1/sqrt(pivot of row r) sits in lane r
-              const double isq = 1.0 / sq;
-#pragma unroll
-              for (int v = 0; v < 4; ++v) {
-                const int r = r4 + 4 * v;
-                const double ir = __shfl(isq, r, 64);
-                Linv[tsw(r, cc)] = cc <= r ? m[v] * ir : 0.0;
-              }
-            }
-          }
-        } else if (K >= 1) {
-          // Meanwhile the other waves (i) finish tile column K below the diagonal tile with its last term J = K-1 (the
-          // diagonal tile itself got that term from wave 0 in the previous solve phase, below) and (ii) look ahead: the
-          // finished columns J < K are subtracted from tile column K+1.
-          for (int I = K + 1 + (wv - 1); I < NT16; I += SOLVE_THREADS / 64 - 1) rank_update(K, I, K - 1, K);
-          if (K + 1 < NT16)
-            for (int I = K + 1 + (wv - 1); I < NT16; I += SOLVE_THREADS / 64 - 1) rank_update(K + 1, I, 0, K);
-        }
-        __syncthreads();
-#ifdef VPL_STAMPS
-        { const long long t1 = __builtin_readcyclecounter(); tb += t1 - t0; t0 = t1; }
-#endif
-        if (flag[0]) break;
-        // tiles below the diagonal tile (the rhs row is in tile row 10): X = A(I,K) L(K,K)^-T = A(I,K) Linv^T on the
-        // matrix cores, X[m][n] = sum_k A[m][k] Linv[n][k]
-        for (int I = K + 1 + wv; I < NT16; I += SOLVE_THREADS / 64) {
-          const int m = lane & 15, kk = lane >> 4;
-          double* At = S + ((I * (I + 1) / 2 + K) << 8);
-          v4d c = {0.0, 0.0, 0.0, 0.0};
-          double av[4], bv[4];
-#pragma unroll
-          for (int ks = 0; ks < 4; ++ks) { av[ks] = At[tsw(m, 4 * ks + kk)]; bv[ks] = Linv[tsw(m, 4 * ks + kk)]; }
-#pragma unroll
-          for (int ks = 0; ks < 4; ++ks) c = __builtin_amdgcn_mfma_f64_16x16x4f64(av[ks], bv[ks], c, 0, 0, 0);
-          At[tsw(kk, m)] = c.x; At[tsw(kk + 4, m)] = c.y; At[tsw(kk + 8, m)] = c.z; At[tsw(kk + 12, m)] = c.w;
-          if (I == K + 1) {
-            // wave 0 has just made L(K+1, K): it gives the next diagonal tile its last term right away, so that the
-            // factorisation of D(K+1) starts after this phase's barrier instead of after an update phase of its own
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-            rank_update(K + 1, K + 1, K, K + 1);
-          }
-        }
-        __syncthreads();
-#ifdef VPL_STAMPS
-        { const long long t1 = __builtin_readcyclecounter(); tc += t1 - t0; t0 = t1; }
-#endif
-      }
-#ifdef VPL_STAMPS
-      if (tid == 0) { B.dbg[(size_t)w * 64 + 40] = ta; B.dbg[(size_t)w * 64 + 41] = tb; B.dbg[(size_t)w * 64 + 42] = tc; B.dbg[(size_t)w * 64 + 43] = td; }
-#endif
-      __syncthreads();
-      if (flag[0]) {   // LINEAR_SOLVER_FAILURE: raise mu and retry from the stored linearisation
+      // ---- left-looking tile Cholesky of the reduced system; the rhs row (row NC, inside tile row 10) rides along
+      if (!tile_cholesky(S, Linv, isd, flag, NT16, NC, SOLVE_THREADS / 64, lane, wv, B.dbg + (size_t)w * 64 + 40)) {
+        // LINEAR_SOLVER_FAILURE: raise mu and retry from the stored linearisation
         mu *= kMuIncrease;
         first_attempt = false;
         __syncthreads();
@@ -623,41 +674,8 @@ __device__ __forceinline__ void solve_body(const DevBatch& B, const int w, doubl
       return;
     }
     VPL_STAMP(B, w, 4);
-    // ---- back substitution L^T y = z, tile by tile from the bottom: the diagonal tile is solved by one
-    //      wave (16 dependent register steps), the update z_J -= L(K,J)^T y_K is spread over the workgroup.
-    for (int c = tid; c < 176; c += T) yv[c] = c < NC ? S[tix(NC, c)] : 0.0;
-    __syncthreads();
-    for (int K = NT16 - 1; K >= 0; --K) {
-      const double* D = S + ((K * (K + 1) / 2 + K) << 8);
-      if (wv == 0) {
-        // diagonal tile: lane i keeps y_i in a register and has its column L[j][i] preloaded; the 16 dependent steps are
-        // a v_readlane + two multiplies each (no LDS round trip inside the chain)
-        const int ncol = min(16, NC - 16 * K);
-        double yl = lane < 16 ? yv[16 * K + lane] : 0.0;
-        const double isdl = lane < ncol ? isd[16 * K + lane] : 0.0;
-        double Lcol[16];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) Lcol[j] = (lane < j && j < ncol) ? D[tsw(j, lane & 15)] : 0.0;
-#pragma unroll
-        for (int j = 15; j >= 0; --j) {
-          if (j < ncol) {
-            const double yj = readlane_f64(yl, j) * readlane_f64(isdl, j);
-            if (lane < j) yl -= Lcol[j] * yj;
-            if (lane == j) yl = yj;
-          }
-        }
-        if (lane < ncol) yv[16 * K + lane] = yl;
-      }
-      __syncthreads();
-      for (int c = tid; c < 16 * K; c += T) {
-        const double* Lk = S + ((K * (K + 1) / 2 + (c >> 4)) << 8);
-        double s2 = 0.0;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s2 += Lk[tsw(r, c & 15)] * yv[16 * K + r];
-        yv[c] -= s2;
-      }
-      __syncthreads();
-    }
+    // ---- back substitution L^T y = z of the reduced system
+    tile_back_substitute(S, isd, yv, NT16, NC, tid, T, lane, wv);
     VPL_STAMP(B, w, 5);
     // y_c (scaled space) in yv; uc <- S_c y_c ; gn_c = -diag y
     double a2 = 0.0, a3 = 0.0;

@@ -945,128 +945,16 @@ __device__ __forceinline__ void chol_body(const DevBatch& B, const int w, double
   __syncthreads();
   VPL_STAMP(B, w, 10);
 
-  // ================= phase 3: left-looking tile Cholesky of the dense system (the scheme of ba_solve.h, 6 tile columns,
-  // 4 waves); the rhs row rides along ===================================================================================
-  {
-    constexpr int NWV = CHOL_THREADS / 64;
-    for (int K = 0; K < DNT; ++K) {
-      auto rank_update = [&](int col, int I, int J0, int J1) {
-        const int m = lane & 15, kk = lane >> 4;
-        double* Ct = S + ((I * (I + 1) / 2 + col) << 8);
-        v4d c;
-        c.x = Ct[tsw(kk, m)]; c.y = Ct[tsw(kk + 4, m)]; c.z = Ct[tsw(kk + 8, m)]; c.w = Ct[tsw(kk + 12, m)];
-        for (int J = J0; J < J1; ++J) {
-          const double* Ai = S + ((I * (I + 1) / 2 + J) << 8);
-          const double* Bk = S + ((col * (col + 1) / 2 + J) << 8);
-#pragma unroll
-          for (int ks = 0; ks < 4; ++ks) {
-            const double av = -Ai[tsw(m, 4 * ks + kk)];
-            const double bv = Bk[tsw(m, 4 * ks + kk)];
-            c = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, c, 0, 0, 0);
-          }
-        }
-        Ct[tsw(kk, m)] = c.x; Ct[tsw(kk + 4, m)] = c.y; Ct[tsw(kk + 8, m)] = c.z; Ct[tsw(kk + 12, m)] = c.w;
-      };
-      if (wv == 0) {
-        double* D = S + ((K * (K + 1) / 2 + K) << 8);
-        const int r4 = lane >> 4, cc = lane & 15;
-        double d[4], mm[4];
-#pragma unroll
-        for (int v = 0; v < 4; ++v) { d[v] = D[tsw(r4 + 4 * v, cc)]; mm[v] = (r4 + 4 * v == cc) ? 1.0 : 0.0; }
-        const int ncol = min(16, DN - 16 * K);
-        double pivc = 1.0;
-        bool bad = false;
-#define VPL_DSTEP(J) diag_tile_step<J>(d, mm, r4, cc, ncol, pivc, bad);
-        VPL_DSTEP(0) VPL_DSTEP(1) VPL_DSTEP(2) VPL_DSTEP(3) VPL_DSTEP(4) VPL_DSTEP(5) VPL_DSTEP(6) VPL_DSTEP(7)
-        VPL_DSTEP(8) VPL_DSTEP(9) VPL_DSTEP(10) VPL_DSTEP(11) VPL_DSTEP(12) VPL_DSTEP(13) VPL_DSTEP(14) VPL_DSTEP(15)
-#undef VPL_DSTEP
-        if (bad) {
-          if (lane == 0) flag[0] = 1;
-        } else {
-          const double sq = sqrt(pivc);
-          if (cc < ncol) {
-#pragma unroll
-            for (int v = 0; v < 4; ++v) {
-              const int r = r4 + 4 * v;
-              if (r > cc) D[tsw(r, cc)] = d[v] / sq;
-              else if (r == cc) { const double id = 1.0 / sq; isd[16 * K + cc] = id; D[tsw(r, cc)] = 1.0 / id; }
-            }
-          }
-          if (K < DNT - 1) {
-            const double isq = 1.0 / sq;
-#pragma unroll
-            for (int v = 0; v < 4; ++v) {
-              const int r = r4 + 4 * v;
-              const double ir = __shfl(isq, r, 64);
-              Linv[tsw(r, cc)] = cc <= r ? mm[v] * ir : 0.0;
-            }
-          }
-        }
-      } else if (K >= 1) {
-        for (int I = K + 1 + (wv - 1); I < DNT; I += NWV - 1) rank_update(K, I, K - 1, K);
-        if (K + 1 < DNT)
-          for (int I = K + 1 + (wv - 1); I < DNT; I += NWV - 1) rank_update(K + 1, I, 0, K);
-      }
-      __syncthreads();
-      if (flag[0]) break;
-      for (int I = K + 1 + wv; I < DNT; I += NWV) {
-        const int m = lane & 15, kk = lane >> 4;
-        double* At = S + ((I * (I + 1) / 2 + K) << 8);
-        v4d c = {0.0, 0.0, 0.0, 0.0};
-        double av[4], bv[4];
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) { av[ks] = At[tsw(m, 4 * ks + kk)]; bv[ks] = Linv[tsw(m, 4 * ks + kk)]; }
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) c = __builtin_amdgcn_mfma_f64_16x16x4f64(av[ks], bv[ks], c, 0, 0, 0);
-        At[tsw(kk, m)] = c.x; At[tsw(kk + 4, m)] = c.y; At[tsw(kk + 8, m)] = c.z; At[tsw(kk + 12, m)] = c.w;
-        if (I == K + 1) {
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-          __builtin_amdgcn_wave_barrier();
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-          rank_update(K + 1, K + 1, K, K + 1);
-        }
-      }
-      __syncthreads();
-    }
-  }
-  __syncthreads();
-  if (flag[0]) {   // LINEAR_SOLVER_FAILURE: the retry with a larger mu is k_solve's loop
+  // ================= phase 3: left-looking tile Cholesky of the dense system (tile_cholesky of ba_solve.h, 6 tile columns,
+  // 4 waves); the rhs row rides along ==================================================================================
+  if (!tile_cholesky(S, Linv, isd, flag, DNT, DN, CHOL_THREADS / 64, lane, wv, nullptr)) {
+    // LINEAR_SOLVER_FAILURE: the retry with a larger mu is k_solve's loop
     if (tid == 0) B.path[w] = 2;
     return;
   }
   VPL_STAMP(B, w, 11);
   // ================= phase 4: back substitution L^T y = z of the dense part =============================================
-  for (int c = tid; c < 96; c += T) yv[c] = c < DN ? S[tix(DN, c)] : 0.0;
-  __syncthreads();
-  for (int K = DNT - 1; K >= 0; --K) {
-    const double* D = S + ((K * (K + 1) / 2 + K) << 8);
-    if (wv == 0) {
-      const int ncol = min(16, DN - 16 * K);
-      double yl = lane < 16 ? yv[16 * K + lane] : 0.0;
-      const double isdl = lane < ncol ? isd[16 * K + lane] : 0.0;
-      double Lcol[16];
-#pragma unroll
-      for (int j = 0; j < 16; ++j) Lcol[j] = (lane < j && j < ncol) ? D[tsw(j, lane & 15)] : 0.0;
-#pragma unroll
-      for (int j = 15; j >= 0; --j) {
-        if (j < ncol) {
-          const double yj = readlane_f64(yl, j) * readlane_f64(isdl, j);
-          if (lane < j) yl -= Lcol[j] * yj;
-          if (lane == j) yl = yj;
-        }
-      }
-      if (lane < ncol) yv[16 * K + lane] = yl;
-    }
-    __syncthreads();
-    for (int c = tid; c < 16 * K; c += T) {
-      const double* Lk = S + ((K * (K + 1) / 2 + (c >> 4)) << 8);
-      double s2 = 0.0;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) s2 += Lk[tsw(r, c & 15)] * yv[16 * K + r];
-      yv[c] -= s2;
-    }
-    __syncthreads();
-  }
+  tile_back_substitute(S, isd, yv, DNT, DN, tid, T, lane, wv);
   for (int d = tid; d < DN; d += T) ycam[dense2cam(d)] = yv[d];
   __syncthreads();
   VPL_STAMP(B, w, 12);
