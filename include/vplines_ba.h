@@ -358,6 +358,90 @@ int vpl_ba_marginalize_async(vpl_ctx* ctx, int n_windows, const vpl_window* wind
 /* Completes the pending asynchronous call, if any (waits for the stream, writes the results).  Returns its status. */
 int vpl_ba_collect(vpl_ctx* ctx);
 
+/* ---- keyframe session: the feature manager and the window resident on the device ---------------------------------------- *
+ * Estimator::processImage's loop (estimator.cpp:121-200, 624-648, 1731-1851) for n_seq independent sequences, one call per
+ * keyframe: the session owns what the reference's FeatureManager and window state own -- every track's observations, inverse
+ * depth, Pluecker line and triangulation flag, the 11 states, the extrinsic, the 11 pre-integrations and the last prior --
+ * in device memory, from keyframe to keyframe.  Per keyframe only the NEW frame travels host -> device (its observations, one
+ * state, one pre-integration) beside the kernels' integer layout tables, and only the result struct and a few integers per
+ * track (triangulated / erased / depth sign) and per prior block travel back.  The host keeps the integer side of the tracks
+ * (id, start, number of observations, triangulated), in insertion order (f_manager.feature is a std::list).
+ * The session borrows `ctx` (one session per context; the context's other entry points stay usable between keyframes and the
+ * prior rule set on it applies); sequence i is window i of the context's batches, so n_seq <= max_windows, and the tracks one
+ * solve takes must fit the context's max_points / max_lines / *_obs. */
+typedef struct vpl_odo vpl_odo;
+/* max_point_tracks / max_line_tracks: per sequence, ALL tracks of the feature manager, short ones included. */
+int vpl_odo_create(vpl_odo** out, vpl_ctx* ctx, int n_seq, const vpl_ba_options* opt, double init_depth, int line_min_obs,
+                   int max_point_tracks, int max_line_tracks);
+void vpl_odo_destroy(vpl_odo* odo);
+
+typedef struct vpl_odo_frame {   /* one image of one sequence, as processImage() receives it */
+  double pose[7], speed_bias[9]; /* the propagated state of the new frame (processIMU's Ps / Rs / Vs / Bas / Bgs) */
+  vpl_preintegration preint;     /* of the interval that ends in this frame (the IMU buffers stay the caller's, as for
+                                    vpl_ba_slide_window; after VPL_MARGIN_SECOND_NEW slot 9 keeps its pre-integration) */
+  int n_points; const int* point_id; const double* point_obs; /* [n][3]  x,y,1 */
+  int n_lines;  const int* line_id;  const double* line_obs;  /* [n][8]  as vpl_window.line_obs */
+} vpl_odo_frame;
+
+/* Frames 0..10 of sequence `seq` before its first keyframe (the window the initialisation hands over): states, extrinsic,
+ * pre-integrations 1..10 (entry 0 unused) and the observations frame by frame (frames[f]: n_*, *_id, *_obs only).  Replaces
+ * whatever the sequence held, its prior included. */
+int vpl_odo_set_window(vpl_odo* odo, int seq, const double pose[][7], const double speed_bias[][9], const double ex_pose[7],
+                       const vpl_preintegration* preint, const vpl_odo_frame* frames);
+
+typedef struct vpl_odo_result {  /* per sequence */
+  double pose[VPL_NFRAMES][7], speed_bias[VPL_NFRAMES][9], ex_pose[7]; /* after double2vector2, BEFORE the slide */
+  vpl_solve_report line_report, report; /* onlyLineOpt's, the solve's */
+  int n_points_solved, n_lines_solved;  /* tracks that took part in the solve */
+  int n_point_tracks, n_line_tracks;    /* tracks alive after the slide and the new frame */
+  int n_ignored;                        /* observations of an id that had been lost and came back (not continued) */
+} vpl_odo_result;
+
+/* One keyframe of every sequence: solveOdometry on the full window (points used_num >= 2 && start < WINDOW_SIZE - 2, lines
+ * used_num >= line_min_obs likewise, estimator.cpp:1100-1102, 1132-1133) -> removeFailures (solved points whose inverse depth is
+ * not > 0) and the lines the solve's removeLineOutlier erased -> slideWindow(flag) on EVERY track -> the pre-integrations move
+ * down -> next[seq] enters slot 10: an id continues its track only if the track's last observation is in slot 9, an unknown id
+ * starts a track, an id whose track has a gap is ignored and counted.
+ * marginalization_flag[seq]: VPL_MARGIN_OLD or VPL_MARGIN_SECOND_NEW; the batched solve marginalises one way per batch, so all
+ * sequences of one call carry the same flag (VPL_E_INVALID otherwise).
+ * Refusals leave the session as it was: null arrays, a flag other than the two, a sequence without a window (VPL_E_INVALID);
+ * more tracks than the capacities (VPL_E_CAPACITY) -- checked BEFORE the solve, when it is not yet known what the solve will
+ * erase: tracks alive + ids of next[seq] that belong to no track <= max_*_tracks, and the solve's selection within the context's
+ * capacities.  A non-finite measurement is not refused: the solve fails as it does elsewhere (termination 2). */
+int vpl_odo_keyframe(vpl_odo* odo, const vpl_odo_frame* next, const int* marginalization_flag, vpl_odo_result* out);
+/* The two halves of vpl_odo_keyframe, for a caller whose new frame depends on the solve -- the reference starts the new
+ * interval's pre-integration from the bias the solve has just estimated (estimator.cpp:1786-1797), so `next` cannot be complete
+ * before `out` is known:  vpl_odo_solve = solveOdometry (out: n_*_tracks as they are before the slide, n_ignored 0);
+ * vpl_odo_advance = removeFailures -> slideWindow(the solve's flag) -> next enters slot 10 (out may be NULL; n_*_tracks and
+ * n_ignored are updated).  They alternate: VPL_E_INVALID out of turn; a refused vpl_odo_advance can be repeated. */
+int vpl_odo_solve(vpl_odo* odo, const int* marginalization_flag, vpl_odo_result* out);
+int vpl_odo_advance(vpl_odo* odo, const vpl_odo_frame* next, vpl_odo_result* out);
+
+/* What a caller may want to look at; none of it is needed to keep going.  Arrays may be NULL (not wanted); the track arrays
+ * need room for max_*_tracks entries.  Tracks come in the feature manager's order. */
+int vpl_odo_get_prior(vpl_odo* odo, int seq, vpl_prior* out);   /* n = 0: no prior yet */
+int vpl_odo_get_tracks(vpl_odo* odo, int seq, int* n_points, int* point_id, int* point_start, int* point_nobs, double* inv_depth,
+                       int* n_lines, int* line_id, int* line_start, int* line_nobs, int* line_triangulated, double* line_plk);
+/* Host <-> device traffic of the last keyframe: the new frames' doubles | the integer tables (layout tables of the stages, track
+ * index tables) | everything that came back.  d2h_bytes is exact: the read-backs are packed without padding
+ * (VPL_ODO_D2H_PAD_BYTES of alignment padding). */
+#define VPL_ODO_D2H_PAD_BYTES 0
+int vpl_odo_stats(vpl_odo* odo, long long* h2d_payload_bytes, long long* h2d_table_bytes, long long* d2h_bytes);
+/* wall clock of the stages of the last keyframe in ms: triangulations | onlyLineOpt | solve | slide + new frame */
+int vpl_odo_debug_ms(vpl_odo* odo, double* ms4);
+
+/* Host only, no device call (like vpl_ba_debug_point_units): the integer bookkeeping of ONE kind of tracks of ONE sequence
+ * replayed from a script, by the code vpl_odo_keyframe runs.  Step s: flag[s] == VPL_MARGIN_NONE -- the window is still filling,
+ * the frame enters the next free slot (VPL_E_INVALID once 11 frames are in); otherwise erase[s * max_tracks + i] != 0 erases
+ * track i (standing in for the device's decisions), the slide of flag[s] runs on the rest and the frame enters slot 10
+ * (VPL_E_INVALID before 11 frames are in).  ids: the frames' ids one after the other, n_ids[s] of step s.
+ * Out, per step: status[s] = VPL_OK or VPL_E_CAPACITY (the step was refused by the rule of vpl_odo_keyframe, the table is
+ * unchanged); n_slide[s] tracks entered the slide, slide[(s * max_tracks + i) * 3 ..] = their start, nobs (0: erased), dropped
+ * observation (-1: none) as vpl_slide_tracks reports them; n_tracks[s] and table[(s * max_tracks + i) * 3 ..] = id, start, nobs
+ * after the step; ignored[s]. */
+int vpl_odo_debug_tracks(int max_tracks, int n_steps, const int* flag, const int* n_ids, const int* ids, const unsigned char* erase,
+                         int* status, int* n_slide, int* slide, int* n_tracks, int* table, int* ignored);
+
 /* ---- instrumentation (bench.py) ------------------------------------------ */
 /* Per-kernel device time of the last solve measured with hipEvents on the
  * context's stream. names/ms arrays of length *count on input; count updated. */

@@ -1,0 +1,64 @@
+"""wall time of the keyframe session (vpl_odo_solve + vpl_odo_advance) per keyframe over the sequence of
+tests/test_gpu_sequence.py -- the companion of tools/time_odometry.py, which times the same 32 keyframes through
+vpl_ba_solve_odometry + vpl_ba_slide_window with the feature manager on the host.  Medians over keyframes 4..31 of the C calls
+alone and of the stages inside them; then --batch N sequences (default 64) in one session for --batch-keyframes keyframes:
+keyframes per second.  Every C call ends in a stream synchronise, so the host clock around it is the time of the work."""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np
+import vplines_slam_amd as v
+import test_gpu_sequence as T
+import test_gpu_odo_session as S
+
+
+def run(seeds, n_keyframes):
+    opt = v.default_options()
+    n = len(seeds)
+    Ms = [T.Measurements(T.NF + n_keyframes, seed=s) for s in seeds]
+    ctx = S._ctxn(n)
+    ses = v.Session(ctx, n_seq=n, opt=opt, init_depth=5.0, line_min_obs=T.LINE_MIN_OBS, max_point_tracks=S.MAX_PT, max_line_tracks=S.MAX_LT)
+    for i, M in enumerate(Ms):
+        S.feed_window(ses, i, ctx, M, opt)
+    acc = {"solve_c_call": [], "advance_c_call": [], "stage_triangulate": [], "stage_only_line_opt": [], "stage_solve": [],
+           "stage_slide_new_frame": [], "h2d_payload_B": [], "h2d_table_B": [], "d2h_B": []}
+    for k in range(n_keyframes):
+        res = ses.solve()
+        acc["solve_c_call"].append(ses.last_call_s)
+        frames = [S.next_frame(ctx, Ms[i], T.NF + k, res[i], opt) for i in range(n)]
+        ses.advance(frames)
+        acc["advance_c_call"].append(ses.last_call_s)
+        for nm, ms in zip(("stage_triangulate", "stage_only_line_opt", "stage_solve", "stage_slide_new_frame"), ses.stage_ms()):
+            acc[nm].append(ms * 1e-3)
+        for nm, b in zip(("h2d_payload_B", "h2d_table_B", "d2h_B"), ses.stats()):
+            acc[nm].append(b)
+    ses.close()
+    ctx.close()
+    return acc
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--batch-keyframes", type=int, default=12)
+    a = ap.parse_args()
+    acc = run([77], T.N_KEYFRAMES)
+    tot = np.array(acc["solve_c_call"][4:]) + np.array(acc["advance_c_call"][4:])
+    print("keyframe_c_calls: median %.2f ms, min %.2f, max %.2f over %d keyframes (solve + advance, one sequence)"
+          % (np.median(tot) * 1e3, tot.min() * 1e3, tot.max() * 1e3, len(tot)))
+    for k, x in acc.items():
+        x = np.array(x[4:], float)
+        if k.endswith("_B"):
+            print("%s: median %d bytes per keyframe" % (k, np.median(x)))
+        else:
+            print("%s: median %.2f ms, min %.2f, max %.2f over %d keyframes" % (k, np.median(x) * 1e3, x.min() * 1e3, x.max() * 1e3, len(x)))
+    if a.batch > 1:
+        acc = run(list(range(77, 77 + a.batch)), a.batch_keyframes)
+        tot = np.array(acc["solve_c_call"][4:]) + np.array(acc["advance_c_call"][4:])
+        print("batch of %d sequences: median %.2f ms per call pair = %.0f keyframes / s (stages: %s ms)"
+              % (a.batch, np.median(tot) * 1e3, a.batch / np.median(tot),
+                 " | ".join("%.2f" % (np.median(acc[s][4:]) * 1e3) for s in ("stage_triangulate", "stage_only_line_opt", "stage_solve", "stage_slide_new_frame"))))

@@ -154,6 +154,23 @@ class Window:
         self.ex_pose[:] = np.ctypeslib.as_array(cw.ex_pose)
 
 
+class OdoFrame(C.Structure):
+    """vpl_odo_frame: one image of one sequence (the arrays are the caller's; Session keeps them alive for the call)"""
+    _fields_ = [("pose", C.c_double * 7), ("speed_bias", C.c_double * 9), ("preint", Preintegration),
+                ("n_points", C.c_int), ("point_id", _ip), ("point_obs", _dp),
+                ("n_lines", C.c_int), ("line_id", _ip), ("line_obs", _dp)]
+
+
+class OdoResult(C.Structure):
+    _fields_ = [("pose", (C.c_double * 7) * NF), ("speed_bias", (C.c_double * 9) * NF), ("ex_pose", C.c_double * 7),
+                ("line_report", SolveReport), ("report", SolveReport),
+                ("n_points_solved", C.c_int), ("n_lines_solved", C.c_int), ("n_point_tracks", C.c_int),
+                ("n_line_tracks", C.c_int), ("n_ignored", C.c_int)]
+
+
+ODO_D2H_PAD_BYTES = 0    # VPL_ODO_D2H_PAD_BYTES: the session's read-backs are packed without alignment padding
+
+
 class CSlideTracks(C.Structure):
     _fields_ = [("point_start", _ip), ("point_nobs", _ip), ("point_drop", _ip),
                 ("line_start", _ip), ("line_nobs", _ip), ("line_drop", _ip)]
@@ -232,6 +249,19 @@ def load_hip_library():
     lib.vpl_ba_enable_kernel_timing.argtypes = [vp, C.c_int]
     lib.vpl_ba_kernel_times.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_char_p), _dp, _ip]
     lib.vpl_ba_launch_profile.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_char_p), _dp, _ip]
+    lib.vpl_odo_create.argtypes = [C.POINTER(vp), vp, C.c_int, C.POINTER(BaOptions), C.c_double, C.c_int, C.c_int, C.c_int]
+    lib.vpl_odo_destroy.argtypes = [vp]
+    lib.vpl_odo_destroy.restype = None
+    lib.vpl_odo_set_window.argtypes = [vp, C.c_int, _dp, _dp, _dp, C.POINTER(Preintegration), C.POINTER(OdoFrame)]
+    lib.vpl_odo_keyframe.argtypes = [vp, C.POINTER(OdoFrame), _ip, C.POINTER(OdoResult)]
+    lib.vpl_odo_solve.argtypes = [vp, _ip, C.POINTER(OdoResult)]
+    lib.vpl_odo_advance.argtypes = [vp, C.POINTER(OdoFrame), C.POINTER(OdoResult)]
+    lib.vpl_odo_get_prior.argtypes = [vp, C.c_int, C.POINTER(Prior)]
+    lib.vpl_odo_get_tracks.argtypes = [vp, C.c_int, _ip, _ip, _ip, _ip, _dp, _ip, _ip, _ip, _ip, _ip, _dp]
+    _llp = C.POINTER(C.c_longlong)
+    lib.vpl_odo_stats.argtypes = [vp, _llp, _llp, _llp]
+    lib.vpl_odo_debug_ms.argtypes = [vp, _dp]
+    lib.vpl_odo_debug_tracks.argtypes = [C.c_int, C.c_int, _ip, _ip, _ip, C.POINTER(C.c_ubyte), _ip, _ip, _ip, _ip, _ip, _ip]
     _hip = lib
     return lib
 
@@ -525,3 +555,172 @@ class Context:
         act = (C.c_int * 256)()
         self._check(self.lib.vpl_ba_launch_profile(self.h, C.byref(cnt), names, ms, act), "vpl_ba_launch_profile")
         return [(names[i].decode(), ms[i], tuple(act[4 * i + k] for k in range(4))) for i in range(cnt.value)]
+
+
+class Frame:
+    """One image of one sequence for Session: the propagated state, the pre-integration of the interval that ends in it and
+    its observations -- point_obs [n][3] (x, y, 1) and line_obs [n][8] (as Window.line_obs) with their feature ids."""
+
+    def __init__(self, point_id=(), point_obs=(), line_id=(), line_obs=(), pose=None, speed_bias=None, preint=None):
+        self.point_id = _arr(point_id, np.int32).reshape(-1)
+        self.point_obs = _arr(point_obs, np.float64).reshape(-1, 3)
+        self.line_id = _arr(line_id, np.int32).reshape(-1)
+        self.line_obs = _arr(line_obs, np.float64).reshape(-1, 8)
+        assert len(self.point_id) == len(self.point_obs) and len(self.line_id) == len(self.line_obs)
+        self.pose = None if pose is None else _arr(pose, np.float64).reshape(7)
+        self.speed_bias = None if speed_bias is None else _arr(speed_bias, np.float64).reshape(9)
+        self.preint = preint
+
+    def to_c(self, cf):
+        if self.pose is not None:
+            C.memmove(cf.pose, self.pose.ctypes.data, 56)
+        if self.speed_bias is not None:
+            C.memmove(cf.speed_bias, self.speed_bias.ctypes.data, 72)
+        if self.preint is not None:
+            C.memmove(C.byref(cf.preint), C.byref(self.preint), C.sizeof(Preintegration))
+        cf.n_points, cf.n_lines = len(self.point_id), len(self.line_id)
+        cf.point_id, cf.point_obs = self.point_id.ctypes.data_as(_ip), self.point_obs.ctypes.data_as(_dp)
+        cf.line_id, cf.line_obs = self.line_id.ctypes.data_as(_ip), self.line_obs.ctypes.data_as(_dp)
+
+
+class Session:
+    """vpl_odo: the feature manager and the window of n_seq sequences resident on the device, fed one keyframe at a time
+    (include/vplines_ba.h, "keyframe session").  Borrows `ctx` (one session per context) or makes a context of its own from
+    ctx_args -- which fails loudly without a GPU, like Context."""
+
+    def __init__(self, ctx=None, n_seq=1, opt=None, init_depth=5.0, line_min_obs=5, max_point_tracks=1024, max_line_tracks=512,
+                 **ctx_args):
+        self.own_ctx = ctx is None
+        if ctx is None:
+            ctx_args.setdefault("max_windows", n_seq)
+            ctx = Context(**ctx_args)
+        self.ctx, self.lib, self.n_seq = ctx, ctx.lib, n_seq
+        self.max_point_tracks, self.max_line_tracks = max_point_tracks, max_line_tracks
+        opt = opt if opt is not None else default_options()
+        self.h = C.c_void_p()
+        ctx._settle()
+        rc = self.lib.vpl_odo_create(C.byref(self.h), ctx.h, n_seq, C.byref(opt), init_depth, line_min_obs, max_point_tracks,
+                                     max_line_tracks)
+        if rc != 0:
+            msg = self.lib.vpl_last_error(ctx.h)
+            raise RuntimeError("vpl_odo_create failed (%d): %s" % (rc, msg.decode() if msg else ""))
+
+    def close(self):
+        if self.h:
+            self.lib.vpl_odo_destroy(self.h)
+            self.h = C.c_void_p()
+        if self.own_ctx and self.ctx is not None:
+            self.ctx.close()
+            self.ctx = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_window(self, seq, pose, speed_bias, ex_pose, preint, frames):
+        """frames 0..10 of sequence seq: states [11][7] / [11][9], extrinsic, (Preintegration * 11) (entry 0 unused) and 11
+        Frames (observations only)"""
+        pose, sb, ex = _arr(pose, np.float64).reshape(NF, 7), _arr(speed_bias, np.float64).reshape(NF, 9), _arr(ex_pose, np.float64).reshape(7)
+        assert len(frames) == NF
+        cf = (OdoFrame * NF)()
+        for i, f in enumerate(frames):
+            f.to_c(cf[i])
+        self.ctx._settle()
+        self.ctx._check(self.lib.vpl_odo_set_window(self.h, seq, _p(pose), _p(sb), _p(ex), preint, cf), "vpl_odo_set_window")
+
+    def keyframe(self, frames, flags=None):
+        """vpl_odo_keyframe: solveOdometry -> removeFailures -> slideWindow(flag) -> the Frames enter slot 10; one
+        OdoResult per sequence (states BEFORE the slide)"""
+        assert len(frames) == self.n_seq
+        cf = (OdoFrame * self.n_seq)()
+        for i, f in enumerate(frames):
+            f.to_c(cf[i])
+        fl = _arr([MARGIN_OLD] * self.n_seq if flags is None else flags, np.int32)
+        assert len(fl) == self.n_seq
+        res = (OdoResult * self.n_seq)()
+        self.ctx._settle()
+        t0 = time.perf_counter()
+        rc = self.lib.vpl_odo_keyframe(self.h, cf, fl.ctypes.data_as(_ip), res)
+        self.last_call_s = time.perf_counter() - t0      # the C call alone (tools/time_session.py)
+        self.last_rc = rc
+        self.ctx._check(rc, "vpl_odo_keyframe")
+        return res
+
+    def solve(self, flags=None):
+        """vpl_odo_solve: the first half of keyframe (solveOdometry); the Frames of advance may be built from its results"""
+        fl = _arr([MARGIN_OLD] * self.n_seq if flags is None else flags, np.int32)
+        assert len(fl) == self.n_seq
+        self._res = (OdoResult * self.n_seq)()
+        self.ctx._settle()
+        t0 = time.perf_counter()
+        rc = self.lib.vpl_odo_solve(self.h, fl.ctypes.data_as(_ip), self._res)
+        self.last_call_s = time.perf_counter() - t0
+        self.last_rc = rc
+        self.ctx._check(rc, "vpl_odo_solve")
+        return self._res
+
+    def advance(self, frames):
+        """vpl_odo_advance: removeFailures -> slideWindow -> the Frames enter slot 10; updates the counts of solve's results"""
+        assert len(frames) == self.n_seq
+        cf = (OdoFrame * self.n_seq)()
+        for i, f in enumerate(frames):
+            f.to_c(cf[i])
+        self.ctx._settle()
+        t0 = time.perf_counter()
+        rc = self.lib.vpl_odo_advance(self.h, cf, getattr(self, "_res", None))
+        self.last_call_s = time.perf_counter() - t0
+        self.last_rc = rc
+        self.ctx._check(rc, "vpl_odo_advance")
+        return self._res
+
+    def get_prior(self, seq=0):
+        p = Prior()
+        self.ctx._check(self.lib.vpl_odo_get_prior(self.h, seq, C.byref(p)), "vpl_odo_get_prior")
+        return p
+
+    def get_tracks(self, seq=0):
+        """dict: point_id / point_start / point_nobs / inv_depth, line_id / line_start / line_nobs / line_triangulated / line_plk,
+        in the feature manager's order"""
+        mp, ml = self.max_point_tracks, self.max_line_tracks
+        n = (C.c_int * 2)()
+        pi, ps, pn = (np.zeros(mp, np.int32) for _ in range(3))
+        li, ls, ln, lt = (np.zeros(ml, np.int32) for _ in range(4))
+        invd, plk = np.zeros(mp), np.zeros((ml, 6))
+        ip = lambda a: a.ctypes.data_as(_ip)
+        rc = self.lib.vpl_odo_get_tracks(self.h, seq, C.cast(C.byref(n, 0), _ip), ip(pi), ip(ps), ip(pn), _p(invd),
+                                         C.cast(C.byref(n, 4), _ip), ip(li), ip(ls), ip(ln), ip(lt), _p(plk))
+        self.ctx._check(rc, "vpl_odo_get_tracks")
+        a, b = n[0], n[1]
+        return dict(point_id=pi[:a], point_start=ps[:a], point_nobs=pn[:a], inv_depth=invd[:a], line_id=li[:b],
+                    line_start=ls[:b], line_nobs=ln[:b], line_triangulated=lt[:b], line_plk=plk[:b])
+
+    def stats(self):
+        """(h2d_payload_bytes, h2d_table_bytes, d2h_bytes) of the last keyframe"""
+        a, b, c = C.c_longlong(), C.c_longlong(), C.c_longlong()
+        self.ctx._check(self.lib.vpl_odo_stats(self.h, C.byref(a), C.byref(b), C.byref(c)), "vpl_odo_stats")
+        return a.value, b.value, c.value
+
+    def stage_ms(self):
+        """wall clock of the last keyframe's stages: triangulations | onlyLineOpt | solve | slide + new frame"""
+        ms = np.zeros(4)
+        self.ctx._check(self.lib.vpl_odo_debug_ms(self.h, _p(ms)), "vpl_odo_debug_ms")
+        return ms
+
+
+def odo_debug_tracks(max_tracks, flags, frames_ids, erase):
+    """vpl_odo_debug_tracks (host only): flags [n_steps], frames_ids: list of id lists, erase [n_steps][max_tracks] uint8.
+    Returns rc, status, n_slide, slide [n][max][3], n_tracks, table [n][max][3], ignored"""
+    lib = load_hip_library()
+    n = len(flags)
+    fl = _arr(flags, np.int32)
+    n_ids = _arr([len(f) for f in frames_ids], np.int32)
+    ids = _arr([i for f in frames_ids for i in f] + [0], np.int32)
+    er = _arr(erase, np.uint8).reshape(n, max_tracks)
+    status, n_slide, n_tracks, ignored = (np.zeros(max(n, 1), np.int32) for _ in range(4))
+    slide, table = (np.full((max(n, 1), max_tracks, 3), -7, np.int32) for _ in range(2))
+    ip = lambda a: a.ctypes.data_as(_ip)
+    rc = lib.vpl_odo_debug_tracks(max_tracks, n, ip(fl), ip(n_ids), ip(ids), er.ctypes.data_as(C.POINTER(C.c_ubyte)), ip(status),
+                                  ip(n_slide), ip(slide), ip(n_tracks), ip(table), ip(ignored))
+    return rc, status[:n], n_slide[:n], slide[:n], n_tracks[:n], table[:n], ignored[:n]

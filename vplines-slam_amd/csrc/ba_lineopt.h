@@ -154,6 +154,32 @@ __global__ __launch_bounds__(128) void k_triangulate_points(DevBatch B, double i
 // FeatureManager::removeBackShiftDepth (feature_manager.cpp:800-874), the arithmetic: one lane per track that started in
 // the marginalised frame and survives.  fr: per window pose[0], pose[1] (before the shift) and ex_pose, 21 doubles.
 // Points pd[i] = {u, v, 1, inv_depth} -> inv_depth in the next frame; lines ld[i] = plk -> plk_to_pose(plk, Rji, tji).
+// (the arithmetic as device functions: k_slide_shift works on gathered copies, k_odo_slide of ba_odo.h in place on a session's store)
+struct SlideFrames {   // camera frames of window frame 0 (marginalised) and frame 1 (the new frame 0)
+  M3 marg_R, new_R;
+  V3 marg_P, new_P;
+};
+__device__ inline SlideFrames slide_frames(const double* f) {
+  const M3 ric = qmat(qnormalized(qpose(f + 14)));
+  const V3 tic{f[14], f[15], f[16]};
+  const M3 Rs0 = qmat(qnormalized(qpose(f))), Rs1 = qmat(qnormalized(qpose(f + 7)));
+  SlideFrames F;
+  F.marg_R = mul(Rs0, ric); F.new_R = mul(Rs1, ric);
+  F.marg_P = V3{f[0], f[1], f[2]} + mul(Rs0, tic); F.new_P = V3{f[7], f[8], f[9]} + mul(Rs1, tic);
+  return F;
+}
+__device__ inline double slide_point_invd(const SlideFrames& F, double u, double v, double one, double invd, double init_depth) {
+  const double depth = 1.0 / invd;
+  const V3 pts_i = V3{u, v, one} * depth;
+  const V3 w_pts_i = mul(F.marg_R, pts_i) + F.marg_P;
+  const V3 pts_j = mulT(F.new_R, w_pts_i - F.new_P);
+  return 1.0 / (pts_j.z > 0 ? pts_j.z : init_depth);
+}
+__device__ inline Plk slide_line_plk(const SlideFrames& F, const Plk& L) {
+  const M3 Rji = mulTA(F.new_R, F.marg_R);
+  const V3 tji = mulT(F.new_R, F.marg_P - F.new_P);
+  return plk_to_pose(L, Rji, tji);
+}
 __global__ __launch_bounds__(256) void k_slide_shift(const double* __restrict__ fr, int nPts, const int* __restrict__ pw,
                                                      double* __restrict__ pd, int nLns, const int* __restrict__ lw,
                                                      double* __restrict__ ld, double init_depth) {
@@ -161,24 +187,13 @@ __global__ __launch_bounds__(256) void k_slide_shift(const double* __restrict__ 
   if (i >= nPts + nLns) return;
   const bool is_pt = i < nPts;
   const int k = is_pt ? i : i - nPts;
-  const double* f = fr + (size_t)(is_pt ? pw[k] : lw[k]) * 21;
-  const M3 ric = qmat(qnormalized(qpose(f + 14)));
-  const V3 tic{f[14], f[15], f[16]};
-  const M3 Rs0 = qmat(qnormalized(qpose(f))), Rs1 = qmat(qnormalized(qpose(f + 7)));
-  const M3 marg_R = mul(Rs0, ric), new_R = mul(Rs1, ric);
-  const V3 marg_P = V3{f[0], f[1], f[2]} + mul(Rs0, tic), new_P = V3{f[7], f[8], f[9]} + mul(Rs1, tic);
+  const SlideFrames F = slide_frames(fr + (size_t)(is_pt ? pw[k] : lw[k]) * 21);
   if (is_pt) {
     double* d = pd + (size_t)k * 4;
-    const double depth = 1.0 / d[3];
-    const V3 pts_i = V3{d[0], d[1], d[2]} * depth;
-    const V3 w_pts_i = mul(marg_R, pts_i) + marg_P;
-    const V3 pts_j = mulT(new_R, w_pts_i - new_P);
-    d[3] = 1.0 / (pts_j.z > 0 ? pts_j.z : init_depth);
+    d[3] = slide_point_invd(F, d[0], d[1], d[2], d[3], init_depth);
   } else {
     double* d = ld + (size_t)k * 6;
-    const M3 Rji = mulTA(new_R, marg_R);
-    const V3 tji = mulT(new_R, marg_P - new_P);
-    const Plk L = plk_to_pose(Plk{V3{d[0], d[1], d[2]}, V3{d[3], d[4], d[5]}}, Rji, tji);
+    const Plk L = slide_line_plk(F, Plk{V3{d[0], d[1], d[2]}, V3{d[3], d[4], d[5]}});
     d[0] = L.n.x; d[1] = L.n.y; d[2] = L.n.z; d[3] = L.v.x; d[4] = L.v.y; d[5] = L.v.z;
   }
 }

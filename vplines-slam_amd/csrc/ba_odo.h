@@ -1,0 +1,342 @@
+// Device side of a keyframe session (include/vplines_ba.h, vpl_odo_*): the feature manager's observations, inverse depths,
+// Pluecker lines and triangulation flags, the 11 states, the extrinsic and the 11 pre-integrations of n_seq sequences stay in
+// HBM from keyframe to keyframe (OdoStore); these kernels move them between the store and the batch (DevBatch) the existing
+// stages work on.  All of them are small and memory bound: one work-group column per sequence, plain loads and stores.
+//
+// Store layout: a track owns a fixed slot of 11 observation records (a track never holds more than the window's 11 frames), so
+// the track's index in the host's book (odo_tracks.h) is its address and no observation offsets have to be kept or compacted:
+//   pobs [seq][maxPT][11][3]   lobs [seq][maxLT][11][8] (64-byte records)   invd [seq][maxPT]   plk [seq][maxLT][6]   tri [seq][maxLT]
+// Records are read and written whole by consecutive lanes of consecutive doubles (the loops below run over doubles, not over
+// records), so a wave touches contiguous 512-byte runs whatever the record size.
+// The slide reads one store and writes the other (the host swaps them): a stable compaction in place would have track j's
+// writer race track j's reader.
+#pragma once
+#include "ba_types.h"
+#include "ba_lineopt.h"
+#include "vplines_ba.h"
+
+namespace vpl {
+
+constexpr int ODO_THREADS = 256;
+constexpr int ODO_PRE_D = sizeof(DevPreint) / 8;            // a DevPreint is all doubles
+constexpr int ODO_RAW_PRE_D = sizeof(vpl_preintegration) / 8;
+
+struct OdoStore {
+  double *pobs, *lobs, *invd, *plk;
+  int* tri;
+  double *pose, *sb, *ex;   // [seq][77] [seq][99] [seq][7]
+  DevPreint* pre;           // [seq][11]
+  int maxPT, maxLT;
+};
+
+// The prior a session keeps between keyframes (the marginalisation's output, device to device)
+struct OdoPrior {
+  double *J0, *r0, *x0;     // [seq][MAXKEEP^2] compact n x n, [seq][MAXKEEP], [seq][MAXPB * 9]
+};
+
+// ---- store -> batch: exactly what pack_window + the upload's copy put there for the equivalent vpl_window ---------------
+// psrc [W][maxP], lsrc [W][maxL]: selected track (device line) -> store track.  The integer tables (nP, nL, pt_*, ln_*, lo_ln,
+// nLO) have been uploaded by the host before this runs.
+__global__ __launch_bounds__(ODO_THREADS) void k_odo_gather(DevBatch B, OdoStore S, const int* __restrict__ psrc,
+                                                            const int* __restrict__ lsrc) {
+  const int w = blockIdx.x, tid = threadIdx.x;
+  const int nP = B.nP[w], nL = B.nL[w];
+  for (int i = tid; i < 77; i += ODO_THREADS) { const double v = S.pose[w * 77 + i]; B.pose[w * 77 + i] = v; B.pose_0[w * 77 + i] = v; }
+  for (int i = tid; i < 99; i += ODO_THREADS) { const double v = S.sb[w * 99 + i]; B.sb[w * 99 + i] = v; B.sb_0[w * 99 + i] = v; }
+  for (int i = tid; i < 7; i += ODO_THREADS) { const double v = S.ex[w * 7 + i]; B.ex[w * 7 + i] = v; B.ex_0[w * 7 + i] = v; }
+  for (int i = tid; i < 13; i += ODO_THREADS) B.fail_ref[w * 13 + i] = 0.0;
+  for (int i = tid; i < B.maxL * 4; i += ODO_THREADS) B.orth[(size_t)w * B.maxL * 4 + i] = 0.0;
+  {
+    const double* src = reinterpret_cast<const double*>(S.pre + (size_t)w * NF);
+    double* dst = reinterpret_cast<double*>(B.pre + (size_t)w * NF);
+    for (int i = tid; i < NF * ODO_PRE_D; i += ODO_THREADS) dst[i] = src[i];
+  }
+  for (int p = tid; p < B.maxP; p += ODO_THREADS) {
+    const size_t pi = (size_t)w * B.maxP + p;
+    const double v = p < nP ? S.invd[(size_t)w * S.maxPT + psrc[pi]] : 1.0;
+    B.invd[pi] = v; B.invd_0[pi] = v;
+  }
+  for (int i = tid; i < B.maxL * 6; i += ODO_THREADS) {
+    const int l = i / 6;
+    const size_t li = (size_t)w * B.maxL + l;
+    const double v = l < nL ? S.plk[((size_t)w * S.maxLT + lsrc[li]) * 6 + i % 6] : 0.0;
+    B.plk[li * 6 + i % 6] = v; B.plk_0[li * 6 + i % 6] = v;
+  }
+  // point observations: track p's nobs records go to pt_off[p]; the rest of the array is zero, as the upload leaves it
+  int nPO = 0;
+  if (nP > 0) nPO = B.pt_off[(size_t)w * B.maxP + nP - 1] + B.pt_nobs[(size_t)w * B.maxP + nP - 1];
+  double* po = B.pt_obs + (size_t)w * B.maxPO * 3;
+  for (int i = tid; i < nP * NF * 3; i += ODO_THREADS) {
+    const int p = i / (NF * 3), r = i % (NF * 3);
+    const size_t pi = (size_t)w * B.maxP + p;
+    if (r < B.pt_nobs[pi] * 3) po[(size_t)B.pt_off[pi] * 3 + r] = S.pobs[((size_t)w * S.maxPT + psrc[pi]) * NF * 3 + r];
+  }
+  for (int i = nPO * 3 + tid; i < B.maxPO * 3; i += ODO_THREADS) po[i] = 0.0;
+  // line observations: lo_ln names the line of every observation
+  const int nLO = B.nLO[w];
+  double* lo = B.ln_obs + (size_t)w * B.maxLO * 8;
+  for (int i = tid; i < B.maxLO * 8; i += ODO_THREADS) {
+    const int o = i >> 3;
+    double v = 0.0;
+    if (o < nLO) {
+      const size_t li = (size_t)w * B.maxL + B.lo_ln[(size_t)w * B.maxLO + o];
+      v = S.lobs[(((size_t)w * S.maxLT + lsrc[li]) * NF + (o - B.ln_off[li])) * 8 + (i & 7)];
+    }
+    lo[i] = v;
+  }
+}
+
+// the session's prior into the batch's input prior (the block table went through the host); has[w] = 0: no prior yet
+__global__ __launch_bounds__(ODO_THREADS) void k_odo_prior_load(DevBatch B, OdoPrior P, const int* __restrict__ has) {
+  const int w = blockIdx.x;
+  if (!has[w]) return;
+  const int n = B.pr_n[w];
+  double* Jo = B.pr_J0 + (size_t)w * B.prS;
+  const double* J = P.J0 + (size_t)w * MAXKEEP * MAXKEEP;
+  for (int i = threadIdx.x; i < n * n; i += ODO_THREADS) Jo[i] = J[i];
+  for (int i = threadIdx.x; i < n; i += ODO_THREADS) B.pr_r0[(size_t)w * MAXPN + i] = P.r0[(size_t)w * MAXKEEP + i];
+  for (int i = threadIdx.x; i < MAXPB * 9; i += ODO_THREADS) B.pr_x0[(size_t)w * MAXPB * 9 + i] = P.x0[(size_t)w * MAXPB * 9 + i];
+}
+
+// ---- batch -> store, after each stage; the integer decisions the host's book needs go to `flags` (read back) ------------
+// after the two triangulations (all selected lines in the batch): every selected point's inverse depth; a line that was not
+// triangulated and now is takes its Pluecker vector.  flags: the windows' lines one after the other, is_triangulation afterwards.
+__device__ inline int odo_prefix(const int* __restrict__ a, int w) {   // (a few dozen sequences at most)
+  int s = 0;
+  for (int v = 0; v < w; ++v) s += a[v];
+  return s;
+}
+__global__ __launch_bounds__(ODO_THREADS) void k_odo_scatter_tri(DevBatch B, OdoStore S, const int* __restrict__ psrc,
+                                                                 const int* __restrict__ lsrc, int* __restrict__ flags) {
+  const int w = blockIdx.x;
+  const int nP = B.nP[w], nL = B.nL[w];
+  const int foff = odo_prefix(B.nL, w);
+  for (int p = threadIdx.x; p < nP; p += ODO_THREADS) {
+    const size_t pi = (size_t)w * B.maxP + p;
+    S.invd[(size_t)w * S.maxPT + psrc[pi]] = B.invd[pi];
+  }
+  for (int l = threadIdx.x; l < nL; l += ODO_THREADS) {
+    const size_t li = (size_t)w * B.maxL + l, t = (size_t)w * S.maxLT + lsrc[li];
+    int tri = S.tri[t];
+    if (!tri && B.ln_tri[li]) {
+      for (int k = 0; k < 6; ++k) S.plk[t * 6 + k] = B.plk[li * 6 + k];
+      S.tri[t] = tri = 1;
+    }
+    flags[foff + l] = tri;
+  }
+}
+
+__device__ inline void odo_report(vpl_solve_report& r, const TrState& t) {   // fill_report of the host side
+  r.iterations = t.iter;
+  r.num_successful_steps = t.num_successful;
+  r.termination = t.status == 1 ? 1 : t.status == 2 ? 2 : 0;
+  r.initial_cost = t.initial_cost;
+  r.final_cost = t.x_cost;
+  r.n_lines_removed = 0;   // (counted by the host from the flags)
+  r.prior_m = 0;
+  r.prior_n = 0;
+}
+
+// after onlyLineOpt (the triangulated lines in the batch): windows with fewer than four lines are left untouched; otherwise a
+// line removeLineOutlier erased loses its triangulation flag and keeps its vector, the others take the optimised one.
+// flags: the windows' lines one after the other, 1 = erased.  res[w].line_report: onlyLineOpt's.
+__global__ __launch_bounds__(ODO_THREADS) void k_odo_scatter_lopt(DevBatch B, OdoStore S, const int* __restrict__ lsrc,
+                                                                  int* __restrict__ flags, vpl_odo_result* __restrict__ res) {
+  const int w = blockIdx.x;
+  const int nL = B.nL[w];
+  const int foff = odo_prefix(B.nL, w);
+  if (threadIdx.x == 0) {
+    vpl_solve_report r;
+    TrState zero = {};
+    odo_report(r, nL < 4 ? zero : B.tr[w]);
+    res[w].line_report = r;
+  }
+  for (int l = threadIdx.x; l < nL; l += ODO_THREADS) {
+    const size_t li = (size_t)w * B.maxL + l, t = (size_t)w * S.maxLT + lsrc[li];
+    const int rem = nL < 4 ? 0 : B.ln_removed[li];
+    flags[foff + l] = rem;
+    if (nL < 4) continue;
+    if (rem) S.tri[t] = 0;
+    else
+      for (int k = 0; k < 6; ++k) S.plk[t * 6 + k] = B.plk[li * 6 + k];
+  }
+}
+
+// after the solve: states, inverse depths, the Pluecker vectors of the lines the solve did not erase; res[w]: states and
+// report.  marg[w] = 1 + the host's count of kept blocks: the marginalisation wrote a new prior for this window (0: it did
+// not) -- it is copied into the session's buffer.  flags, three parts, each the windows one after the other:
+//   nP ints: inverse depth > 0 (removeFailures keeps the track)
+//   per window with a new prior 2 + 3 * (marg[w] - 1) ints: n, n_blocks, kind[], frame[], idx[] (packed by n_blocks)
+//   nL ints: erased by the solve's removeLineOutlier (the host reads them only when that is switched on)
+__device__ inline int odo_ptab_len(int m) { return m ? 2 + 3 * (m - 1) : 0; }
+__global__ __launch_bounds__(ODO_THREADS) void k_odo_scatter_solve(DevBatch B, OdoStore S, const int* __restrict__ psrc,
+                                                                   const int* __restrict__ lsrc, int* __restrict__ flags,
+                                                                   vpl_odo_result* __restrict__ res, OdoPrior P,
+                                                                   const int* __restrict__ marg) {
+  const int w = blockIdx.x, tid = threadIdx.x;
+  const int nP = B.nP[w], nL = B.nL[w];
+  int offP = 0, totP = 0, offT = 0, totT = 0, offL = 0;
+  for (int v = 0; v < B.nW; ++v) {
+    const int p = B.nP[v], t = odo_ptab_len(marg[v]);
+    if (v < w) { offP += p; offT += t; offL += B.nL[v]; }
+    totP += p; totT += t;
+  }
+  double* rp = &res[w].pose[0][0];
+  double* rs = &res[w].speed_bias[0][0];
+  for (int i = tid; i < 77; i += ODO_THREADS) { const double v = B.pose[w * 77 + i]; S.pose[w * 77 + i] = v; rp[i] = v; }
+  for (int i = tid; i < 99; i += ODO_THREADS) { const double v = B.sb[w * 99 + i]; S.sb[w * 99 + i] = v; rs[i] = v; }
+  for (int i = tid; i < 7; i += ODO_THREADS) { const double v = B.ex[w * 7 + i]; S.ex[w * 7 + i] = v; res[w].ex_pose[i] = v; }
+  for (int p = tid; p < nP; p += ODO_THREADS) {
+    const size_t pi = (size_t)w * B.maxP + p;
+    const double v = B.invd[pi];
+    S.invd[(size_t)w * S.maxPT + psrc[pi]] = v;
+    flags[offP + p] = v > 0 ? 1 : 0;
+  }
+  for (int l = tid; l < nL; l += ODO_THREADS) {
+    const size_t li = (size_t)w * B.maxL + l, t = (size_t)w * S.maxLT + lsrc[li];
+    const int rem = B.ln_removed[li];
+    flags[totP + totT + offL + l] = rem;
+    if (!rem)
+      for (int k = 0; k < 6; ++k) S.plk[t * 6 + k] = B.plk[li * 6 + k];
+  }
+  const int n = marg[w] ? B.mg_n[w] : 0, nb = marg[w] ? min(B.mg_nb[w], marg[w] - 1) : 0;
+  if (tid == 0) {
+    vpl_solve_report r;
+    odo_report(r, B.tr[w]);
+    r.prior_m = B.mg_m[w];
+    r.prior_n = n;
+    res[w].report = r;
+  }
+  if (!marg[w]) return;
+  int* pt = flags + totP + offT;
+  if (tid == 0) { pt[0] = n; pt[1] = nb; }
+  for (int b = tid; b < nb && b < MAXPB; b += ODO_THREADS) {
+    pt[2 + b] = B.mg_kind[w * MAXPB + b];
+    pt[2 + nb + b] = B.mg_frame[w * MAXPB + b];
+    pt[2 + 2 * nb + b] = B.mg_idx[w * MAXPB + b];
+  }
+  const double* J = B.mg_J0 + (size_t)w * MAXKEEP * MAXKEEP;
+  double* Jo = P.J0 + (size_t)w * MAXKEEP * MAXKEEP;
+  for (int i = tid; i < n * n; i += ODO_THREADS) Jo[i] = J[i];
+  for (int i = tid; i < n; i += ODO_THREADS) P.r0[(size_t)w * MAXKEEP + i] = B.mg_r0[(size_t)w * MAXKEEP + i];
+  for (int i = tid; i < MAXPB * 9; i += ODO_THREADS) P.x0[(size_t)w * MAXPB * 9 + i] = B.mg_x0[(size_t)w * MAXPB * 9 + i];
+}
+
+// ---- Estimator::slideWindow on the store: from store A into store B ---------------------------------------------------
+// pmv [seq][maxPT], lmv [seq][maxLT]: new track j = odo_pack_move(store track, dropped observation, re-anchor) (odo_tracks.h);
+// cnt [seq][2] = tracks after the slide.  The re-anchoring is k_slide_shift's (slide_frames / slide_point_invd / slide_line_plk)
+// on frame 0, frame 1 and the extrinsic as the solve left them.  States: MARGIN_OLD frames 1..10 -> 0..9 (10 keeps its state)
+// and pre-integrations 2..10 -> 1..9; MARGIN_SECOND_NEW frame 10 -> 9.  grid (n_seq, ODO_SLIDE_Y).
+constexpr int ODO_SLIDE_Y = 4;
+__global__ __launch_bounds__(ODO_THREADS) void k_odo_slide(OdoStore A, OdoStore D, const int* __restrict__ pmv, const int* __restrict__ lmv,
+                                                           const int* __restrict__ cnt, int second_new, double init_depth) {
+  const int w = blockIdx.x;
+  const int tid = blockIdx.y * ODO_THREADS + threadIdx.x, nthr = ODO_SLIDE_Y * ODO_THREADS;
+  const int nP = cnt[2 * w], nL = cnt[2 * w + 1];
+  double f[21];
+  for (int i = 0; i < 14; ++i) f[i] = A.pose[w * 77 + i];
+  for (int i = 0; i < 7; ++i) f[14 + i] = A.ex[w * 7 + i];
+  // (the frames are only needed by lanes that re-anchor a track; they are cheap next to the copies)
+  const SlideFrames F = slide_frames(f);
+  for (int j = tid; j < nP; j += nthr) {
+    const int m = pmv[(size_t)w * A.maxPT + j];
+    const size_t s = (size_t)w * A.maxPT + (m & 0xFFFFF), d = (size_t)w * D.maxPT + j;
+    const double* o = A.pobs + s * NF * 3;
+    double v = A.invd[s];
+    if (m >> 24 & 1) v = slide_point_invd(F, o[0], o[1], o[2], v, init_depth);
+    D.invd[d] = v;
+  }
+  for (int j = tid; j < nL; j += nthr) {
+    const int m = lmv[(size_t)w * A.maxLT + j];
+    const size_t s = (size_t)w * A.maxLT + (m & 0xFFFFF), d = (size_t)w * D.maxLT + j;
+    Plk L{V3{A.plk[s * 6], A.plk[s * 6 + 1], A.plk[s * 6 + 2]}, V3{A.plk[s * 6 + 3], A.plk[s * 6 + 4], A.plk[s * 6 + 5]}};
+    if (m >> 24 & 1) L = slide_line_plk(F, L);
+    D.plk[d * 6] = L.n.x; D.plk[d * 6 + 1] = L.n.y; D.plk[d * 6 + 2] = L.n.z;
+    D.plk[d * 6 + 3] = L.v.x; D.plk[d * 6 + 4] = L.v.y; D.plk[d * 6 + 5] = L.v.z;
+    D.tri[d] = A.tri[s];
+  }
+  // observation records: consecutive lanes take consecutive doubles of a track's slot
+  for (int i = tid; i < nP * NF * 3; i += nthr) {
+    const int j = i / (NF * 3), r = i % (NF * 3), k = r / 3;
+    const int m = pmv[(size_t)w * A.maxPT + j];
+    const int drop = (m >> 20 & 15) - 1;
+    const int ks = (drop >= 0 && k >= drop) ? k + 1 : k;
+    D.pobs[((size_t)w * D.maxPT + j) * NF * 3 + r] = ks < NF ? A.pobs[(((size_t)w * A.maxPT + (m & 0xFFFFF)) * NF + ks) * 3 + r % 3] : 0.0;
+  }
+  for (int i = tid; i < nL * NF * 8; i += nthr) {
+    const int j = i / (NF * 8), r = i % (NF * 8), k = r >> 3;
+    const int m = lmv[(size_t)w * A.maxLT + j];
+    const int drop = (m >> 20 & 15) - 1;
+    const int ks = (drop >= 0 && k >= drop) ? k + 1 : k;
+    D.lobs[((size_t)w * D.maxLT + j) * NF * 8 + r] = ks < NF ? A.lobs[(((size_t)w * A.maxLT + (m & 0xFFFFF)) * NF + ks) * 8 + (r & 7)] : 0.0;
+  }
+  for (int i = tid; i < NF * 7; i += nthr) {
+    const int fr = i / 7;
+    const int src = second_new ? (fr == NF - 2 ? NF - 1 : fr) : (fr < NF - 1 ? fr + 1 : fr);
+    D.pose[w * 77 + i] = A.pose[w * 77 + src * 7 + i % 7];
+  }
+  for (int i = tid; i < NF * 9; i += nthr) {
+    const int fr = i / 9;
+    const int src = second_new ? (fr == NF - 2 ? NF - 1 : fr) : (fr < NF - 1 ? fr + 1 : fr);
+    D.sb[w * 99 + i] = A.sb[w * 99 + src * 9 + i % 9];
+  }
+  for (int i = tid; i < 7; i += nthr) D.ex[w * 7 + i] = A.ex[w * 7 + i];
+  const double* ps = reinterpret_cast<const double*>(A.pre + (size_t)w * NF);
+  double* pd = reinterpret_cast<double*>(D.pre + (size_t)w * NF);
+  for (int i = tid; i < NF * ODO_PRE_D; i += nthr) {
+    const int fr = i / ODO_PRE_D;
+    const int src = (!second_new && fr >= 1 && fr < NF - 1) ? fr + 1 : fr;
+    pd[i] = ps[(size_t)src * ODO_PRE_D + i % ODO_PRE_D];
+  }
+}
+
+// ---- the new frame into slot 10 ------------------------------------------------------------------------------------------
+// hdr [seq][5] = payload offset (doubles), n_points, n_lines, offset of the point entries in tab, of the line entries.
+// Payload of a sequence: pose[7], speed_bias[9], the vpl_preintegration as the caller holds it, point observations [n][3],
+// line observations [n][8].  tab entry of an observation: track | k << 20 | isnew << 24 (odo_add_frame), -1 = ignored.
+// One lane per observation; a track that starts here gets inv_depth = -1, plk = 0, tri = 0.
+__global__ __launch_bounds__(ODO_THREADS) void k_odo_append(OdoStore S, const double* __restrict__ payload, const int* __restrict__ hdr,
+                                                            const int* __restrict__ tab) {
+  const int w = blockIdx.x, tid = threadIdx.x;
+  const int* h = hdr + 5 * w;
+  const double* in = payload + h[0];
+  const int nP = h[1], nL = h[2];
+  for (int i = tid; i < 7; i += ODO_THREADS) S.pose[w * 77 + (NF - 1) * 7 + i] = in[i];
+  for (int i = tid; i < 9; i += ODO_THREADS) S.sb[w * 99 + (NF - 1) * 9 + i] = in[7 + i];
+  {   // to_dev_preint of the host side: the first 17 doubles as they are, five 3 x 3 blocks of the Jacobian, the covariance
+    const double* r = in + 16;
+    double* d = reinterpret_cast<double*>(S.pre + (size_t)w * NF + (NF - 1));
+    const double* jac = r + 17;
+    const double* cov = r + 17 + 225;
+    for (int i = tid; i < ODO_PRE_D; i += ODO_THREADS) {
+      double v = 0.0;                                   // sqrt_info (k_prep writes it)
+      if (i < 17) v = r[i];
+      else if (i < 17 + 45) {
+        const int b = (i - 17) / 9, e = (i - 17) % 9;   // dp_dba, dp_dbg, dq_dbg, dv_dba, dv_dbg
+        const int r0 = b < 2 ? 0 : b == 2 ? 3 : 6, c0 = (b == 0 || b == 3) ? 9 : 12;
+        v = jac[(r0 + e / 3) * 15 + c0 + e % 3];
+      } else if (i < 17 + 45 + 225) v = cov[i - 62];
+      d[i] = v;
+    }
+  }
+  const double* pin = in + 16 + ODO_RAW_PRE_D;
+  for (int i = tid; i < nP; i += ODO_THREADS) {
+    const int e = tab[h[3] + i];
+    if (e < 0) continue;
+    const size_t t = (size_t)w * S.maxPT + (e & 0xFFFFF);
+    double* o = S.pobs + (t * NF + (e >> 20 & 15)) * 3;
+    o[0] = pin[3 * i]; o[1] = pin[3 * i + 1]; o[2] = pin[3 * i + 2];
+    if (e >> 24 & 1) S.invd[t] = -1.0;
+  }
+  const double* lin = pin + (size_t)nP * 3;
+  for (int i = tid; i < nL * 8; i += ODO_THREADS) {
+    const int e = tab[h[4] + (i >> 3)];
+    if (e < 0) continue;
+    const size_t t = (size_t)w * S.maxLT + (e & 0xFFFFF);
+    S.lobs[(t * NF + (e >> 20 & 15)) * 8 + (i & 7)] = lin[i];
+    if ((e >> 24 & 1) && (i & 7) < 6) S.plk[t * 6 + (i & 7)] = 0.0;
+    if ((e >> 24 & 1) && (i & 7) == 6) S.tri[t] = 0;
+  }
+}
+
+}  // namespace vpl
