@@ -301,7 +301,7 @@ inline int pack_schur_ksteps(int nP, const int* ps_list, const int* cnt, int nL,
   return nks;
 }
 
-// ---- shared by the upload (vplines_ba.hip) and tests/native/pack_fuzz.cpp ----------------------------------------------------
+// ---- shared by the upload (ba_upload.h) and tests/native/pack_fuzz.cpp ----------------------------------------------------
 
 // Capacities of the per-window layout tables; vpl_ctx_create sizes the device arrays with them.
 // Point work units of k_lin: (start frame, chunk of <= 16 tracks, observation); a unit needs at most one quarter-wave slot;

@@ -1,0 +1,595 @@
+// The keyframe session (vpl_odo_* of include/vplines_ba.h); vplines_ba.hip includes this once, behind the window entry points
+// whose stages it runs.
+// The reference's FeatureManager + window state for n_seq sequences, resident on the device (csrc/ba_odo.h); the host keeps
+// the integer side of the tracks (csrc/odo_tracks.h), from which the existing host code builds the kernels' layout tables.
+// A keyframe runs the stages of vpl_ba_solve_odometry -- the same uploads of tables, the same launches -- with every double
+// of the batch gathered from the store instead of packed from the caller's arrays, and the results scattered back into it.
+#pragma once
+#include "ba_upload.h"
+#include "odo_tracks.h"
+
+struct OdoSeq {
+  OdoBook P, L;
+  double sum_dt[NF] = {};          // of the 11 pre-integrations (the kept-block table asks for preint[1].sum_dt)
+  HostTab prior;                   // block table of the prior the session holds on the device
+  bool has_prior = false, set = false;
+};
+
+struct vpl_odo {
+  vpl_ctx* c = nullptr;
+  int nS = 0, line_min_obs = 0, maxPT = 0, maxLT = 0;
+  vpl_ba_options opt;
+  double init_depth = 5.0;
+  OdoStore st[2];
+  int cur = 0;
+  OdoPrior prior;
+  int *d_psrc = nullptr, *d_lsrc = nullptr, *d_has = nullptr, *d_marg = nullptr;
+  char *d_in = nullptr, *h_in = nullptr, *d_out = nullptr, *h_out = nullptr;   // new frames + slide tables in | results + flags out (h_*: pinned)
+  size_t in_cap = 0, out_cap = 0;
+  size_t alloc0 = 0, alloc1 = 0;   // the session's arrays in the context's allocation record
+  std::vector<OdoSeq> seq;
+  // the integer-only windows handed to the uploads, and what they point to
+  std::vector<vpl_window> win;
+  std::vector<std::vector<int>> pstart, pnobs, lstart, lnobs, ltri, psrc, lsrc;
+  std::vector<HostTab> tabs;
+  std::vector<unsigned char> has;
+  long long h2d_payload = 0, h2d_table = 0, d2h = 0;
+  double ms[4] = {0, 0, 0, 0};
+  // between vpl_odo_solve and vpl_odo_advance: what the solve decided (its flags are in h_out) and on which batch
+  bool solved = false;
+  int flag = VPL_MARGIN_OLD, remove_line_outliers = 0;
+  std::vector<int> s_nP, s_nL;
+  std::vector<std::vector<int>> s_lmap;
+  size_t s_totP = 0, s_totT = 0;
+};
+
+static size_t odo_result_bytes(int nS) { return (size_t)nS * sizeof(vpl_odo_result); }
+
+static int odo_alloc_store(vpl_ctx* c, OdoStore& S, size_t nS, int maxPT, int maxLT) {
+  hipError_t e = hipSuccess;
+  S.maxPT = maxPT; S.maxLT = maxLT;
+#define OAL(ptr, n) if (e == hipSuccess) e = dalloc(c, &S.ptr, (size_t)(n))
+  OAL(pobs, nS * maxPT * NF * 3); OAL(lobs, nS * maxLT * NF * 8); OAL(invd, nS * maxPT); OAL(plk, nS * maxLT * 6); OAL(tri, nS * maxLT);
+  OAL(pose, nS * 77); OAL(sb, nS * 99); OAL(ex, nS * 7); OAL(pre, nS * NF);
+#undef OAL
+  return e == hipSuccess ? VPL_OK : VPL_E_HIP;
+}
+
+static OdoSrc odo_src(vpl_odo* o, bool with_prior) {
+  OdoSrc s;
+  s.store = o->st[o->cur];
+  s.prior = o->prior;
+  s.d_psrc = o->d_psrc; s.d_lsrc = o->d_lsrc; s.d_has = o->d_has; s.d_marg = o->d_marg;
+  s.psrc = o->psrc.data(); s.lsrc = o->lsrc.data();
+  s.tab = with_prior ? o->tabs.data() : nullptr;
+  s.has = o->has.data();
+  return s;
+}
+
+// the tracks the solve takes (estimator.cpp:1100-1102, 1132-1133) as integer-only windows; lines with their flags
+static void odo_select(vpl_odo* o) {
+  for (int w = 0; w < o->nS; ++w) {
+    OdoSeq& q = o->seq[w];
+    auto &ps = o->pstart[w], &pn = o->pnobs[w], &px = o->psrc[w], &ls = o->lstart[w], &ln = o->lnobs[w], &lt = o->ltri[w], &lx = o->lsrc[w];
+    ps.clear(); pn.clear(); px.clear(); ls.clear(); ln.clear(); lt.clear(); lx.clear();
+    for (size_t i = 0; i < q.P.t.size(); ++i) {
+      const OdoTrack& t = q.P.t[i];
+      if (t.nobs >= 2 && t.start < NF - 3) { ps.push_back(t.start); pn.push_back(t.nobs); px.push_back((int)i); }
+    }
+    for (size_t i = 0; i < q.L.t.size(); ++i) {
+      const OdoTrack& t = q.L.t[i];
+      if (t.nobs >= o->line_min_obs && t.start < NF - 3) { ls.push_back(t.start); ln.push_back(t.nobs); lt.push_back(t.tri); lx.push_back((int)i); }
+    }
+    vpl_window& v = o->win[w];
+    v.n_points = (int)ps.size(); v.point_start = ps.data(); v.point_nobs = pn.data();
+    v.n_lines = (int)ls.size(); v.line_start = ls.data(); v.line_nobs = ln.data(); v.line_triangulated = lt.data();
+    v.preint[1].sum_dt = q.sum_dt[1];
+    o->tabs[w] = q.prior;
+    o->has[w] = q.has_prior ? 1 : 0;
+  }
+}
+
+static int odo_check_frame(const vpl_odo_frame& f) {
+  if (f.n_points < 0 || f.n_lines < 0) return VPL_E_INVALID;
+  if (f.n_points > 0 && (!f.point_id || !f.point_obs)) return VPL_E_INVALID;
+  if (f.n_lines > 0 && (!f.line_id || !f.line_obs)) return VPL_E_INVALID;
+  return VPL_OK;
+}
+
+extern "C" {
+
+int vpl_odo_create(vpl_odo** out, vpl_ctx* c, int n_seq, const vpl_ba_options* opt, double init_depth, int line_min_obs,
+                   int max_point_tracks, int max_line_tracks) {
+  if (!out || !c || !opt || n_seq < 1 || !(init_depth > 0.0) || line_min_obs < 1 || max_point_tracks < 1 || max_line_tracks < 1)
+    return VPL_E_INVALID;
+  if (max_point_tracks >= (1 << 20) || max_line_tracks >= (1 << 20)) return fail(c, VPL_E_CAPACITY, "odo: at most 2^20 - 1 tracks per sequence");
+  if (c->odo) return fail(c, VPL_E_INVALID, "odo: the context already lends itself to a session");
+  if (n_seq > c->maxW) return fail(c, VPL_E_CAPACITY, "odo: more sequences than the context's max_windows");
+  HIPCHK(c, hipSetDevice(c->device));
+  { const int rs = settle(c); if (rs) return rs; }
+  vpl_odo* o = new vpl_odo();
+  o->c = c; o->nS = n_seq; o->opt = *opt; o->init_depth = init_depth; o->line_min_obs = line_min_obs;
+  o->maxPT = max_point_tracks; o->maxLT = max_line_tracks;
+  const size_t nS = n_seq;
+  o->alloc0 = c->allocs.size();
+  int rc = odo_alloc_store(c, o->st[0], nS, o->maxPT, o->maxLT);
+  if (!rc) rc = odo_alloc_store(c, o->st[1], nS, o->maxPT, o->maxLT);
+  hipError_t e = hipSuccess;
+  // per sequence in: pose + speed/bias + pre-integration + one observation per track, header, one table entry per observation
+  // and per track (the slide's moves), two counts; out: the result, three flags per track, the prior's block table
+  o->in_cap = nS * (8 * (16 + ODO_RAW_PRE_D + 3 * (size_t)o->maxPT + 8 * (size_t)o->maxLT) + 4 * (8 + 2 * ((size_t)o->maxPT + o->maxLT))) + 64;
+  o->out_cap = odo_result_bytes(n_seq) + nS * 4 * (3 * ((size_t)o->maxPT + o->maxLT) + 2 + 3 * MAXPB);
+  char *din = nullptr, *dout = nullptr;
+  if (!rc) {
+    if (e == hipSuccess) e = dalloc(c, &o->prior.J0, nS * MAXKEEP * MAXKEEP);
+    if (e == hipSuccess) e = dalloc(c, &o->prior.r0, nS * MAXKEEP);
+    if (e == hipSuccess) e = dalloc(c, &o->prior.x0, nS * MAXPB * 9);
+    if (e == hipSuccess) e = dalloc(c, &o->d_psrc, nS * c->B.maxP);
+    if (e == hipSuccess) e = dalloc(c, &o->d_lsrc, nS * c->B.maxL);
+    if (e == hipSuccess) e = dalloc(c, &o->d_has, nS);
+    if (e == hipSuccess) e = dalloc(c, &o->d_marg, nS);
+    if (e == hipSuccess) e = dalloc(c, &din, o->in_cap);
+    if (e == hipSuccess) e = dalloc(c, &dout, o->out_cap);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&o->h_in, o->in_cap, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&o->h_out, o->out_cap, hipHostMallocDefault);
+  }
+  o->d_in = din; o->d_out = dout;
+  o->alloc1 = c->allocs.size();
+  if (rc || e != hipSuccess) {
+    c->odo = o;              // (so that destroy releases through the one path)
+    vpl_odo_destroy(o);
+    return rc ? rc : fail(c, VPL_E_HIP, "odo: device allocation failed");
+  }
+  o->seq.resize(nS);
+  o->win.resize(nS);
+  for (auto& v : o->win) std::memset(&v, 0, sizeof(v));
+  o->pstart.resize(nS); o->pnobs.resize(nS); o->lstart.resize(nS); o->lnobs.resize(nS); o->ltri.resize(nS); o->psrc.resize(nS); o->lsrc.resize(nS);
+  o->tabs.resize(nS); o->has.assign(nS, 0);
+  c->odo = o;
+  *out = o;
+  return VPL_OK;
+}
+
+void vpl_odo_destroy(vpl_odo* o) {
+  if (!o) return;
+  vpl_ctx* c = o->c;
+  // (teardown: a failure has nobody to be reported to)
+  (void)hipSetDevice(c->device);
+  (void)settle(c);
+  (void)hipStreamSynchronize(c->stream);
+  for (size_t i = o->alloc0; i < o->alloc1 && i < c->allocs.size(); ++i) (void)hipFree(c->allocs[i]);
+  if (o->alloc1 <= c->allocs.size()) {
+    c->allocs.erase(c->allocs.begin() + o->alloc0, c->allocs.begin() + o->alloc1);
+    c->alloc_bytes.erase(c->alloc_bytes.begin() + o->alloc0, c->alloc_bytes.begin() + o->alloc1);
+  }
+  if (o->h_in) (void)hipHostFree(o->h_in);
+  if (o->h_out) (void)hipHostFree(o->h_out);
+  if (c->odo == o) c->odo = nullptr;
+  delete o;
+}
+
+int vpl_odo_set_window(vpl_odo* o, int seq, const double pose[][7], const double speed_bias[][9], const double ex_pose[7],
+                       const vpl_preintegration* preint, const vpl_odo_frame* frames) {
+  if (!o || seq < 0 || seq >= o->nS || !pose || !speed_bias || !ex_pose || !preint || !frames) return VPL_E_INVALID;
+  vpl_ctx* c = o->c;
+  for (int f = 0; f < NF; ++f)
+    if (odo_check_frame(frames[f])) return fail(c, VPL_E_INVALID, "odo_set_window: null observation array");
+  // the bookkeeping on a copy: a refusal leaves the sequence as it was
+  OdoBook P, L;
+  std::vector<std::vector<int>> pd(NF), ld(NF);
+  for (int f = 0; f < NF; ++f) {
+    if ((int)P.t.size() + odo_count_unknown(P, frames[f].n_points, frames[f].point_id) > o->maxPT ||
+        (int)L.t.size() + odo_count_unknown(L, frames[f].n_lines, frames[f].line_id) > o->maxLT)
+      return fail(c, VPL_E_CAPACITY, "odo_set_window: more tracks than the session's capacity");
+    pd[f].resize(frames[f].n_points); ld[f].resize(frames[f].n_lines);
+    odo_add_frame(P, f, frames[f].n_points, frames[f].point_id, pd[f].data());
+    odo_add_frame(L, f, frames[f].n_lines, frames[f].line_id, ld[f].data());
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  { const int rs = settle(c); if (rs) return rs; }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  // an image of the sequence's part of the store, copied array by array (not on the per-keyframe path)
+  const OdoStore& S = o->st[o->cur];
+  const size_t nP = P.t.size(), nL = L.t.size();
+  std::vector<double> pobs(std::max<size_t>(nP, 1) * NF * 3, 0.0), lobs(std::max<size_t>(nL, 1) * NF * 8, 0.0), invd(std::max<size_t>(nP, 1), -1.0),
+      plk(std::max<size_t>(nL, 1) * 6, 0.0);
+  std::vector<int> tri(std::max<size_t>(nL, 1), 0);
+  for (int f = 0; f < NF; ++f) {
+    for (int i = 0; i < frames[f].n_points; ++i) {
+      const int e = pd[f][i];
+      if (e >= 0) std::memcpy(&pobs[((size_t)(e & 0xFFFFF) * NF + (e >> 20 & 15)) * 3], frames[f].point_obs + 3 * (size_t)i, 24);
+    }
+    for (int i = 0; i < frames[f].n_lines; ++i) {
+      const int e = ld[f][i];
+      if (e >= 0) std::memcpy(&lobs[((size_t)(e & 0xFFFFF) * NF + (e >> 20 & 15)) * 8], frames[f].line_obs + 8 * (size_t)i, 64);
+    }
+  }
+  std::vector<DevPreint> pre(NF);
+  std::memset(pre.data(), 0, sizeof(DevPreint) * NF);
+  for (int f = 1; f < NF; ++f) to_dev_preint(preint[f], pre[f]);
+  const size_t q = seq;
+  HIPCHK(c, hipMemcpy(S.pobs + q * S.maxPT * NF * 3, pobs.data(), nP * NF * 3 * 8, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(S.lobs + q * S.maxLT * NF * 8, lobs.data(), nL * NF * 8 * 8, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(S.invd + q * S.maxPT, invd.data(), nP * 8, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(S.plk + q * S.maxLT * 6, plk.data(), nL * 6 * 8, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(S.tri + q * S.maxLT, tri.data(), nL * 4, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(S.pose + q * 77, pose, 77 * 8, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(S.sb + q * 99, speed_bias, 99 * 8, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(S.ex + q * 7, ex_pose, 7 * 8, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(S.pre + q * NF, pre.data(), sizeof(DevPreint) * NF, hipMemcpyHostToDevice));
+  OdoSeq& Q = o->seq[seq];
+  Q.P = std::move(P); Q.L = std::move(L);
+  Q.sum_dt[0] = 0.0;
+  for (int f = 1; f < NF; ++f) Q.sum_dt[f] = preint[f].sum_dt;
+  Q.prior = HostTab();
+  Q.has_prior = false;
+  Q.set = true;
+  o->solved = false;
+  return VPL_OK;
+}
+
+// the refusals of a new frame: null arrays, more tracks than the session holds (counted on the book as it stands)
+static int odo_check_next(vpl_odo* o, const vpl_odo_frame* next) {
+  vpl_ctx* c = o->c;
+  for (int w = 0; w < o->nS; ++w) {
+    if (odo_check_frame(next[w])) return fail(c, VPL_E_INVALID, "odo: null observation array");
+    // (the inbox holds one observation per track and frame)
+    if (next[w].n_points > o->maxPT || next[w].n_lines > o->maxLT) return fail(c, VPL_E_CAPACITY, "odo: more observations in a frame than tracks in the session");
+    const OdoSeq& q = o->seq[w];
+    if ((int)q.P.t.size() + odo_count_unknown(q.P, next[w].n_points, next[w].point_id) > o->maxPT ||
+        (int)q.L.t.size() + odo_count_unknown(q.L, next[w].n_lines, next[w].line_id) > o->maxLT)
+      return fail(c, VPL_E_CAPACITY, "odo: more tracks than the session's capacity");
+  }
+  return VPL_OK;
+}
+
+int vpl_odo_solve(vpl_odo* o, const int* flags, vpl_odo_result* out) {
+  if (!o || !flags || !out) return VPL_E_INVALID;
+  vpl_ctx* c = o->c;
+  const int nS = o->nS;
+  const int flag = flags[0];
+  if (flag != VPL_MARGIN_OLD && flag != VPL_MARGIN_SECOND_NEW) return fail(c, VPL_E_INVALID, "odo_solve: marginalization_flag");
+  if (o->solved) return fail(c, VPL_E_INVALID, "odo_solve: the window has been solved and not advanced (vpl_odo_advance)");
+  for (int w = 0; w < nS; ++w) {
+    if (flags[w] != flag) return fail(c, VPL_E_INVALID, "odo_solve: the sequences of one call must carry the same marginalization_flag");
+    if (!o->seq[w].set) return fail(c, VPL_E_INVALID, "odo_solve: a sequence has no window (vpl_odo_set_window)");
+  }
+  if (c->maxL > LOPT_THREADS) return fail(c, VPL_E_CAPACITY, "onlyLineOpt handles at most 256 lines per window");
+  // capacities, before anything is touched
+  odo_select(o);
+  const DevBatch& B = c->B;
+  bool any_lines = false;
+  for (int w = 0; w < nS; ++w) {
+    long po = 0, lo = 0;
+    for (int n : o->pnobs[w]) po += n;
+    for (int n : o->lnobs[w]) lo += n;
+    if ((int)o->pstart[w].size() > B.maxP || (int)o->lstart[w].size() > B.maxL || po > B.maxPO || lo > B.maxLO)
+      return fail(c, VPL_E_CAPACITY, "odo_solve: the solve's tracks exceed the context's capacities");
+    any_lines = any_lines || !o->lstart[w].empty();
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  { const int rs = settle(c); if (rs) return rs; }
+  using oclk = std::chrono::steady_clock;
+  auto t0 = oclk::now();
+  auto lap = [&](int k) { const auto t = oclk::now(); o->ms[k] = std::chrono::duration<double, std::milli>(t - t0).count(); t0 = t; };
+  hipStream_t s = c->stream;
+  const dim3 grid(nS), blk(ODO_THREADS);
+  const OdoStore S = o->st[o->cur];
+  vpl_odo_result* d_res = reinterpret_cast<vpl_odo_result*>(o->d_out);
+  int* d_flags = reinterpret_cast<int*>(o->d_out + odo_result_bytes(nS));
+  const int* h_flags = reinterpret_cast<const int*>(o->h_out + odo_result_bytes(nS));
+  const vpl_odo_result* h_res = reinterpret_cast<const vpl_odo_result*>(o->h_out);
+  o->h2d_payload = o->h2d_table = o->d2h = 0;
+  vpl_ba_options solve_opt = o->opt;
+  solve_opt.marginalization_flag = flag;
+  int rc;
+
+  // 1. f_manager.triangulate || f_manager.triangulateLine: every selected point, every selected line with its flag
+  {
+    vpl_ba_options topt;
+    vpl_ba_default_options(&topt);
+    topt.marginalization_flag = VPL_MARGIN_NONE;
+    const OdoSrc src = odo_src(o, false);
+    if ((rc = upload_impl(c, nS, o->win.data(), &topt, true, false, &src))) return rc;
+    o->h2d_table += (long long)c->last_upload_bytes;
+    launch_triangulate(c, nS, true, any_lines, o->init_depth);
+    hipLaunchKernelGGL(k_odo_scatter_tri, grid, blk, 0, s, c->B, S, (const int*)o->d_psrc, (const int*)o->d_lsrc, d_flags);
+    HIPCHK(c, hipGetLastError());
+    if (any_lines) {
+      size_t nl = 0;
+      for (int w = 0; w < nS; ++w) nl += o->lstart[w].size();
+      HIPCHK(c, hipMemcpyAsync(o->h_out + odo_result_bytes(nS), d_flags, nl * 4, hipMemcpyDeviceToHost, s));
+      o->d2h += (long long)nl * 4;
+      HIPCHK(c, hipStreamSynchronize(s));
+      size_t k = 0;
+      for (int w = 0; w < nS; ++w)
+        for (size_t l = 0; l < o->lstart[w].size(); ++l, ++k) {
+          o->ltri[w][l] = h_flags[k];
+          o->seq[w].L.t[o->lsrc[w][l]].tri = h_flags[k];
+        }
+    }
+  }
+  lap(0);
+
+  // 2. onlyLineOpt on the triangulated lines, uploaded with the solve's options (the batch stays for the solve when no line is erased)
+  bool batch_resident = false;
+  std::vector<int> lrem1(nS, 0);
+  if (any_lines) {
+    const OdoSrc src = odo_src(o, true);
+    if ((rc = upload_impl(c, nS, o->win.data(), &solve_opt, false, false, &src))) return rc;
+    o->h2d_table += (long long)c->last_upload_bytes;
+    launch_line_opt(c, nS);
+    hipLaunchKernelGGL(k_odo_scatter_lopt, grid, blk, 0, s, c->B, S, (const int*)o->d_lsrc, d_flags, d_res);
+    HIPCHK(c, hipGetLastError());
+    size_t nl = 0;
+    for (int w = 0; w < nS; ++w) nl += c->h_nL[w];
+    if (nl) HIPCHK(c, hipMemcpyAsync(o->h_out + odo_result_bytes(nS), d_flags, nl * 4, hipMemcpyDeviceToHost, s));
+    o->d2h += (long long)nl * 4;
+    HIPCHK(c, hipStreamSynchronize(s));
+    bool erased = false;
+    size_t k = 0;
+    for (int w = 0; w < nS; ++w)
+      for (int dl = 0; dl < c->h_nL[w]; ++dl, ++k)
+        if (h_flags[k]) {   // f_manager.removeLineOutlier erased the track's line (estimator.cpp:1037): it takes no part in the solve
+          const int l = c->h_lmap[w][dl];
+          o->ltri[w][l] = 0;
+          o->seq[w].L.t[o->lsrc[w][l]].tri = 0;
+          ++lrem1[w];
+          erased = true;
+        }
+    batch_resident = !erased;
+  }
+  lap(1);
+
+  // 3. optimizationwithLine: on the batch where it lies, or on a fresh upload of the lines that are left
+  if (batch_resident) {
+    if ((rc = reuse_line_opt_batch(c))) return rc;
+  } else {
+    const OdoSrc src = odo_src(o, true);
+    if ((rc = upload_impl(c, nS, o->win.data(), &solve_opt, false, false, &src))) return rc;
+    o->h2d_table += (long long)c->last_upload_bytes;
+  }
+  if ((rc = vpl_ba_solve(c))) return rc;
+  c->prior_resident = false;   // (the session keeps the prior in its own buffer; the batch is rewritten before the next solve)
+  hipLaunchKernelGGL(k_odo_scatter_solve, grid, blk, 0, s, c->B, S, (const int*)o->d_psrc, (const int*)o->d_lsrc, d_flags, d_res,
+                     o->prior, (const int*)o->d_marg);
+  HIPCHK(c, hipGetLastError());
+  size_t totP = 0, totT = 0, totL = 0;
+  std::vector<int> marg(nS, 0);
+  for (int w = 0; w < nS; ++w) {
+    totP += c->h_nP[w]; totL += c->h_nL[w];
+    marg[w] = c->h_passthrough[w] < 0 ? 1 + c->h_mg_nb[w] : 0;
+    totT += marg[w] ? 2 + 3 * (marg[w] - 1) : 0;
+  }
+  {
+    const size_t bytes = odo_result_bytes(nS) + 4 * (totP + totT + (solve_opt.remove_line_outliers ? totL : 0));
+    HIPCHK(c, hipMemcpyAsync(o->h_out, o->d_out, bytes, hipMemcpyDeviceToHost, s));
+    o->d2h += (long long)bytes;
+    HIPCHK(c, hipStreamSynchronize(s));
+  }
+  lap(2);
+
+  // the results, and the prior the marginalisation left: its block table (the values stayed on the device)
+  o->s_nP = c->h_nP; o->s_nL = c->h_nL; o->s_lmap = c->h_lmap;
+  o->s_totP = totP; o->s_totT = totT;
+  o->flag = flag; o->remove_line_outliers = solve_opt.remove_line_outliers;
+  size_t kT = 0, kL = 0;
+  for (int w = 0; w < nS; ++w) {
+    OdoSeq& q = o->seq[w];
+    vpl_odo_result& r = out[w];
+    r = h_res[w];
+    if (o->lstart[w].empty()) std::memset(&r.line_report, 0, sizeof(r.line_report));
+    r.line_report.n_lines_removed = lrem1[w];
+    r.n_points_solved = c->h_nP[w];
+    r.n_lines_solved = c->h_nL[w];
+    r.n_point_tracks = (int)q.P.t.size();
+    r.n_line_tracks = (int)q.L.t.size();
+    r.n_ignored = 0;
+    int lrem2 = 0;
+    if (solve_opt.remove_line_outliers)
+      for (int dl = 0; dl < c->h_nL[w]; ++dl) lrem2 += h_flags[totP + totT + kL + dl] ? 1 : 0;
+    kL += c->h_nL[w];
+    r.report.n_lines_removed = lrem2;
+    if (marg[w]) {
+      const int* pt = h_flags + totP + kT;
+      kT += 2 + 3 * (marg[w] - 1);
+      HostTab T;
+      T.n = pt[0]; T.nb = pt[1];
+      if (T.n < 0 || T.n > MAXKEEP || T.nb < 0 || T.nb > marg[w] - 1) return fail(c, VPL_E_HIP, "odo_solve: prior table out of range");
+      for (int b = 0; b < T.nb; ++b) { T.kind[b] = pt[2 + b]; T.frame[b] = pt[2 + T.nb + b]; T.idx[b] = pt[2 + 2 * T.nb + b]; }
+      q.prior = T;
+      q.has_prior = T.n > 0;
+    } else {
+      r.report.prior_n = q.has_prior ? q.prior.n : 0;   // MARGIN_SECOND_NEW left the prior as it was (estimator.cpp:1385)
+    }
+  }
+  o->solved = true;
+  return VPL_OK;
+}
+
+int vpl_odo_advance(vpl_odo* o, const vpl_odo_frame* next, vpl_odo_result* out) {
+  if (!o || !next) return VPL_E_INVALID;
+  vpl_ctx* c = o->c;
+  if (!o->solved) return fail(c, VPL_E_INVALID, "odo_advance: no solved window (vpl_odo_solve)");
+  { const int rn = odo_check_next(o, next); if (rn) return rn; }
+  const int nS = o->nS, flag = o->flag;
+  HIPCHK(c, hipSetDevice(c->device));
+  { const int rs = settle(c); if (rs) return rs; }
+  using oclk = std::chrono::steady_clock;
+  const auto t0 = oclk::now();
+  hipStream_t s = c->stream;
+  const dim3 grid(nS), blk(ODO_THREADS);
+  const OdoStore S = o->st[o->cur];
+  const int* h_flags = reinterpret_cast<const int*>(o->h_out + odo_result_bytes(nS));
+  const size_t totP = o->s_totP, totT = o->s_totT;
+  // 4. the book: removeFailures and the solve's removeLineOutlier, the slide, the new frame -- and the tables that tell the
+  // device what moved where; then ONE copy host -> device (the new frames' doubles, then the tables) and two launches
+  double* pay = reinterpret_cast<double*>(o->h_in);
+  size_t npay = 0;
+  for (int w = 0; w < nS; ++w) npay += 16 + ODO_RAW_PRE_D + 3 * (size_t)next[w].n_points + 8 * (size_t)next[w].n_lines;
+  int* tab = reinterpret_cast<int*>(o->h_in + npay * 8);
+  size_t ntab = 0;
+  int* hdr = tab; ntab += 5 * (size_t)nS;
+  int* cnt = tab + ntab; ntab += 2 * (size_t)nS;
+  int* pmv = tab + ntab; ntab += (size_t)nS * o->maxPT;
+  int* lmv = tab + ntab; ntab += (size_t)nS * o->maxLT;
+  int* ent = tab + ntab;
+  size_t nent = 0, poff = 0, kP = 0, kL = 0;
+  std::vector<OdoMove> mv;
+  std::vector<unsigned char> er;
+  for (int w = 0; w < nS; ++w) {
+    OdoSeq& q = o->seq[w];
+    vpl_odo_result scratch;
+    vpl_odo_result& r = out ? out[w] : scratch;
+    // removeFailures: solved points whose inverse depth is not > 0 (feature_manager.cpp:254-263)
+    er.assign(q.P.t.size(), 0);
+    for (int p = 0; p < o->s_nP[w]; ++p, ++kP)
+      if (!h_flags[kP]) er[o->psrc[w][p]] = 1;
+    odo_erase_slide(q.P, er.data(), flag == VPL_MARGIN_SECOND_NEW, mv, nullptr);
+    cnt[2 * w] = (int)mv.size();
+    for (size_t j = 0; j < mv.size(); ++j) pmv[(size_t)w * o->maxPT + j] = odo_pack_move(mv[j]);
+    // the lines the solve's removeLineOutlier erased
+    er.assign(q.L.t.size(), 0);
+    if (o->remove_line_outliers)
+      for (int dl = 0; dl < o->s_nL[w]; ++dl)
+        if (h_flags[totP + totT + kL + dl]) er[o->lsrc[w][o->s_lmap[w][dl]]] = 1;
+    kL += o->s_nL[w];
+    odo_erase_slide(q.L, er.data(), flag == VPL_MARGIN_SECOND_NEW, mv, nullptr);
+    cnt[2 * w + 1] = (int)mv.size();
+    for (size_t j = 0; j < mv.size(); ++j) lmv[(size_t)w * o->maxLT + j] = odo_pack_move(mv[j]);
+    // pre-integrations: MARGIN_OLD moves 2..10 down, the new interval enters slot 10
+    if (flag == VPL_MARGIN_OLD)
+      for (int j = 1; j < NF - 1; ++j) q.sum_dt[j] = q.sum_dt[j + 1];
+    q.sum_dt[NF - 1] = next[w].preint.sum_dt;
+    // the new frame
+    const vpl_odo_frame& f = next[w];
+    hdr[5 * w] = (int)poff; hdr[5 * w + 1] = f.n_points; hdr[5 * w + 2] = f.n_lines;
+    hdr[5 * w + 3] = (int)(ntab + nent); hdr[5 * w + 4] = (int)(ntab + nent + f.n_points);
+    r.n_ignored = odo_add_frame(q.P, NF - 1, f.n_points, f.point_id, ent + nent);
+    r.n_ignored += odo_add_frame(q.L, NF - 1, f.n_lines, f.line_id, ent + nent + f.n_points);
+    nent += (size_t)f.n_points + f.n_lines;
+    r.n_point_tracks = (int)q.P.t.size();
+    r.n_line_tracks = (int)q.L.t.size();
+    double* d = pay + poff;
+    std::memcpy(d, f.pose, 56); std::memcpy(d + 7, f.speed_bias, 72); std::memcpy(d + 16, &f.preint, sizeof(f.preint));
+    if (f.n_points) std::memcpy(d + 16 + ODO_RAW_PRE_D, f.point_obs, (size_t)f.n_points * 24);
+    if (f.n_lines) std::memcpy(d + 16 + ODO_RAW_PRE_D + 3 * (size_t)f.n_points, f.line_obs, (size_t)f.n_lines * 64);
+    poff += 16 + ODO_RAW_PRE_D + 3 * (size_t)f.n_points + 8 * (size_t)f.n_lines;
+  }
+  const size_t in_bytes = npay * 8 + (ntab + nent) * 4;   // (within in_cap: odo_check_next bounds a frame's observations)
+  HIPCHK(c, hipMemcpyAsync(o->d_in, o->h_in, in_bytes, hipMemcpyHostToDevice, s));
+  o->h2d_payload = (long long)npay * 8;
+  o->h2d_table += (long long)(ntab + nent) * 4;
+  const int* d_tab = reinterpret_cast<const int*>(o->d_in + npay * 8);
+  const OdoStore D = o->st[o->cur ^ 1];
+  hipLaunchKernelGGL(k_odo_slide, dim3(nS, ODO_SLIDE_Y), blk, 0, s, S, D, d_tab + (pmv - tab), d_tab + (lmv - tab), d_tab + (cnt - tab),
+                     flag == VPL_MARGIN_SECOND_NEW ? 1 : 0, o->init_depth);
+  hipLaunchKernelGGL(k_odo_append, grid, blk, 0, s, D, reinterpret_cast<const double*>(o->d_in), d_tab, d_tab);
+  HIPCHK(c, hipGetLastError());
+  o->cur ^= 1;
+  // (the pinned inbox is rewritten by the next keyframe: the copy above must have left it)
+  HIPCHK(c, hipStreamSynchronize(s));
+  o->solved = false;
+  o->ms[3] = std::chrono::duration<double, std::milli>(oclk::now() - t0).count();
+  return VPL_OK;
+}
+
+int vpl_odo_keyframe(vpl_odo* o, const vpl_odo_frame* next, const int* flags, vpl_odo_result* out) {
+  if (!o || !next || !flags || !out) return VPL_E_INVALID;
+  if (o->solved) return fail(o->c, VPL_E_INVALID, "odo_keyframe: the window has been solved and not advanced (vpl_odo_advance)");
+  int rc = odo_check_next(o, next);
+  if (!rc) rc = vpl_odo_solve(o, flags, out);
+  if (!rc) rc = vpl_odo_advance(o, next, out);
+  return rc;
+}
+
+int vpl_odo_get_prior(vpl_odo* o, int seq, vpl_prior* out) {
+  if (!o || seq < 0 || seq >= o->nS || !out) return VPL_E_INVALID;
+  vpl_ctx* c = o->c;
+  std::memset(out, 0, sizeof(int) * (2 + 3 * VPL_MAX_PRIOR_BLOCKS));
+  const OdoSeq& q = o->seq[seq];
+  if (!q.has_prior) return VPL_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const HostTab& T = q.prior;
+  out->n = T.n; out->n_blocks = T.nb;
+  for (int b = 0; b < T.nb; ++b) { out->block_kind[b] = T.kind[b]; out->block_frame[b] = T.frame[b]; out->block_idx[b] = T.idx[b]; }
+  std::vector<double> x0(MAXPB * 9);
+  HIPCHK(c, hipMemcpy(x0.data(), o->prior.x0 + (size_t)seq * MAXPB * 9, MAXPB * 9 * 8, hipMemcpyDeviceToHost));
+  for (int b = 0; b < T.nb; ++b) std::memcpy(out->x0[b], &x0[(size_t)b * 9], 72);
+  HIPCHK(c, hipMemcpy(out->J0, o->prior.J0 + (size_t)seq * MAXKEEP * MAXKEEP, (size_t)T.n * T.n * 8, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(out->r0, o->prior.r0 + (size_t)seq * MAXKEEP, (size_t)T.n * 8, hipMemcpyDeviceToHost));
+  return VPL_OK;
+}
+
+int vpl_odo_get_tracks(vpl_odo* o, int seq, int* n_points, int* point_id, int* point_start, int* point_nobs, double* inv_depth,
+                       int* n_lines, int* line_id, int* line_start, int* line_nobs, int* line_triangulated, double* line_plk) {
+  if (!o || seq < 0 || seq >= o->nS) return VPL_E_INVALID;
+  vpl_ctx* c = o->c;
+  const OdoSeq& q = o->seq[seq];
+  const OdoStore& S = o->st[o->cur];
+  const size_t nP = q.P.t.size(), nL = q.L.t.size();
+  if (n_points) *n_points = (int)nP;
+  if (n_lines) *n_lines = (int)nL;
+  for (size_t i = 0; i < nP; ++i) {
+    if (point_id) point_id[i] = q.P.t[i].id;
+    if (point_start) point_start[i] = q.P.t[i].start;
+    if (point_nobs) point_nobs[i] = q.P.t[i].nobs;
+  }
+  for (size_t i = 0; i < nL; ++i) {
+    if (line_id) line_id[i] = q.L.t[i].id;
+    if (line_start) line_start[i] = q.L.t[i].start;
+    if (line_nobs) line_nobs[i] = q.L.t[i].nobs;
+    if (line_triangulated) line_triangulated[i] = q.L.t[i].tri;
+  }
+  if (!inv_depth && !line_plk) return VPL_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (inv_depth && nP) HIPCHK(c, hipMemcpy(inv_depth, S.invd + (size_t)seq * S.maxPT, nP * 8, hipMemcpyDeviceToHost));
+  if (line_plk && nL) HIPCHK(c, hipMemcpy(line_plk, S.plk + (size_t)seq * S.maxLT * 6, nL * 6 * 8, hipMemcpyDeviceToHost));
+  return VPL_OK;
+}
+
+int vpl_odo_stats(vpl_odo* o, long long* h2d_payload_bytes, long long* h2d_table_bytes, long long* d2h_bytes) {
+  if (!o) return VPL_E_INVALID;
+  if (h2d_payload_bytes) *h2d_payload_bytes = o->h2d_payload;
+  if (h2d_table_bytes) *h2d_table_bytes = o->h2d_table;
+  if (d2h_bytes) *d2h_bytes = o->d2h;
+  return VPL_OK;
+}
+int vpl_odo_debug_ms(vpl_odo* o, double* ms4) {
+  if (!o || !ms4) return VPL_E_INVALID;
+  for (int k = 0; k < 4; ++k) ms4[k] = o->ms[k];
+  return VPL_OK;
+}
+
+// Host only: the book of one kind of tracks of one sequence replayed from a script (tests/test_odo_tracks.py)
+int vpl_odo_debug_tracks(int max_tracks, int n_steps, const int* flag, const int* n_ids, const int* ids, const unsigned char* erase,
+                         int* status, int* n_slide, int* slide, int* n_tracks, int* table, int* ignored) {
+  if (max_tracks < 1 || n_steps < 0 || !flag || !n_ids || !ids || !erase || !status || !n_slide || !slide || !n_tracks || !table || !ignored)
+    return VPL_E_INVALID;
+  OdoBook b;
+  int frames = 0;
+  std::vector<OdoMove> mv;
+  for (int s = 0; s < n_steps; ids += n_ids[s], ++s) {
+    if (n_ids[s] < 0) return VPL_E_INVALID;
+    const bool filling = flag[s] == VPL_MARGIN_NONE;
+    if (!filling && flag[s] != VPL_MARGIN_OLD && flag[s] != VPL_MARGIN_SECOND_NEW) return VPL_E_INVALID;
+    if (filling ? frames >= NF : frames < NF) return VPL_E_INVALID;
+    status[s] = VPL_OK; n_slide[s] = 0; ignored[s] = 0;
+    if ((int)b.t.size() + odo_count_unknown(b, n_ids[s], ids) > max_tracks) status[s] = VPL_E_CAPACITY;
+    else {
+      if (!filling) n_slide[s] = odo_erase_slide(b, erase + (size_t)s * max_tracks, flag[s] == VPL_MARGIN_SECOND_NEW, mv, slide + (size_t)s * max_tracks * 3);
+      ignored[s] = odo_add_frame(b, filling ? frames : NF - 1, n_ids[s], ids, nullptr);
+      if (filling) ++frames;
+    }
+    n_tracks[s] = (int)b.t.size();
+    for (size_t i = 0; i < b.t.size(); ++i) {
+      int* e = table + ((size_t)s * max_tracks + i) * 3;
+      e[0] = b.t[i].id; e[1] = b.t[i].start; e[2] = b.t[i].nobs;
+    }
+  }
+  return VPL_OK;
+}
+
+}  // extern "C"

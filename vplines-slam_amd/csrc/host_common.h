@@ -1,5 +1,5 @@
-// Host plumbing shared by the two contexts (vplines_ba.hip, vplines_frontend.hip): the error path of an entry point and the
-// guarded device arrays.  A context type Ctx provides `std::string err`, `int device`, `bool guards` and the allocation
+// Host plumbing shared by the two contexts (vpl_ctx: ba_ctx.h, used by vplines_ba.hip and its host headers ba_upload.h and
+// ba_session.h; the front-end's: vplines_frontend.hip): the error path of an entry point and the guarded device arrays.  A context type Ctx provides `std::string err`, `int device`, `bool guards` and the allocation
 // record `std::vector<void*> allocs` / `std::vector<size_t> alloc_bytes`.
 #pragma once
 #include <hip/hip_runtime.h>
