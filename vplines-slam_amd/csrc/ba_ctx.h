@@ -48,6 +48,7 @@ struct vpl_ctx {
   bool schur_mostly_wide = false;                // more than 35 % of the landmark elimination's weight sits in wide entries: k_schur<5>
   bool schur_never_wide = false;                 // VPL_BA_SCHUR_WIDE=-1: k_schur_mixed whatever the share of wide entries (A/B runs)
   bool schur_wide_all = false;                   // VPL_BA_SCHUR_WIDE=1: round 3's k_schur<5> for batches with long tracks (A/B runs, tests)
+  bool step_fused = true;                        // VPL_BA_STEP_FUSED=0: the step as k_schur, k_chol, k_back instead of k_step (A/B runs, tests); a timed solve always is
   size_t marg_smem = 0;
   int marg_nmax = 0;                             // largest kept block of the uploaded batch (k_prior_eigen's LDS layout)
   bool marg_small = false;                       // k_marg<256> (two work-groups per CU) instead of k_marg<512>

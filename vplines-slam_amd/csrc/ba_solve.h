@@ -239,12 +239,13 @@ __device__ __forceinline__ void chol4(double* A, bool& ok) {   // packed lower 4
   }
 }
 
-__device__ __forceinline__ void solve_body(const DevBatch& B, const int w, double* sm) {
+// (returns whether the window took this path)
+__device__ __forceinline__ bool solve_body(const DevBatch& B, const int w, double* sm) {
   const int tid = threadIdx.x, T = SOLVE_THREADS;
   const int lane = tid & 63, wv = tid >> 6;
   TrState* tr = &B.tr[w];
-  if (tr->status != 0) return;
-  if (B.path[w] == 0) return;     // the window takes the three-kernel path (ba_step.h)
+  if (tr->status != 0) return false;
+  if (B.path[w] == 0) return false;     // the window takes the three-kernel path (ba_step.h)
   count_active(B, tr->reuse ? 2 : 1);
   double* S = sm;                 // NAP tile-major lower (row NC = rhs); first used as 2 staging buffers
   double* sc = S + NAP;           // 176 jacobi scale of cam dims
@@ -671,7 +672,7 @@ __device__ __forceinline__ void solve_body(const DevBatch& B, const int w, doubl
         tr->mu *= kMuIncrease;   // StepIsInvalid
         tr->reuse = 0;
       }
-      return;
+      return true;
     }
     VPL_STAMP(B, w, 4);
     // ---- back substitution L^T y = z of the reduced system
@@ -852,7 +853,7 @@ __device__ __forceinline__ void solve_body(const DevBatch& B, const int w, doubl
       tr->mu *= kMuIncrease;
       tr->reuse = 0;
     }
-    return;
+    return true;
   }
 
   // ---- delta = step * jacobi scale; candidate = Plus(x, delta) -----------------------------------
@@ -915,12 +916,21 @@ __device__ __forceinline__ void solve_body(const DevBatch& B, const int w, doubl
     tr->step_valid = 1;
     tr->num_invalid = 0;
   }
+  return true;
 }
 __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(DevBatch B) {
   extern __shared__ double sm[];
   // the list k_cost of THIS iteration fills is emptied here (k_cost runs after this whole kernel)
   if (blockIdx.x == 0 && threadIdx.x == 0) { B.ord_cnt[2 * ((B.ord_it + 1) & 1)] = 0; B.ord_cnt[2 * ((B.ord_it + 1) & 1) + 1] = 0; }
-  solve_body(B, ordered_window(B), sm);
+  const int w = ordered_window(B);
+  const bool took = solve_body(B, w, sm);
+  // After k_step (B.step_fused) this kernel is the last reader of B.path in the iteration: a flag raised for this iteration
+  // only (2: a factorisation of the fast path failed) comes down here, under the condition k_back applies in the
+  // three-launch form, where it follows this kernel and does it.
+  if (took && B.step_fused) {
+    __syncthreads();                     // (everybody has read the flag)
+    if (threadIdx.x == 0 && B.tr[w].status == 0 && B.path[w] == 2) B.path[w] = 0;
+  }
 }
 
 constexpr size_t SOLVE_SMEM = (size_t)(NAP + 5 * 176 + 256 + 24) * sizeof(double) + 4 * sizeof(int);   // + (maxP + maxL) ints, see solve_smem

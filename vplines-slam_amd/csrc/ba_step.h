@@ -1,20 +1,23 @@
-// The trust-region step of a window as three kernels, each shaped for what it does (round 3):
+// The trust-region step of a window as three bodies of one launch shape (256 threads, two work-groups per CU, no scratch):
+// k_step runs them one after the other in ONE launch per step (the default); k_schur / k_chol / k_back run the same bodies
+// as three launches for the per-kernel attribution of the timing mode and for A/B runs (VPL_BA_STEP_FUSED=0).
 //
-//   k_schur  (512 threads, ~45 KB LDS, two work-groups per CU)  Jacobi scaling, dogleg diagonal / gradient, Cauchy point,
+//   k_schur  (~76 KB LDS at 200 points + 80 lines)  Jacobi scaling, dogleg diagonal / gradient, Cauchy point,
 //            regularised landmark blocks, and the landmark elimination: the rows of X = C^-1 S [W | g | e] go from HBM
 //            straight into the FP64 matrix cores -- the lane that supplies operand element (row, column) loads exactly that
 //            element -- in the COMPACT coordinates of the rows' start frame (WS + 2 columns instead of 80), every wave on its
 //            own span of rows.  No staging buffers, no work-group barriers in the product.
-//   k_chol   (256 threads, ~62 KB LDS, two work-groups per CU)  the reduced camera system.  The 99 speed/bias dims touch IMU
+//   k_chol   (~62 KB LDS)  the reduced camera system.  The 99 speed/bias dims touch IMU
 //            factors and the prior only: the blocks of frames 1..4 and 10..6 are eliminated first as two block chains (one
 //            wave each, 9-row strips held in registers with the columns in the lanes), which leaves the DENSE system
 //            [72 pose / extrinsic dims | speed/bias 0 | speed/bias 5 | rhs] = 91 rows = 6 tile columns instead of 11.
-//   k_back   (512 threads, ~16 KB LDS)  landmark back-substitution, dogleg step, model cost change, candidate x (Plus).
+//   k_back   (~16 KB LDS)  landmark back-substitution, dogleg step, model cost change, candidate x (Plus).
 //
 // Any elimination order gives the same Gauss-Newton step up to rounding; the arithmetic per entry is
 // the one of ba_solve.h.  Windows the fast path does not cover -- a prior that holds a speed/bias block of another frame
 // than 0, a factorisation that failed and is retried with a larger mu (ceres' LINEAR_SOLVER_FAILURE loop) -- are flagged in
-// B.path and take k_solve (ba_solve.h), which is launched between k_chol and k_back and leaves at once for everybody else.
+// B.path and take k_solve (ba_solve.h), which is launched after k_step (three launches: between k_chol and k_back) and leaves
+// at once for everybody else.
 // Restates ceres-solver 1.12 DoglegStrategy::ComputeStep / SchurEliminator / TrustRegionMinimizer (third party, absent
 // from the reference tree) for the configuration at vins_estimator/src/estimator.cpp:1207-1215.
 #pragma once
@@ -1024,13 +1027,17 @@ constexpr size_t CHOL_SMEM = (size_t)(((XROWS_A + XROWS_B) * XLD > DNAP ? (XROWS
 // the model cost change and the candidate x (+) delta -- for a window that re-uses the Gauss-Newton step of a rejected
 // iteration only the latter (the arithmetic is the one of ba_solve.h).
 // ---------------------------------------------------------------------------------------------------------------------
+// FUSED (k_step): k_solve runs AFTER this body and is the flag's last reader -- a window of the general path leaves without
+// touching B.path, k_solve takes a one-iteration flag down itself.
+template <bool FUSED = false>
 __device__ __forceinline__ void back_body(const DevBatch& B, const int w, double* sm) {
   const int tid = threadIdx.x, T = BACK_THREADS;
   const int lane = tid & 63;
   TrState* tr = &B.tr[w];
   if (tr->status != 0) return;
   const int path = B.path[w];
-  if (path != 0) {                       // k_solve did this window's whole step
+  if (path != 0) {                       // k_solve does / did this window's whole step
+    if (FUSED) return;
     __syncthreads();                     // (everybody has read the flag)
     if (tid == 0 && path == 2) B.path[w] = 0;
     return;
@@ -1284,6 +1291,32 @@ __global__ __launch_bounds__(BACK_THREADS, VPL_BACK_WAVES) void k_back(DevBatch 
 inline size_t back_smem(int maxP, int maxL) {
   const int nfull = NC + maxP + 4 * maxL;
   return (size_t)(176 + 4 * maxL + 2 * nfull + 24) * sizeof(double) + (size_t)(maxP + maxL) * sizeof(int);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// k_step : the three bodies above, one after the other, for the window of this work-group -- one launch per step.
+// ---------------------------------------------------------------------------------------------------------------------
+// Data flows from a window to the same window only, so the two device-wide joins of the three-launch form are work-group
+// barriers here.  A body hands over through HBM exactly as between launches (B.path, sacc, ycs, sx, the scale / diag / grad
+// vectors, tr: written by a few lanes, read by all): __syncthreads() is a release / acquire pair at work-group scope, which
+// completes the stores of every wave before any wave of the work-group goes on to load.  One LDS block, the largest of the
+// three layouts; every body initialises what it reads of it.  The general path follows this kernel (k_step -> k_solve ->
+// k_cost), see back_body<true>.
+static_assert(SCHUR_THREADS == CHOL_THREADS && CHOL_THREADS == BACK_THREADS, "k_step runs the three bodies with one work-group shape");
+template <int NTC, bool MIXED>
+__global__ __launch_bounds__(SCHUR_THREADS, 2) void k_step(DevBatch B) {
+  extern __shared__ double sm[];
+  // the list k_cost of THIS iteration fills is emptied here (k_cost runs after this whole kernel)
+  if (blockIdx.x == 0 && threadIdx.x == 0) { B.ord_cnt[2 * ((B.ord_it + 1) & 1)] = 0; B.ord_cnt[2 * ((B.ord_it + 1) & 1) + 1] = 0; }
+  const int w = ordered_window(B);
+  schur_body<NTC, MIXED>(B, w, sm);
+  __syncthreads();
+  chol_body(B, w, sm);
+  __syncthreads();
+  back_body<true>(B, w, sm);
+}
+inline size_t step_smem(int maxP, int maxL, int ntc = 5) {
+  return std::max(std::max(schur_smem(maxP, maxL, ntc), (size_t)CHOL_SMEM), back_smem(maxP, maxL));
 }
 
 }  // namespace vpl

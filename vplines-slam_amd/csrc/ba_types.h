@@ -159,6 +159,9 @@ struct DevBatch {
   // which k_chol's elimination order does not cover); 2: general path for this iteration (a factorisation failed: the retry
   // with a larger mu runs in k_solve).  k_solve (ba_solve.h) is that general path.
   int *path;                                     // [W]
+  // 1: the step is one launch, k_step -> k_solve -> k_cost, and k_solve takes a flag 2 down; 0: k_schur -> k_chol -> k_solve
+  // -> k_back, and k_back does (set by the host per solve)
+  int step_fused;
   // Entries of the packed camera Hessian that the factors of a fast-path window can fill (vis x vis, the 15-dim frame blocks
   // and their sub-diagonal neighbours, speed/bias 0 against everything: 6147 of 14706), as idx | r << 14 | c << 22: the
   // passes of k_schur that need every non-zero of Hcc walk this list instead of the whole triangle.

@@ -186,16 +186,18 @@ static int ctx_init(vpl_ctx* c, int device, int max_windows, int max_points, int
     if ((int)nz.size() != NZ_N || hipMemcpy(B.nz_tab, nz.data(), nz.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return VPL_E_HIP;
   }
   // the attribute is per kernel, not per context: never lower what a larger context of this process has asked for
-  static size_t lin_max = 0, solve_max = 0, schur_max = 0, back_max = 0;
+  static size_t lin_max = 0, solve_max = 0, schur_max = 0, back_max = 0, step_max = 0;
   lin_max = std::max(lin_max, lin_smem(c->maxP, c->maxL));
   solve_max = std::max(solve_max, solve_smem(c->maxP, c->maxL));
   schur_max = std::max(schur_max, schur_smem(c->maxP, c->maxL));
   back_max = std::max(back_max, back_smem(c->maxP, c->maxL));
+  step_max = std::max(step_max, step_smem(c->maxP, c->maxL));
   if (schur_max > 159 * 1024 || back_max > 159 * 1024) return VPL_E_CAPACITY;
   const std::pair<const void*, size_t> lds[] = {
       {(const void*)k_lin2, lin_max}, {(const void*)k_lin<1>, lin_max}, {(const void*)k_lin<2>, lin_max},
       {(const void*)k_solve, solve_max}, {(const void*)k_schur<3>, schur_max}, {(const void*)k_schur<5>, schur_max},
       {(const void*)k_schur_mixed, schur_max}, {(const void*)k_chol, CHOL_SMEM}, {(const void*)k_back, back_max},
+      {(const void*)k_step<3, false>, step_max}, {(const void*)k_step<3, true>, step_max}, {(const void*)k_step<5, false>, step_max},
       {(const void*)k_prep, PREP_SMEM}, {(const void*)k_marg<MARG_THREADS>, 159 * 1024}, {(const void*)k_marg<256>, MARG_LDS_SMALL},
       {(const void*)k_prior_eigen, prior_eig_layout(MAXKEEP).bytes}};
   for (const auto& k : lds)
@@ -203,6 +205,7 @@ static int ctx_init(vpl_ctx* c, int device, int max_windows, int max_points, int
   vpl_ba_default_options(&c->opt);
   if (const char* gv = std::getenv("VPL_BA_GRAPH")) c->use_graph = std::atoi(gv) != 0;
   if (const char* gv = std::getenv("VPL_BA_GENERAL")) c->force_general = std::atoi(gv) != 0;
+  if (const char* gv = std::getenv("VPL_BA_STEP_FUSED")) c->step_fused = std::atoi(gv) != 0;
   if (const char* gv = std::getenv("VPL_BA_SCHUR_WIDE")) { c->schur_wide_all = std::atoi(gv) > 0; c->schur_never_wide = std::atoi(gv) < 0; }
   return VPL_OK;
 }
@@ -698,6 +701,7 @@ static void launch_solve(vpl_ctx* c, int w0, int nw, hipStream_t s) {
   // with kernel timing on, every launch also counts the windows that did work in it (vpl_ba_launch_profile)
   B.act = c->timing ? c->d_act : nullptr;
   B.launch = 0;
+  B.step_fused = c->step_fused && !c->timing;
   if (c->timing) { c->ltimes.clear(); (void)hipMemsetAsync(c->d_act, 0, sizeof(int) * ACT_SLOTS * 4, s); }   // (counts only)
   const dim3 grid(nw);
   launch_prep(c, B, nw, s);
@@ -706,20 +710,32 @@ static void launch_solve(vpl_ctx* c, int w0, int nw, hipStream_t s) {
   ++B.launch;
   for (int it = 0; it < c->opt.num_iterations; ++it) {
     B.ord_it = it;      // k_solve / k_cost of iteration `it` walk order[it & 1]; k_cost fills order[(it + 1) & 1]
-    // the step: landmark elimination -> reduced camera system -> (general path: windows flagged in B.path only) -> landmark
-    // back-substitution + dogleg + candidate.
-    { KTimer t(c, "k_schur");
-      if (B.WS + 2 <= 48) hipLaunchKernelGGL(k_schur<3>, grid, dim3(SCHUR_THREADS), schur_smem(B.maxP, B.maxL, 3), s, B);
-      else if (c->schur_wide_all || (c->schur_mostly_wide && !c->schur_never_wide)) hipLaunchKernelGGL(k_schur<5>, grid, dim3(SCHUR_THREADS), schur_smem(B.maxP, B.maxL, 5), s, B);
+    // the step: landmark elimination -> reduced camera system -> landmark back-substitution + dogleg + candidate; the general
+    // path (windows flagged in B.path only) after it, or before the back-substitution in the three-launch form.
+    // One launch (k_step) unless the solve is timed kernel by kernel: the timing mode attributes time and active windows
+    // per phase (vpl_ba_launch_profile) and issues the same bodies as three launches -- the same bits.
+    const bool wide = c->schur_wide_all || (c->schur_mostly_wide && !c->schur_never_wide);
+    if (B.step_fused) {
+      if (B.WS + 2 <= 48) hipLaunchKernelGGL((k_step<3, false>), grid, dim3(SCHUR_THREADS), step_smem(B.maxP, B.maxL, 3), s, B);
+      else if (wide) hipLaunchKernelGGL((k_step<5, false>), grid, dim3(SCHUR_THREADS), step_smem(B.maxP, B.maxL, 5), s, B);
       // rows wider than 6 frames: narrow view for the entries of short tracks, all tiles for the flagged ones (round 4)
-      else hipLaunchKernelGGL(k_schur_mixed, grid, dim3(SCHUR_THREADS), schur_smem(B.maxP, B.maxL, 3), s, B); }
-    ++B.launch;
-    { KTimer t(c, "k_chol"); hipLaunchKernelGGL(k_chol, grid, dim3(CHOL_THREADS), CHOL_SMEM, s, B); }
-    ++B.launch;
-    { KTimer t(c, "k_solve"); hipLaunchKernelGGL(k_solve, grid, dim3(SOLVE_THREADS), solve_smem(B.maxP, B.maxL), s, B); }
-    ++B.launch;
-    { KTimer t(c, "k_back"); hipLaunchKernelGGL(k_back, grid, dim3(BACK_THREADS), back_smem(B.maxP, B.maxL), s, B); }
-    ++B.launch;
+      else hipLaunchKernelGGL((k_step<3, true>), grid, dim3(SCHUR_THREADS), step_smem(B.maxP, B.maxL, 3), s, B);
+      ++B.launch;
+      hipLaunchKernelGGL(k_solve, grid, dim3(SOLVE_THREADS), solve_smem(B.maxP, B.maxL), s, B);
+      ++B.launch;
+    } else {
+      { KTimer t(c, "k_schur");
+        if (B.WS + 2 <= 48) hipLaunchKernelGGL(k_schur<3>, grid, dim3(SCHUR_THREADS), schur_smem(B.maxP, B.maxL, 3), s, B);
+        else if (wide) hipLaunchKernelGGL(k_schur<5>, grid, dim3(SCHUR_THREADS), schur_smem(B.maxP, B.maxL, 5), s, B);
+        else hipLaunchKernelGGL(k_schur_mixed, grid, dim3(SCHUR_THREADS), schur_smem(B.maxP, B.maxL, 3), s, B); }
+      ++B.launch;
+      { KTimer t(c, "k_chol"); hipLaunchKernelGGL(k_chol, grid, dim3(CHOL_THREADS), CHOL_SMEM, s, B); }
+      ++B.launch;
+      { KTimer t(c, "k_solve"); hipLaunchKernelGGL(k_solve, grid, dim3(SOLVE_THREADS), solve_smem(B.maxP, B.maxL), s, B); }
+      ++B.launch;
+      { KTimer t(c, "k_back"); hipLaunchKernelGGL(k_back, grid, dim3(BACK_THREADS), back_smem(B.maxP, B.maxL), s, B); }
+      ++B.launch;
+    }
     { KTimer t(c, "k_cost"); hipLaunchKernelGGL(k_cost, grid, dim3(COST_THREADS), 0, s, B); }
     ++B.launch;
     if (it + 1 < c->opt.num_iterations) {
