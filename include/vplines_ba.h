@@ -378,7 +378,8 @@ void vpl_odo_destroy(vpl_odo* odo);
 typedef struct vpl_odo_frame {   /* one image of one sequence, as processImage() receives it */
   double pose[7], speed_bias[9]; /* the propagated state of the new frame (processIMU's Ps / Rs / Vs / Bas / Bgs) */
   vpl_preintegration preint;     /* of the interval that ends in this frame (the IMU buffers stay the caller's, as for
-                                    vpl_ba_slide_window; after VPL_MARGIN_SECOND_NEW slot 9 keeps its pre-integration) */
+                                    vpl_ba_slide_window; after VPL_MARGIN_SECOND_NEW slot 9 keeps its pre-integration -- the
+                                    IMU form below, vpl_odo_enable_imu, merges it as the reference does) */
   int n_points; const int* point_id; const double* point_obs; /* [n][3]  x,y,1 */
   int n_lines;  const int* line_id;  const double* line_obs;  /* [n][8]  as vpl_window.line_obs */
 } vpl_odo_frame;
@@ -416,6 +417,52 @@ int vpl_odo_keyframe(vpl_odo* odo, const vpl_odo_frame* next, const int* margina
  * n_ignored are updated).  They alternate: VPL_E_INVALID out of turn; a refused vpl_odo_advance can be repeated. */
 int vpl_odo_solve(vpl_odo* odo, const int* marginalization_flag, vpl_odo_result* out);
 int vpl_odo_advance(vpl_odo* odo, const vpl_odo_frame* next, vpl_odo_result* out);
+
+/* ---- keyframe session, IMU samples in: pre-integration, merge and propagation on the device -------------------------------- *
+ * With the plain calls above the IMU side of processImage stays the caller's: a finished vpl_preintegration and a propagated
+ * state per frame -- which needs the bias vpl_odo_solve has just estimated, i.e. a read-back, vpl_preintegrate_batch and a host
+ * propagation between the two halves -- and after VPL_MARGIN_SECOND_NEW slot 9 keeps a pre-integration that ends one image early.
+ * An IMU-enabled session takes the raw samples instead and does what the estimator does (estimator.cpp:82-117, 1766, 1786-1810):
+ *   - the new interval is integrated on the device from the bias the solve has just left in slot 10 (IntegrationBase::push_back,
+ *     the arithmetic of vpl_preintegrate_batch bit for bit) and becomes pre_integrations[10];
+ *   - the new frame's pose and velocity are propagated on the device from the newest solved state (processIMU, :107-113);
+ *   - on VPL_MARGIN_SECOND_NEW the samples slot 10 held are pushed onto pre_integrations[9] (:1786-1799), continuing it under
+ *     its own linearisation bias, so that IMU factor (8, 9) spans the interval up to what is now frame 9.
+ * vpl_odo_enable_imu: once per session (a second call: VPL_E_INVALID), max_samples >= 1 = the longest interval, in samples.
+ * Allocates per sequence the sample buffer of slot 10 ([max_samples][7]) and its linearized_acc / _gyr through the context's
+ * guarded allocator; the last measurement seen (the estimator's acc_0 / gyr_0) is the last row of that buffer.  From then on
+ * vpl_odo_keyframe / vpl_odo_advance return VPL_E_INVALID (they would desynchronise the IMU book); vpl_odo_solve stays usable.
+ * Without it the _imu calls and vpl_odo_set_imu return VPL_E_INVALID. */
+int vpl_odo_enable_imu(vpl_odo* odo, int max_samples);
+/* After vpl_odo_set_window: samples10 [n10][7] = (dt, ax, ay, az, gx, gy, gz), the samples of the interval that ends in frame 10
+ * (dt_buf[10] and its two companions); acc0_10 / gyr0_10 [3] = linearized_acc / linearized_gyr of pre_integrations[10], the last
+ * measurement before that interval (by the reference's construction the last sample of interval 9).  The session's last
+ * measurement becomes samples10[n10 - 1].  Both are needed because the first image may be a non-keyframe.  n10 < 1:
+ * VPL_E_INVALID; n10 > max_samples: VPL_E_CAPACITY.  vpl_odo_set_window on an IMU-enabled session invalidates the sequence's IMU
+ * side until this is called again; an _imu call on such a sequence returns VPL_E_INVALID. */
+int vpl_odo_set_imu(vpl_odo* odo, int seq, int n10, const double* samples10, const double* acc0_10, const double* gyr0_10);
+
+typedef struct vpl_odo_imu_frame { /* one image of one sequence with the IMU samples since the previous image */
+  int n_samples; const double* samples;                       /* [n][7]  dt, ax, ay, az, gx, gy, gz; acc_0 / gyr_0 of the
+                                                                 interval are the last measurement the session has seen */
+  int n_points; const int* point_id; const double* point_obs; /* as vpl_odo_frame */
+  int n_lines;  const int* line_id;  const double* line_obs;
+} vpl_odo_imu_frame;
+typedef struct vpl_odo_imu_out {   /* per sequence */
+  double pose[7], speed_bias[9];   /* the propagated state of the frame that entered slot 10 (what the reference publishes) */
+  double sum_dt[2];                /* of pre_integrations[9] and [10] after the call */
+} vpl_odo_imu_out;
+/* vpl_odo_advance / vpl_odo_keyframe with samples (keyframe_imu = vpl_odo_solve, then advance_imu).  imu_out may be NULL.
+ * Refusals as for the plain calls, checked before anything is written, and: NULL samples or n_samples < 1 (an empty interval has
+ * zero covariance, which cannot be whitened): VPL_E_INVALID; n_samples > max_samples: VPL_E_CAPACITY.  A non-finite sample is not
+ * refused: the next solve fails with termination 2. */
+int vpl_odo_advance_imu(vpl_odo* odo, const vpl_odo_imu_frame* next, vpl_odo_result* out, vpl_odo_imu_out* imu_out);
+int vpl_odo_keyframe_imu(vpl_odo* odo, const vpl_odo_imu_frame* next, const int* marginalization_flag, vpl_odo_result* out,
+                         vpl_odo_imu_out* imu_out);
+/* The 11 pre-integrations the session holds (any session), out[VPL_NFRAMES]; entry 0 is zeroed.  jacobian: columns 9..14 (the bias
+ * columns, the only ones IMUFactor reads) as held, rows 9..14 of them the identity; columns 0..8 are NOT held by the session and
+ * come back zero. */
+int vpl_odo_get_preint(vpl_odo* odo, int seq, vpl_preintegration* out);
 
 /* What a caller may want to look at; none of it is needed to keep going.  Arrays may be NULL (not wanted); the track arrays
  * need room for max_*_tracks entries.  Tracks come in the feature manager's order. */

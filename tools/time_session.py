@@ -2,7 +2,10 @@
 tests/test_gpu_sequence.py -- the companion of tools/time_odometry.py, which times the same 32 keyframes through
 vpl_ba_solve_odometry + vpl_ba_slide_window with the feature manager on the host.  Medians over keyframes 4..31 of the C calls
 alone and of the stages inside them; then --batch N sequences (default 64) in one session for --batch-keyframes keyframes:
-keyframes per second.  Every C call ends in a stream synchronise, so the host clock around it is the time of the work."""
+keyframes per second.  Every C call ends in a stream synchronise, so the host clock around it is the time of the work.
+--mode imu: the same sequence through vpl_odo_keyframe_imu (raw samples in; pre-integration, merge and propagation on the device).
+--mode halves: the only faithful alternative without it -- vpl_odo_solve, vpl_preintegrate_batch from the bias it returned, the
+propagation on the host (not timed: a C++ caller's costs microseconds), vpl_odo_advance; the three C calls are summed."""
 import argparse
 import os
 import sys
@@ -41,11 +44,61 @@ def run(seeds, n_keyframes):
     return acc
 
 
+def run_imu(M, n_keyframes, halves):
+    """one sequence on the consistent IMU stream of tests/test_gpu_odo_imu.py; seconds per keyframe of the C calls and of the
+    session's fourth stage (slide + new frame)"""
+    import ctypes as C
+    import time
+    import test_gpu_odo_imu as I
+    opt = v.default_options()
+    st = I.Stream(M)
+    ctx = S._ctxn(1)
+    ses = I.session(ctx, 1, opt, imu=not halves)
+    I.feed(ses, 0, ctx, st, opt, imu=not halves)
+    acc = {"keyframe_c_calls": [], "stage_slide_new_frame": [], "preintegrate_c_call": []}
+    for k in range(n_keyframes):
+        F = T.NF + k
+        if not halves:
+            ses.keyframe_imu([v.ImuFrame(st.imu[F], *I.obs_of(M, F))])
+            acc["keyframe_c_calls"].append(ses.last_call_s)
+            acc["preintegrate_c_call"].append(0.0)
+        else:
+            res = ses.solve()
+            t = ses.last_call_s
+            sb = np.zeros(9)
+            sb[:3], sb[3:] = M.pred[F][1][:3], I.sb10(res[0])[3:]
+            args = [np.ascontiguousarray(a) for a in (np.zeros(1, np.int32), np.array([len(st.imu[F])], np.int32), st.imu[F],
+                                                      st.acc0(F)[None], st.gyr0(F)[None], sb[None, 3:6], sb[None, 6:9])]
+            pre = (v.capi.Preintegration * 1)()
+            ptr = [a.ctypes.data_as(C.POINTER(C.c_int if a.dtype == np.int32 else C.c_double)) for a in args]
+            t0 = time.perf_counter()
+            rc = ctx.lib.vpl_preintegrate_batch(ctx.h, 1, *ptr, C.byref(opt), pre)
+            tp = time.perf_counter() - t0
+            assert rc == 0
+            ses.advance([v.Frame(*I.obs_of(M, F), pose=M.pred[F][0], speed_bias=sb, preint=pre[0])])
+            acc["keyframe_c_calls"].append(t + tp + ses.last_call_s)
+            acc["preintegrate_c_call"].append(tp)
+        acc["stage_slide_new_frame"].append(ses.stage_ms()[3] * 1e-3)
+    ses.close()
+    ctx.close()
+    return acc
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--batch-keyframes", type=int, default=12)
+    ap.add_argument("--mode", choices=("plain", "imu", "halves"), default="plain")
+    ap.add_argument("--repeat", type=int, default=1, help="imu / halves: run the sequence this many times, the two modes alternating")
     a = ap.parse_args()
+    if a.mode != "plain":
+        M = T.Measurements(T.NF + T.N_KEYFRAMES)
+        for r in range(a.repeat):
+            for mode in (("imu", "halves") if a.repeat > 1 else (a.mode,)):
+                acc = run_imu(M, T.N_KEYFRAMES, mode == "halves")
+                print("%s run %d: %s" % (mode, r, " | ".join("%s median %.3f ms (min %.3f, max %.3f)" % (
+                    k, np.median(x[4:]) * 1e3, np.min(x[4:]) * 1e3, np.max(x[4:]) * 1e3) for k, x in acc.items())))
+        sys.exit(0)
     acc = run([77], T.N_KEYFRAMES)
     tot = np.array(acc["solve_c_call"][4:]) + np.array(acc["advance_c_call"][4:])
     print("keyframe_c_calls: median %.2f ms, min %.2f, max %.2f over %d keyframes (solve + advance, one sequence)"

@@ -8,7 +8,7 @@ implementation."""
 from . import _build  # noqa: F401
 from .capi import (  # noqa: F401
     BaOptions, Preintegration, Prior, Window, SolveReport, Context, SlideTracks, default_options, load_hip_library,
-    Session, Frame, OdoResult,
+    Session, Frame, ImuFrame, OdoResult, OdoImuOut,
     MARGIN_OLD, MARGIN_SECOND_NEW, MARGIN_NONE, PRIOR_PIVOTED_CHOLESKY, PRIOR_EIGEN,
 )
 from . import workload  # noqa: F401

@@ -168,6 +168,18 @@ class OdoResult(C.Structure):
                 ("n_line_tracks", C.c_int), ("n_ignored", C.c_int)]
 
 
+class OdoImuFrame(C.Structure):
+    """vpl_odo_imu_frame: one image of one sequence with the IMU samples since the previous image"""
+    _fields_ = [("n_samples", C.c_int), ("samples", _dp),
+                ("n_points", C.c_int), ("point_id", _ip), ("point_obs", _dp),
+                ("n_lines", C.c_int), ("line_id", _ip), ("line_obs", _dp)]
+
+
+class OdoImuOut(C.Structure):
+    """vpl_odo_imu_out: the propagated state of the frame that entered slot 10, sum_dt of slots 9 and 10"""
+    _fields_ = [("pose", C.c_double * 7), ("speed_bias", C.c_double * 9), ("sum_dt", C.c_double * 2)]
+
+
 ODO_D2H_PAD_BYTES = 0    # VPL_ODO_D2H_PAD_BYTES: the session's read-backs are packed without alignment padding
 
 
@@ -258,6 +270,11 @@ def load_hip_library():
     lib.vpl_odo_advance.argtypes = [vp, C.POINTER(OdoFrame), C.POINTER(OdoResult)]
     lib.vpl_odo_get_prior.argtypes = [vp, C.c_int, C.POINTER(Prior)]
     lib.vpl_odo_get_tracks.argtypes = [vp, C.c_int, _ip, _ip, _ip, _ip, _dp, _ip, _ip, _ip, _ip, _ip, _dp]
+    lib.vpl_odo_enable_imu.argtypes = [vp, C.c_int]
+    lib.vpl_odo_set_imu.argtypes = [vp, C.c_int, C.c_int, _dp, _dp, _dp]
+    lib.vpl_odo_advance_imu.argtypes = [vp, C.POINTER(OdoImuFrame), C.POINTER(OdoResult), C.POINTER(OdoImuOut)]
+    lib.vpl_odo_keyframe_imu.argtypes = [vp, C.POINTER(OdoImuFrame), _ip, C.POINTER(OdoResult), C.POINTER(OdoImuOut)]
+    lib.vpl_odo_get_preint.argtypes = [vp, C.c_int, C.POINTER(Preintegration)]
     _llp = C.POINTER(C.c_longlong)
     lib.vpl_odo_stats.argtypes = [vp, _llp, _llp, _llp]
     lib.vpl_odo_debug_ms.argtypes = [vp, _dp]
@@ -583,6 +600,25 @@ class Frame:
         cf.line_id, cf.line_obs = self.line_id.ctypes.data_as(_ip), self.line_obs.ctypes.data_as(_dp)
 
 
+class ImuFrame:
+    """One image of one sequence for an IMU-enabled Session: its observations as in Frame, and samples [n][7] = (dt, ax, ay, az,
+    gx, gy, gz) of the interval that ends in it -- the session integrates and propagates them on the device."""
+
+    def __init__(self, samples, point_id=(), point_obs=(), line_id=(), line_obs=()):
+        self.samples = _arr(samples, np.float64).reshape(-1, 7)
+        self.point_id = _arr(point_id, np.int32).reshape(-1)
+        self.point_obs = _arr(point_obs, np.float64).reshape(-1, 3)
+        self.line_id = _arr(line_id, np.int32).reshape(-1)
+        self.line_obs = _arr(line_obs, np.float64).reshape(-1, 8)
+        assert len(self.point_id) == len(self.point_obs) and len(self.line_id) == len(self.line_obs)
+
+    def to_c(self, cf):
+        cf.n_samples, cf.samples = len(self.samples), self.samples.ctypes.data_as(_dp)
+        cf.n_points, cf.n_lines = len(self.point_id), len(self.line_id)
+        cf.point_id, cf.point_obs = self.point_id.ctypes.data_as(_ip), self.point_obs.ctypes.data_as(_dp)
+        cf.line_id, cf.line_obs = self.line_id.ctypes.data_as(_ip), self.line_obs.ctypes.data_as(_dp)
+
+
 class Session:
     """vpl_odo: the feature manager and the window of n_seq sequences resident on the device, fed one keyframe at a time
     (include/vplines_ba.h, "keyframe session").  Borrows `ctx` (one session per context) or makes a context of its own from
@@ -674,6 +710,63 @@ class Session:
         self.last_rc = rc
         self.ctx._check(rc, "vpl_odo_advance")
         return self._res
+
+    # ---- IMU samples in (vpl_odo_enable_imu): pre-integration, merge and propagation on the device ----
+    def enable_imu(self, max_samples):
+        """vpl_odo_enable_imu: from now on the session takes ImuFrames (keyframe_imu / advance_imu); once per session"""
+        self.ctx._settle()
+        rc = self.lib.vpl_odo_enable_imu(self.h, int(max_samples))
+        self.last_rc = rc
+        self.ctx._check(rc, "vpl_odo_enable_imu")
+
+    def set_imu(self, seq, samples10, acc0_10, gyr0_10):
+        """vpl_odo_set_imu, after set_window: the samples [n][7] of the interval that ends in frame 10 and linearized_acc / _gyr
+        of its pre-integration (the last measurement before that interval)"""
+        smp = _arr(samples10, np.float64).reshape(-1, 7)
+        a0, g0 = _arr(acc0_10, np.float64).reshape(3), _arr(gyr0_10, np.float64).reshape(3)
+        self.ctx._settle()
+        rc = self.lib.vpl_odo_set_imu(self.h, seq, len(smp), _p(smp), _p(a0), _p(g0))
+        self.last_rc = rc
+        self.ctx._check(rc, "vpl_odo_set_imu")
+
+    def _imu_frames(self, frames):
+        assert len(frames) == self.n_seq
+        cf = (OdoImuFrame * self.n_seq)()
+        for i, f in enumerate(frames):
+            f.to_c(cf[i])
+        return cf
+
+    def keyframe_imu(self, frames, flags=None):
+        """vpl_odo_keyframe_imu: keyframe() with ImuFrames; (one OdoResult per sequence, one OdoImuOut per sequence)"""
+        cf = self._imu_frames(frames)
+        fl = _arr([MARGIN_OLD] * self.n_seq if flags is None else flags, np.int32)
+        assert len(fl) == self.n_seq
+        res, imu = (OdoResult * self.n_seq)(), (OdoImuOut * self.n_seq)()
+        self.ctx._settle()
+        t0 = time.perf_counter()
+        rc = self.lib.vpl_odo_keyframe_imu(self.h, cf, fl.ctypes.data_as(_ip), res, imu)
+        self.last_call_s = time.perf_counter() - t0
+        self.last_rc = rc
+        self.ctx._check(rc, "vpl_odo_keyframe_imu")
+        return res, imu
+
+    def advance_imu(self, frames):
+        """vpl_odo_advance_imu, after solve(): (solve's results with the counts updated, one OdoImuOut per sequence)"""
+        cf = self._imu_frames(frames)
+        imu = (OdoImuOut * self.n_seq)()
+        self.ctx._settle()
+        t0 = time.perf_counter()
+        rc = self.lib.vpl_odo_advance_imu(self.h, cf, getattr(self, "_res", None), imu)
+        self.last_call_s = time.perf_counter() - t0
+        self.last_rc = rc
+        self.ctx._check(rc, "vpl_odo_advance_imu")
+        return self._res, imu
+
+    def get_preint(self, seq=0):
+        """vpl_odo_get_preint: (Preintegration * 11) as the session holds them (entry 0 zero; jacobian columns 0..8 zero)"""
+        out = (Preintegration * NF)()
+        self.ctx._check(self.lib.vpl_odo_get_preint(self.h, seq, out), "vpl_odo_get_preint")
+        return out
 
     def get_prior(self, seq=0):
         p = Prior()

@@ -211,61 +211,65 @@ __device__ __forceinline__ V3 m3row(const M3& A, int r) {
             A.m[2] * w0 + A.m[5] * w1 + A.m[8] * w2};
 }
 
-__global__ __launch_bounds__(64) void k_preintegrate(int n, const int* offset, const int* nsamples, const double* samples,
-                                                     const double* acc0, const double* gyr0, const double* lba,
-                                                     const double* lbg, double an2, double gn2, double aw2, double gw2,
-                                                     DevPreint* out) {
-  __shared__ double tile[4][15 * PREINT_GROUP];
-  const int grp = threadIdx.x / PREINT_GROUP, j = threadIdx.x % PREINT_GROUP;
-  const int iv = blockIdx.x * 4 + grp;
-  const bool live = iv < n;
-  const int i = live ? iv : n - 1;            // idle groups shadow the last interval (no stores) so that barriers stay uniform
-  const int jc = j < 15 ? j : 14, jb = jc / 3, jj = jc % 3;
+// What a lane carries through the steps: column jc of the jacobian and of the covariance, and (the same in every lane of the
+// group) the deltas, the elapsed time and the previous measurement
+struct PreintLane {
   double Jc[15], Pc[15];
+  V3 dp, dv;
+  Q4 dq;
+  double sum_dt;
+  V3 a0, g0;
+};
+// IntegrationBase's constructor: identity, zero covariance; acc_0 / gyr_0 = the last measurement before the interval
+__device__ __forceinline__ void preint_identity(PreintLane& s, int jc, V3 a0, V3 g0) {
 #pragma unroll
-  for (int k = 0; k < 15; ++k) { Jc[k] = (k == jc) ? 1.0 : 0.0; Pc[k] = 0.0; }
-  V3 dp{0, 0, 0}, dv{0, 0, 0};
-  Q4 dq{1, 0, 0, 0};
-  double sum_dt = 0.0;
-  V3 a0{acc0[3 * i], acc0[3 * i + 1], acc0[3 * i + 2]}, g0{gyr0[3 * i], gyr0[3 * i + 1], gyr0[3 * i + 2]};
-  const V3 ba{lba[3 * i], lba[3 * i + 1], lba[3 * i + 2]}, bg{lbg[3 * i], lbg[3 * i + 1], lbg[3 * i + 2]};
-  const double* sp = samples + (size_t)offset[i] * 7;
-  // every group of the block runs the same number of steps (barriers inside); a group past its own count idles
-  int ns = nsamples[i], nmax = ns;
-  nmax = max(nmax, __shfl_xor(nmax, 16, 64));
-  nmax = max(nmax, __shfl_xor(nmax, 32, 64));
-  double* tl = tile[grp];
+  for (int k = 0; k < 15; ++k) { s.Jc[k] = (k == jc) ? 1.0 : 0.0; s.Pc[k] = 0.0; }
+  s.dp = V3{0, 0, 0}; s.dv = V3{0, 0, 0};
+  s.dq = Q4{1, 0, 0, 0};
+  s.sum_dt = 0.0;
+  s.a0 = a0; s.g0 = g0;
+}
+// push_back for samples 0 .. ns - 1 at sp ([.][7]: dt, acc, gyr) on the state s -- an identity (k_preintegrate) or a state loaded
+// from a stored pre-integration that is continued (k_odo_imu): ONE body for both, so that a continuation gives the bits of the
+// integration over the concatenated samples.  Every group of the block runs nmax >= ns steps (barriers inside); a group past its
+// own count idles.  tl: the group's 15 x 16 LDS tile, j: the lane within the group, jc / jb / jj: its column.
+__device__ __forceinline__ void preint_steps(PreintLane& s, int j, const double* sp, int ns, int nmax, V3 ba, V3 bg, double an2,
+                                             double gn2, double aw2, double gw2, double* tl) {
+  const int jc = j < 15 ? j : 14, jb = jc / 3, jj = jc % 3;
   for (int k = 0; k < nmax; ++k) {
     const bool on = k < ns;
     const double* p = sp + 7 * (on ? k : 0);
     const double dt = on ? p[0] : 0.0;   // a group past its own sample count applies F = I, N = 0 (exact: every term carries dt)
     const V3 a1{p[1], p[2], p[3]}, g1{p[4], p[5], p[6]};
     // midPointIntegration (:54-198)
-    const V3 un_acc_0 = qrot(dq, a0 - ba);
-    const V3 un_gyr = (g0 + g1) * 0.5 - bg;
-    const Q4 rq = qmul(dq, Q4{1, un_gyr.x * dt / 2, un_gyr.y * dt / 2, un_gyr.z * dt / 2});
+    const V3 un_acc_0 = qrot(s.dq, s.a0 - ba);
+    const V3 un_gyr = (s.g0 + g1) * 0.5 - bg;
+    const Q4 rq = qmul(s.dq, Q4{1, un_gyr.x * dt / 2, un_gyr.y * dt / 2, un_gyr.z * dt / 2});
     const V3 un_acc_1 = qrot(rq, a1 - ba);
     const V3 un_acc = (un_acc_0 + un_acc_1) * 0.5;
-    const V3 rp = dp + dv * dt + un_acc * (0.5 * dt * dt);
-    const V3 rv = dv + un_acc * dt;
-    const M3 Rq = qmat(dq), Rr = qmat(rq);
+    const V3 rp = s.dp + s.dv * dt + un_acc * (0.5 * dt * dt);
+    const V3 rv = s.dv + un_acc * dt;
+    const M3 Rq = qmat(s.dq), Rr = qmat(rq);
     PreintF f;
     f.dt = dt;
     f.ImW = add(ident(), scale(skew(un_gyr), -dt));
     f.S2 = mul(Rr, skew(a1 - ba));                       // Rr [a1 - ba]x
-    f.S3 = add(mul(Rq, skew(a0 - ba)), mul(f.S2, f.ImW));
+    f.S3 = add(mul(Rq, skew(s.a0 - ba)), mul(f.S2, f.ImW));
     f.S1 = add(Rq, Rr);
     // J <- F J ; T = F P (both in place; an idle group keeps working on its registers and never stores them)
-    preint_apply_F(f, Jc);
-    preint_apply_F(f, Pc);
+    preint_apply_F(f, s.Jc);
+    preint_apply_F(f, s.Pc);
     // rows of T through LDS: lane k wrote column k, lane j reads row j
     __syncthreads();
 #pragma unroll
-    for (int r = 0; r < 15; ++r) tl[r * PREINT_GROUP + j] = Pc[r];
+    for (int r = 0; r < 15; ++r) tl[r * PREINT_GROUP + j] = s.Pc[r];
     __syncthreads();
 #pragma unroll
-    for (int c = 0; c < 15; ++c) Pc[c] = on ? tl[jc * PREINT_GROUP + c] : Pc[c];
-    preint_apply_F(f, Pc);                               // column j of F T^T = column j of (T F^T)^T = column j of P'
+    for (int c = 0; c < 15; ++c) {
+      const double t = tl[jc * PREINT_GROUP + c];        // (a VALUE is chosen: `on ? tl[..] : s.Pc[c]` is an lvalue, a choice
+      if (on) s.Pc[c] = t;                               //  between two addresses, and keeps s.Pc on the stack)
+    }
+    preint_apply_F(f, s.Pc);                             // column j of F T^T = column j of (T F^T)^T = column j of P'
     // + column j of N = V Q V^T (V of :107-125; Q = diag(an2, gn2, an2, gn2, aw2, gw2) x I3).  With A = Rq, B = Rr,
     // C = Rr [a1]x: G = A A^T + B B^T and C C^T are symmetric, so their column jj is the matrix times its own row jj
     {
@@ -288,31 +292,49 @@ __global__ __launch_bounds__(64) void k_preintegrate(int n, const int* offset, c
         n1 = V3{jj == 0 ? 1.0 : 0.0, jj == 1 ? 1.0 : 0.0, jj == 2 ? 1.0 : 0.0} * (2.0 * gn2 * c * c);
         n2 = m3col(f.S2, jj) * (2.0 * gn2 * c * e);
       }
-      Pc[0] += n0.x; Pc[1] += n0.y; Pc[2] += n0.z; Pc[3] += n1.x; Pc[4] += n1.y; Pc[5] += n1.z;
-      Pc[6] += n2.x; Pc[7] += n2.y; Pc[8] += n2.z;
+      s.Pc[0] += n0.x; s.Pc[1] += n0.y; s.Pc[2] += n0.z; s.Pc[3] += n1.x; s.Pc[4] += n1.y; s.Pc[5] += n1.z;
+      s.Pc[6] += n2.x; s.Pc[7] += n2.y; s.Pc[8] += n2.z;
 #pragma unroll
       for (int q = 0; q < 3; ++q) {
-        Pc[9 + q] += (jb == 3 && jj == q) ? aw2 * dt * dt : 0.0;
-        Pc[12 + q] += (jb == 4 && jj == q) ? gw2 * dt * dt : 0.0;
+        s.Pc[9 + q] += (jb == 3 && jj == q) ? aw2 * dt * dt : 0.0;
+        s.Pc[12 + q] += (jb == 4 && jj == q) ? gw2 * dt * dt : 0.0;
       }
     }
     if (on) {
-      dp = rp; dv = rv; dq = qnormalized(rq);
-      sum_dt += dt;
-      a0 = a1; g0 = g1;
+      s.dp = rp; s.dv = rv; s.dq = qnormalized(rq);
+      s.sum_dt += dt;
+      s.a0 = a1; s.g0 = g1;
     }
   }
+}
+
+__global__ __launch_bounds__(64) void k_preintegrate(int n, const int* offset, const int* nsamples, const double* samples,
+                                                     const double* acc0, const double* gyr0, const double* lba,
+                                                     const double* lbg, double an2, double gn2, double aw2, double gw2,
+                                                     DevPreint* out) {
+  __shared__ double tile[4][15 * PREINT_GROUP];
+  const int grp = threadIdx.x / PREINT_GROUP, j = threadIdx.x % PREINT_GROUP;
+  const int iv = blockIdx.x * 4 + grp;
+  const bool live = iv < n;
+  const int i = live ? iv : n - 1;            // idle groups shadow the last interval (no stores) so that barriers stay uniform
+  PreintLane s;
+  preint_identity(s, j < 15 ? j : 14, V3{acc0[3 * i], acc0[3 * i + 1], acc0[3 * i + 2]}, V3{gyr0[3 * i], gyr0[3 * i + 1], gyr0[3 * i + 2]});
+  const V3 ba{lba[3 * i], lba[3 * i + 1], lba[3 * i + 2]}, bg{lbg[3 * i], lbg[3 * i + 1], lbg[3 * i + 2]};
+  int ns = nsamples[i], nmax = ns;
+  nmax = max(nmax, __shfl_xor(nmax, 16, 64));
+  nmax = max(nmax, __shfl_xor(nmax, 32, 64));
+  preint_steps(s, j, samples + (size_t)offset[i] * 7, ns, nmax, ba, bg, an2, gn2, aw2, gw2, tile[grp]);
   if (!live || j >= 15) return;
   DevPreint& o = out[iv];
   if (j == 0) {
-    o.sum_dt = sum_dt;
-    o.dp[0] = dp.x; o.dp[1] = dp.y; o.dp[2] = dp.z;
-    o.dv[0] = dv.x; o.dv[1] = dv.y; o.dv[2] = dv.z;
-    o.dq[0] = dq.x; o.dq[1] = dq.y; o.dq[2] = dq.z; o.dq[3] = dq.w;
+    o.sum_dt = s.sum_dt;
+    o.dp[0] = s.dp.x; o.dp[1] = s.dp.y; o.dp[2] = s.dp.z;
+    o.dv[0] = s.dv.x; o.dv[1] = s.dv.y; o.dv[2] = s.dv.z;
+    o.dq[0] = s.dq.x; o.dq[1] = s.dq.y; o.dq[2] = s.dq.z; o.dq[3] = s.dq.w;
     for (int k = 0; k < 3; ++k) { o.lba[k] = lba[3 * iv + k]; o.lbg[k] = lbg[3 * iv + k]; }
   }
 #pragma unroll
-  for (int r = 0; r < 15; ++r) { o.cov[r * 15 + j] = Pc[r]; o.sqrt_info[r * 15 + j] = Jc[r]; }  // sqrt_info slot carries the 15x15 jacobian out
+  for (int r = 0; r < 15; ++r) { o.cov[r * 15 + j] = s.Pc[r]; o.sqrt_info[r * 15 + j] = s.Jc[r]; }  // sqrt_info slot carries the 15x15 jacobian out
 }
 
 }  // namespace vpl

@@ -13,6 +13,7 @@
 #pragma once
 #include "ba_types.h"
 #include "ba_lineopt.h"
+#include "ba_factors.h"
 #include "vplines_ba.h"
 
 namespace vpl {
@@ -30,6 +31,16 @@ struct OdoStore {
 };
 
 // The prior a session keeps between keyframes (the marginalisation's output, device to device)
+// The IMU side of a session that takes raw samples (vpl_odo_enable_imu), per sequence: the samples of the interval that ends in
+// slot 10 (dt_buf / linear_acceleration_buf / angular_velocity_buf [WINDOW_SIZE]), their count, and linearized_acc / _gyr of
+// pre_integrations[10].  The last measurement seen (the estimator's acc_0 / gyr_0) is the last row of smp.  Two of them, swapped
+// with the stores.
+struct OdoImu {
+  double *smp, *lin;        // [seq][max][7] dt, acc, gyr   [seq][6]
+  int* n;                   // [seq]
+  int max;
+};
+
 struct OdoPrior {
   double *J0, *r0, *x0;     // [seq][MAXKEEP^2] compact n x n, [seq][MAXKEEP], [seq][MAXPB * 9]
 };
@@ -291,19 +302,23 @@ __global__ __launch_bounds__(ODO_THREADS) void k_odo_slide(OdoStore A, OdoStore 
 }
 
 // ---- the new frame into slot 10 ------------------------------------------------------------------------------------------
-// hdr [seq][5] = payload offset (doubles), n_points, n_lines, offset of the point entries in tab, of the line entries.
-// Payload of a sequence: pose[7], speed_bias[9], the vpl_preintegration as the caller holds it, point observations [n][3],
-// line observations [n][8].  tab entry of an observation: track | k << 20 | isnew << 24 (odo_add_frame), -1 = ignored.
+// hdr [seq][6] = payload offset (doubles), n_points, n_lines, offset of the point entries in tab, of the line entries, n_samples.
+// Payload of a sequence, n_samples < 0 (vpl_odo_advance): pose[7], speed_bias[9], the vpl_preintegration as the caller holds it,
+// point observations [n][3], line observations [n][8]; n_samples >= 0 (vpl_odo_advance_imu): samples [n_samples][7], then the
+// observations -- state and pre-integration of slot 10 are k_odo_imu's.
+// tab entry of an observation: track | k << 20 | isnew << 24 (odo_add_frame), -1 = ignored.
 // One lane per observation; a track that starts here gets inv_depth = -1, plk = 0, tri = 0.
+constexpr int ODO_HDR = 6;
 __global__ __launch_bounds__(ODO_THREADS) void k_odo_append(OdoStore S, const double* __restrict__ payload, const int* __restrict__ hdr,
                                                             const int* __restrict__ tab) {
   const int w = blockIdx.x, tid = threadIdx.x;
-  const int* h = hdr + 5 * w;
+  const int* h = hdr + ODO_HDR * w;
   const double* in = payload + h[0];
   const int nP = h[1], nL = h[2];
-  for (int i = tid; i < 7; i += ODO_THREADS) S.pose[w * 77 + (NF - 1) * 7 + i] = in[i];
-  for (int i = tid; i < 9; i += ODO_THREADS) S.sb[w * 99 + (NF - 1) * 9 + i] = in[7 + i];
-  {   // to_dev_preint of the host side: the first 17 doubles as they are, five 3 x 3 blocks of the Jacobian, the covariance
+  if (h[5] < 0) {
+    for (int i = tid; i < 7; i += ODO_THREADS) S.pose[w * 77 + (NF - 1) * 7 + i] = in[i];
+    for (int i = tid; i < 9; i += ODO_THREADS) S.sb[w * 99 + (NF - 1) * 9 + i] = in[7 + i];
+    // to_dev_preint of the host side: the first 17 doubles as they are, five 3 x 3 blocks of the Jacobian, the covariance
     const double* r = in + 16;
     double* d = reinterpret_cast<double*>(S.pre + (size_t)w * NF + (NF - 1));
     const double* jac = r + 17;
@@ -319,7 +334,7 @@ __global__ __launch_bounds__(ODO_THREADS) void k_odo_append(OdoStore S, const do
       d[i] = v;
     }
   }
-  const double* pin = in + 16 + ODO_RAW_PRE_D;
+  const double* pin = in + (h[5] < 0 ? 16 + ODO_RAW_PRE_D : 7 * h[5]);
   for (int i = tid; i < nP; i += ODO_THREADS) {
     const int e = tab[h[3] + i];
     if (e < 0) continue;
@@ -336,6 +351,156 @@ __global__ __launch_bounds__(ODO_THREADS) void k_odo_append(OdoStore S, const do
     S.lobs[(t * NF + (e >> 20 & 15)) * 8 + (i & 7)] = lin[i];
     if ((e >> 24 & 1) && (i & 7) < 6) S.plk[t * 6 + (i & 7)] = 0.0;
     if ((e >> 24 & 1) && (i & 7) == 6) S.tri[t] = 0;
+  }
+}
+
+// ---- the IMU side of the new frame (vpl_odo_advance_imu), after k_odo_slide: one wave per sequence, 16 lanes per integration
+// as in k_preintegrate, whose step body it shares (preint_steps).  A / IA: the store and IMU side before the slide (read);
+// D / ID: after it (D as k_odo_slide left it).
+//   group 0, VPL_MARGIN_SECOND_NEW only: D.pre[9] CONTINUED over the samples slot 10 held -- push_back sample by sample on slot 9's
+//     deltas, covariance and bias columns of the jacobian under slot 9's linearisation bias, the first mid-point from IA.lin (the
+//     last sample of interval 9): estimator.cpp:1786-1799.  Columns 9..14 of J are all IMUFactor reads and all DevPreint holds;
+//     J <- F J acts column by column, rows 9..14 of those columns are the identity and the dq_dba block is zero, so continuing
+//     them alone is exact (the lanes of columns 0..8 carry values nobody stores).
+//   group 1: D.pre[10] from the identity over the new samples, linearised at D.sb[10][3..8] -- the bias the solve has just
+//     estimated, which both slides leave in slot 10 (estimator.cpp:1766, :1810); sqrt_info = 0 (k_prep writes it).
+//   group 2, one lane: processIMU's propagation (estimator.cpp:107-113) of D.pose[10], D.sb[10][0..2] over the new samples, the
+//     rotation carried as a matrix like Rs[j] and converted once, as vector2double does.
+// The new samples become ID's buffer; out [seq][18] = the propagated pose[7], speed_bias[9], sum_dt of slots 9 and 10.
+constexpr int ODO_IMU_OUT_D = 18;
+// mat2q (Eigen's Quaternion(Matrix3), what vector2double applies to Rs) with the three cases of its second branch written out:
+// the same arithmetic, and no run-time index into the matrix, which would put it on the stack
+__device__ __forceinline__ Q4 odo_mat2q(const M3& m) {
+  const double* a = m.m;
+  double t = a[0] + a[4] + a[8];
+  if (t > 0) {
+    t = sqrt(t + 1.0);
+    const double h = 0.5 / t;
+    return Q4{0.5 * t, (a[7] - a[5]) * h, (a[2] - a[6]) * h, (a[3] - a[1]) * h};
+  }
+  const int i = a[8] > (a[4] > a[0] ? a[4] : a[0]) ? 2 : (a[4] > a[0] ? 1 : 0);
+  if (i == 0) {
+    t = sqrt(a[0] - a[4] - a[8] + 1.0);
+    const double h = 0.5 / t;
+    return Q4{(a[7] - a[5]) * h, 0.5 * t, (a[3] + a[1]) * h, (a[6] + a[2]) * h};
+  }
+  if (i == 1) {
+    t = sqrt(a[4] - a[8] - a[0] + 1.0);
+    const double h = 0.5 / t;
+    return Q4{(a[2] - a[6]) * h, (a[1] + a[3]) * h, 0.5 * t, (a[7] + a[5]) * h};
+  }
+  t = sqrt(a[8] - a[0] - a[4] + 1.0);
+  const double h = 0.5 / t;
+  return Q4{(a[3] - a[1]) * h, (a[2] + a[6]) * h, (a[5] + a[7]) * h, 0.5 * t};
+}
+__device__ __forceinline__ void odo_store_preint(DevPreint& o, const PreintLane& s, int j, V3 ba, V3 bg, bool zero_sqrt_info) {
+  if (j >= 15) return;
+  if (j == 0) {
+    o.sum_dt = s.sum_dt;
+    o.dp[0] = s.dp.x; o.dp[1] = s.dp.y; o.dp[2] = s.dp.z;
+    o.dv[0] = s.dv.x; o.dv[1] = s.dv.y; o.dv[2] = s.dv.z;
+    o.dq[0] = s.dq.x; o.dq[1] = s.dq.y; o.dq[2] = s.dq.z; o.dq[3] = s.dq.w;
+    o.lba[0] = ba.x; o.lba[1] = ba.y; o.lba[2] = ba.z;
+    o.lbg[0] = bg.x; o.lbg[1] = bg.y; o.lbg[2] = bg.z;
+  }
+#pragma unroll
+  for (int r = 0; r < 15; ++r) o.cov[r * 15 + j] = s.Pc[r];
+  if (zero_sqrt_info)
+    for (int r = 0; r < 15; ++r) o.sqrt_info[r * 15 + j] = 0.0;
+  if (j >= 9) {   // column j of J: rows 0..2, 3..5 (bg columns only), 6..8 of the block that holds it
+    const bool isbg = j >= 12;
+    const int c = j - (isbg ? 12 : 9);
+    double* bp = isbg ? o.dp_dbg : o.dp_dba;
+    double* bv = isbg ? o.dv_dbg : o.dv_dba;
+    bp[c] = s.Jc[0]; bp[3 + c] = s.Jc[1]; bp[6 + c] = s.Jc[2];
+    bv[c] = s.Jc[6]; bv[3 + c] = s.Jc[7]; bv[6 + c] = s.Jc[8];
+    if (isbg) { o.dq_dbg[c] = s.Jc[3]; o.dq_dbg[3 + c] = s.Jc[4]; o.dq_dbg[6 + c] = s.Jc[5]; }
+  }
+}
+__global__ __launch_bounds__(64) void k_odo_imu(OdoStore D, OdoImu IA, OdoImu ID, const double* __restrict__ payload,
+                                                const int* __restrict__ hdr, int second_new, double an2, double gn2, double aw2,
+                                                double gw2, double g_norm, double* __restrict__ out) {
+  __shared__ double tile[4][15 * PREINT_GROUP];
+  const int w = blockIdx.x;
+  const int grp = threadIdx.x / PREINT_GROUP, j = threadIdx.x % PREINT_GROUP;
+  const int jc = j < 15 ? j : 14;
+  const double* nsp = payload + hdr[ODO_HDR * w];                  // the new samples
+  const int nn = hdr[ODO_HDR * w + 5];
+  const double* osp = IA.smp + (size_t)w * IA.max * 7;             // the samples slot 10 held
+  const int no = IA.n[w];
+  const V3 la{osp[7 * (no - 1) + 1], osp[7 * (no - 1) + 2], osp[7 * (no - 1) + 3]};   // the last measurement seen
+  const V3 lg{osp[7 * (no - 1) + 4], osp[7 * (no - 1) + 5], osp[7 * (no - 1) + 6]};
+  DevPreint& p9 = D.pre[(size_t)w * NF + NF - 2];
+  const double* sb10 = D.sb + w * 99 + (NF - 1) * 9;
+  const V3 nba{sb10[3], sb10[4], sb10[5]}, nbg{sb10[6], sb10[7], sb10[8]};
+  PreintLane s;
+  preint_identity(s, jc, la, lg);
+  V3 ba = nba, bg = nbg;
+  const double* sp = nsp;
+  int ns = grp == 1 ? nn : 0;
+  if (grp == 0 && second_new) {
+    sp = osp; ns = no;
+    ba = V3{p9.lba[0], p9.lba[1], p9.lba[2]}; bg = V3{p9.lbg[0], p9.lbg[1], p9.lbg[2]};
+    s.a0 = V3{IA.lin[w * 6], IA.lin[w * 6 + 1], IA.lin[w * 6 + 2]};
+    s.g0 = V3{IA.lin[w * 6 + 3], IA.lin[w * 6 + 4], IA.lin[w * 6 + 5]};
+    s.sum_dt = p9.sum_dt;
+    s.dp = V3{p9.dp[0], p9.dp[1], p9.dp[2]}; s.dv = V3{p9.dv[0], p9.dv[1], p9.dv[2]};
+    s.dq = Q4{p9.dq[3], p9.dq[0], p9.dq[1], p9.dq[2]};
+#pragma unroll
+    for (int r = 0; r < 15; ++r) s.Pc[r] = p9.cov[r * 15 + jc];
+    if (jc >= 9) {
+      const bool isbg = jc >= 12;
+      const int c = jc - (isbg ? 12 : 9);
+      const double* bp = isbg ? p9.dp_dbg : p9.dp_dba;
+      const double* bv = isbg ? p9.dv_dbg : p9.dv_dba;
+      s.Jc[0] = bp[c]; s.Jc[1] = bp[3 + c]; s.Jc[2] = bp[6 + c];
+      s.Jc[3] = isbg ? p9.dq_dbg[c] : 0.0; s.Jc[4] = isbg ? p9.dq_dbg[3 + c] : 0.0; s.Jc[5] = isbg ? p9.dq_dbg[6 + c] : 0.0;
+      s.Jc[6] = bv[c]; s.Jc[7] = bv[3 + c]; s.Jc[8] = bv[6 + c];
+    }
+  }
+  int nmax = ns;
+  nmax = max(nmax, __shfl_xor(nmax, 16, 64));
+  nmax = max(nmax, __shfl_xor(nmax, 32, 64));
+  preint_steps(s, j, sp, ns, nmax, ba, bg, an2, gn2, aw2, gw2, tile[grp]);
+  double* o = out + (size_t)w * ODO_IMU_OUT_D;
+  if (grp == 0) {
+    if (second_new) odo_store_preint(p9, s, j, ba, bg, false);
+    if (j == 0) o[16] = second_new ? s.sum_dt : p9.sum_dt;
+  } else if (grp == 1) {
+    odo_store_preint(D.pre[(size_t)w * NF + NF - 1], s, j, ba, bg, true);
+    if (j == 0) o[17] = s.sum_dt;
+  } else if (grp == 2) {
+    if (j == 0) {
+      double* pose = D.pose + w * 77 + (NF - 1) * 7;
+      double* sb = D.sb + w * 99 + (NF - 1) * 9;
+      M3 R = qmat(qnormalized(qpose(pose)));
+      V3 P{pose[0], pose[1], pose[2]}, V{sb[0], sb[1], sb[2]}, a0 = la, g0 = lg;
+      const V3 g{0.0, 0.0, g_norm};
+      for (int k = 0; k < nn; ++k) {
+        const double dt = nsp[7 * k];
+        const V3 a1{nsp[7 * k + 1], nsp[7 * k + 2], nsp[7 * k + 3]}, g1{nsp[7 * k + 4], nsp[7 * k + 5], nsp[7 * k + 6]};
+        const V3 un_acc_0 = mul(R, a0 - nba) - g;
+        const V3 un_gyr = 0.5 * (g0 + g1) - nbg;
+        R = mul(R, qmat(deltaQ(un_gyr * dt)));
+        const V3 un_acc_1 = mul(R, a1 - nba) - g;
+        const V3 un_acc = 0.5 * (un_acc_0 + un_acc_1);
+        P = P + dt * V + 0.5 * dt * dt * un_acc;
+        V = V + dt * un_acc;
+        a0 = a1; g0 = g1;
+      }
+      const Q4 q = odo_mat2q(R);
+      pose[0] = P.x; pose[1] = P.y; pose[2] = P.z; pose[3] = q.x; pose[4] = q.y; pose[5] = q.z; pose[6] = q.w;
+      sb[0] = V.x; sb[1] = V.y; sb[2] = V.z;
+      o[0] = P.x; o[1] = P.y; o[2] = P.z; o[3] = q.x; o[4] = q.y; o[5] = q.z; o[6] = q.w;
+      o[7] = V.x; o[8] = V.y; o[9] = V.z;
+      o[10] = nba.x; o[11] = nba.y; o[12] = nba.z; o[13] = nbg.x; o[14] = nbg.y; o[15] = nbg.z;
+    }
+  } else {
+    // the new interval becomes slot 10's buffer, the measurement before it its linearized_acc / _gyr
+    double* dsp = ID.smp + (size_t)w * ID.max * 7;
+    for (int i = j; i < 7 * nn; i += PREINT_GROUP) dsp[i] = nsp[i];
+    if (j == 0) ID.n[w] = nn;
+    if (j < 3) { ID.lin[w * 6 + j] = get(la, j); ID.lin[w * 6 + 3 + j] = get(lg, j); }
   }
 }
 

@@ -13,6 +13,7 @@ struct OdoSeq {
   double sum_dt[NF] = {};          // of the 11 pre-integrations (the kept-block table asks for preint[1].sum_dt)
   HostTab prior;                   // block table of the prior the session holds on the device
   bool has_prior = false, set = false;
+  bool imu_set = false;            // vpl_odo_set_imu since the last vpl_odo_set_window (IMU-enabled sessions)
 };
 
 struct vpl_odo {
@@ -27,6 +28,11 @@ struct vpl_odo {
   char *d_in = nullptr, *h_in = nullptr, *d_out = nullptr, *h_out = nullptr;   // new frames + slide tables in | results + flags out (h_*: pinned)
   size_t in_cap = 0, out_cap = 0;
   size_t alloc0 = 0, alloc1 = 0;   // the session's arrays in the context's allocation record
+  // vpl_odo_enable_imu: the IMU side (two, swapped with the stores), its arrays in the allocation record (behind alloc1)
+  bool imu = false;
+  int max_samples = 0;
+  OdoImu im[2] = {};
+  size_t imu_alloc0 = 0, imu_alloc1 = 0;
   std::vector<OdoSeq> seq;
   // the integer-only windows handed to the uploads, and what they point to
   std::vector<vpl_window> win;
@@ -89,12 +95,32 @@ static void odo_select(vpl_odo* o) {
   }
 }
 
-static int odo_check_frame(const vpl_odo_frame& f) {
+// the observations of one image, whichever frame struct carries them
+struct OdoObs {
+  int n_points; const int* point_id; const double* point_obs;
+  int n_lines; const int* line_id; const double* line_obs;
+};
+static OdoObs odo_obs(const vpl_odo_frame& f) { return OdoObs{f.n_points, f.point_id, f.point_obs, f.n_lines, f.line_id, f.line_obs}; }
+static OdoObs odo_obs(const vpl_odo_imu_frame& f) { return OdoObs{f.n_points, f.point_id, f.point_obs, f.n_lines, f.line_id, f.line_obs}; }
+static int odo_check_frame(const OdoObs& f) {
   if (f.n_points < 0 || f.n_lines < 0) return VPL_E_INVALID;
   if (f.n_points > 0 && (!f.point_id || !f.point_obs)) return VPL_E_INVALID;
   if (f.n_lines > 0 && (!f.line_id || !f.line_obs)) return VPL_E_INVALID;
   return VPL_OK;
 }
+// The new frames of one call.  What enters slot 10 beside the observations is chosen HERE and nowhere else: the caller's state
+// and finished pre-integration (vpl_odo_advance), or raw samples the device integrates and propagates (vpl_odo_advance_imu).
+struct OdoNext {
+  const vpl_odo_frame* plain = nullptr;
+  const vpl_odo_imu_frame* imu = nullptr;
+  OdoObs obs(int w) const { return plain ? odo_obs(plain[w]) : odo_obs(imu[w]); }
+  int n_samples(int w) const { return plain ? -1 : imu[w].n_samples; }                 // hdr[5] of k_odo_append
+  size_t head(int w) const { return plain ? 16 + ODO_RAW_PRE_D : 7 * (size_t)imu[w].n_samples; }   // doubles before the observations
+  void write_head(int w, double* d) const {
+    if (plain) { std::memcpy(d, plain[w].pose, 56); std::memcpy(d + 7, plain[w].speed_bias, 72); std::memcpy(d + 16, &plain[w].preint, sizeof(plain[w].preint)); }
+    else std::memcpy(d, imu[w].samples, 56 * (size_t)imu[w].n_samples);
+  }
+};
 
 extern "C" {
 
@@ -157,6 +183,11 @@ void vpl_odo_destroy(vpl_odo* o) {
   (void)hipSetDevice(c->device);
   (void)settle(c);
   (void)hipStreamSynchronize(c->stream);
+  for (size_t i = o->imu_alloc0; i < o->imu_alloc1 && i < c->allocs.size(); ++i) (void)hipFree(c->allocs[i]);
+  if (o->imu_alloc1 > o->imu_alloc0 && o->imu_alloc1 <= c->allocs.size()) {   // (behind the session's own range: erased first)
+    c->allocs.erase(c->allocs.begin() + o->imu_alloc0, c->allocs.begin() + o->imu_alloc1);
+    c->alloc_bytes.erase(c->alloc_bytes.begin() + o->imu_alloc0, c->alloc_bytes.begin() + o->imu_alloc1);
+  }
   for (size_t i = o->alloc0; i < o->alloc1 && i < c->allocs.size(); ++i) (void)hipFree(c->allocs[i]);
   if (o->alloc1 <= c->allocs.size()) {
     c->allocs.erase(c->allocs.begin() + o->alloc0, c->allocs.begin() + o->alloc1);
@@ -173,7 +204,7 @@ int vpl_odo_set_window(vpl_odo* o, int seq, const double pose[][7], const double
   if (!o || seq < 0 || seq >= o->nS || !pose || !speed_bias || !ex_pose || !preint || !frames) return VPL_E_INVALID;
   vpl_ctx* c = o->c;
   for (int f = 0; f < NF; ++f)
-    if (odo_check_frame(frames[f])) return fail(c, VPL_E_INVALID, "odo_set_window: null observation array");
+    if (odo_check_frame(odo_obs(frames[f]))) return fail(c, VPL_E_INVALID, "odo_set_window: null observation array");
   // the bookkeeping on a copy: a refusal leaves the sequence as it was
   OdoBook P, L;
   std::vector<std::vector<int>> pd(NF), ld(NF);
@@ -224,20 +255,31 @@ int vpl_odo_set_window(vpl_odo* o, int seq, const double pose[][7], const double
   Q.prior = HostTab();
   Q.has_prior = false;
   Q.set = true;
+  Q.imu_set = false;
   o->solved = false;
   return VPL_OK;
 }
 
 // the refusals of a new frame: null arrays, more tracks than the session holds (counted on the book as it stands)
-static int odo_check_next(vpl_odo* o, const vpl_odo_frame* next) {
+// ... and on the IMU form: the session's mode, a sequence without its IMU side, the sample arrays
+static int odo_check_next(vpl_odo* o, const OdoNext& next) {
   vpl_ctx* c = o->c;
+  if (o->imu != (next.imu != nullptr))
+    return fail(c, VPL_E_INVALID, o->imu ? "odo: the session takes IMU samples (vpl_odo_advance_imu / vpl_odo_keyframe_imu)"
+                                         : "odo: the session does not take IMU samples (vpl_odo_enable_imu)");
   for (int w = 0; w < o->nS; ++w) {
-    if (odo_check_frame(next[w])) return fail(c, VPL_E_INVALID, "odo: null observation array");
+    const OdoObs f = next.obs(w);
+    if (odo_check_frame(f)) return fail(c, VPL_E_INVALID, "odo: null observation array");
+    if (next.imu) {
+      if (!o->seq[w].imu_set) return fail(c, VPL_E_INVALID, "odo: a sequence has no IMU side (vpl_odo_set_imu after vpl_odo_set_window)");
+      if (!next.imu[w].samples || next.imu[w].n_samples < 1) return fail(c, VPL_E_INVALID, "odo: an interval needs at least one IMU sample");
+      if (next.imu[w].n_samples > o->max_samples) return fail(c, VPL_E_CAPACITY, "odo: more IMU samples in an interval than max_samples");
+    }
     // (the inbox holds one observation per track and frame)
-    if (next[w].n_points > o->maxPT || next[w].n_lines > o->maxLT) return fail(c, VPL_E_CAPACITY, "odo: more observations in a frame than tracks in the session");
+    if (f.n_points > o->maxPT || f.n_lines > o->maxLT) return fail(c, VPL_E_CAPACITY, "odo: more observations in a frame than tracks in the session");
     const OdoSeq& q = o->seq[w];
-    if ((int)q.P.t.size() + odo_count_unknown(q.P, next[w].n_points, next[w].point_id) > o->maxPT ||
-        (int)q.L.t.size() + odo_count_unknown(q.L, next[w].n_lines, next[w].line_id) > o->maxLT)
+    if ((int)q.P.t.size() + odo_count_unknown(q.P, f.n_points, f.point_id) > o->maxPT ||
+        (int)q.L.t.size() + odo_count_unknown(q.L, f.n_lines, f.line_id) > o->maxLT)
       return fail(c, VPL_E_CAPACITY, "odo: more tracks than the session's capacity");
   }
   return VPL_OK;
@@ -407,8 +449,10 @@ int vpl_odo_solve(vpl_odo* o, const int* flags, vpl_odo_result* out) {
   return VPL_OK;
 }
 
-int vpl_odo_advance(vpl_odo* o, const vpl_odo_frame* next, vpl_odo_result* out) {
-  if (!o || !next) return VPL_E_INVALID;
+}  // extern "C"
+
+// vpl_odo_advance / vpl_odo_advance_imu
+static int odo_advance_impl(vpl_odo* o, const OdoNext& next, vpl_odo_result* out, vpl_odo_imu_out* imu_out) {
   vpl_ctx* c = o->c;
   if (!o->solved) return fail(c, VPL_E_INVALID, "odo_advance: no solved window (vpl_odo_solve)");
   { const int rn = odo_check_next(o, next); if (rn) return rn; }
@@ -426,10 +470,10 @@ int vpl_odo_advance(vpl_odo* o, const vpl_odo_frame* next, vpl_odo_result* out) 
   // device what moved where; then ONE copy host -> device (the new frames' doubles, then the tables) and two launches
   double* pay = reinterpret_cast<double*>(o->h_in);
   size_t npay = 0;
-  for (int w = 0; w < nS; ++w) npay += 16 + ODO_RAW_PRE_D + 3 * (size_t)next[w].n_points + 8 * (size_t)next[w].n_lines;
+  for (int w = 0; w < nS; ++w) npay += next.head(w) + 3 * (size_t)next.obs(w).n_points + 8 * (size_t)next.obs(w).n_lines;
   int* tab = reinterpret_cast<int*>(o->h_in + npay * 8);
   size_t ntab = 0;
-  int* hdr = tab; ntab += 5 * (size_t)nS;
+  int* hdr = tab; ntab += ODO_HDR * (size_t)nS;
   int* cnt = tab + ntab; ntab += 2 * (size_t)nS;
   int* pmv = tab + ntab; ntab += (size_t)nS * o->maxPT;
   int* lmv = tab + ntab; ntab += (size_t)nS * o->maxLT;
@@ -457,26 +501,29 @@ int vpl_odo_advance(vpl_odo* o, const vpl_odo_frame* next, vpl_odo_result* out) 
     odo_erase_slide(q.L, er.data(), flag == VPL_MARGIN_SECOND_NEW, mv, nullptr);
     cnt[2 * w + 1] = (int)mv.size();
     for (size_t j = 0; j < mv.size(); ++j) lmv[(size_t)w * o->maxLT + j] = odo_pack_move(mv[j]);
-    // pre-integrations: MARGIN_OLD moves 2..10 down, the new interval enters slot 10
+    // pre-integrations: MARGIN_OLD moves 2..10 down, the new interval enters slot 10 (from samples: the device's sum_dt of
+    // slots 9 and 10 comes back below)
     if (flag == VPL_MARGIN_OLD)
       for (int j = 1; j < NF - 1; ++j) q.sum_dt[j] = q.sum_dt[j + 1];
-    q.sum_dt[NF - 1] = next[w].preint.sum_dt;
+    if (next.plain) q.sum_dt[NF - 1] = next.plain[w].preint.sum_dt;
     // the new frame
-    const vpl_odo_frame& f = next[w];
-    hdr[5 * w] = (int)poff; hdr[5 * w + 1] = f.n_points; hdr[5 * w + 2] = f.n_lines;
-    hdr[5 * w + 3] = (int)(ntab + nent); hdr[5 * w + 4] = (int)(ntab + nent + f.n_points);
+    const OdoObs f = next.obs(w);
+    int* h = hdr + ODO_HDR * w;
+    h[0] = (int)poff; h[1] = f.n_points; h[2] = f.n_lines;
+    h[3] = (int)(ntab + nent); h[4] = (int)(ntab + nent + f.n_points); h[5] = next.n_samples(w);
     r.n_ignored = odo_add_frame(q.P, NF - 1, f.n_points, f.point_id, ent + nent);
     r.n_ignored += odo_add_frame(q.L, NF - 1, f.n_lines, f.line_id, ent + nent + f.n_points);
     nent += (size_t)f.n_points + f.n_lines;
     r.n_point_tracks = (int)q.P.t.size();
     r.n_line_tracks = (int)q.L.t.size();
     double* d = pay + poff;
-    std::memcpy(d, f.pose, 56); std::memcpy(d + 7, f.speed_bias, 72); std::memcpy(d + 16, &f.preint, sizeof(f.preint));
-    if (f.n_points) std::memcpy(d + 16 + ODO_RAW_PRE_D, f.point_obs, (size_t)f.n_points * 24);
-    if (f.n_lines) std::memcpy(d + 16 + ODO_RAW_PRE_D + 3 * (size_t)f.n_points, f.line_obs, (size_t)f.n_lines * 64);
-    poff += 16 + ODO_RAW_PRE_D + 3 * (size_t)f.n_points + 8 * (size_t)f.n_lines;
+    next.write_head(w, d);
+    d += next.head(w);
+    if (f.n_points) std::memcpy(d, f.point_obs, (size_t)f.n_points * 24);
+    if (f.n_lines) std::memcpy(d + 3 * (size_t)f.n_points, f.line_obs, (size_t)f.n_lines * 64);
+    poff += next.head(w) + 3 * (size_t)f.n_points + 8 * (size_t)f.n_lines;
   }
-  const size_t in_bytes = npay * 8 + (ntab + nent) * 4;   // (within in_cap: odo_check_next bounds a frame's observations)
+  const size_t in_bytes = npay * 8 + (ntab + nent) * 4;   // (within in_cap: odo_check_next bounds a frame's observations and samples)
   HIPCHK(c, hipMemcpyAsync(o->d_in, o->h_in, in_bytes, hipMemcpyHostToDevice, s));
   o->h2d_payload = (long long)npay * 8;
   o->h2d_table += (long long)(ntab + nent) * 4;
@@ -485,22 +532,147 @@ int vpl_odo_advance(vpl_odo* o, const vpl_odo_frame* next, vpl_odo_result* out) 
   hipLaunchKernelGGL(k_odo_slide, dim3(nS, ODO_SLIDE_Y), blk, 0, s, S, D, d_tab + (pmv - tab), d_tab + (lmv - tab), d_tab + (cnt - tab),
                      flag == VPL_MARGIN_SECOND_NEW ? 1 : 0, o->init_depth);
   hipLaunchKernelGGL(k_odo_append, grid, blk, 0, s, D, reinterpret_cast<const double*>(o->d_in), d_tab, d_tab);
+  if (next.imu) {   // merge into slot 9 (MARGIN_SECOND_NEW), the new interval, the propagated state: 18 doubles per sequence come back
+    const vpl_ba_options& p = o->opt;
+    hipLaunchKernelGGL(k_odo_imu, grid, dim3(64), 0, s, D, o->im[o->cur], o->im[o->cur ^ 1], reinterpret_cast<const double*>(o->d_in), d_tab,
+                       flag == VPL_MARGIN_SECOND_NEW ? 1 : 0, p.acc_n * p.acc_n, p.gyr_n * p.gyr_n, p.acc_w * p.acc_w, p.gyr_w * p.gyr_w,
+                       p.g_norm, reinterpret_cast<double*>(o->d_out));
+    HIPCHK(c, hipMemcpyAsync(o->h_out, o->d_out, (size_t)nS * ODO_IMU_OUT_D * 8, hipMemcpyDeviceToHost, s));
+    o->d2h += (long long)nS * ODO_IMU_OUT_D * 8;
+  }
   HIPCHK(c, hipGetLastError());
   o->cur ^= 1;
   // (the pinned inbox is rewritten by the next keyframe: the copy above must have left it)
   HIPCHK(c, hipStreamSynchronize(s));
+  if (next.imu) {
+    const double* r = reinterpret_cast<const double*>(o->h_out);
+    for (int w = 0; w < nS; ++w, r += ODO_IMU_OUT_D) {
+      // the mirror that decides whether IMU factor (0, 1) is in the marginalisation: the device's own sums, bit for bit
+      o->seq[w].sum_dt[NF - 2] = r[16];
+      o->seq[w].sum_dt[NF - 1] = r[17];
+      if (imu_out) { std::memcpy(imu_out[w].pose, r, 56); std::memcpy(imu_out[w].speed_bias, r + 7, 72); imu_out[w].sum_dt[0] = r[16]; imu_out[w].sum_dt[1] = r[17]; }
+    }
+  }
   o->solved = false;
   o->ms[3] = std::chrono::duration<double, std::milli>(oclk::now() - t0).count();
   return VPL_OK;
 }
 
-int vpl_odo_keyframe(vpl_odo* o, const vpl_odo_frame* next, const int* flags, vpl_odo_result* out) {
-  if (!o || !next || !flags || !out) return VPL_E_INVALID;
+static int odo_keyframe_impl(vpl_odo* o, const OdoNext& next, const int* flags, vpl_odo_result* out, vpl_odo_imu_out* imu_out) {
   if (o->solved) return fail(o->c, VPL_E_INVALID, "odo_keyframe: the window has been solved and not advanced (vpl_odo_advance)");
   int rc = odo_check_next(o, next);
   if (!rc) rc = vpl_odo_solve(o, flags, out);
-  if (!rc) rc = vpl_odo_advance(o, next, out);
+  if (!rc) rc = odo_advance_impl(o, next, out, imu_out);
   return rc;
+}
+
+extern "C" {
+
+int vpl_odo_advance(vpl_odo* o, const vpl_odo_frame* next, vpl_odo_result* out) {
+  if (!o || !next) return VPL_E_INVALID;
+  OdoNext n;
+  n.plain = next;
+  return odo_advance_impl(o, n, out, nullptr);
+}
+int vpl_odo_keyframe(vpl_odo* o, const vpl_odo_frame* next, const int* flags, vpl_odo_result* out) {
+  if (!o || !next || !flags || !out) return VPL_E_INVALID;
+  OdoNext n;
+  n.plain = next;
+  return odo_keyframe_impl(o, n, flags, out, nullptr);
+}
+int vpl_odo_advance_imu(vpl_odo* o, const vpl_odo_imu_frame* next, vpl_odo_result* out, vpl_odo_imu_out* imu_out) {
+  if (!o || !next) return VPL_E_INVALID;
+  OdoNext n;
+  n.imu = next;
+  return odo_advance_impl(o, n, out, imu_out);
+}
+int vpl_odo_keyframe_imu(vpl_odo* o, const vpl_odo_imu_frame* next, const int* flags, vpl_odo_result* out, vpl_odo_imu_out* imu_out) {
+  if (!o || !next || !flags || !out) return VPL_E_INVALID;
+  OdoNext n;
+  n.imu = next;
+  return odo_keyframe_impl(o, n, flags, out, imu_out);
+}
+
+// The IMU side: allocated once, through the context's guarded allocator; the inbox grows when max_samples rows outweigh the
+// state + pre-integration they replace
+int vpl_odo_enable_imu(vpl_odo* o, int max_samples) {
+  if (!o || max_samples < 1) return VPL_E_INVALID;
+  vpl_ctx* c = o->c;
+  if (o->imu) return fail(c, VPL_E_INVALID, "odo_enable_imu: already enabled");
+  if (o->solved) return fail(c, VPL_E_INVALID, "odo_enable_imu: between vpl_odo_solve and vpl_odo_advance");
+  HIPCHK(c, hipSetDevice(c->device));
+  { const int rs = settle(c); if (rs) return rs; }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const size_t nS = o->nS;
+  hipError_t e = hipSuccess;
+  o->imu_alloc0 = c->allocs.size();
+  for (OdoImu& m : o->im) {
+    m.max = max_samples;
+    if (e == hipSuccess) e = dalloc(c, &m.smp, nS * max_samples * 7);
+    if (e == hipSuccess) e = dalloc(c, &m.lin, nS * 6);
+    if (e == hipSuccess) e = dalloc(c, &m.n, nS);
+  }
+  const size_t head = 16 + ODO_RAW_PRE_D;
+  if (e == hipSuccess && 7 * (size_t)max_samples > head) {
+    const size_t cap = o->in_cap + nS * 8 * (7 * (size_t)max_samples - head);
+    char *din = nullptr, *hin = nullptr;
+    e = dalloc(c, &din, cap);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&hin, cap, hipHostMallocDefault);
+    if (e == hipSuccess) {   // (the smaller device inbox stays in the session's range until vpl_odo_destroy)
+      (void)hipHostFree(o->h_in);
+      o->d_in = din; o->h_in = hin; o->in_cap = cap;
+    }
+  }
+  o->imu_alloc1 = c->allocs.size();
+  if (e != hipSuccess) return fail(c, VPL_E_HIP, "odo_enable_imu: allocation failed");
+  o->max_samples = max_samples;
+  o->imu = true;
+  for (OdoSeq& q : o->seq) q.imu_set = false;
+  return VPL_OK;
+}
+
+int vpl_odo_set_imu(vpl_odo* o, int seq, int n10, const double* samples10, const double* acc0_10, const double* gyr0_10) {
+  if (!o || seq < 0 || seq >= o->nS || !samples10 || !acc0_10 || !gyr0_10) return VPL_E_INVALID;
+  vpl_ctx* c = o->c;
+  if (!o->imu) return fail(c, VPL_E_INVALID, "odo_set_imu: the session does not take IMU samples (vpl_odo_enable_imu)");
+  if (!o->seq[seq].set) return fail(c, VPL_E_INVALID, "odo_set_imu: the sequence has no window (vpl_odo_set_window)");
+  if (n10 < 1) return fail(c, VPL_E_INVALID, "odo_set_imu: an interval needs at least one IMU sample");
+  if (n10 > o->max_samples) return fail(c, VPL_E_CAPACITY, "odo_set_imu: more IMU samples than max_samples");
+  HIPCHK(c, hipSetDevice(c->device));
+  { const int rs = settle(c); if (rs) return rs; }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const OdoImu& m = o->im[o->cur];
+  double lin[6];
+  std::memcpy(lin, acc0_10, 24); std::memcpy(lin + 3, gyr0_10, 24);
+  HIPCHK(c, hipMemcpy(m.smp + (size_t)seq * m.max * 7, samples10, (size_t)n10 * 56, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(m.lin + (size_t)seq * 6, lin, 48, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(m.n + seq, &n10, 4, hipMemcpyHostToDevice));
+  o->seq[seq].imu_set = true;
+  return VPL_OK;
+}
+
+// the inverse of to_dev_preint for what DevPreint holds: columns 0..8 of the jacobian are not held and come back zero
+int vpl_odo_get_preint(vpl_odo* o, int seq, vpl_preintegration* out) {
+  if (!o || seq < 0 || seq >= o->nS || !out) return VPL_E_INVALID;
+  vpl_ctx* c = o->c;
+  if (!o->seq[seq].set) return fail(c, VPL_E_INVALID, "odo_get_preint: the sequence has no window (vpl_odo_set_window)");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  std::vector<DevPreint> h(NF);
+  HIPCHK(c, hipMemcpy(h.data(), o->st[o->cur].pre + (size_t)seq * NF, sizeof(DevPreint) * NF, hipMemcpyDeviceToHost));
+  std::memset(out, 0, sizeof(vpl_preintegration) * NF);
+  for (int f = 1; f < NF; ++f) {
+    const DevPreint& d = h[f];
+    vpl_preintegration& p = out[f];
+    std::memcpy(&p, &d, 17 * 8);   // sum_dt, delta_p, delta_q, delta_v, linearized_ba, linearized_bg: the same 17 doubles
+    const double* blk[5] = {d.dp_dba, d.dp_dbg, d.dq_dbg, d.dv_dba, d.dv_dbg};
+    const int r0[5] = {0, 0, 3, 6, 6}, c0[5] = {9, 12, 12, 9, 12};
+    for (int b = 0; b < 5; ++b)
+      for (int e = 0; e < 9; ++e) p.jacobian[(r0[b] + e / 3) * 15 + c0[b] + e % 3] = blk[b][e];
+    for (int k = 9; k < 15; ++k) p.jacobian[k * 15 + k] = 1.0;
+    std::memcpy(p.covariance, d.cov, sizeof(p.covariance));
+  }
+  return VPL_OK;
 }
 
 int vpl_odo_get_prior(vpl_odo* o, int seq, vpl_prior* out) {
