@@ -221,6 +221,80 @@ int vpl_line_track_ids(int n_new, const float* ends_new, int n_prev, const int* 
                        const int* prev_to_new, int max_h_lines, int max_v_lines, int* allfeature_cnt, int* keep, int* id_out,
                        int* tcnt_out, int* vertical_new, int* n_vertical_new);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Tracker session: LineFeatureTracker::readImage (line_feature_tracker.cpp:57-286) and the wire format of
+ * line_feature_tracker_node.cpp:77-153 for n_seq independent cameras or sequences, one call per image.  What survives
+ * from frame to frame -- the prepared image of the last frame taken over, its kept lines, ids, t_cnt, allfeature_cnt
+ * and the VP stage's frame counter -- lives in HBM.  vpl_trk_frame copies the raw frames and one VP seed per sequence
+ * down, the observations and one result per sequence back (one copy each way), and synchronises once, at the end.
+ * The semantics are those of the host mirror vplhost::LineFeatureTracker (vplines-slam_amd/host/vpl_frontend.hpp),
+ * quirks included:
+ *   - first image of a sequence: every detected line is kept, in the detector's order, with fresh ids; t_cnt 0; no
+ *     match, no quota, no VP stage; the VP part of every observation is 0;
+ *   - a frame without a detected line: lines_exist = 0, no rows; it is NOT taken over (the next frame is matched
+ *     against the last frame that had lines);
+ *   - a FIRST frame without lines followed by a frame with lines: as in the mirror, the second frame is no "first
+ *     image" any more and there is nothing to match against, so all its lines are kept with id -1, t_cnt 0, no VP stage,
+ *     and allfeature_cnt is untouched; the frame after it matches against those lines, and because vpl_line_track_ids
+ *     reads an inherited id of -1 as "no id", every line then gets a fresh id (its t_cnt still counts up);
+ *   - otherwise: Matching() against the kept lines of the last frame taken over, then vpl_line_track_ids as written
+ *     (see above), then the VP stage when more than two lines are kept: hypotheses from verticalLine when it has more
+ *     than two entries, else from the kept lines; first_frame = this sequence's VP stage has not run before; a status
+ *     other than 0 classifies every line as "none";
+ *   - observation row j: the end points of kept line j as (x - cx) / fx, (y - cy) / fy in float, widened; then the VP
+ *     entry of kept line 0 for EVERY row (node.cpp:104-109): (v0, v1, v2, v2 / v2) when classified, zeros otherwise.
+ * The session borrows the context (one session per context; destroy the session before the context -- vpl_fe_destroy
+ * destroys a session that is still open, whose pointer is invalid from then on) and uses image
+ * slots [0, n_seq) for the new frames and [n_seq, 2 n_seq) for the previous ones, so the context needs
+ * max_images >= 2 * n_seq and vpl_match_reserve(ctx, >= n_seq, max_kps).  Other calls on the context between two frames
+ * overwrite what the session keeps in those slots; vpl_pre_set_maps is the exception and is what sets the maps.
+ * Undistortion maps are optional: without them (vpl_pre_set_maps never called, or with NULL) the frames are not
+ * remapped, exactly as in the mirror; no option depends on them, so their absence is never an error.
+ * Refusals: VPL_E_INVALID for null pointers, n_seq < 1, options out of range (fx or fy 0, a negative quota, a bad CLAHE
+ * grid, bad detector / matcher parameters) or a second session on one context; VPL_E_CAPACITY when max_images < 2 n_seq,
+ * when vpl_match_reserve has not been called for n_seq pairs, when max_lines_per_image > 1024 (the VP stage's limit),
+ * when a frame yields more lines than max_lines_per_image or a pair more key points than max_kps.  A refused
+ * vpl_trk_frame leaves every sequence as it was: the new state is written beside the old and taken over on the device
+ * only when no sequence of the call overflowed.
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct vpl_trk vpl_trk;
+typedef struct vpl_trk_options {
+  vpl_edline_param ed;
+  vpl_match_param match;
+  int max_h_lines, max_v_lines;   /* the quota of :178-229 (euroc_config.yaml: 25, 25) */
+  int equalize;                   /* CLAHE of :62-68 */
+  double clip_limit;              /* 3.0 */
+  int tiles_x, tiles_y;           /* 8, 8 */
+  float fx, fy, cx, cy;           /* K_ of readIntrinsicParameter: end-point normalisation, and fx, cx, cy for the VP stage */
+} vpl_trk_options;
+void vpl_trk_default_options(vpl_trk_options* opt);   /* detector / matcher defaults, 25 / 25, CLAHE 3.0 8 x 8, K = identity */
+int vpl_trk_create(vpl_trk** out, vpl_fe_ctx* ctx, int n_seq, const vpl_trk_options* opt);
+void vpl_trk_destroy(vpl_trk* trk);
+/* the sequence starts again with its next frame (first image, VP counter 0); allfeature_cnt is kept.  Asynchronous. */
+int vpl_trk_reset(vpl_trk* trk, int seq);
+
+typedef struct vpl_trk_result {   /* per sequence */
+  int n_detected, n_lines;        /* the detector's lines | lines kept = rows of line_id / line_obs */
+  int lines_exist;                /* the mirror's lines_exit: 0 = nothing detected, the frame was not taken over */
+  int matched, n_tracked;         /* Matching()'s return value | kept lines that continue an id */
+  int vp_ran, vp_status;          /* the VP stage ran (more than two kept lines) | its status */
+  double vps[9];                  /* 0 when the stage did not run */
+  int allfeature_cnt;
+} vpl_trk_result;
+/* raw [n_seq][H][W]; vp_seed [n_seq] (consumed only by sequences whose VP stage runs, as the mirror's vp_seed());
+ * res [n_seq]; line_id [n_seq][max_lines], line_obs [n_seq][max_lines][8]: the first n_lines rows of a sequence are written */
+int vpl_trk_frame(vpl_trk* trk, const uint8_t* raw, const uint32_t* vp_seed, vpl_trk_result* res, int* line_id, double* line_obs);
+/* test access, any pointer may be NULL: what curframe_ holds after the last call -- img [H*W], lines / ids [max_lines]
+ * (the kept ones first; the rest is not defined), t_cnt [max_lines] with its length *n_tcnt -- and the last accepted
+ * call's match vector [max_lines] (-1 past the previous frame's kept lines, or when Matching() returned false) and VP
+ * ids [max_lines] (3 past the kept lines, or when the stage did not run).  Synchronous. */
+int vpl_trk_get_frame(vpl_trk* trk, int seq, uint8_t* img, vpl_line* lines, int* ids, int* t_cnt, int* n_tcnt, int* match,
+                      int* vp_ids);
+/* test access: the session's id kernel alone on the arguments of vpl_line_track_ids (at most 4096 entries per list) */
+int vpl_trk_debug_ids(vpl_fe_ctx* ctx, int n_new, const float* ends_new, int n_prev, const int* id_prev, const int* tcnt_prev,
+                      int n_tcnt_prev, const int* prev_to_new, int max_h_lines, int max_v_lines, int* allfeature_cnt, int* keep,
+                      int* id_out, int* tcnt_out, int* vertical_new, int* n_vertical_new);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,3 +14,4 @@ from .capi import (  # noqa: F401
 from . import workload  # noqa: F401
 from . import shard  # noqa: F401
 from . import frontend  # noqa: F401
+from .frontend import TrackerSession, TrackerOptions, TrackerResult, default_tracker_options  # noqa: F401

@@ -18,6 +18,8 @@
 
 using namespace vpl;
 
+struct vpl_trk;
+
 struct vpl_fe_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -53,6 +55,7 @@ struct vpl_fe_ctx {
   std::string err;
   bool timing = false;                                    // vpl_fe_enable_kernel_timing
   std::vector<std::pair<const char*, double>> ktimes;     // (kernel, ms) of the launches since timing was enabled
+  vpl_trk* trk = nullptr;                                 // the tracker session this context lends itself to (trk_session.h)
 };
 
 // times one kernel launch with hipEvents on the context's stream when timing is on (bench.py: k_ed_grad GB/s)
@@ -187,6 +190,7 @@ int vpl_fe_create(vpl_fe_ctx** out, int device, int max_images, int width, int h
 
 void vpl_fe_destroy(vpl_fe_ctx* c) {
   if (!c) return;
+  if (c->trk) vpl_trk_destroy(c->trk);   // a session that is still open goes first (its arrays are the context's)
   // (teardown: a failure has nobody to be reported to)
   (void)hipSetDevice(c->device);
   (void)hipDeviceSynchronize();
@@ -246,38 +250,44 @@ int vpl_pre_set_maps(vpl_fe_ctx* c, const float* map_x, const float* map_y) {
   return VPL_OK;
 }
 
+// the raw frames and the remapped ones between the two stages
+static int pre_reserve(vpl_fe_ctx* c) {
+  const size_t PX = (size_t)c->W * c->H;
+  if (!c->d_raw) { HIPCHK(c, dalloc(c, &c->d_raw, (size_t)c->maxN * PX)); HIPCHK(c, dalloc(c, &c->d_mid, (size_t)c->maxN * PX)); }
+  return VPL_OK;
+}
+
 int vpl_pre_upload(vpl_fe_ctx* c, int n, const uint8_t* raw) {
   if (!c || !raw || n < 1) return VPL_E_INVALID;
   if (n > c->maxN) return fail(c, VPL_E_CAPACITY, "more images than max_images");
   HIPCHK(c, hipSetDevice(c->device));
   const size_t PX = (size_t)c->W * c->H;
-  if (!c->d_raw) { HIPCHK(c, dalloc(c, &c->d_raw, (size_t)c->maxN * PX)); HIPCHK(c, dalloc(c, &c->d_mid, (size_t)c->maxN * PX)); }
+  { const int rc = pre_reserve(c); if (rc) return rc; }
   HIPCHK(c, hipMemcpyAsync(c->d_raw, raw, (size_t)n * PX, hipMemcpyHostToDevice, c->stream));
   c->n = n;
   c->B.N = n;
   return VPL_OK;
 }
 
-int vpl_pre_run(vpl_fe_ctx* c, int equalize, double clip_limit, int tiles_x, int tiles_y) {
-  if (!c || c->n < 1 || !c->d_raw) return VPL_E_INVALID;
+// the launches of vpl_pre_run on `n` raw frames that lie at `raw` in HBM; the result goes to image slots [0, n)
+static int pre_launch(vpl_fe_ctx* c, int n, const uint8_t* raw, int equalize, double clip_limit, int tiles_x, int tiles_y) {
   if (equalize && (tiles_x < 1 || tiles_y < 1 || tiles_x > c->W || tiles_y > c->H)) return fail(c, VPL_E_INVALID, "bad CLAHE grid");
-  HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = c->stream;
   const size_t PX = (size_t)c->W * c->H;
   PreBatch P;
   std::memset(&P, 0, sizeof(P));
-  P.N = c->n; P.W = c->W; P.H = c->H;
-  P.raw = c->d_raw; P.mapx = c->d_mapx; P.mapy = c->d_mapy; P.mid = c->d_mid; P.out = (uint8_t*)c->B.img;
+  P.N = n; P.W = c->W; P.H = c->H;
+  P.raw = raw; P.mapx = c->d_mapx; P.mapy = c->d_mapy; P.mid = c->d_mid; P.out = (uint8_t*)c->B.img;
   const int W4 = (c->W + 3) / 4;
-  const dim3 gpx((W4 * c->H + 255) / 256, c->n);
+  const dim3 gpx((W4 * c->H + 255) / 256, n);
   // stage 1: remap into `mid` (or straight into the frame batch when no CLAHE follows)
-  const uint8_t* clahe_in = c->d_raw;
+  const uint8_t* clahe_in = raw;
   if (c->haveMaps) {
     uint8_t* dst = equalize ? c->d_mid : P.out;
     hipLaunchKernelGGL(k_pre_remap, gpx, dim3(256), 0, s, P, dst);
     clahe_in = dst;
   } else if (!equalize) {
-    HIPCHK(c, hipMemcpyAsync(P.out, c->d_raw, (size_t)c->n * PX, hipMemcpyDeviceToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(P.out, raw, (size_t)n * PX, hipMemcpyDeviceToDevice, s));
   }
   if (equalize) {
     const int tiles = tiles_x * tiles_y;
@@ -290,11 +300,17 @@ int vpl_pre_run(vpl_fe_ctx* c, int equalize, double clip_limit, int tiles_x, int
     P.lutScale = (float)255 / area;
     P.clipLimit = clip_limit > 0.0 ? std::max((int)(clip_limit * area / 256), 1) : 0;   // clahe.cpp: clipLimit_ * tileSizeTotal / histSize
     P.inv_tw = 1.0f / P.tw; P.inv_th = 1.0f / P.th;
-    hipLaunchKernelGGL(k_pre_clahe_lut, dim3(tiles, c->n), dim3(256), 0, s, P, clahe_in);
+    hipLaunchKernelGGL(k_pre_clahe_lut, dim3(tiles, n), dim3(256), 0, s, P, clahe_in);
     hipLaunchKernelGGL(k_pre_clahe_interp, gpx, dim3(256), 0, s, P, clahe_in);
   }
   HIPCHK(c, hipGetLastError());
   return VPL_OK;
+}
+
+int vpl_pre_run(vpl_fe_ctx* c, int equalize, double clip_limit, int tiles_x, int tiles_y) {
+  if (!c || c->n < 1 || !c->d_raw) return VPL_E_INVALID;
+  HIPCHK(c, hipSetDevice(c->device));
+  return pre_launch(c, c->n, c->d_raw, equalize, clip_limit, tiles_x, tiles_y);
 }
 
 int vpl_pre_download(vpl_fe_ctx* c, int n, uint8_t* images) {
@@ -369,11 +385,9 @@ int vpl_fe_keep_blurred(vpl_fe_ctx* c, int enable) {
   return VPL_OK;
 }
 
-// EDLineDetector::EDline(image, lines, smoothed) for the uploaded batch (edline_detector.cpp:1176-1198 -> EdgeDrawing :81-710)
-int vpl_edlines_detect_ex(vpl_fe_ctx* c, const vpl_edline_param* p, int smoothed) {
-  if (!c || !p || c->n < 1) return VPL_E_INVALID;
+// EDLineDetector::EDline(image, lines, smoothed) for image slots [0, n) (edline_detector.cpp:1176-1198 -> EdgeDrawing :81-710)
+static int ed_launch(vpl_fe_ctx* c, const vpl_edline_param* p, int smoothed, int n) {
   if (p->scanIntervals < 1 || p->minLineLen < 2) return fail(c, VPL_E_INVALID, "bad EDLine parameters");
-  HIPCHK(c, hipSetDevice(c->device));
   EdBatch& B = c->B;
   // member types of EDLineDetector: short gradienThreshold_, unsigned char anchorThreshold_ (edline_detector.h:113-117)
   B.gradTh = (int)(short)p->gradientThreshold;
@@ -383,7 +397,7 @@ int vpl_edlines_detect_ex(vpl_fe_ctx* c, const vpl_edline_param* p, int smoothed
   B.fitErr = p->lineFitErrThreshold;
   const int PX = c->W * c->H;
   hipStream_t s = c->stream;
-  HIPCHK(c, hipMemsetAsync(B.nLines, 0, c->n * sizeof(int), s));
+  HIPCHK(c, hipMemsetAsync(B.nLines, 0, n * sizeof(int), s));
   int ksz = 1;
   if (!smoothed) {   // cv::GaussianBlur(image, image_, cv::Size(ksize_, ksize_), sigma_), edline_detector.cpp:82-84
     ksz = gauss_kernel_q8(p->ksize, (double)p->sigma, c->blurMode, B.blurK, 2 * EDB_RMAX + 1);
@@ -393,25 +407,31 @@ int vpl_edlines_detect_ex(vpl_fe_ctx* c, const vpl_edline_param* p, int smoothed
   }
   if (smoothed || ksz == 1) {   // a 1 x 1 kernel copies (GaussianBlur's early return)
     FeTimer t(c, "k_ed_grad");
-    hipLaunchKernelGGL(k_ed_grad, dim3((PX + 255) / 256, c->n), dim3(256), 0, s, B);
-    if (!smoothed && B.blurOut) HIPCHK(c, hipMemcpyAsync(B.blurOut, B.img, (size_t)c->n * PX, hipMemcpyDeviceToDevice, s));
+    hipLaunchKernelGGL(k_ed_grad, dim3((PX + 255) / 256, n), dim3(256), 0, s, B);
+    if (!smoothed && B.blurOut) HIPCHK(c, hipMemcpyAsync(B.blurOut, B.img, (size_t)n * PX, hipMemcpyDeviceToDevice, s));
   } else {
     FeTimer t(c, "k_ed_blur_grad");
-    hipLaunchKernelGGL(k_ed_blur_grad, dim3((c->W + EDB_TW - 1) / EDB_TW, (c->H + EDB_TH - 1) / EDB_TH, c->n), dim3(256), 0, s, B);
+    hipLaunchKernelGGL(k_ed_blur_grad, dim3((c->W + EDB_TW - 1) / EDB_TW, (c->H + EDB_TH - 1) / EDB_TH, n), dim3(256), 0, s, B);
   }
   {
     FeTimer t(c, "k_ed_anchor");
     const int nWs = (c->W - 2 + B.scan - 1) / B.scan, nHs = (c->H - 2 + B.scan - 1) / B.scan;
     const size_t abytes = (size_t)nWs * ((nHs + 31) / 32) * 4;
     if (abytes > 60 * 1024) return fail(c, VPL_E_CAPACITY, "anchor bitmask exceeds LDS (frame too large for this scanIntervals)");
-    hipLaunchKernelGGL(k_ed_anchor, dim3(c->n), dim3(1024), abytes, s, B);
+    hipLaunchKernelGGL(k_ed_anchor, dim3(n), dim3(1024), abytes, s, B);
   }
-  { FeTimer t(c, "k_ed_code"); hipLaunchKernelGGL(k_ed_code, dim3((PX + 255) / 256, c->n), dim3(256), 0, s, B); }
-  { FeTimer t(c, "k_ed_route"); hipLaunchKernelGGL(k_ed_route, dim3(c->n), dim3(64 * ED_ROUTE_WAVES), c->routeSmem, s, B); }
-  { FeTimer t(c, "k_ed_fit"); hipLaunchKernelGGL(k_ed_fit, dim3(ED_FIT_BLOCKS, c->n), dim3(64), 0, s, B); }
-  { FeTimer t(c, "k_ed_sort_lines"); hipLaunchKernelGGL(k_ed_sort_lines, dim3(c->n), dim3(256), 0, s, B, c->d_sorted, c->d_sortedCnt, c->maxLines); }
+  { FeTimer t(c, "k_ed_code"); hipLaunchKernelGGL(k_ed_code, dim3((PX + 255) / 256, n), dim3(256), 0, s, B); }
+  { FeTimer t(c, "k_ed_route"); hipLaunchKernelGGL(k_ed_route, dim3(n), dim3(64 * ED_ROUTE_WAVES), c->routeSmem, s, B); }
+  { FeTimer t(c, "k_ed_fit"); hipLaunchKernelGGL(k_ed_fit, dim3(ED_FIT_BLOCKS, n), dim3(64), 0, s, B); }
+  { FeTimer t(c, "k_ed_sort_lines"); hipLaunchKernelGGL(k_ed_sort_lines, dim3(n), dim3(256), 0, s, B, c->d_sorted, c->d_sortedCnt, c->maxLines); }
   HIPCHK(c, hipGetLastError());
   return VPL_OK;
+}
+
+int vpl_edlines_detect_ex(vpl_fe_ctx* c, const vpl_edline_param* p, int smoothed) {
+  if (!c || !p || c->n < 1) return VPL_E_INVALID;
+  HIPCHK(c, hipSetDevice(c->device));
+  return ed_launch(c, p, smoothed, c->n);
 }
 
 // the production call: smoothed = true (feature_tracker/src/line_feature_tracker.cpp:87)
@@ -651,26 +671,31 @@ int vpl_match_counts(vpl_fe_ctx* c, int n_pairs, int* n_ref, int* n_cur) {
   return VPL_OK;
 }
 
-int vpl_match_run(vpl_fe_ctx* c, const vpl_match_param* p) {
-  if (!c || !p || !c->lmReserved || c->nPairs < 1) return VPL_E_INVALID;
+// the matcher's launches on `n_pairs` pairs whose lists lie in HBM; the pyramids of image slots [0, n_images) are built
+static int lm_launch(vpl_fe_ctx* c, const vpl_match_param* p, int n_images, int n_pairs) {
   if (p->step < 1) return fail(c, VPL_E_INVALID, "bad LineMatching parameters");
-  HIPCHK(c, hipSetDevice(c->device));
   LmBatch& M = c->M;
-  M.N = c->n; M.nPairs = c->nPairs; M.prm = *p;
+  M.N = n_images; M.nPairs = n_pairs; M.prm = *p;
   double eps = std::min(std::max(0.001, 0.), 10.);   // TermCriteria(COUNT|EPS, 30, 0.001) through KLT::KLT, klt.cpp:28-33
   M.epsilon = eps * eps;
   hipStream_t s = c->stream;
   auto blocks = [&](int l) { return (unsigned)(((size_t)M.ls[l] * (M.lh[l] + 2 * LM_WIN) + 255) / 256); };
   { FeTimer t(c, "k_lm_pyramid");
-    hipLaunchKernelGGL(k_lm_level0, dim3(blocks(0), c->n), dim3(256), 0, s, M);
-    for (int l = 1; l < M.nLevels; ++l) hipLaunchKernelGGL(k_lm_down, dim3(blocks(l), c->n), dim3(256), 0, s, M, l); }
-  { FeTimer t(c, "k_lm_scharr"); hipLaunchKernelGGL(k_lm_scharr, dim3(blocks(0), c->n, M.nLevels), dim3(256), 0, s, M); }
-  { FeTimer t(c, "k_lm_anchors"); hipLaunchKernelGGL(k_lm_anchors, dim3(c->nPairs), dim3(256), (size_t)M.maxLines * sizeof(int), s, M);
+    hipLaunchKernelGGL(k_lm_level0, dim3(blocks(0), n_images), dim3(256), 0, s, M);
+    for (int l = 1; l < M.nLevels; ++l) hipLaunchKernelGGL(k_lm_down, dim3(blocks(l), n_images), dim3(256), 0, s, M, l); }
+  { FeTimer t(c, "k_lm_scharr"); hipLaunchKernelGGL(k_lm_scharr, dim3(blocks(0), n_images, M.nLevels), dim3(256), 0, s, M); }
+  { FeTimer t(c, "k_lm_anchors"); hipLaunchKernelGGL(k_lm_anchors, dim3(n_pairs), dim3(256), (size_t)M.maxLines * sizeof(int), s, M);
     hipLaunchKernelGGL(k_lm_plan, dim3(1), dim3(64), 0, s, M); }
   { FeTimer t(c, "k_lm_klt"); hipLaunchKernelGGL(k_lm_klt, dim3(LM_KLT_GRID), dim3(64), LM_KLT_SMEM, s, M); }
-  { FeTimer t(c, "k_lm_vote"); hipLaunchKernelGGL(k_lm_vote, dim3(c->nPairs), dim3(256), (2 * M.maxLines + 1) * sizeof(int), s, M); }
+  { FeTimer t(c, "k_lm_vote"); hipLaunchKernelGGL(k_lm_vote, dim3(n_pairs), dim3(256), (2 * M.maxLines + 1) * sizeof(int), s, M); }
   HIPCHK(c, hipGetLastError());
   return VPL_OK;
+}
+
+int vpl_match_run(vpl_fe_ctx* c, const vpl_match_param* p) {
+  if (!c || !p || !c->lmReserved || c->nPairs < 1) return VPL_E_INVALID;
+  HIPCHK(c, hipSetDevice(c->device));
+  return lm_launch(c, p, c->n, c->nPairs);
 }
 
 int vpl_match_download(vpl_fe_ctx* c, int n_pairs, int* r2c, int* matched) {
@@ -760,6 +785,21 @@ static int vp_reserve(vpl_fe_ctx* c) {
   return VPL_OK;
 }
 
+// the VP stage's launches for `n` frames whose inputs (end points, counts, seeds, first_frame) lie in HBM
+static int vp_launch(vpl_fe_ctx* c, int n, float f, float cx, float cy) {
+  hipStream_t s = c->stream;
+  VpBatch& V = c->V;
+  V.N = n; V.f = f; V.ppx = cx; V.ppy = cy;
+  HIPCHK(c, hipMemsetAsync(V.g, 0, (size_t)n * VP_CELLS * 8, s));
+  hipLaunchKernelGGL(k_vp_grid, dim3(n, 2), dim3(64), 0, s, V);
+  hipLaunchKernelGGL(k_vp_smooth, dim3((VP_CELLS + 255) / 256, n), dim3(256), 0, s, V);
+  hipLaunchKernelGGL(k_vp_score, dim3(VP_SCORE_BLOCKS, n), dim3(256), 0, s, V);
+  const size_t pickSmem = (size_t)c->maxLines * (3 * 8 + 4 + 3 * 4);
+  hipLaunchKernelGGL(k_vp_pick, dim3(n), dim3(64), pickSmem, s, V);
+  HIPCHK(c, hipGetLastError());
+  return VPL_OK;
+}
+
 int vpl_vp_detect_batch(vpl_fe_ctx* c, int n, const vpl_line* hyp_lines, const int* n_hyp, const vpl_line* all_lines,
                         const int* n_all, float f, float cx, float cy, const uint32_t* seeds, const int* first_frame, double* vps,
                         int* vp_ids, int* status) {
@@ -779,20 +819,14 @@ int vpl_vp_detect_batch(vpl_fe_ctx* c, int n, const vpl_line* hyp_lines, const i
   }
   hipStream_t s = c->stream;
   VpBatch& V = c->V;
-  V.N = n; V.f = f; V.ppx = cx; V.ppy = cy;
   HIPCHK(c, hipMemcpyAsync(c->d_vpHyp, eh.data(), eh.size() * 4, hipMemcpyHostToDevice, s));
   HIPCHK(c, hipMemcpyAsync(c->d_vpAll, ea.data(), ea.size() * 4, hipMemcpyHostToDevice, s));
   HIPCHK(c, hipMemcpyAsync(c->d_vpNHyp, n_hyp, (size_t)n * 4, hipMemcpyHostToDevice, s));
   HIPCHK(c, hipMemcpyAsync(c->d_vpNAll, n_all, (size_t)n * 4, hipMemcpyHostToDevice, s));
   HIPCHK(c, hipMemcpyAsync(c->d_vpSeed, seeds, (size_t)n * 4, hipMemcpyHostToDevice, s));
   HIPCHK(c, hipMemcpyAsync(c->d_vpFirst, first_frame, (size_t)n * 4, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemsetAsync(V.g, 0, (size_t)n * VP_CELLS * 8, s));
-  hipLaunchKernelGGL(k_vp_grid, dim3(n, 2), dim3(64), 0, s, V);
-  hipLaunchKernelGGL(k_vp_smooth, dim3((VP_CELLS + 255) / 256, n), dim3(256), 0, s, V);
-  hipLaunchKernelGGL(k_vp_score, dim3(VP_SCORE_BLOCKS, n), dim3(256), 0, s, V);
-  const size_t pickSmem = ML * (3 * 8 + 4 + 3 * 4);
-  hipLaunchKernelGGL(k_vp_pick, dim3(n), dim3(64), pickSmem, s, V);
-  HIPCHK(c, hipGetLastError());
+  rc = vp_launch(c, n, f, cx, cy);
+  if (rc) return rc;
   HIPCHK(c, hipMemcpyAsync(vps, V.vps, (size_t)n * 72, hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipMemcpyAsync(status, V.status, (size_t)n * 4, hipMemcpyDeviceToHost, s));
   std::vector<int> ids((size_t)n * ML);
@@ -860,3 +894,5 @@ int vpl_line_track_ids(int n_new, const float* ends, int n_prev, const int* id_p
 }
 
 }  // extern "C"
+
+#include "trk_session.h"

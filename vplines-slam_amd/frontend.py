@@ -31,6 +31,20 @@ def default_match_param(illumination_adapt=True, topological_filter=True):
     return MatchParam(10, 0.5, 0.4, 3.0, 40.0, int(illumination_adapt), int(topological_filter), 15.0, 0.2, 0.05)
 
 
+class TrackerOptions(C.Structure):
+    """vpl_trk_options"""
+    _fields_ = [("ed", EdlineParam), ("match", MatchParam), ("max_h_lines", C.c_int), ("max_v_lines", C.c_int),
+                ("equalize", C.c_int), ("clip_limit", C.c_double), ("tiles_x", C.c_int), ("tiles_y", C.c_int),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float)]
+
+
+class TrackerResult(C.Structure):
+    """vpl_trk_result"""
+    _fields_ = [("n_detected", C.c_int), ("n_lines", C.c_int), ("lines_exist", C.c_int), ("matched", C.c_int),
+                ("n_tracked", C.c_int), ("vp_ran", C.c_int), ("vp_status", C.c_int), ("vps", C.c_double * 9),
+                ("allfeature_cnt", C.c_int)]
+
+
 # numpy view of vpl_line (56 bytes) for bulk packing / unpacking without per-line Python loops
 LINE_DTYPE = np.dtype({"names": ["line_endpoint", "line_equation", "center", "length"],
                        "formats": [("<f4", 4), ("<f8", 3), ("<f4", 2), "<f4"],
@@ -125,6 +139,16 @@ def _bind(lib):
     lib.vpl_match_debug_level.argtypes = [vp, C.c_int, C.c_int, C.c_void_p, C.c_void_p, ip, ip]
     lib.vpl_fe_enable_kernel_timing.argtypes = [vp, C.c_int]
     lib.vpl_fe_kernel_times.argtypes = [vp, ip, C.POINTER(C.c_char_p), C.POINTER(C.c_double)]
+    fp = C.POINTER(C.c_float)
+    lib.vpl_trk_default_options.argtypes = [C.POINTER(TrackerOptions)]
+    lib.vpl_trk_default_options.restype = None
+    lib.vpl_trk_create.argtypes = [C.POINTER(vp), vp, C.c_int, C.POINTER(TrackerOptions)]
+    lib.vpl_trk_destroy.argtypes = [vp]
+    lib.vpl_trk_destroy.restype = None
+    lib.vpl_trk_reset.argtypes = [vp, C.c_int]
+    lib.vpl_trk_frame.argtypes = [vp, C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(TrackerResult), ip, C.POINTER(C.c_double)]
+    lib.vpl_trk_get_frame.argtypes = [vp, C.c_int, C.POINTER(C.c_uint8), C.POINTER(Line), ip, ip, ip, ip, ip]
+    lib.vpl_trk_debug_ids.argtypes = [vp, C.c_int, fp, C.c_int, ip, ip, C.c_int, ip, C.c_int, C.c_int, ip, ip, ip, ip, ip, ip]
     _bound = True
 
 
@@ -146,6 +170,8 @@ class FrontendContext:
         return int(self.lib.vpl_fe_debug_guards(self.h))
 
     def close(self):
+        if self.h and getattr(self, "_trk", None) is not None:
+            self._trk.close()                      # the session goes before the context it borrows
         if self.h:
             bad = self.debug_guards() if os.environ.get("VPL_DEBUG_GUARDS") == "1" else 0
             msg = self.lib.vpl_fe_last_error(self.h).decode() if bad else ""
@@ -403,3 +429,79 @@ class FrontendContext:
                                                    C.c_void_p(d.ctypes.data), C.byref(w), C.byref(h)),
                     "vpl_match_debug_level")
         return px, d
+
+
+def default_tracker_options(max_h_lines=25, max_v_lines=25, fx=1.0, fy=1.0, cx=0.0, cy=0.0, equalize=True):
+    """vpl_trk_default_options with the quota and K_ filled in"""
+    lib = load_hip_library()
+    _bind(lib)
+    o = TrackerOptions()
+    lib.vpl_trk_default_options(C.byref(o))
+    o.max_h_lines, o.max_v_lines, o.equalize = max_h_lines, max_v_lines, int(equalize)
+    o.fx, o.fy, o.cx, o.cy = fx, fy, cx, cy
+    return o
+
+
+class TrackerSession:
+    """vpl_trk_*: LineFeatureTracker::readImage for n_seq sequences with the tracker's state resident on the device.
+    Borrows a FrontendContext made with max_images >= 2 * n_seq on which match_reserve(>= n_seq, max_kps) was called."""
+
+    def __init__(self, fe, n_seq, options=None):
+        self.fe, self.lib, self.n_seq = fe, fe.lib, n_seq
+        self.opt = options or default_tracker_options()
+        self.h = C.c_void_p()
+        fe._check(self.lib.vpl_trk_create(C.byref(self.h), fe.h, n_seq, C.byref(self.opt)), "vpl_trk_create")
+        fe._trk = self
+        ML = fe.max_lines
+        self._res = (TrackerResult * n_seq)()
+        self._ids = np.zeros((n_seq, ML), np.int32)
+        self._obs = np.zeros((n_seq, ML, 8))
+
+    def close(self):
+        if self.h:
+            self.lib.vpl_trk_destroy(self.h)
+            self.h = C.c_void_p()
+            if getattr(self.fe, "_trk", None) is self:
+                self.fe._trk = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self, seq):
+        self.fe._check(self.lib.vpl_trk_reset(self.h, seq), "vpl_trk_reset")
+
+    def frame(self, raw, vp_seed):
+        """raw [n_seq][H][W] uint8, vp_seed [n_seq] -> per sequence a dict: the fields of vpl_trk_result, `ids` [n_lines] and
+        `obs` [n_lines][8] (x1 y1 x2 y2 normalised, vp x y z, vp flag): what vpl_odo_frame takes as line_id / line_obs"""
+        raw = np.ascontiguousarray(raw, np.uint8)
+        assert raw.shape == (self.n_seq, self.fe.H, self.fe.W)
+        seed = np.ascontiguousarray(vp_seed, np.uint32)
+        assert seed.shape == (self.n_seq,)
+        self.fe._check(self.lib.vpl_trk_frame(self.h, raw.ctypes.data_as(C.POINTER(C.c_uint8)), seed.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                              self._res, self._ids.ctypes.data_as(C.POINTER(C.c_int)),
+                                              self._obs.ctypes.data_as(C.POINTER(C.c_double))), "vpl_trk_frame")
+        out = []
+        for s in range(self.n_seq):
+            r = self._res[s]
+            d = {f: getattr(r, f) for f, _ in TrackerResult._fields_ if f != "vps"}
+            d["vps"] = np.array(r.vps).reshape(3, 3)
+            d["ids"] = self._ids[s, :r.n_lines].copy()
+            d["obs"] = self._obs[s, :r.n_lines].copy()
+            out.append(d)
+        return out
+
+    def get_frame(self, seq):
+        """test access: what curframe_ holds (img, lines records [max_lines], ids, t_cnt) and the last call's match / VP ids"""
+        ML, fe = self.fe.max_lines, self.fe
+        img = np.zeros((fe.H, fe.W), np.uint8)
+        rec = np.zeros(ML, LINE_DTYPE)
+        ids, tc, match, vpi = (np.zeros(ML, np.int32) for _ in range(4))
+        n_tc = C.c_int(0)
+        ip = C.POINTER(C.c_int)
+        fe._check(self.lib.vpl_trk_get_frame(self.h, seq, img.ctypes.data_as(C.POINTER(C.c_uint8)), rec.ctypes.data_as(C.POINTER(Line)),
+                                             ids.ctypes.data_as(ip), tc.ctypes.data_as(ip), C.byref(n_tc), match.ctypes.data_as(ip),
+                                             vpi.ctypes.data_as(ip)), "vpl_trk_get_frame")
+        return dict(img=img, lines=rec, ids=ids, t_cnt=tc[:n_tc.value].copy(), match=match, vp_ids=vpi)
