@@ -404,7 +404,8 @@ typedef struct vpl_odo_result {  /* per sequence */
  * down -> next[seq] enters slot 10: an id continues its track only if the track's last observation is in slot 9, an unknown id
  * starts a track, an id whose track has a gap is ignored and counted.
  * marginalization_flag[seq]: VPL_MARGIN_OLD or VPL_MARGIN_SECOND_NEW; the batched solve marginalises one way per batch, so all
- * sequences of one call carry the same flag (VPL_E_INVALID otherwise).
+ * sequences of one call carry the same flag (VPL_E_INVALID otherwise) -- also when the flags are the session's own decisions
+ * (vpl_odo_*_auto below): sequences that disagree are refused there, with the count for each flag in vpl_last_error.
  * Refusals leave the session as it was: null arrays, a flag other than the two, a sequence without a window (VPL_E_INVALID);
  * more tracks than the capacities (VPL_E_CAPACITY) -- checked BEFORE the solve, when it is not yet known what the solve will
  * erase: tracks alive + ids of next[seq] that belong to no track <= max_*_tracks, and the solve's selection within the context's
@@ -464,6 +465,72 @@ int vpl_odo_keyframe_imu(vpl_odo* odo, const vpl_odo_imu_frame* next, const int*
  * come back zero. */
 int vpl_odo_get_preint(vpl_odo* odo, int seq, vpl_preintegration* out);
 
+/* ---- keyframe session: the keyframe decision and the failure check ---------------------------------------------------------- *
+ * The two per-image decisions of Estimator::processImage that the session's caller had to take from a feature manager of its own:
+ *   - marginalization_flag = addFeatureCheckParallax(frame_count = WINDOW_SIZE, image) ? MARGIN_OLD : MARGIN_SECOND_NEW
+ *     (estimator.cpp:126-129, feature_manager.cpp:106-189, compensatedParallax2 :958-996): needs every point track's observations in
+ *     frames 8 and 9, which only the device holds;
+ *   - failureDetection() (estimator.cpp:902-948, called at :225) on the states the solve returns.
+ * vpl_odo_enable_keyframe_rule switches the first on for a session; a session without it behaves, and moves the bytes, it did
+ * before.  With it, whenever an image enters slot 10 (vpl_odo_advance / _advance_imu behind the new frame, vpl_odo_set_window) the
+ * device decides for the window as it then stands (k_odo_parallax, one more launch) and one record of
+ * VPL_ODO_DECISION_RECORD_BYTES per sequence comes back in the synchronisation the call ends in -- in the IMU form in the same copy
+ * as the propagated states: vpl_odo_stats' d2h_bytes grows by exactly n_seq * VPL_ODO_DECISION_RECORD_BYTES, the table bytes by
+ * 3 ints per sequence + one int per qualifying track (the list the host's book writes, in the one host-to-device copy).
+ *   qualifying track: start <= 8 && start + nobs - 1 >= 9 (a track that ends in frame 9 and is not in the new image included);
+ *   its parallax: sqrt(du^2 + dv^2), du = x8 / z8 - x9, dv = y8 / z8 - y9 -- the frame-9 observation is NOT divided by its z, as in
+ *     the reference; parallax_sum adds them in a fixed order, so a sequence's sum has the same bits wherever it sits in a session;
+ *   last_track_num: observations of the new image that continued a track (ids that start a track or are ignored do not count);
+ *   flag = VPL_MARGIN_OLD when last_track_num < min_track_num || parallax_num == 0 || parallax_sum / parallax_num >= min_parallax,
+ *     else VPL_MARGIN_SECOND_NEW.  (The reference does not compute the sum when last_track_num is small; the record always holds it.)
+ * Line tracks take no part.  The decision is advice: the explicit-flag calls keep working on such a session. */
+typedef struct vpl_odo_keyframe_rule {
+  double min_parallax; /* MIN_PARALLAX = keyframe_parallax / FOCAL_LENGTH (parameters.cpp:79-80) */
+  int min_track_num;   /* 20 (feature_manager.cpp:166) */
+} vpl_odo_keyframe_rule;
+void vpl_odo_default_keyframe_rule(vpl_odo_keyframe_rule* rule); /* 10.0 / 460.0, 20 */
+#define VPL_ODO_DECISION_RECORD_BYTES 24
+/* Allowed whenever the session is not between vpl_odo_solve and vpl_odo_advance (VPL_E_INVALID there, and for a NULL or NaN
+ * threshold).  Sequences that hold a window get their decision computed in this call.  A second call replaces the thresholds and
+ * recomputes the decisions.  The first call grows the session's inbox by the list through the context's guarded allocator. */
+int vpl_odo_enable_keyframe_rule(vpl_odo* odo, const vpl_odo_keyframe_rule* rule);
+
+#define VPL_FAIL_ACC_BIAS 1     /* |Ba| > max_acc_bias          (estimator.cpp:909) */
+#define VPL_FAIL_GYR_BIAS 2     /* |Bg| > max_gyr_bias          (:914) */
+#define VPL_FAIL_TRANSLATION 4  /* |P - last_P| > max_translation (:927) */
+#define VPL_FAIL_Z 8            /* |P.z - last_P.z| > max_z     (:932) */
+typedef struct vpl_failure_limits {
+  double max_acc_bias, max_gyr_bias, max_translation, max_z; /* 2.5, 1.0, 5.0, 1.0; every comparison is a strict > */
+} vpl_failure_limits;
+void vpl_failure_default_limits(vpl_failure_limits* limits);
+/* The four conditions under which Estimator::failureDetection returns true, as a bit mask (0: no failure); host only, no device,
+ * no state.  speed_bias10 / pose10: frame WINDOW_SIZE after the solve; last_pose: last_P (only its position is read).  limits NULL:
+ * the defaults.  A NULL state: VPL_E_INVALID.  The conditions the reference only logs (few tracks, a large rotation) are left out. */
+int vpl_failure_detection(const vpl_failure_limits* limits, const double speed_bias10[9], const double pose10[7],
+                          const double last_pose[7]);
+
+typedef struct vpl_odo_decision { /* per sequence */
+  int flag;              /* VPL_MARGIN_OLD / VPL_MARGIN_SECOND_NEW for the window as it stands */
+  int last_track_num, parallax_num;
+  int failure;           /* VPL_FAIL_* mask of the sequence's last vpl_odo_solve under the default limits; 0 before the first */
+  double parallax_sum;
+  double parallax_mean;  /* parallax_sum / parallax_num, 0 when parallax_num == 0 */
+} vpl_odo_decision;
+/* VPL_E_INVALID when the rule is off or the sequence has no window.  The session keeps last_P per sequence on the host:
+ * vpl_odo_set_window stores pose[9] (Ps[9] equals last_P after either slide), every vpl_odo_solve compares with it and then stores
+ * the result's pose[10].  The session does nothing else on a failure: the reference restarts the estimator, here the caller
+ * decides (vpl_odo_set_window again).  Estimator::failure_occur / last_P0 / last_R0 stay unexposed: clearState() zeroes
+ * failure_occur right after it is set (estimator.cpp:75, 228-229), so that gauge path never runs. */
+int vpl_odo_get_decision(vpl_odo* odo, int seq, vpl_odo_decision* out);
+/* vpl_odo_solve / vpl_odo_keyframe / vpl_odo_keyframe_imu with the stored decisions as marginalization_flag: thin wrappers that
+ * build the flag array and call those.  The one-flag rule above holds for them too -- the batched solve marginalises one way per
+ * batch -- so when the sequences' decisions disagree the call is refused with VPL_E_INVALID before anything is touched, and
+ * vpl_last_error names how many sequences want each flag.  The caller can then pass explicit flags (solving the sequences of one
+ * mind together, say); the stored decisions stay readable.  VPL_E_INVALID too when the rule is off or a sequence has no window. */
+int vpl_odo_solve_auto(vpl_odo* odo, vpl_odo_result* out);
+int vpl_odo_keyframe_auto(vpl_odo* odo, const vpl_odo_frame* next, vpl_odo_result* out);
+int vpl_odo_keyframe_imu_auto(vpl_odo* odo, const vpl_odo_imu_frame* next, vpl_odo_result* out, vpl_odo_imu_out* imu_out);
+
 /* What a caller may want to look at; none of it is needed to keep going.  Arrays may be NULL (not wanted); the track arrays
  * need room for max_*_tracks entries.  Tracks come in the feature manager's order. */
 int vpl_odo_get_prior(vpl_odo* odo, int seq, vpl_prior* out);   /* n = 0: no prior yet */
@@ -488,6 +555,12 @@ int vpl_odo_debug_ms(vpl_odo* odo, double* ms4);
  * after the step; ignored[s]. */
 int vpl_odo_debug_tracks(int max_tracks, int n_steps, const int* flag, const int* n_ids, const int* ids, const unsigned char* erase,
                          int* status, int* n_slide, int* slide, int* n_tracks, int* table, int* ignored);
+/* The same replay (same arguments in, same refusals) for what the keyframe rule reads off the book: per step, once 11 frames are in
+ * and the step was not refused, n_list[s] and list[s * max_tracks + i] = the qualifying tracks as the device is told them
+ * (track | (8 - start) << 20, in the book's order) and last_track_num[s]; n_list[s] = -1 for a step while the window fills or a
+ * refused one (last_track_num[s] = 0). */
+int vpl_odo_debug_parallax_list(int max_tracks, int n_steps, const int* flag, const int* n_ids, const int* ids,
+                                const unsigned char* erase, int* n_list, int* list, int* last_track_num);
 
 /* ---- instrumentation (bench.py) ------------------------------------------ */
 /* Per-kernel device time of the last solve measured with hipEvents on the

@@ -5,7 +5,10 @@ alone and of the stages inside them; then --batch N sequences (default 64) in on
 keyframes per second.  Every C call ends in a stream synchronise, so the host clock around it is the time of the work.
 --mode imu: the same sequence through vpl_odo_keyframe_imu (raw samples in; pre-integration, merge and propagation on the device).
 --mode halves: the only faithful alternative without it -- vpl_odo_solve, vpl_preintegrate_batch from the bias it returned, the
-propagation on the host (not timed: a C++ caller's costs microseconds), vpl_odo_advance; the three C calls are summed."""
+propagation on the host (not timed: a C++ caller's costs microseconds), vpl_odo_advance; the three C calls are summed.
+--mode rule: what the keyframe rule (vpl_odo_enable_keyframe_rule: one more launch and a 24-byte record per image) costs -- the plain
+sequence through a rule-enabled session and through a plain one, alternating, --repeat times (default there: 3), with explicit
+MARGIN_OLD flags in both so that the two do the same work; medians over keyframes 4..31 of "slide + new frame" and of the keyframe."""
 import argparse
 import os
 import sys
@@ -19,12 +22,14 @@ import test_gpu_sequence as T
 import test_gpu_odo_session as S
 
 
-def run(seeds, n_keyframes):
+def run(seeds, n_keyframes, rule=False):
     opt = v.default_options()
     n = len(seeds)
     Ms = [T.Measurements(T.NF + n_keyframes, seed=s) for s in seeds]
     ctx = S._ctxn(n)
     ses = v.Session(ctx, n_seq=n, opt=opt, init_depth=5.0, line_min_obs=T.LINE_MIN_OBS, max_point_tracks=S.MAX_PT, max_line_tracks=S.MAX_LT)
+    if rule:
+        ses.enable_keyframe_rule()
     for i, M in enumerate(Ms):
         S.feed_window(ses, i, ctx, M, opt)
     acc = {"solve_c_call": [], "advance_c_call": [], "stage_triangulate": [], "stage_only_line_opt": [], "stage_solve": [],
@@ -88,9 +93,18 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--batch-keyframes", type=int, default=12)
-    ap.add_argument("--mode", choices=("plain", "imu", "halves"), default="plain")
+    ap.add_argument("--mode", choices=("plain", "imu", "halves", "rule"), default="plain")
     ap.add_argument("--repeat", type=int, default=1, help="imu / halves: run the sequence this many times, the two modes alternating")
     a = ap.parse_args()
+    if a.mode == "rule":
+        for r in range(a.repeat if a.repeat > 1 else 3):
+            for name, rule in (("rule", True), ("plain", False)):
+                acc = run([77], T.N_KEYFRAMES, rule=rule)
+                acc["keyframe_c_calls"] = list(np.array(acc["solve_c_call"]) + np.array(acc["advance_c_call"]))
+                print("%s run %d: %s | d2h %d B, tables %d B" % (name, r, " | ".join("%s median %.4f ms (min %.4f, max %.4f)" % (
+                    k, np.median(acc[k][4:]) * 1e3, np.min(acc[k][4:]) * 1e3, np.max(acc[k][4:]) * 1e3)
+                    for k in ("stage_slide_new_frame", "advance_c_call", "keyframe_c_calls")), np.median(acc["d2h_B"][4:]), np.median(acc["h2d_table_B"][4:])))
+        sys.exit(0)
     if a.mode != "plain":
         M = T.Measurements(T.NF + T.N_KEYFRAMES)
         for r in range(a.repeat):

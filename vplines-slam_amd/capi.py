@@ -183,6 +183,26 @@ class OdoImuOut(C.Structure):
 ODO_D2H_PAD_BYTES = 0    # VPL_ODO_D2H_PAD_BYTES: the session's read-backs are packed without alignment padding
 
 
+class OdoKeyframeRule(C.Structure):
+    """vpl_odo_keyframe_rule: MIN_PARALLAX (keyframe_parallax / FOCAL_LENGTH) and the track count below which every image is a keyframe"""
+    _fields_ = [("min_parallax", C.c_double), ("min_track_num", C.c_int)]
+
+
+class OdoDecision(C.Structure):
+    """vpl_odo_decision: addFeatureCheckParallax's decision for the window as it stands, failureDetection's mask of the last solve"""
+    _fields_ = [("flag", C.c_int), ("last_track_num", C.c_int), ("parallax_num", C.c_int), ("failure", C.c_int),
+                ("parallax_sum", C.c_double), ("parallax_mean", C.c_double)]
+
+
+class FailureLimits(C.Structure):
+    """vpl_failure_limits: the four thresholds of Estimator::failureDetection (every comparison a strict >)"""
+    _fields_ = [("max_acc_bias", C.c_double), ("max_gyr_bias", C.c_double), ("max_translation", C.c_double), ("max_z", C.c_double)]
+
+
+ODO_DECISION_RECORD_BYTES = 24    # VPL_ODO_DECISION_RECORD_BYTES: what a rule-enabled session reads back per sequence and image
+FAIL_ACC_BIAS, FAIL_GYR_BIAS, FAIL_TRANSLATION, FAIL_Z = 1, 2, 4, 8
+
+
 class CSlideTracks(C.Structure):
     _fields_ = [("point_start", _ip), ("point_nobs", _ip), ("point_drop", _ip),
                 ("line_start", _ip), ("line_nobs", _ip), ("line_drop", _ip)]
@@ -279,6 +299,17 @@ def load_hip_library():
     lib.vpl_odo_stats.argtypes = [vp, _llp, _llp, _llp]
     lib.vpl_odo_debug_ms.argtypes = [vp, _dp]
     lib.vpl_odo_debug_tracks.argtypes = [C.c_int, C.c_int, _ip, _ip, _ip, C.POINTER(C.c_ubyte), _ip, _ip, _ip, _ip, _ip, _ip]
+    lib.vpl_odo_default_keyframe_rule.argtypes = [C.POINTER(OdoKeyframeRule)]
+    lib.vpl_odo_default_keyframe_rule.restype = None
+    lib.vpl_odo_enable_keyframe_rule.argtypes = [vp, C.POINTER(OdoKeyframeRule)]
+    lib.vpl_odo_get_decision.argtypes = [vp, C.c_int, C.POINTER(OdoDecision)]
+    lib.vpl_odo_solve_auto.argtypes = [vp, C.POINTER(OdoResult)]
+    lib.vpl_odo_keyframe_auto.argtypes = [vp, C.POINTER(OdoFrame), C.POINTER(OdoResult)]
+    lib.vpl_odo_keyframe_imu_auto.argtypes = [vp, C.POINTER(OdoImuFrame), C.POINTER(OdoResult), C.POINTER(OdoImuOut)]
+    lib.vpl_failure_default_limits.argtypes = [C.POINTER(FailureLimits)]
+    lib.vpl_failure_default_limits.restype = None
+    lib.vpl_failure_detection.argtypes = [C.POINTER(FailureLimits), _dp, _dp, _dp]
+    lib.vpl_odo_debug_parallax_list.argtypes = [C.c_int, C.c_int, _ip, _ip, _ip, C.POINTER(C.c_ubyte), _ip, _ip, _ip]
     _hip = lib
     return lib
 
@@ -762,6 +793,66 @@ class Session:
         self.ctx._check(rc, "vpl_odo_advance_imu")
         return self._res, imu
 
+    # ---- the keyframe decision and the failure check (vpl_odo_enable_keyframe_rule) ----
+    def enable_keyframe_rule(self, min_parallax=None, min_track_num=None):
+        """vpl_odo_enable_keyframe_rule: from now on the device decides, image by image, which way the next solve marginalises
+        (decision / the _auto calls); None = the reference's default.  A second call replaces the thresholds."""
+        r = default_keyframe_rule()
+        if min_parallax is not None:
+            r.min_parallax = float(min_parallax)
+        if min_track_num is not None:
+            r.min_track_num = int(min_track_num)
+        self.ctx._settle()
+        rc = self.lib.vpl_odo_enable_keyframe_rule(self.h, C.byref(r))
+        self.last_rc = rc
+        self.ctx._check(rc, "vpl_odo_enable_keyframe_rule")
+
+    def decision(self, seq=0):
+        """vpl_odo_get_decision: OdoDecision of the window as it stands (and the failure mask of the last solve)"""
+        d = OdoDecision()
+        rc = self.lib.vpl_odo_get_decision(self.h, seq, C.byref(d))
+        self.last_rc = rc
+        self.ctx._check(rc, "vpl_odo_get_decision")
+        return d
+
+    def solve_auto(self):
+        """vpl_odo_solve_auto: solve() with the stored decisions as flags (refused when the sequences disagree)"""
+        self._res = (OdoResult * self.n_seq)()
+        self.ctx._settle()
+        t0 = time.perf_counter()
+        rc = self.lib.vpl_odo_solve_auto(self.h, self._res)
+        self.last_call_s = time.perf_counter() - t0
+        self.last_rc = rc
+        self.ctx._check(rc, "vpl_odo_solve_auto")
+        return self._res
+
+    def keyframe_auto(self, frames):
+        """vpl_odo_keyframe_auto: keyframe() with the stored decisions as flags"""
+        assert len(frames) == self.n_seq
+        cf = (OdoFrame * self.n_seq)()
+        for i, f in enumerate(frames):
+            f.to_c(cf[i])
+        res = (OdoResult * self.n_seq)()
+        self.ctx._settle()
+        t0 = time.perf_counter()
+        rc = self.lib.vpl_odo_keyframe_auto(self.h, cf, res)
+        self.last_call_s = time.perf_counter() - t0
+        self.last_rc = rc
+        self.ctx._check(rc, "vpl_odo_keyframe_auto")
+        return res
+
+    def keyframe_imu_auto(self, frames):
+        """vpl_odo_keyframe_imu_auto: keyframe_imu() with the stored decisions as flags"""
+        cf = self._imu_frames(frames)
+        res, imu = (OdoResult * self.n_seq)(), (OdoImuOut * self.n_seq)()
+        self.ctx._settle()
+        t0 = time.perf_counter()
+        rc = self.lib.vpl_odo_keyframe_imu_auto(self.h, cf, res, imu)
+        self.last_call_s = time.perf_counter() - t0
+        self.last_rc = rc
+        self.ctx._check(rc, "vpl_odo_keyframe_imu_auto")
+        return res, imu
+
     def get_preint(self, seq=0):
         """vpl_odo_get_preint: (Preintegration * 11) as the session holds them (entry 0 zero; jacobian columns 0..8 zero)"""
         out = (Preintegration * NF)()
@@ -817,3 +908,38 @@ def odo_debug_tracks(max_tracks, flags, frames_ids, erase):
     rc = lib.vpl_odo_debug_tracks(max_tracks, n, ip(fl), ip(n_ids), ip(ids), er.ctypes.data_as(C.POINTER(C.c_ubyte)), ip(status),
                                   ip(n_slide), ip(slide), ip(n_tracks), ip(table), ip(ignored))
     return rc, status[:n], n_slide[:n], slide[:n], n_tracks[:n], table[:n], ignored[:n]
+
+
+def default_keyframe_rule():
+    r = OdoKeyframeRule()
+    load_hip_library().vpl_odo_default_keyframe_rule(C.byref(r))
+    return r
+
+
+def default_failure_limits():
+    l = FailureLimits()
+    load_hip_library().vpl_failure_default_limits(C.byref(l))
+    return l
+
+
+def failure_detection(speed_bias10, pose10, last_pose, limits=None):
+    """vpl_failure_detection (host only): the FAIL_* mask of Estimator::failureDetection; limits None = the defaults"""
+    sb, p, q = _arr(speed_bias10, np.float64).reshape(9), _arr(pose10, np.float64).reshape(7), _arr(last_pose, np.float64).reshape(7)
+    return load_hip_library().vpl_failure_detection(None if limits is None else C.byref(limits), _p(sb), _p(p), _p(q))
+
+
+def odo_debug_parallax_list(max_tracks, flags, frames_ids, erase):
+    """vpl_odo_debug_parallax_list (host only), arguments as odo_debug_tracks.  Returns rc, n_list [n_steps] (-1: no decision at
+    that step), list [n_steps][max_tracks], last_track_num [n_steps]"""
+    lib = load_hip_library()
+    n = len(flags)
+    fl = _arr(flags, np.int32)
+    n_ids = _arr([len(f) for f in frames_ids], np.int32)
+    ids = _arr([i for f in frames_ids for i in f] + [0], np.int32)
+    er = _arr(erase, np.uint8).reshape(n, max_tracks)
+    n_list, last = (np.zeros(max(n, 1), np.int32) for _ in range(2))
+    lst = np.full((max(n, 1), max_tracks), -7, np.int32)
+    ip = lambda a: a.ctypes.data_as(_ip)
+    rc = lib.vpl_odo_debug_parallax_list(max_tracks, n, ip(fl), ip(n_ids), ip(ids), er.ctypes.data_as(C.POINTER(C.c_ubyte)), ip(n_list),
+                                         ip(lst), ip(last))
+    return rc, n_list[:n], lst[:n], last[:n]

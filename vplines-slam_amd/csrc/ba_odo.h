@@ -504,4 +504,54 @@ __global__ __launch_bounds__(64) void k_odo_imu(OdoStore D, OdoImu IA, OdoImu ID
   }
 }
 
+// ---- the keyframe decision (vpl_odo_enable_keyframe_rule): FeatureManager::addFeatureCheckParallax's return value for the window
+// as it stands with the new image in slot 10 (feature_manager.cpp:166-188), behind k_odo_append.  One work-group per sequence;
+// block b works on sequence seq0 + b of the store and on entry b of par and out.
+// par [b][3] = offset of the sequence's list in tab, its entries, last_track_num (odo_parallax_list: the host's book knows which
+// tracks qualify and where their frame-8 observation lies; the observations themselves are only here).
+// Per track compensatedParallax2 (feature_manager.cpp:958-996) as it is written: the frame-8 observation divided by its z, the
+// frame-9 observation as stored; the compensated variant is the same expression, so the min of the two is that expression.
+// The sum has one shape whatever the session looks like: lane t adds entries t, t + 256, ... in list order (a lane without an
+// entry adds nothing), the 64 lanes of a wave are folded by the xor butterfly 32, 16, .. 1, and lane 0 adds the four waves as
+// (w0 + w1) + (w2 + w3).  No atomics; the bits depend on the list and the observations alone.
+struct OdoParallaxRec {   // VPL_ODO_DECISION_RECORD_BYTES
+  int flag, last_track_num, parallax_num, reserved;
+  double parallax_sum;
+};
+static_assert(sizeof(OdoParallaxRec) == VPL_ODO_DECISION_RECORD_BYTES, "the decision record is part of the documented traffic");
+constexpr int ODO_PAR_HDR = 3;
+static_assert(ODO_THREADS == 4 * 64, "k_odo_parallax combines four waves");
+__global__ __launch_bounds__(ODO_THREADS) void k_odo_parallax(OdoStore S, const int* __restrict__ tab, const int* __restrict__ par, int seq0,
+                                                              double min_parallax, int min_track_num, OdoParallaxRec* __restrict__ out) {
+  __shared__ double wave_sum[ODO_THREADS / 64];
+  const int b = blockIdx.x, w = seq0 + b, tid = threadIdx.x;
+  const int* list = tab + par[ODO_PAR_HDR * b];
+  const int n = par[ODO_PAR_HDR * b + 1];
+  const double* po = S.pobs + (size_t)w * S.maxPT * NF * 3;
+  double acc = 0.0;
+  for (int i = tid; i < n; i += ODO_THREADS) {
+    const int e = list[i];
+    const double* o = po + ((size_t)(e & 0xFFFFF) * NF + (e >> 20 & 15)) * 3;   // frame 8's record, frame 9's behind it
+    const double u_i = o[0] / o[2], v_i = o[1] / o[2];
+    const double du = u_i - o[3], dv = v_i - o[4];
+    const double d = sqrt(du * du + dv * dv);
+    acc += 0.0 < d ? d : 0.0;   // max(ans = 0, .) of std::max: a NaN counts as zero
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  if ((tid & 63) == 0) wave_sum[tid >> 6] = acc;
+  __syncthreads();
+  if (tid == 0) {
+    const double sum = (wave_sum[0] + wave_sum[1]) + (wave_sum[2] + wave_sum[3]);
+    const int last = par[ODO_PAR_HDR * b + 2];
+    OdoParallaxRec r;
+    r.flag = (last < min_track_num || n == 0 || sum / n >= min_parallax) ? VPL_MARGIN_OLD : VPL_MARGIN_SECOND_NEW;
+    r.last_track_num = last;
+    r.parallax_num = n;
+    r.reserved = 0;
+    r.parallax_sum = sum;
+    out[b] = r;
+  }
+}
+
 }  // namespace vpl

@@ -14,6 +14,11 @@ struct OdoSeq {
   HostTab prior;                   // block table of the prior the session holds on the device
   bool has_prior = false, set = false;
   bool imu_set = false;            // vpl_odo_set_imu since the last vpl_odo_set_window (IMU-enabled sessions)
+  // the keyframe decision of the window as it stands (vpl_odo_enable_keyframe_rule) and the failure check's memory
+  OdoParallaxRec dec = {};
+  bool dec_set = false;
+  double last_pose[7] = {};        // Estimator::last_P (failureDetection): pose[9] of vpl_odo_set_window, then pose[10] of every solve
+  int failure = 0;                 // VPL_FAIL_* of the last solve, default limits
 };
 
 struct vpl_odo {
@@ -33,6 +38,10 @@ struct vpl_odo {
   int max_samples = 0;
   OdoImu im[2] = {};
   size_t imu_alloc0 = 0, imu_alloc1 = 0;
+  // vpl_odo_enable_keyframe_rule: thresholds; the grown inbox in the allocation record (its own range, behind alloc1)
+  bool rule = false;
+  vpl_odo_keyframe_rule kf_rule = {};
+  size_t rule_alloc0 = 0, rule_alloc1 = 0;
   std::vector<OdoSeq> seq;
   // the integer-only windows handed to the uploads, and what they point to
   std::vector<vpl_window> win;
@@ -122,6 +131,45 @@ struct OdoNext {
   }
 };
 
+// ---- the keyframe rule (vpl_odo_enable_keyframe_rule) ------------------------------------------------------------------------
+// k_odo_parallax's tables for sequences seq0 .. seq0 + n - 1 at dst, which lies tab_off ints into the table the kernel is given:
+// par [n][3], then the lists (odo_parallax_list).  Returns the ints written -- at most n * (3 + max_point_tracks), the room
+// vpl_odo_enable_keyframe_rule adds to the inbox.
+static size_t odo_write_parallax_tab(vpl_odo* o, int seq0, int n, int* dst, size_t tab_off) {
+  size_t k = (size_t)ODO_PAR_HDR * n;
+  for (int b = 0; b < n; ++b) {
+    int* h = dst + ODO_PAR_HDR * b;
+    h[0] = (int)(tab_off + k);
+    h[1] = odo_parallax_list(o->seq[seq0 + b].P, dst + k, &h[2]);
+    k += h[1];
+  }
+  return k;
+}
+static void odo_read_decisions(vpl_odo* o, int seq0, int n, const char* recs) {
+  for (int b = 0; b < n; ++b) {
+    OdoSeq& q = o->seq[seq0 + b];
+    std::memcpy(&q.dec, recs + sizeof(OdoParallaxRec) * b, sizeof(OdoParallaxRec));
+    q.dec_set = q.set;
+  }
+}
+// the decision of sequences that already hold a window (vpl_odo_set_window, vpl_odo_enable_keyframe_rule): tables down, one
+// launch, records back, synchronous; not on the per-keyframe path and not counted in vpl_odo_stats.  The caller has set the device
+// and is not between vpl_odo_solve and vpl_odo_advance (the flags of a solve wait in h_out).
+static int odo_decide(vpl_odo* o, int seq0, int n) {
+  vpl_ctx* c = o->c;
+  hipStream_t s = c->stream;
+  const size_t nt = odo_write_parallax_tab(o, seq0, n, reinterpret_cast<int*>(o->h_in), 0);
+  HIPCHK(c, hipMemcpyAsync(o->d_in, o->h_in, nt * 4, hipMemcpyHostToDevice, s));
+  const int* d_tab = reinterpret_cast<const int*>(o->d_in);
+  hipLaunchKernelGGL(k_odo_parallax, dim3(n), dim3(ODO_THREADS), 0, s, o->st[o->cur], d_tab, d_tab, seq0, o->kf_rule.min_parallax,
+                     o->kf_rule.min_track_num, reinterpret_cast<OdoParallaxRec*>(o->d_out));
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(o->h_out, o->d_out, (size_t)n * sizeof(OdoParallaxRec), hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  odo_read_decisions(o, seq0, n, o->h_out);
+  return VPL_OK;
+}
+
 extern "C" {
 
 int vpl_odo_create(vpl_odo** out, vpl_ctx* c, int n_seq, const vpl_ba_options* opt, double init_depth, int line_min_obs,
@@ -183,10 +231,15 @@ void vpl_odo_destroy(vpl_odo* o) {
   (void)hipSetDevice(c->device);
   (void)settle(c);
   (void)hipStreamSynchronize(c->stream);
-  for (size_t i = o->imu_alloc0; i < o->imu_alloc1 && i < c->allocs.size(); ++i) (void)hipFree(c->allocs[i]);
-  if (o->imu_alloc1 > o->imu_alloc0 && o->imu_alloc1 <= c->allocs.size()) {   // (behind the session's own range: erased first)
-    c->allocs.erase(c->allocs.begin() + o->imu_alloc0, c->allocs.begin() + o->imu_alloc1);
-    c->alloc_bytes.erase(c->alloc_bytes.begin() + o->imu_alloc0, c->alloc_bytes.begin() + o->imu_alloc1);
+  // (the ranges of the two enable calls lie behind the session's own, in the order of the calls: the later one is erased first)
+  size_t late[2][2] = {{o->imu_alloc0, o->imu_alloc1}, {o->rule_alloc0, o->rule_alloc1}};
+  if (late[0][0] < late[1][0]) std::swap(late[0], late[1]);
+  for (const auto& r : late) {
+    for (size_t i = r[0]; i < r[1] && i < c->allocs.size(); ++i) (void)hipFree(c->allocs[i]);
+    if (r[1] > r[0] && r[1] <= c->allocs.size()) {
+      c->allocs.erase(c->allocs.begin() + r[0], c->allocs.begin() + r[1]);
+      c->alloc_bytes.erase(c->alloc_bytes.begin() + r[0], c->alloc_bytes.begin() + r[1]);
+    }
   }
   for (size_t i = o->alloc0; i < o->alloc1 && i < c->allocs.size(); ++i) (void)hipFree(c->allocs[i]);
   if (o->alloc1 <= c->allocs.size()) {
@@ -256,8 +309,11 @@ int vpl_odo_set_window(vpl_odo* o, int seq, const double pose[][7], const double
   Q.has_prior = false;
   Q.set = true;
   Q.imu_set = false;
+  std::memcpy(Q.last_pose, pose[NF - 2], 56);
+  Q.failure = 0;
+  Q.dec_set = false;
   o->solved = false;
-  return VPL_OK;
+  return o->rule ? odo_decide(o, seq, 1) : VPL_OK;
 }
 
 // the refusals of a new frame: null arrays, more tracks than the session holds (counted on the book as it stands)
@@ -427,6 +483,8 @@ int vpl_odo_solve(vpl_odo* o, const int* flags, vpl_odo_result* out) {
     r.n_point_tracks = (int)q.P.t.size();
     r.n_line_tracks = (int)q.L.t.size();
     r.n_ignored = 0;
+    q.failure = vpl_failure_detection(nullptr, r.speed_bias[NF - 1], r.pose[NF - 1], q.last_pose);
+    std::memcpy(q.last_pose, r.pose[NF - 1], 56);
     int lrem2 = 0;
     if (solve_opt.remove_line_outliers)
       for (int dl = 0; dl < c->h_nL[w]; ++dl) lrem2 += h_flags[totP + totT + kL + dl] ? 1 : 0;
@@ -523,10 +581,13 @@ static int odo_advance_impl(vpl_odo* o, const OdoNext& next, vpl_odo_result* out
     if (f.n_lines) std::memcpy(d + 3 * (size_t)f.n_points, f.line_obs, (size_t)f.n_lines * 64);
     poff += next.head(w) + 3 * (size_t)f.n_points + 8 * (size_t)f.n_lines;
   }
-  const size_t in_bytes = npay * 8 + (ntab + nent) * 4;   // (within in_cap: odo_check_next bounds a frame's observations and samples)
+  // the keyframe rule: what the book knows of the window with the new image in it rides behind the other tables
+  size_t npar = 0;
+  if (o->rule) npar = odo_write_parallax_tab(o, 0, nS, ent + nent, ntab + nent);
+  const size_t in_bytes = npay * 8 + (ntab + nent + npar) * 4;   // (within in_cap: odo_check_next bounds a frame's observations and samples)
   HIPCHK(c, hipMemcpyAsync(o->d_in, o->h_in, in_bytes, hipMemcpyHostToDevice, s));
   o->h2d_payload = (long long)npay * 8;
-  o->h2d_table += (long long)(ntab + nent) * 4;
+  o->h2d_table += (long long)(ntab + nent + npar) * 4;
   const int* d_tab = reinterpret_cast<const int*>(o->d_in + npay * 8);
   const OdoStore D = o->st[o->cur ^ 1];
   hipLaunchKernelGGL(k_odo_slide, dim3(nS, ODO_SLIDE_Y), blk, 0, s, S, D, d_tab + (pmv - tab), d_tab + (lmv - tab), d_tab + (cnt - tab),
@@ -537,8 +598,15 @@ static int odo_advance_impl(vpl_odo* o, const OdoNext& next, vpl_odo_result* out
     hipLaunchKernelGGL(k_odo_imu, grid, dim3(64), 0, s, D, o->im[o->cur], o->im[o->cur ^ 1], reinterpret_cast<const double*>(o->d_in), d_tab,
                        flag == VPL_MARGIN_SECOND_NEW ? 1 : 0, p.acc_n * p.acc_n, p.gyr_n * p.gyr_n, p.acc_w * p.acc_w, p.gyr_w * p.gyr_w,
                        p.g_norm, reinterpret_cast<double*>(o->d_out));
-    HIPCHK(c, hipMemcpyAsync(o->h_out, o->d_out, (size_t)nS * ODO_IMU_OUT_D * 8, hipMemcpyDeviceToHost, s));
-    o->d2h += (long long)nS * ODO_IMU_OUT_D * 8;
+  }
+  // what comes back: the 18 doubles per sequence of the IMU form, the decision records behind them, in one copy
+  const size_t imu_bytes = next.imu ? (size_t)nS * ODO_IMU_OUT_D * 8 : 0, dec_bytes = o->rule ? (size_t)nS * sizeof(OdoParallaxRec) : 0;
+  if (o->rule)
+    hipLaunchKernelGGL(k_odo_parallax, grid, blk, 0, s, D, d_tab, d_tab + (ent + nent - tab), 0, o->kf_rule.min_parallax, o->kf_rule.min_track_num,
+                       reinterpret_cast<OdoParallaxRec*>(o->d_out + imu_bytes));
+  if (imu_bytes + dec_bytes) {
+    HIPCHK(c, hipMemcpyAsync(o->h_out, o->d_out, imu_bytes + dec_bytes, hipMemcpyDeviceToHost, s));
+    o->d2h += (long long)(imu_bytes + dec_bytes);
   }
   HIPCHK(c, hipGetLastError());
   o->cur ^= 1;
@@ -553,6 +621,7 @@ static int odo_advance_impl(vpl_odo* o, const OdoNext& next, vpl_odo_result* out
       if (imu_out) { std::memcpy(imu_out[w].pose, r, 56); std::memcpy(imu_out[w].speed_bias, r + 7, 72); imu_out[w].sum_dt[0] = r[16]; imu_out[w].sum_dt[1] = r[17]; }
     }
   }
+  if (o->rule) odo_read_decisions(o, 0, nS, o->h_out + imu_bytes);
   o->solved = false;
   o->ms[3] = std::chrono::duration<double, std::milli>(oclk::now() - t0).count();
   return VPL_OK;
@@ -651,6 +720,115 @@ int vpl_odo_set_imu(vpl_odo* o, int seq, int n10, const double* samples10, const
   return VPL_OK;
 }
 
+// ---- the keyframe decision and the failure check ------------------------------------------------------------------------------
+void vpl_odo_default_keyframe_rule(vpl_odo_keyframe_rule* r) {
+  if (!r) return;
+  r->min_parallax = 10.0 / 460.0;
+  r->min_track_num = 20;
+}
+
+// The inbox was sized at create without the list; the first call replaces it by one with room for it (the smaller one stays in
+// the session's range until vpl_odo_destroy, like vpl_odo_enable_imu's)
+int vpl_odo_enable_keyframe_rule(vpl_odo* o, const vpl_odo_keyframe_rule* rule) {
+  if (!o || !rule) return VPL_E_INVALID;
+  vpl_ctx* c = o->c;
+  if (!(rule->min_parallax == rule->min_parallax)) return fail(c, VPL_E_INVALID, "odo_enable_keyframe_rule: min_parallax is not a number");
+  if (o->solved) return fail(c, VPL_E_INVALID, "odo_enable_keyframe_rule: between vpl_odo_solve and vpl_odo_advance");
+  HIPCHK(c, hipSetDevice(c->device));
+  { const int rs = settle(c); if (rs) return rs; }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (!o->rule) {
+    const size_t cap = o->in_cap + (size_t)o->nS * 4 * (ODO_PAR_HDR + (size_t)o->maxPT);
+    char *din = nullptr, *hin = nullptr;
+    o->rule_alloc0 = c->allocs.size();
+    hipError_t e = dalloc(c, &din, cap);
+    o->rule_alloc1 = c->allocs.size();
+    if (e == hipSuccess) e = hipHostMalloc((void**)&hin, cap, hipHostMallocDefault);
+    if (e != hipSuccess) return fail(c, VPL_E_HIP, "odo_enable_keyframe_rule: allocation failed");
+    (void)hipHostFree(o->h_in);
+    o->d_in = din; o->h_in = hin; o->in_cap = cap;
+    o->rule = true;
+  }
+  o->kf_rule = *rule;
+  return odo_decide(o, 0, o->nS);
+}
+
+void vpl_failure_default_limits(vpl_failure_limits* l) {
+  if (!l) return;
+  l->max_acc_bias = 2.5; l->max_gyr_bias = 1.0; l->max_translation = 5.0; l->max_z = 1.0;
+}
+
+// Estimator::failureDetection (estimator.cpp:909-936): Eigen's norm() is the square root of the sum of squares, taken in order
+int vpl_failure_detection(const vpl_failure_limits* limits, const double* sb, const double* pose, const double* last_pose) {
+  if (!sb || !pose || !last_pose) return VPL_E_INVALID;
+  vpl_failure_limits l;
+  if (limits) l = *limits; else vpl_failure_default_limits(&l);
+  const auto norm3 = [](double x, double y, double z) { return std::sqrt(x * x + y * y + z * z); };
+  const double dx = pose[0] - last_pose[0], dy = pose[1] - last_pose[1], dz = pose[2] - last_pose[2];
+  int mask = 0;
+  if (norm3(sb[3], sb[4], sb[5]) > l.max_acc_bias) mask |= VPL_FAIL_ACC_BIAS;
+  if (norm3(sb[6], sb[7], sb[8]) > l.max_gyr_bias) mask |= VPL_FAIL_GYR_BIAS;
+  if (norm3(dx, dy, dz) > l.max_translation) mask |= VPL_FAIL_TRANSLATION;
+  if (std::fabs(dz) > l.max_z) mask |= VPL_FAIL_Z;
+  return mask;
+}
+
+int vpl_odo_get_decision(vpl_odo* o, int seq, vpl_odo_decision* out) {
+  if (!o || seq < 0 || seq >= o->nS || !out) return VPL_E_INVALID;
+  vpl_ctx* c = o->c;
+  if (!o->rule) return fail(c, VPL_E_INVALID, "odo_get_decision: the keyframe rule is off (vpl_odo_enable_keyframe_rule)");
+  const OdoSeq& q = o->seq[seq];
+  if (!q.set || !q.dec_set) return fail(c, VPL_E_INVALID, "odo_get_decision: the sequence has no window (vpl_odo_set_window)");
+  out->flag = q.dec.flag;
+  out->last_track_num = q.dec.last_track_num;
+  out->parallax_num = q.dec.parallax_num;
+  out->failure = q.failure;
+  out->parallax_sum = q.dec.parallax_sum;
+  out->parallax_mean = q.dec.parallax_num ? q.dec.parallax_sum / q.dec.parallax_num : 0.0;
+  return VPL_OK;
+}
+
+}  // extern "C"
+
+// the flag array of an _auto call: the stored decisions, when there is one for every sequence and they agree
+static int odo_auto_flags(vpl_odo* o, std::vector<int>& flags) {
+  vpl_ctx* c = o->c;
+  if (!o->rule) return fail(c, VPL_E_INVALID, "odo: the keyframe rule is off (vpl_odo_enable_keyframe_rule)");
+  int n_old = 0, n_new = 0;
+  flags.resize(o->nS);
+  for (int w = 0; w < o->nS; ++w) {
+    const OdoSeq& q = o->seq[w];
+    if (!q.set || !q.dec_set) return fail(c, VPL_E_INVALID, "odo: a sequence has no window (vpl_odo_set_window)");
+    flags[w] = q.dec.flag;
+    ++(q.dec.flag == VPL_MARGIN_OLD ? n_old : n_new);
+  }
+  if (n_old && n_new)
+    return fail(c, VPL_E_INVALID, "odo: the sequences' keyframe decisions disagree (" + std::to_string(n_old) + " want VPL_MARGIN_OLD, " +
+                                      std::to_string(n_new) + " VPL_MARGIN_SECOND_NEW) and the batched solve marginalises one way per batch: pass explicit flags");
+  return VPL_OK;
+}
+
+extern "C" {
+
+int vpl_odo_solve_auto(vpl_odo* o, vpl_odo_result* out) {
+  if (!o || !out) return VPL_E_INVALID;
+  std::vector<int> flags;
+  const int rc = odo_auto_flags(o, flags);
+  return rc ? rc : vpl_odo_solve(o, flags.data(), out);
+}
+int vpl_odo_keyframe_auto(vpl_odo* o, const vpl_odo_frame* next, vpl_odo_result* out) {
+  if (!o || !next || !out) return VPL_E_INVALID;
+  std::vector<int> flags;
+  const int rc = odo_auto_flags(o, flags);
+  return rc ? rc : vpl_odo_keyframe(o, next, flags.data(), out);
+}
+int vpl_odo_keyframe_imu_auto(vpl_odo* o, const vpl_odo_imu_frame* next, vpl_odo_result* out, vpl_odo_imu_out* imu_out) {
+  if (!o || !next || !out) return VPL_E_INVALID;
+  std::vector<int> flags;
+  const int rc = odo_auto_flags(o, flags);
+  return rc ? rc : vpl_odo_keyframe_imu(o, next, flags.data(), out, imu_out);
+}
+
 // the inverse of to_dev_preint for what DevPreint holds: columns 0..8 of the jacobian are not held and come back zero
 int vpl_odo_get_preint(vpl_odo* o, int seq, vpl_preintegration* out) {
   if (!o || seq < 0 || seq >= o->nS || !out) return VPL_E_INVALID;
@@ -735,11 +913,13 @@ int vpl_odo_debug_ms(vpl_odo* o, double* ms4) {
   return VPL_OK;
 }
 
-// Host only: the book of one kind of tracks of one sequence replayed from a script (tests/test_odo_tracks.py)
-int vpl_odo_debug_tracks(int max_tracks, int n_steps, const int* flag, const int* n_ids, const int* ids, const unsigned char* erase,
-                         int* status, int* n_slide, int* slide, int* n_tracks, int* table, int* ignored) {
-  if (max_tracks < 1 || n_steps < 0 || !flag || !n_ids || !ids || !erase || !status || !n_slide || !slide || !n_tracks || !table || !ignored)
-    return VPL_E_INVALID;
+}  // extern "C"
+
+// Host only: the book of one kind of tracks of one sequence replayed from a script (tests/test_odo_tracks.py); slide: [max_tracks][3]
+// per step, may be null.  after(s, book, status, n_slide, ignored, frames in the window) reports each step.
+template <class F>
+static int odo_replay(int max_tracks, int n_steps, const int* flag, const int* n_ids, const int* ids, const unsigned char* erase, int* slide,
+                      F&& after) {
   OdoBook b;
   int frames = 0;
   std::vector<OdoMove> mv;
@@ -748,20 +928,42 @@ int vpl_odo_debug_tracks(int max_tracks, int n_steps, const int* flag, const int
     const bool filling = flag[s] == VPL_MARGIN_NONE;
     if (!filling && flag[s] != VPL_MARGIN_OLD && flag[s] != VPL_MARGIN_SECOND_NEW) return VPL_E_INVALID;
     if (filling ? frames >= NF : frames < NF) return VPL_E_INVALID;
-    status[s] = VPL_OK; n_slide[s] = 0; ignored[s] = 0;
-    if ((int)b.t.size() + odo_count_unknown(b, n_ids[s], ids) > max_tracks) status[s] = VPL_E_CAPACITY;
+    int status = VPL_OK, n_slide = 0, ignored = 0;
+    if ((int)b.t.size() + odo_count_unknown(b, n_ids[s], ids) > max_tracks) status = VPL_E_CAPACITY;
     else {
-      if (!filling) n_slide[s] = odo_erase_slide(b, erase + (size_t)s * max_tracks, flag[s] == VPL_MARGIN_SECOND_NEW, mv, slide + (size_t)s * max_tracks * 3);
-      ignored[s] = odo_add_frame(b, filling ? frames : NF - 1, n_ids[s], ids, nullptr);
+      if (!filling) n_slide = odo_erase_slide(b, erase + (size_t)s * max_tracks, flag[s] == VPL_MARGIN_SECOND_NEW, mv, slide ? slide + (size_t)s * max_tracks * 3 : nullptr);
+      ignored = odo_add_frame(b, filling ? frames : NF - 1, n_ids[s], ids, nullptr);
       if (filling) ++frames;
     }
+    after(s, b, status, n_slide, ignored, frames);
+  }
+  return VPL_OK;
+}
+
+extern "C" {
+
+int vpl_odo_debug_tracks(int max_tracks, int n_steps, const int* flag, const int* n_ids, const int* ids, const unsigned char* erase,
+                         int* status, int* n_slide, int* slide, int* n_tracks, int* table, int* ignored) {
+  if (max_tracks < 1 || n_steps < 0 || !flag || !n_ids || !ids || !erase || !status || !n_slide || !slide || !n_tracks || !table || !ignored)
+    return VPL_E_INVALID;
+  return odo_replay(max_tracks, n_steps, flag, n_ids, ids, erase, slide, [&](int s, const OdoBook& b, int st, int nsl, int ig, int) {
+    status[s] = st; n_slide[s] = nsl; ignored[s] = ig;
     n_tracks[s] = (int)b.t.size();
     for (size_t i = 0; i < b.t.size(); ++i) {
       int* e = table + ((size_t)s * max_tracks + i) * 3;
       e[0] = b.t[i].id; e[1] = b.t[i].start; e[2] = b.t[i].nobs;
     }
-  }
-  return VPL_OK;
+  });
+}
+
+// ... and what the keyframe rule reads off the book after each step (tests/test_odo_keyframe_rule_api.py)
+int vpl_odo_debug_parallax_list(int max_tracks, int n_steps, const int* flag, const int* n_ids, const int* ids, const unsigned char* erase,
+                                int* n_list, int* list, int* last_track_num) {
+  if (max_tracks < 1 || n_steps < 0 || !flag || !n_ids || !ids || !erase || !n_list || !list || !last_track_num) return VPL_E_INVALID;
+  return odo_replay(max_tracks, n_steps, flag, n_ids, ids, erase, nullptr, [&](int s, const OdoBook& b, int st, int, int, int frames) {
+    n_list[s] = -1; last_track_num[s] = 0;
+    if (st == VPL_OK && frames == NF) n_list[s] = odo_parallax_list(b, list + (size_t)s * max_tracks, &last_track_num[s]);
+  });
 }
 
 }  // extern "C"

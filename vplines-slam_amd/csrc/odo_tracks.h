@@ -110,4 +110,21 @@ inline int odo_add_frame(OdoBook& b, int slot, int n, const int* ids, int* dest)
   return ignored;
 }
 
+// What addFeatureCheckParallax(frame_count = WINDOW_SIZE, image) decides on (feature_manager.cpp:166-188), read off the point
+// book once the new image is in slot 10.  list (room for one int per track): the tracks with start <= 8 whose last observation is
+// in frame 9 or later, in the book's order, as track | (8 - start) << 20 -- the index of the frame-8 observation within the track;
+// the frame-9 observation follows it.  *last_track_num: the observations of the new image that continued a track, i.e. the tracks
+// that began before slot 10 and end in it (an id continues at most one track, once).  Returns the number of list entries.
+inline int odo_parallax_list(const OdoBook& b, int* list, int* last_track_num) {
+  constexpr int WS = ODO_NF - 1;
+  int n = 0, last = 0;
+  for (size_t i = 0; i < b.t.size(); ++i) {
+    const OdoTrack& t = b.t[i];
+    if (t.start <= WS - 2 && t.start + t.nobs - 1 >= WS - 1) list[n++] = (int)i | (WS - 2 - t.start) << 20;
+    if (t.start < WS && t.start + t.nobs - 1 == WS) ++last;
+  }
+  *last_track_num = last;
+  return n;
+}
+
 }  // namespace vpl
