@@ -223,6 +223,7 @@ class SlideTracks:
 
 
 _hip = None
+PSD_WAVE16, PSD_WAVE48, PSD_WAVE4, PSD_WORKGROUP = 0, 1, 2, 3   # forms of vpl_ba_debug_psd_factor
 
 
 def load_hip_library():
@@ -310,6 +311,8 @@ def load_hip_library():
     lib.vpl_failure_default_limits.restype = None
     lib.vpl_failure_detection.argtypes = [C.POINTER(FailureLimits), _dp, _dp, _dp]
     lib.vpl_odo_debug_parallax_list.argtypes = [C.c_int, C.c_int, _ip, _ip, _ip, C.POINTER(C.c_ubyte), _ip, _ip, _ip]
+    lib.vpl_ba_debug_marg_Ab.argtypes = [vp, C.c_int, _dp, _dp]
+    lib.vpl_ba_debug_psd_factor.argtypes = [vp, C.c_int, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _ip, _ip, _dp, _dp]
     _hip = lib
     return lib
 
@@ -337,6 +340,31 @@ class Context:
     def debug_guards(self):
         """VPL_DEBUG_GUARDS=1 (set before the context is made): number of device arrays with a write behind their end"""
         return int(self.lib.vpl_ba_debug_guards(self.h))
+
+    def debug_psd_factor(self, form, threads, cases):
+        """vpl_ba_debug_psd_factor: one form of the pivoted Cholesky factorisation of csrc/ba_marg.h (PSD_WAVE16, PSD_WAVE48,
+        PSD_WAVE4, PSD_WORKGROUP) on `threads` threads over cases = [(A (n x n), b (n), abs_tol, rel_tol), ...], one launch.
+        -> list of (rank, perm (n), J0 (n x n), r0 (n)); J0 and r0 hold NaN where the kernel wrote nothing.  Returns the
+        VPL_E_* code instead when the call is refused."""
+        import numpy as np
+        N, M = len(cases), 80
+        ns = np.array([np.asarray(c[0]).shape[0] for c in cases], dtype=np.int32)
+        A = np.zeros((N, M * M)); b = np.zeros((N, M)); at = np.zeros(N); rt = np.zeros(N)
+        for i, (Ai, bi, ai, ri) in enumerate(cases):
+            n = int(ns[i])
+            if n <= M:
+                A[i, : n * n] = np.asarray(Ai, dtype=np.float64).reshape(-1)
+                b[i, :n] = bi
+            at[i], rt[i] = ai, ri
+        rank = np.zeros(N, dtype=np.int32); perm = np.zeros((N, M), dtype=np.int32)
+        J0 = np.zeros((N, M * M)); r0 = np.zeros((N, M))
+        ip = lambda a: a.ctypes.data_as(_ip)
+        rc = self.lib.vpl_ba_debug_psd_factor(self.h, form, threads, N, ip(ns), _p(A), _p(b), _p(at), _p(rt), ip(rank), ip(perm),
+                                              _p(J0), _p(r0))
+        if rc != 0:
+            return rc
+        return [(int(rank[i]), perm[i, : ns[i]].copy(), J0[i, : ns[i] * ns[i]].reshape(ns[i], ns[i]).copy(), r0[i, : ns[i]].copy())
+                for i in range(N)]
 
     def close(self):
         if self.h:

@@ -146,7 +146,8 @@ __global__ __launch_bounds__(128) void k_gauge(DevBatch B) { gauge_body(B, block
 // Returns the rank.  Needs blockDim.x >= 8 * ((n + 1) / 2).  rel_tol: pivots <= max(n eps, rel_tol) * max_i a_ii stop the
 // factorisation (the trailing block is then treated as zero).
 // Cholesky with diagonal pivoting of the PSD matrix A (LDS, full storage): P A P^T = L L^T, L = n x rank lower trapezoidal
-// left in A (upper part zeroed), perm[t] = original index of row t.  An optional right-hand side c (length n, permuted in
+// left in A (upper part zeroed), perm[t] = original index of row t (positions rank..n-1: the indices that never were pivots,
+// ascending).  An optional right-hand side c (length n, permuted in
 // step) rides along: on exit c[k] = y_k for k < rank, where L(0:rank,0:rank) y = (P c)(0:rank).
 // Stops at the first pivot <= max(abs_tol, max(n eps, rel_tol) * max_i a_ii); the trailing block is then treated as zero.
 __device__ __forceinline__ int psd_pivoted_cholesky(double* A, int n, int ld, int* perm, double* red, int* iflag, double rel_tol,
@@ -216,6 +217,27 @@ __device__ __forceinline__ int psd_pivoted_cholesky(double* A, int n, int ld, in
     }
   }
   __syncthreads();
+  // positions rank..n-1: the indices that never were pivots, in ascending order as the one-wave versions leave them (the swaps
+  // leave them in any order).  Row t of L moves to row dst[t] = rank + the number of smaller indices among them: thread k
+  // carries column k over the tail of row k (upper part, not part of L, zeroed below).  Same L entries, same J0.
+  if (rank < n) {
+    int* dst = (int*)col;                       // (col is free: n ints in n doubles)
+    int pt = 0, dt = 0;
+    if (tid >= rank && tid < n) {
+      pt = perm[tid];
+      dt = rank;
+      for (int s = rank; s < n; ++s) dt += perm[s] < pt ? 1 : 0;
+    }
+    __syncthreads();
+    if (tid >= rank && tid < n) { dst[tid] = dt; perm[dt] = pt; }
+    __syncthreads();
+    for (int k = tid; k < rank; k += T)
+      for (int t = rank; t < n; ++t) A[k * ld + dst[t]] = A[t * ld + k];
+    __syncthreads();
+    for (int k = tid; k < rank; k += T)
+      for (int t = rank; t < n; ++t) A[t * ld + k] = A[k * ld + t];
+    __syncthreads();
+  }
   // columns rank..n-1 do not exist
   for (int it = tid; it < n * (n - rank); it += T) A[(it / (n - rank)) * ld + rank + it % (n - rank)] = 0.0;
   __syncthreads();
@@ -563,6 +585,23 @@ __host__ __device__ inline MargLayout marg_layout(int n, bool small = false) {
   while (L.mtrows > 32 && (size_t)(fixed + L.mtrows * 74) * sizeof(double) > (small ? MARG_LDS_SMALL : MARG_LDS_BIG)) L.mtrows -= 32;
   L.total = fixed + L.mtrows * 74;
   return L;
+}
+
+// The prior out of the factor the routines above leave in LDS (G: L, n x rank lower trapezoidal, row stride ldm; bv: y; perm):
+// J0 = L^T P^T, i.e. J0[k][perm[t]] = L[t][k], and r0 = y, rows rank..n-1 zero.  k_marg and the test kernel k_psd_factor share it.
+template <int T>
+__device__ __forceinline__ void marg_write_prior(double* J0, double* r0, const double* G, const double* bv, const int* perm,
+                                                 const int n, const int ldm, const int rank) {
+  const int tid = threadIdx.x;
+  // (the block is cleared first: the loop below covers it only if perm is a permutation, and a column it leaves out must not
+  //  keep the prior of the batch the context solved before -- DESIGN.md section 6, the open item of round 4)
+  for (int it = tid; it < n * n; it += T) J0[it] = 0.0;
+  __syncthreads();
+  for (int it = tid; it < n * n; it += T) {
+    const int k = it / n, t = it % n;   // J0[k][perm[t]] = L[t][k]
+    J0[k * n + perm[t]] = (k < rank && t >= k) ? G[t * ldm + k] : 0.0;
+  }
+  for (int k = tid; k < n; k += T) r0[k] = k < rank ? bv[k] : 0.0;
 }
 
 template <int T>
@@ -933,17 +972,7 @@ __device__ __forceinline__ void marg_body(const DevBatch& B, const int w, double
     if (rank < 0) rank = psd_pivoted_cholesky(G, n, ldm, perm, red, s_flag, kMargNoiseRel, kMargEps, bv, lam);
   } else rank = psd_pivoted_cholesky(G, n, ldm, perm, red, s_flag, kMargNoiseRel, kMargEps, bv, lam);
   VPL_STAMP(B, w, 36);
-  double* J0 = B.mg_J0 + (size_t)w * MAXKEEP * MAXKEEP;
-  double* r0 = B.mg_r0 + (size_t)w * MAXKEEP;
-  // (the block is cleared first: the loop below covers it only if perm is a permutation, and a column it leaves out must not
-  //  keep the prior of the batch the context solved before -- DESIGN.md section 6, the open item of round 4)
-  for (int it = tid; it < n * n; it += T) J0[it] = 0.0;
-  __syncthreads();
-  for (int it = tid; it < n * n; it += T) {
-    const int k = it / n, t = it % n;   // J0[k][perm[t]] = L[t][k]
-    J0[k * n + perm[t]] = (k < rank && t >= k) ? G[t * ldm + k] : 0.0;
-  }
-  for (int k = tid; k < n; k += T) r0[k] = k < rank ? bv[k] : 0.0;
+  marg_write_prior<T>(B.mg_J0 + (size_t)w * MAXKEEP * MAXKEEP, B.mg_r0 + (size_t)w * MAXKEEP, G, bv, perm, n, ldm, rank);
   // x0 of the kept blocks: the linearisation point (preMarginalize copies, :110-129)
   if (tid < nb) {
     const int kind = B.mg_kind[(size_t)w * MAXPB + tid];
@@ -959,6 +988,51 @@ template <int T>
 __global__ __launch_bounds__(T) void k_marg(DevBatch B) {
   extern __shared__ double sm[];
   marg_body<T>(B, blockIdx.x, sm);
+}
+
+// Test kernel of vpl_ba_debug_psd_factor: every form of the pivoted Cholesky factorisation on matrices the caller supplies, one
+// work-group per case, through k_marg's own write-out and in its geometry (row stride n | 1, the scratch the routines ask for,
+// the iflag / phase words).  form: 0 wave<16>, 1 wave<48>, 2 wave4<19, 4> (512 threads only), 3 the work-group version; the host
+// refuses every other pairing of form, thread count and n.  A, J0: [case][MAXKEEP^2] holding n x n; b, r0, perm_out: [case][MAXKEEP].
+// perm starts as zeros (in range: a store that does not land cannot send the write-out outside J0), J0 and r0 arrive filled with
+// NaN from the host.  rank -1: wave4 gave up a wait; nothing else is written for that case.
+// G | Lo (n x ld + NMAX + 24, NMAX <= MAXKEEP) | bv | col | red (24) | perm
+__host__ __device__ inline int psd_test_lds_doubles(int n) {
+  const int nn = n < 2 ? 2 : n, ld = nn | 1;
+  return 2 * nn * ld + MAXKEEP + 24 + 2 * MAXKEEP + 24 + MAXKEEP / 2;
+}
+template <int T>
+__global__ __launch_bounds__(T) void k_psd_factor(const int form, const int* __restrict__ ns, const double* __restrict__ As,
+                                                  const double* __restrict__ bs, const double* __restrict__ abs_tols,
+                                                  const double* __restrict__ rel_tols, int* __restrict__ ranks,
+                                                  int* __restrict__ perm_out, double* __restrict__ J0s, double* __restrict__ r0s) {
+  extern __shared__ double sm[];
+  __shared__ int s_flag[4], s_phase[4];
+  const int tid = threadIdx.x, cs = blockIdx.x;
+  const int n = ns[cs];
+  const int nn = n < 2 ? 2 : n, ld = nn | 1;   // marg_layout's ldm
+  double* G = sm;
+  double* Lo = G + nn * ld;
+  double* bv = Lo + nn * ld + MAXKEEP + 24;
+  double* col = bv + MAXKEEP;
+  double* red = col + MAXKEEP;
+  int* perm = (int*)(red + 24);
+  const double* A = As + (size_t)cs * MAXKEEP * MAXKEEP;
+  for (int it = tid; it < n * n; it += T) G[(it / n) * ld + it % n] = A[it];
+  for (int i = tid; i < MAXKEEP; i += T) { bv[i] = i < n ? bs[(size_t)cs * MAXKEEP + i] : 0.0; perm[i] = 0; }
+  __syncthreads();
+  const double at = abs_tols[cs], rt = rel_tols[cs];
+  int rank;
+  if (form == 0) rank = psd_pivoted_cholesky_wave<16>(G, n, ld, perm, s_flag, rt, at, bv, Lo);
+  else if (form == 1) rank = psd_pivoted_cholesky_wave<48>(G, n, ld, perm, s_flag, rt, at, bv, Lo);
+  else if (form == 2) {
+    if constexpr (T >= 512) rank = psd_pivoted_cholesky_wave4<19, 4>(G, n, ld, perm, s_flag, rt, at, bv, Lo, s_phase);
+    else rank = -1;
+  } else rank = psd_pivoted_cholesky(G, n, ld, perm, red, s_flag, rt, at, bv, col);
+  if (tid == 0) ranks[cs] = rank;
+  if (rank < 0) return;   // (work-group uniform)
+  for (int i = tid; i < n; i += T) perm_out[(size_t)cs * MAXKEEP + i] = perm[i];
+  marg_write_prior<T>(J0s + (size_t)cs * MAXKEEP * MAXKEEP, r0s + (size_t)cs * MAXKEEP, G, bv, perm, n, ld, rank);
 }
 
 // Prior handoff on the device (vpl_ba_upload_chained): the prior the previous solve's marginalisation left in mg_* becomes the

@@ -1052,6 +1052,57 @@ int vpl_ba_debug_marg_Ab(vpl_ctx* c, int w, double* A, double* b) {
   return n;
 }
 
+// Debug/test access to the pivoted Cholesky factorisations of ba_marg.h on caller-supplied matrices (k_psd_factor): n_cases
+// work-groups in one launch.  form 0: psd_pivoted_cholesky_wave<16> (256 threads, n <= 16); 1: _wave<48> (256 or 512, n <= 48);
+// 2: _wave4<19, 4> (512, n <= 76: on fewer than eight waves it would wait out its poll limit); 3: the work-group version (256 or
+// 512, n <= 80).  Any other pairing: VPL_E_INVALID, nothing is launched.  A, J0: [case][80 * 80] holding n x n row-major; b, r0,
+// perm: [case][80].  J0 and r0 are filled with NaN (all bits set) before the launch: what the kernel does not write stays visible.
+// rank[case] = -1: wave4 gave up a wait (nothing else written for that case).
+int vpl_ba_debug_psd_factor(vpl_ctx* c, int form, int threads, int n_cases, const int* n, const double* A, const double* b,
+                            const double* abs_tol, const double* rel_tol, int* rank, int* perm, double* J0, double* r0) {
+  if (!c || n_cases < 1 || !n || !A || !b || !abs_tol || !rel_tol || !rank || !perm || !J0 || !r0) return VPL_E_INVALID;
+  const int nlim = form == 0 ? 16 : form == 1 ? 48 : form == 2 ? 76 : form == 3 ? MAXKEEP : 0;
+  const bool pairing = (form == 0 && threads == 256) || (form == 2 && threads == 512) ||
+                       ((form == 1 || form == 3) && (threads == 256 || threads == 512));
+  if (!pairing) return fail(c, VPL_E_INVALID, "debug_psd_factor: this form does not run on this many threads");
+  int nmax = 0;
+  for (int i = 0; i < n_cases; ++i) {
+    if (n[i] < 1 || n[i] > nlim) return fail(c, VPL_E_INVALID, "debug_psd_factor: n outside the form's range");
+    nmax = std::max(nmax, n[i]);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t N = (size_t)n_cases, M2 = (size_t)MAXKEEP * MAXKEEP;
+  DevBuf dn, dA, db, dat, drt, drank, dperm, dJ, dr;
+  HIPCHK(c, dn.alloc(N * 4)); HIPCHK(c, dA.alloc(N * M2 * 8)); HIPCHK(c, db.alloc(N * MAXKEEP * 8));
+  HIPCHK(c, dat.alloc(N * 8)); HIPCHK(c, drt.alloc(N * 8)); HIPCHK(c, drank.alloc(N * 4)); HIPCHK(c, dperm.alloc(N * MAXKEEP * 4));
+  HIPCHK(c, dJ.alloc(N * M2 * 8)); HIPCHK(c, dr.alloc(N * MAXKEEP * 8));
+  HIPCHK(c, hipMemcpyAsync(dn.p, n, N * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(dA.p, A, N * M2 * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(db.p, b, N * MAXKEEP * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(dat.p, abs_tol, N * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(drt.p, rel_tol, N * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(drank.p, 0xff, N * 4, c->stream));
+  HIPCHK(c, hipMemsetAsync(dperm.p, 0xff, N * MAXKEEP * 4, c->stream));
+  HIPCHK(c, hipMemsetAsync(dJ.p, 0xff, N * M2 * 8, c->stream));
+  HIPCHK(c, hipMemsetAsync(dr.p, 0xff, N * MAXKEEP * 8, c->stream));
+  const size_t smem = (size_t)psd_test_lds_doubles(nmax) * sizeof(double);
+  const void* kern = threads == 256 ? (const void*)k_psd_factor<256> : (const void*)k_psd_factor<512>;
+  HIPCHK(c, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, psd_test_lds_doubles(MAXKEEP) * (int)sizeof(double)));
+  if (threads == 256)
+    hipLaunchKernelGGL(k_psd_factor<256>, dim3(n_cases), dim3(256), smem, c->stream, form, (const int*)dn.p, dA.d(), db.d(), dat.d(),
+                       drt.d(), (int*)drank.p, (int*)dperm.p, dJ.d(), dr.d());
+  else
+    hipLaunchKernelGGL(k_psd_factor<512>, dim3(n_cases), dim3(512), smem, c->stream, form, (const int*)dn.p, dA.d(), db.d(), dat.d(),
+                       drt.d(), (int*)drank.p, (int*)dperm.p, dJ.d(), dr.d());
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(rank, drank.p, N * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(perm, dperm.p, N * MAXKEEP * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(J0, dJ.p, N * M2 * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(r0, dr.p, N * MAXKEEP * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return VPL_OK;
+}
+
 // Debug aid of the randomised sweeps (tools/fuzz_*.py with VPL_DEBUG_GUARDS=1 in the environment when the context is made): the
 // 64 bytes behind every device array then hold 0xA5; returns how many arrays have had theirs written to (a kernel ran past the
 // end of an array), the first one named in vpl_last_error by its allocation index and size.
