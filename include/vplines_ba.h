@@ -492,7 +492,8 @@ void vpl_odo_default_keyframe_rule(vpl_odo_keyframe_rule* rule); /* 10.0 / 460.0
 #define VPL_ODO_DECISION_RECORD_BYTES 24
 /* Allowed whenever the session is not between vpl_odo_solve and vpl_odo_advance (VPL_E_INVALID there, and for a NULL or NaN
  * threshold).  Sequences that hold a window get their decision computed in this call.  A second call replaces the thresholds and
- * recomputes the decisions.  The first call grows the session's inbox by the list through the context's guarded allocator. */
+ * recomputes the decisions.  The first call replaces the session's inbox by one with room for the list (the context's guarded
+ * allocator; the smaller one is freed in the same call). */
 int vpl_odo_enable_keyframe_rule(vpl_odo* odo, const vpl_odo_keyframe_rule* rule);
 
 #define VPL_FAIL_ACC_BIAS 1     /* |Ba| > max_acc_bias          (estimator.cpp:909) */

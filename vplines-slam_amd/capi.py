@@ -312,6 +312,7 @@ def load_hip_library():
     lib.vpl_failure_detection.argtypes = [C.POINTER(FailureLimits), _dp, _dp, _dp]
     lib.vpl_odo_debug_parallax_list.argtypes = [C.c_int, C.c_int, _ip, _ip, _ip, C.POINTER(C.c_ubyte), _ip, _ip, _ip]
     lib.vpl_ba_debug_marg_Ab.argtypes = [vp, C.c_int, _dp, _dp]
+    lib.vpl_ba_debug_allocs.argtypes = [vp, _llp, _llp]
     lib.vpl_ba_debug_psd_factor.argtypes = [vp, C.c_int, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _ip, _ip, _dp, _dp]
     _hip = lib
     return lib
@@ -340,6 +341,13 @@ class Context:
     def debug_guards(self):
         """VPL_DEBUG_GUARDS=1 (set before the context is made): number of device arrays with a write behind their end"""
         return int(self.lib.vpl_ba_debug_guards(self.h))
+
+    def debug_allocs(self):
+        """(arrays in the context's allocation record, their payload bytes): the context's own and those of the session it lends
+        itself to"""
+        n, b = C.c_longlong(0), C.c_longlong(0)
+        self._check(self.lib.vpl_ba_debug_allocs(self.h, C.byref(n), C.byref(b)), "vpl_ba_debug_allocs")
+        return int(n.value), int(b.value)
 
     def debug_psd_factor(self, form, threads, cases):
         """vpl_ba_debug_psd_factor: one form of the pivoted Cholesky factorisation of csrc/ba_marg.h (PSD_WAVE16, PSD_WAVE48,

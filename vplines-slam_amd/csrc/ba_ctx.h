@@ -15,8 +15,7 @@ struct vpl_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
   DevBatch B;
-  std::vector<void*> allocs;
-  std::vector<size_t> alloc_bytes;   // payload of allocs[i]; 64 pad bytes follow (VPL_DEBUG_GUARDS=1: filled with 0xA5, vpl_ba_debug_guards)
+  std::vector<DevAlloc> allocs;      // host_common.h: the context's own arrays (owner null), then those of the session that borrows it
   bool guards = false;
   std::string err;
   // ---- capacities

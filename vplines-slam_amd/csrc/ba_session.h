@@ -21,6 +21,14 @@ struct OdoSeq {
   int failure = 0;                 // VPL_FAIL_* of the last solve, default limits
 };
 
+// What vpl_odo_solve's last copy left in h_out behind the results, for vpl_odo_advance to read: offsets in ints of the three
+// sections -- one flag per solved point | 2 + 3 * (blocks) ints of prior table per marginalised sequence | one flag per solved
+// line (with remove_line_outliers) -- and how many points and lines each sequence solved
+struct OdoOutbox {
+  size_t point_flags = 0, prior_tabs = 0, line_flags = 0, end = 0;
+  std::vector<int> nP, nL;
+};
+
 struct vpl_odo {
   vpl_ctx* c = nullptr;
   int nS = 0, line_min_obs = 0, maxPT = 0, maxLT = 0;
@@ -31,17 +39,14 @@ struct vpl_odo {
   OdoPrior prior;
   int *d_psrc = nullptr, *d_lsrc = nullptr, *d_has = nullptr, *d_marg = nullptr;
   char *d_in = nullptr, *h_in = nullptr, *d_out = nullptr, *h_out = nullptr;   // new frames + slide tables in | results + flags out (h_*: pinned)
-  size_t in_cap = 0, out_cap = 0;
-  size_t alloc0 = 0, alloc1 = 0;   // the session's arrays in the context's allocation record
-  // vpl_odo_enable_imu: the IMU side (two, swapped with the stores), its arrays in the allocation record (behind alloc1)
+  size_t in_cap = 0, out_cap = 0;  // (every device array is recorded in the context with the session as its owner: vpl_odo_destroy)
+  // vpl_odo_enable_imu: the IMU side (two, swapped with the stores)
   bool imu = false;
   int max_samples = 0;
   OdoImu im[2] = {};
-  size_t imu_alloc0 = 0, imu_alloc1 = 0;
-  // vpl_odo_enable_keyframe_rule: thresholds; the grown inbox in the allocation record (its own range, behind alloc1)
+  // vpl_odo_enable_keyframe_rule: thresholds
   bool rule = false;
   vpl_odo_keyframe_rule kf_rule = {};
-  size_t rule_alloc0 = 0, rule_alloc1 = 0;
   std::vector<OdoSeq> seq;
   // the integer-only windows handed to the uploads, and what they point to
   std::vector<vpl_window> win;
@@ -53,17 +58,61 @@ struct vpl_odo {
   // between vpl_odo_solve and vpl_odo_advance: what the solve decided (its flags are in h_out) and on which batch
   bool solved = false;
   int flag = VPL_MARGIN_OLD, remove_line_outliers = 0;
-  std::vector<int> s_nP, s_nL;
+  OdoOutbox box;
   std::vector<std::vector<int>> s_lmap;
-  size_t s_totP = 0, s_totT = 0;
 };
 
-static size_t odo_result_bytes(int nS) { return (size_t)nS * sizeof(vpl_odo_result); }
+// the outbox: nS results, then ints (flags of the stages; after the solve's last copy the three sections of OdoOutbox)
+struct OdoOutViews {
+  vpl_odo_result *d_res, *h_res;
+  int *d_flags, *h_flags;
+};
+static OdoOutViews odo_out_views(const vpl_odo* o) {
+  const size_t res = (size_t)o->nS * sizeof(vpl_odo_result);
+  return OdoOutViews{reinterpret_cast<vpl_odo_result*>(o->d_out), reinterpret_cast<vpl_odo_result*>(o->h_out),
+                     reinterpret_cast<int*>(o->d_out + res), reinterpret_cast<int*>(o->h_out + res)};
+}
 
-static int odo_alloc_store(vpl_ctx* c, OdoStore& S, size_t nS, int maxPT, int maxLT) {
+// Bytes of the inbox, the one place that knows them.  Per sequence: the doubles of a new frame -- pose + speed/bias +
+// pre-integration or, when they are more, max_samples rows of 7, then one observation per track -- and the ints of the tables:
+// header and two counts, one entry per observation and per track (the slide's moves), with the keyframe rule its header and one
+// entry per point track.  odo_check_next bounds a frame's observations and samples by the same capacities.
+static size_t odo_inbox_bytes(size_t nS, size_t maxPT, size_t maxLT, size_t max_samples, bool rule) {
+  const size_t head = std::max<size_t>(16 + ODO_RAW_PRE_D, 7 * max_samples);
+  return nS * (8 * (head + 3 * maxPT + 8 * maxLT) + 4 * (ODO_HDR + 2 + 2 * (maxPT + maxLT)) + (rule ? 4 * (ODO_PAR_HDR + maxPT) : 0)) + 64;
+}
+
+// The inbox for max_samples and the rule on or off: a new device and a new pinned buffer are swapped in and both old ones freed
+// at once; nothing is done when the size stays.  On failure what was got is released and the session is as it was.  The stream
+// is idle (odo_quiesce).
+static int odo_resize_inbox(vpl_odo* o, int max_samples, bool rule) {
+  vpl_ctx* c = o->c;
+  const size_t cap = odo_inbox_bytes(o->nS, o->maxPT, o->maxLT, max_samples, rule);
+  if (cap == o->in_cap) return VPL_OK;
+  char *din = nullptr, *hin = nullptr;
+  hipError_t e = dalloc(c, &din, cap, o);
+  if (e == hipSuccess) e = hipHostMalloc((void**)&hin, cap, hipHostMallocDefault);
+  if (e != hipSuccess) { dfree(c, din); return VPL_E_HIP; }
+  dfree(c, o->d_in);
+  if (o->h_in) (void)hipHostFree(o->h_in);
+  o->d_in = din; o->h_in = hin; o->in_cap = cap;
+  return VPL_OK;
+}
+
+// every entry point off the keyframe path starts here: the device, the asynchronous call that is still pending, an idle stream
+static int odo_quiesce(vpl_odo* o) {
+  vpl_ctx* c = o->c;
+  HIPCHK(c, hipSetDevice(c->device));
+  { const int rs = settle(c); if (rs) return rs; }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return VPL_OK;
+}
+
+static int odo_alloc_store(vpl_odo* o, OdoStore& S, size_t nS, int maxPT, int maxLT) {
+  vpl_ctx* c = o->c;
   hipError_t e = hipSuccess;
   S.maxPT = maxPT; S.maxLT = maxLT;
-#define OAL(ptr, n) if (e == hipSuccess) e = dalloc(c, &S.ptr, (size_t)(n))
+#define OAL(ptr, n) if (e == hipSuccess) e = dalloc(c, &S.ptr, (size_t)(n), o)
   OAL(pobs, nS * maxPT * NF * 3); OAL(lobs, nS * maxLT * NF * 8); OAL(invd, nS * maxPT); OAL(plk, nS * maxLT * 6); OAL(tri, nS * maxLT);
   OAL(pose, nS * 77); OAL(sb, nS * 99); OAL(ex, nS * 7); OAL(pre, nS * NF);
 #undef OAL
@@ -179,36 +228,28 @@ int vpl_odo_create(vpl_odo** out, vpl_ctx* c, int n_seq, const vpl_ba_options* o
   if (max_point_tracks >= (1 << 20) || max_line_tracks >= (1 << 20)) return fail(c, VPL_E_CAPACITY, "odo: at most 2^20 - 1 tracks per sequence");
   if (c->odo) return fail(c, VPL_E_INVALID, "odo: the context already lends itself to a session");
   if (n_seq > c->maxW) return fail(c, VPL_E_CAPACITY, "odo: more sequences than the context's max_windows");
-  HIPCHK(c, hipSetDevice(c->device));
-  { const int rs = settle(c); if (rs) return rs; }
   vpl_odo* o = new vpl_odo();
   o->c = c; o->nS = n_seq; o->opt = *opt; o->init_depth = init_depth; o->line_min_obs = line_min_obs;
   o->maxPT = max_point_tracks; o->maxLT = max_line_tracks;
+  { const int rq = odo_quiesce(o); if (rq) { delete o; return rq; } }
   const size_t nS = n_seq;
-  o->alloc0 = c->allocs.size();
-  int rc = odo_alloc_store(c, o->st[0], nS, o->maxPT, o->maxLT);
-  if (!rc) rc = odo_alloc_store(c, o->st[1], nS, o->maxPT, o->maxLT);
+  int rc = odo_alloc_store(o, o->st[0], nS, o->maxPT, o->maxLT);
+  if (!rc) rc = odo_alloc_store(o, o->st[1], nS, o->maxPT, o->maxLT);
   hipError_t e = hipSuccess;
-  // per sequence in: pose + speed/bias + pre-integration + one observation per track, header, one table entry per observation
-  // and per track (the slide's moves), two counts; out: the result, three flags per track, the prior's block table
-  o->in_cap = nS * (8 * (16 + ODO_RAW_PRE_D + 3 * (size_t)o->maxPT + 8 * (size_t)o->maxLT) + 4 * (8 + 2 * ((size_t)o->maxPT + o->maxLT))) + 64;
-  o->out_cap = odo_result_bytes(n_seq) + nS * 4 * (3 * ((size_t)o->maxPT + o->maxLT) + 2 + 3 * MAXPB);
-  char *din = nullptr, *dout = nullptr;
+  // out, per sequence: the result, three flags per track, the prior's block table (in: odo_inbox_bytes)
+  o->out_cap = nS * (sizeof(vpl_odo_result) + 4 * (3 * ((size_t)o->maxPT + o->maxLT) + 2 + 3 * MAXPB));
   if (!rc) {
-    if (e == hipSuccess) e = dalloc(c, &o->prior.J0, nS * MAXKEEP * MAXKEEP);
-    if (e == hipSuccess) e = dalloc(c, &o->prior.r0, nS * MAXKEEP);
-    if (e == hipSuccess) e = dalloc(c, &o->prior.x0, nS * MAXPB * 9);
-    if (e == hipSuccess) e = dalloc(c, &o->d_psrc, nS * c->B.maxP);
-    if (e == hipSuccess) e = dalloc(c, &o->d_lsrc, nS * c->B.maxL);
-    if (e == hipSuccess) e = dalloc(c, &o->d_has, nS);
-    if (e == hipSuccess) e = dalloc(c, &o->d_marg, nS);
-    if (e == hipSuccess) e = dalloc(c, &din, o->in_cap);
-    if (e == hipSuccess) e = dalloc(c, &dout, o->out_cap);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&o->h_in, o->in_cap, hipHostMallocDefault);
+    if (e == hipSuccess) e = dalloc(c, &o->prior.J0, nS * MAXKEEP * MAXKEEP, o);
+    if (e == hipSuccess) e = dalloc(c, &o->prior.r0, nS * MAXKEEP, o);
+    if (e == hipSuccess) e = dalloc(c, &o->prior.x0, nS * MAXPB * 9, o);
+    if (e == hipSuccess) e = dalloc(c, &o->d_psrc, nS * c->B.maxP, o);
+    if (e == hipSuccess) e = dalloc(c, &o->d_lsrc, nS * c->B.maxL, o);
+    if (e == hipSuccess) e = dalloc(c, &o->d_has, nS, o);
+    if (e == hipSuccess) e = dalloc(c, &o->d_marg, nS, o);
+    if (e == hipSuccess) e = dalloc(c, &o->d_out, o->out_cap, o);
     if (e == hipSuccess) e = hipHostMalloc((void**)&o->h_out, o->out_cap, hipHostMallocDefault);
+    if (e == hipSuccess && odo_resize_inbox(o, 0, false)) e = hipErrorOutOfMemory;
   }
-  o->d_in = din; o->d_out = dout;
-  o->alloc1 = c->allocs.size();
   if (rc || e != hipSuccess) {
     c->odo = o;              // (so that destroy releases through the one path)
     vpl_odo_destroy(o);
@@ -227,25 +268,8 @@ int vpl_odo_create(vpl_odo** out, vpl_ctx* c, int n_seq, const vpl_ba_options* o
 void vpl_odo_destroy(vpl_odo* o) {
   if (!o) return;
   vpl_ctx* c = o->c;
-  // (teardown: a failure has nobody to be reported to)
-  (void)hipSetDevice(c->device);
-  (void)settle(c);
-  (void)hipStreamSynchronize(c->stream);
-  // (the ranges of the two enable calls lie behind the session's own, in the order of the calls: the later one is erased first)
-  size_t late[2][2] = {{o->imu_alloc0, o->imu_alloc1}, {o->rule_alloc0, o->rule_alloc1}};
-  if (late[0][0] < late[1][0]) std::swap(late[0], late[1]);
-  for (const auto& r : late) {
-    for (size_t i = r[0]; i < r[1] && i < c->allocs.size(); ++i) (void)hipFree(c->allocs[i]);
-    if (r[1] > r[0] && r[1] <= c->allocs.size()) {
-      c->allocs.erase(c->allocs.begin() + r[0], c->allocs.begin() + r[1]);
-      c->alloc_bytes.erase(c->alloc_bytes.begin() + r[0], c->alloc_bytes.begin() + r[1]);
-    }
-  }
-  for (size_t i = o->alloc0; i < o->alloc1 && i < c->allocs.size(); ++i) (void)hipFree(c->allocs[i]);
-  if (o->alloc1 <= c->allocs.size()) {
-    c->allocs.erase(c->allocs.begin() + o->alloc0, c->allocs.begin() + o->alloc1);
-    c->alloc_bytes.erase(c->alloc_bytes.begin() + o->alloc0, c->alloc_bytes.begin() + o->alloc1);
-  }
+  (void)odo_quiesce(o);   // (teardown: a failure has nobody to be reported to)
+  dfree_owner(c, o);
   if (o->h_in) (void)hipHostFree(o->h_in);
   if (o->h_out) (void)hipHostFree(o->h_out);
   if (c->odo == o) c->odo = nullptr;
@@ -269,9 +293,7 @@ int vpl_odo_set_window(vpl_odo* o, int seq, const double pose[][7], const double
     odo_add_frame(P, f, frames[f].n_points, frames[f].point_id, pd[f].data());
     odo_add_frame(L, f, frames[f].n_lines, frames[f].line_id, ld[f].data());
   }
-  HIPCHK(c, hipSetDevice(c->device));
-  { const int rs = settle(c); if (rs) return rs; }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  { const int rq = odo_quiesce(o); if (rq) return rq; }
   // an image of the sequence's part of the store, copied array by array (not on the per-keyframe path)
   const OdoStore& S = o->st[o->cur];
   const size_t nP = P.t.size(), nL = L.t.size();
@@ -373,10 +395,10 @@ int vpl_odo_solve(vpl_odo* o, const int* flags, vpl_odo_result* out) {
   hipStream_t s = c->stream;
   const dim3 grid(nS), blk(ODO_THREADS);
   const OdoStore S = o->st[o->cur];
-  vpl_odo_result* d_res = reinterpret_cast<vpl_odo_result*>(o->d_out);
-  int* d_flags = reinterpret_cast<int*>(o->d_out + odo_result_bytes(nS));
-  const int* h_flags = reinterpret_cast<const int*>(o->h_out + odo_result_bytes(nS));
-  const vpl_odo_result* h_res = reinterpret_cast<const vpl_odo_result*>(o->h_out);
+  const OdoOutViews V = odo_out_views(o);
+  vpl_odo_result* const d_res = V.d_res;
+  int* const d_flags = V.d_flags;
+  const int* const h_flags = V.h_flags;
   o->h2d_payload = o->h2d_table = o->d2h = 0;
   vpl_ba_options solve_opt = o->opt;
   solve_opt.marginalization_flag = flag;
@@ -396,7 +418,7 @@ int vpl_odo_solve(vpl_odo* o, const int* flags, vpl_odo_result* out) {
     if (any_lines) {
       size_t nl = 0;
       for (int w = 0; w < nS; ++w) nl += o->lstart[w].size();
-      HIPCHK(c, hipMemcpyAsync(o->h_out + odo_result_bytes(nS), d_flags, nl * 4, hipMemcpyDeviceToHost, s));
+      HIPCHK(c, hipMemcpyAsync(V.h_flags, d_flags, nl * 4, hipMemcpyDeviceToHost, s));
       o->d2h += (long long)nl * 4;
       HIPCHK(c, hipStreamSynchronize(s));
       size_t k = 0;
@@ -421,7 +443,7 @@ int vpl_odo_solve(vpl_odo* o, const int* flags, vpl_odo_result* out) {
     HIPCHK(c, hipGetLastError());
     size_t nl = 0;
     for (int w = 0; w < nS; ++w) nl += c->h_nL[w];
-    if (nl) HIPCHK(c, hipMemcpyAsync(o->h_out + odo_result_bytes(nS), d_flags, nl * 4, hipMemcpyDeviceToHost, s));
+    if (nl) HIPCHK(c, hipMemcpyAsync(V.h_flags, d_flags, nl * 4, hipMemcpyDeviceToHost, s));
     o->d2h += (long long)nl * 4;
     HIPCHK(c, hipStreamSynchronize(s));
     bool erased = false;
@@ -452,15 +474,20 @@ int vpl_odo_solve(vpl_odo* o, const int* flags, vpl_odo_result* out) {
   hipLaunchKernelGGL(k_odo_scatter_solve, grid, blk, 0, s, c->B, S, (const int*)o->d_psrc, (const int*)o->d_lsrc, d_flags, d_res,
                      o->prior, (const int*)o->d_marg);
   HIPCHK(c, hipGetLastError());
-  size_t totP = 0, totT = 0, totL = 0;
+  // what k_odo_scatter_solve wrote behind the results: the layout, here and nowhere else
+  OdoOutbox& box = o->box;
+  box.nP = c->h_nP; box.nL = c->h_nL;
   std::vector<int> marg(nS, 0);
-  for (int w = 0; w < nS; ++w) {
-    totP += c->h_nP[w]; totL += c->h_nL[w];
-    marg[w] = c->h_passthrough[w] < 0 ? 1 + c->h_mg_nb[w] : 0;
-    totT += marg[w] ? 2 + 3 * (marg[w] - 1) : 0;
-  }
   {
-    const size_t bytes = odo_result_bytes(nS) + 4 * (totP + totT + (solve_opt.remove_line_outliers ? totL : 0));
+    size_t totP = 0, totT = 0, totL = 0;
+    for (int w = 0; w < nS; ++w) {
+      totP += c->h_nP[w]; totL += c->h_nL[w];
+      marg[w] = c->h_passthrough[w] < 0 ? 1 + c->h_mg_nb[w] : 0;
+      totT += marg[w] ? 2 + 3 * (marg[w] - 1) : 0;
+    }
+    box.point_flags = 0; box.prior_tabs = totP; box.line_flags = totP + totT;
+    box.end = box.line_flags + (solve_opt.remove_line_outliers ? totL : 0);
+    const size_t bytes = (size_t)nS * sizeof(vpl_odo_result) + 4 * box.end;
     HIPCHK(c, hipMemcpyAsync(o->h_out, o->d_out, bytes, hipMemcpyDeviceToHost, s));
     o->d2h += (long long)bytes;
     HIPCHK(c, hipStreamSynchronize(s));
@@ -468,14 +495,13 @@ int vpl_odo_solve(vpl_odo* o, const int* flags, vpl_odo_result* out) {
   lap(2);
 
   // the results, and the prior the marginalisation left: its block table (the values stayed on the device)
-  o->s_nP = c->h_nP; o->s_nL = c->h_nL; o->s_lmap = c->h_lmap;
-  o->s_totP = totP; o->s_totT = totT;
+  o->s_lmap = c->h_lmap;
   o->flag = flag; o->remove_line_outliers = solve_opt.remove_line_outliers;
   size_t kT = 0, kL = 0;
   for (int w = 0; w < nS; ++w) {
     OdoSeq& q = o->seq[w];
     vpl_odo_result& r = out[w];
-    r = h_res[w];
+    r = V.h_res[w];
     if (o->lstart[w].empty()) std::memset(&r.line_report, 0, sizeof(r.line_report));
     r.line_report.n_lines_removed = lrem1[w];
     r.n_points_solved = c->h_nP[w];
@@ -487,11 +513,11 @@ int vpl_odo_solve(vpl_odo* o, const int* flags, vpl_odo_result* out) {
     std::memcpy(q.last_pose, r.pose[NF - 1], 56);
     int lrem2 = 0;
     if (solve_opt.remove_line_outliers)
-      for (int dl = 0; dl < c->h_nL[w]; ++dl) lrem2 += h_flags[totP + totT + kL + dl] ? 1 : 0;
+      for (int dl = 0; dl < c->h_nL[w]; ++dl) lrem2 += h_flags[box.line_flags + kL + dl] ? 1 : 0;
     kL += c->h_nL[w];
     r.report.n_lines_removed = lrem2;
     if (marg[w]) {
-      const int* pt = h_flags + totP + kT;
+      const int* pt = h_flags + box.prior_tabs + kT;
       kT += 2 + 3 * (marg[w] - 1);
       HostTab T;
       T.n = pt[0]; T.nb = pt[1];
@@ -522,8 +548,8 @@ static int odo_advance_impl(vpl_odo* o, const OdoNext& next, vpl_odo_result* out
   hipStream_t s = c->stream;
   const dim3 grid(nS), blk(ODO_THREADS);
   const OdoStore S = o->st[o->cur];
-  const int* h_flags = reinterpret_cast<const int*>(o->h_out + odo_result_bytes(nS));
-  const size_t totP = o->s_totP, totT = o->s_totT;
+  const int* const h_flags = odo_out_views(o).h_flags;
+  const OdoOutbox& box = o->box;
   // 4. the book: removeFailures and the solve's removeLineOutlier, the slide, the new frame -- and the tables that tell the
   // device what moved where; then ONE copy host -> device (the new frames' doubles, then the tables) and two launches
   double* pay = reinterpret_cast<double*>(o->h_in);
@@ -545,17 +571,17 @@ static int odo_advance_impl(vpl_odo* o, const OdoNext& next, vpl_odo_result* out
     vpl_odo_result& r = out ? out[w] : scratch;
     // removeFailures: solved points whose inverse depth is not > 0 (feature_manager.cpp:254-263)
     er.assign(q.P.t.size(), 0);
-    for (int p = 0; p < o->s_nP[w]; ++p, ++kP)
-      if (!h_flags[kP]) er[o->psrc[w][p]] = 1;
+    for (int p = 0; p < box.nP[w]; ++p, ++kP)
+      if (!h_flags[box.point_flags + kP]) er[o->psrc[w][p]] = 1;
     odo_erase_slide(q.P, er.data(), flag == VPL_MARGIN_SECOND_NEW, mv, nullptr);
     cnt[2 * w] = (int)mv.size();
     for (size_t j = 0; j < mv.size(); ++j) pmv[(size_t)w * o->maxPT + j] = odo_pack_move(mv[j]);
     // the lines the solve's removeLineOutlier erased
     er.assign(q.L.t.size(), 0);
     if (o->remove_line_outliers)
-      for (int dl = 0; dl < o->s_nL[w]; ++dl)
-        if (h_flags[totP + totT + kL + dl]) er[o->lsrc[w][o->s_lmap[w][dl]]] = 1;
-    kL += o->s_nL[w];
+      for (int dl = 0; dl < box.nL[w]; ++dl)
+        if (h_flags[box.line_flags + kL + dl]) er[o->lsrc[w][o->s_lmap[w][dl]]] = 1;
+    kL += box.nL[w];
     odo_erase_slide(q.L, er.data(), flag == VPL_MARGIN_SECOND_NEW, mv, nullptr);
     cnt[2 * w + 1] = (int)mv.size();
     for (size_t j = 0; j < mv.size(); ++j) lmv[(size_t)w * o->maxLT + j] = odo_pack_move(mv[j]);
@@ -584,7 +610,7 @@ static int odo_advance_impl(vpl_odo* o, const OdoNext& next, vpl_odo_result* out
   // the keyframe rule: what the book knows of the window with the new image in it rides behind the other tables
   size_t npar = 0;
   if (o->rule) npar = odo_write_parallax_tab(o, 0, nS, ent + nent, ntab + nent);
-  const size_t in_bytes = npay * 8 + (ntab + nent + npar) * 4;   // (within in_cap: odo_check_next bounds a frame's observations and samples)
+  const size_t in_bytes = npay * 8 + (ntab + nent + npar) * 4;   // (within in_cap: odo_inbox_bytes and odo_check_next go by the same capacities)
   HIPCHK(c, hipMemcpyAsync(o->d_in, o->h_in, in_bytes, hipMemcpyHostToDevice, s));
   o->h2d_payload = (long long)npay * 8;
   o->h2d_table += (long long)(ntab + nent + npar) * 4;
@@ -662,38 +688,26 @@ int vpl_odo_keyframe_imu(vpl_odo* o, const vpl_odo_imu_frame* next, const int* f
   return odo_keyframe_impl(o, n, flags, out, imu_out);
 }
 
-// The IMU side: allocated once, through the context's guarded allocator; the inbox grows when max_samples rows outweigh the
-// state + pre-integration they replace
+// The IMU side: allocated once, through the context's guarded allocator; the inbox is replaced by a larger one when max_samples
+// rows outweigh the state + pre-integration they replace.  A failure leaves nothing behind: a second call is a first call
 int vpl_odo_enable_imu(vpl_odo* o, int max_samples) {
   if (!o || max_samples < 1) return VPL_E_INVALID;
   vpl_ctx* c = o->c;
   if (o->imu) return fail(c, VPL_E_INVALID, "odo_enable_imu: already enabled");
   if (o->solved) return fail(c, VPL_E_INVALID, "odo_enable_imu: between vpl_odo_solve and vpl_odo_advance");
-  HIPCHK(c, hipSetDevice(c->device));
-  { const int rs = settle(c); if (rs) return rs; }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  { const int rq = odo_quiesce(o); if (rq) return rq; }
   const size_t nS = o->nS;
   hipError_t e = hipSuccess;
-  o->imu_alloc0 = c->allocs.size();
   for (OdoImu& m : o->im) {
     m.max = max_samples;
-    if (e == hipSuccess) e = dalloc(c, &m.smp, nS * max_samples * 7);
-    if (e == hipSuccess) e = dalloc(c, &m.lin, nS * 6);
-    if (e == hipSuccess) e = dalloc(c, &m.n, nS);
+    if (e == hipSuccess) e = dalloc(c, &m.smp, nS * max_samples * 7, o);
+    if (e == hipSuccess) e = dalloc(c, &m.lin, nS * 6, o);
+    if (e == hipSuccess) e = dalloc(c, &m.n, nS, o);
   }
-  const size_t head = 16 + ODO_RAW_PRE_D;
-  if (e == hipSuccess && 7 * (size_t)max_samples > head) {
-    const size_t cap = o->in_cap + nS * 8 * (7 * (size_t)max_samples - head);
-    char *din = nullptr, *hin = nullptr;
-    e = dalloc(c, &din, cap);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&hin, cap, hipHostMallocDefault);
-    if (e == hipSuccess) {   // (the smaller device inbox stays in the session's range until vpl_odo_destroy)
-      (void)hipHostFree(o->h_in);
-      o->d_in = din; o->h_in = hin; o->in_cap = cap;
-    }
+  if (e != hipSuccess || odo_resize_inbox(o, max_samples, o->rule)) {
+    for (OdoImu& m : o->im) { dfree(c, m.smp); dfree(c, m.lin); dfree(c, m.n); m = OdoImu{}; }
+    return fail(c, VPL_E_HIP, "odo_enable_imu: allocation failed");
   }
-  o->imu_alloc1 = c->allocs.size();
-  if (e != hipSuccess) return fail(c, VPL_E_HIP, "odo_enable_imu: allocation failed");
   o->max_samples = max_samples;
   o->imu = true;
   for (OdoSeq& q : o->seq) q.imu_set = false;
@@ -707,9 +721,7 @@ int vpl_odo_set_imu(vpl_odo* o, int seq, int n10, const double* samples10, const
   if (!o->seq[seq].set) return fail(c, VPL_E_INVALID, "odo_set_imu: the sequence has no window (vpl_odo_set_window)");
   if (n10 < 1) return fail(c, VPL_E_INVALID, "odo_set_imu: an interval needs at least one IMU sample");
   if (n10 > o->max_samples) return fail(c, VPL_E_CAPACITY, "odo_set_imu: more IMU samples than max_samples");
-  HIPCHK(c, hipSetDevice(c->device));
-  { const int rs = settle(c); if (rs) return rs; }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  { const int rq = odo_quiesce(o); if (rq) return rq; }
   const OdoImu& m = o->im[o->cur];
   double lin[6];
   std::memcpy(lin, acc0_10, 24); std::memcpy(lin + 3, gyr0_10, 24);
@@ -727,26 +739,16 @@ void vpl_odo_default_keyframe_rule(vpl_odo_keyframe_rule* r) {
   r->min_track_num = 20;
 }
 
-// The inbox was sized at create without the list; the first call replaces it by one with room for it (the smaller one stays in
-// the session's range until vpl_odo_destroy, like vpl_odo_enable_imu's)
+// The inbox was sized at create without the list; the first call replaces it by one with room for it (odo_resize_inbox: the
+// smaller one is freed at once)
 int vpl_odo_enable_keyframe_rule(vpl_odo* o, const vpl_odo_keyframe_rule* rule) {
   if (!o || !rule) return VPL_E_INVALID;
   vpl_ctx* c = o->c;
   if (!(rule->min_parallax == rule->min_parallax)) return fail(c, VPL_E_INVALID, "odo_enable_keyframe_rule: min_parallax is not a number");
   if (o->solved) return fail(c, VPL_E_INVALID, "odo_enable_keyframe_rule: between vpl_odo_solve and vpl_odo_advance");
-  HIPCHK(c, hipSetDevice(c->device));
-  { const int rs = settle(c); if (rs) return rs; }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  { const int rq = odo_quiesce(o); if (rq) return rq; }
   if (!o->rule) {
-    const size_t cap = o->in_cap + (size_t)o->nS * 4 * (ODO_PAR_HDR + (size_t)o->maxPT);
-    char *din = nullptr, *hin = nullptr;
-    o->rule_alloc0 = c->allocs.size();
-    hipError_t e = dalloc(c, &din, cap);
-    o->rule_alloc1 = c->allocs.size();
-    if (e == hipSuccess) e = hipHostMalloc((void**)&hin, cap, hipHostMallocDefault);
-    if (e != hipSuccess) return fail(c, VPL_E_HIP, "odo_enable_keyframe_rule: allocation failed");
-    (void)hipHostFree(o->h_in);
-    o->d_in = din; o->h_in = hin; o->in_cap = cap;
+    if (odo_resize_inbox(o, o->max_samples, true)) return fail(c, VPL_E_HIP, "odo_enable_keyframe_rule: allocation failed");
     o->rule = true;
   }
   o->kf_rule = *rule;

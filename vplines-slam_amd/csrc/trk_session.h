@@ -298,31 +298,32 @@ struct vpl_trk {
   char *d_in = nullptr, *d_out = nullptr;   // raw frames | seeds;  the records
   char *h_in = nullptr, *h_out = nullptr;   // pinned
   size_t in_bytes = 0, out_bytes = 0, seed_off = 0;
-  size_t alloc0 = 0, alloc1 = 0;            // the session's range of the context's allocation record
 };
 
-static int trk_alloc_store(vpl_fe_ctx* c, TrkStore& S, size_t nS, size_t ML) {
-  HIPCHK(c, dalloc(c, &S.kept, nS * ML));
-  HIPCHK(c, dalloc(c, &S.ids, nS * ML));
-  HIPCHK(c, dalloc(c, &S.tcnt, nS * ML));
-  HIPCHK(c, dalloc(c, &S.hdr, nS * TRK_HDR));
+// (every device array of the session is recorded in the context with the session as its owner: vpl_trk_destroy)
+static int trk_alloc_store(vpl_trk* t, TrkStore& S, size_t nS, size_t ML) {
+  vpl_fe_ctx* c = t->c;
+  HIPCHK(c, dalloc(c, &S.kept, nS * ML, t));
+  HIPCHK(c, dalloc(c, &S.ids, nS * ML, t));
+  HIPCHK(c, dalloc(c, &S.tcnt, nS * ML, t));
+  HIPCHK(c, dalloc(c, &S.hdr, nS * TRK_HDR, t));
   return VPL_OK;
 }
 
 static int trk_alloc(vpl_trk* t) {
   vpl_fe_ctx* c = t->c;
   const size_t nS = t->nS, ML = c->maxLines;
-  int rc = trk_alloc_store(c, t->st, nS, ML);
+  int rc = trk_alloc_store(t, t->st, nS, ML);
   if (rc) return rc;
-  rc = trk_alloc_store(c, t->nx, nS, ML);
+  rc = trk_alloc_store(t, t->nx, nS, ML);
   if (rc) return rc;
-  HIPCHK(c, dalloc(c, &t->d_keep, nS * ML));
-  HIPCHK(c, dalloc(c, &t->d_vert, nS * ML));
-  HIPCHK(c, dalloc(c, &t->d_take, nS));
-  HIPCHK(c, dalloc(c, &t->d_dbgMatch, nS * ML));
-  HIPCHK(c, dalloc(c, &t->d_dbgVp, nS * ML));
-  HIPCHK(c, dalloc(c, &t->d_in, t->in_bytes));
-  HIPCHK(c, dalloc(c, &t->d_out, t->out_bytes));
+  HIPCHK(c, dalloc(c, &t->d_keep, nS * ML, t));
+  HIPCHK(c, dalloc(c, &t->d_vert, nS * ML, t));
+  HIPCHK(c, dalloc(c, &t->d_take, nS, t));
+  HIPCHK(c, dalloc(c, &t->d_dbgMatch, nS * ML, t));
+  HIPCHK(c, dalloc(c, &t->d_dbgVp, nS * ML, t));
+  HIPCHK(c, dalloc(c, &t->d_in, t->in_bytes, t));
+  HIPCHK(c, dalloc(c, &t->d_out, t->out_bytes, t));
   HIPCHK(c, hipHostMalloc((void**)&t->h_in, t->in_bytes, hipHostMallocDefault));
   HIPCHK(c, hipHostMalloc((void**)&t->h_out, t->out_bytes, hipHostMallocDefault));
   return VPL_OK;
@@ -362,9 +363,7 @@ int vpl_trk_create(vpl_trk** out, vpl_fe_ctx* c, int n_seq, const vpl_trk_option
   t->seed_off = ((size_t)n_seq * PX + 15) & ~(size_t)15;
   t->in_bytes = t->seed_off + (size_t)n_seq * 4;
   t->out_bytes = (size_t)n_seq * trk_rec_bytes(c->maxLines);
-  t->alloc0 = c->allocs.size();
   rc = trk_alloc(t);
-  t->alloc1 = c->allocs.size();
   c->trk = t;
   if (rc) { vpl_trk_destroy(t); return rc; }
   *out = t;
@@ -377,11 +376,7 @@ void vpl_trk_destroy(vpl_trk* t) {
   // (teardown: a failure has nobody to be reported to)
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
-  for (size_t i = t->alloc0; i < t->alloc1 && i < c->allocs.size(); ++i) (void)hipFree(c->allocs[i]);
-  if (t->alloc1 <= c->allocs.size()) {
-    c->allocs.erase(c->allocs.begin() + t->alloc0, c->allocs.begin() + t->alloc1);
-    c->alloc_bytes.erase(c->alloc_bytes.begin() + t->alloc0, c->alloc_bytes.begin() + t->alloc1);
-  }
+  dfree_owner(c, t);   // (what the context allocated for itself while the session was open -- d_blur, a grown d_lut -- stays)
   if (t->h_in) (void)hipHostFree(t->h_in);
   if (t->h_out) (void)hipHostFree(t->h_out);
   if (c->trk == t) c->trk = nullptr;

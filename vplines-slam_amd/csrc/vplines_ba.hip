@@ -1107,6 +1107,8 @@ int vpl_ba_debug_psd_factor(vpl_ctx* c, int form, int threads, int n_cases, cons
 // 64 bytes behind every device array then hold 0xA5; returns how many arrays have had theirs written to (a kernel ran past the
 // end of an array), the first one named in vpl_last_error by its allocation index and size.
 int vpl_ba_debug_guards(vpl_ctx* c) { return debug_guards(c); }
+// Test access (not in the header): the arrays in the context's allocation record and their payload bytes
+int vpl_ba_debug_allocs(vpl_ctx* c, long long* n_arrays, long long* payload_bytes) { return debug_allocs(c, n_arrays, payload_bytes); }
 
 int vpl_ba_debug_stamps(vpl_ctx* c, int w, long long* out) {
   HIPCHK(c, hipMemcpy(out, c->B.dbg + (size_t)w * 64, 64 * 8, hipMemcpyDeviceToHost));

@@ -49,8 +49,7 @@ struct vpl_fe_ctx {
   int *d_vpNHyp = nullptr, *d_vpNAll = nullptr, *d_vpFirst = nullptr;
   uint32_t* d_vpSeed = nullptr;
   int vpN = 0;
-  std::vector<void*> allocs;
-  std::vector<size_t> alloc_bytes;   // payload of allocs[i]; 64 pad bytes follow (VPL_DEBUG_GUARDS=1: 0xA5, vpl_fe_debug_guards)
+  std::vector<DevAlloc> allocs;      // host_common.h: the context's own arrays (owner null, the lazy ones included) and the tracker session's
   bool guards = false;
   std::string err;
   bool timing = false;                                    // vpl_fe_enable_kernel_timing
@@ -225,6 +224,8 @@ const char* vpl_fe_last_error(const vpl_fe_ctx* c) { return c ? c->err.c_str() :
 // Debug aid of the randomised sweeps (VPL_DEBUG_GUARDS=1 when the context is made: the 64 bytes behind every device array hold
 // 0xA5): how many arrays have had theirs written to; the first is named in vpl_fe_last_error.
 int vpl_fe_debug_guards(vpl_fe_ctx* c) { return debug_guards(c); }
+// Test access (not in the header): the arrays in the context's allocation record and their payload bytes
+int vpl_fe_debug_allocs(vpl_fe_ctx* c, long long* n_arrays, long long* payload_bytes) { return debug_allocs(c, n_arrays, payload_bytes); }
 
 int vpl_edlines_upload(vpl_fe_ctx* c, int n, const uint8_t* images) {
   if (!c || !images || n < 1) return VPL_E_INVALID;

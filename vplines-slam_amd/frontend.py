@@ -149,6 +149,7 @@ def _bind(lib):
     lib.vpl_trk_frame.argtypes = [vp, C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(TrackerResult), ip, C.POINTER(C.c_double)]
     lib.vpl_trk_get_frame.argtypes = [vp, C.c_int, C.POINTER(C.c_uint8), C.POINTER(Line), ip, ip, ip, ip, ip]
     lib.vpl_trk_debug_ids.argtypes = [vp, C.c_int, fp, C.c_int, ip, ip, C.c_int, ip, C.c_int, C.c_int, ip, ip, ip, ip, ip, ip]
+    lib.vpl_fe_debug_allocs.argtypes = [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     _bound = True
 
 
@@ -168,6 +169,13 @@ class FrontendContext:
     def debug_guards(self):
         """VPL_DEBUG_GUARDS=1 (set before the context is made): number of device arrays with a write behind their end"""
         return int(self.lib.vpl_fe_debug_guards(self.h))
+
+    def debug_allocs(self):
+        """(arrays in the context's allocation record, their payload bytes): the context's own, the lazily made ones included,
+        and those of the tracker session it lends itself to"""
+        n, b = C.c_longlong(0), C.c_longlong(0)
+        self._check(self.lib.vpl_fe_debug_allocs(self.h, C.byref(n), C.byref(b)), "vpl_fe_debug_allocs")
+        return int(n.value), int(b.value)
 
     def close(self):
         if self.h and getattr(self, "_trk", None) is not None:
