@@ -180,6 +180,70 @@ int vpl_preintegrate_batch(vpl_ctx* ctx, int n, const int* offset, const int* ns
                            const double* lin_ba, const double* lin_bg, const vpl_ba_options* opt,
                            vpl_preintegration* out);
 
+/* ---- visual-inertial alignment  (replaces Estimator::visualInitialAlign, estimator.cpp:512-588, with VisualIMUAlignment =
+ *      solveGyroscopeBias + LinearAlignment + RefineGravity, initial/initial_aligment.cpp:3-207, and Utility::g2R,
+ *      utility.cpp:3-13) for n sequences in one call ------------------------------------------------------------------------ *
+ * The vision-only structure before it (relativePose, GlobalSFM::construct, the PnP of the non-key frames) stays with the
+ * caller, who hands in what it produced: ImageFrame::R and ImageFrame::T of every image frame, and the raw IMU samples between
+ * them.  On the device, per sequence:
+ *   1. the F - 1 image intervals are pre-integrated under (lin_ba, lin_bg), the arithmetic of vpl_preintegrate_batch;
+ *   2. solveGyroscopeBias: delta_bg from the 3 x 3 normal equations, summed in frame order; Bgs[i] += delta_bg for the 11 frames;
+ *   3. the image intervals are integrated again under (0, Bgs[0]), the ten window intervals -- window interval i spans the image
+ *      intervals key[i-1]+1 .. key[i] -- under (0, Bgs[i]): zero accelerometer bias, whatever bas holds, as the reference has it;
+ *   4. LinearAlignment (order 3F + 4), four rounds of RefineGravity (order 3F + 3), the state change and the rotation into the
+ *      gravity frame (k_init_align, one work-group per sequence).
+ * Kept as the reference has them: cov_inv is the identity; the scale column is divided by 100 and every system multiplied by
+ * 1000 before it is solved; RefineGravity zeroes A and b ONCE, before its four rounds, so round k solves what the rounds before
+ * left (times 1000) plus its own blocks; Vs[kv] = R[key[kv]] * x[3 kv .. 3 kv + 2] with kv counting KEY frames, which is another
+ * frame's velocity as soon as a non-key frame lies before it.  The solves are unpivoted LDL^T in float64.
+ * A sequence's result has the same bits wherever it sits in the batch and whatever else the batch holds. */
+#define VPL_INIT_MAX_FRAMES 40
+#define VPL_INIT_FAIL_GRAVITY 1        /* | |g| - g_norm | > 1.0 after LinearAlignment          (initial_aligment.cpp:184) */
+#define VPL_INIT_FAIL_SCALE 2          /* s < 0 after LinearAlignment                            (:184) */
+#define VPL_INIT_FAIL_REFINED_SCALE 4  /* s < 0 after RefineGravity                              (:193) */
+#define VPL_INIT_FAIL_NONFINITE 8      /* a NaN / inf in the solution or in the states it gives */
+typedef struct vpl_init_input {
+  int n_frames;            /* F = all_image_frame.size(), 11 <= F <= VPL_INIT_MAX_FRAMES */
+  const double* R;         /* [F][9] row-major ImageFrame::R = Q_i * RIC^T */
+  const double* T;         /* [F][3] ImageFrame::T, the camera position in the SfM frame */
+  const int* n_samples;    /* [F] samples of the interval that ENDS in image frame f; entry 0 unused */
+  const double* samples;   /* [sum][7] dt, ax, ay, az, gx, gy, gz of intervals 1 .. F-1 one after the other */
+  double acc0[3], gyr0[3]; /* the measurement before interval 1; a later interval starts from the last sample of the one before
+                              (the convention of vpl_odo_set_imu) */
+  const double* lin_ba;    /* [F][3] the bias under which image frame f's pre-integration stands; entry 0 unused */
+  const double* lin_bg;    /* [F][3] */
+  int key[VPL_NFRAMES];    /* image-frame index of window frame i: strictly increasing, key[0] == 0, key[10] == F - 1 */
+  double bas[VPL_NFRAMES][3], bgs[VPL_NFRAMES][3]; /* Bas / Bgs of the window before the alignment */
+  double tic[3];           /* TIC[0] */
+} vpl_init_input;
+typedef struct vpl_init_result {
+  int ok;                  /* 1: VisualIMUAlignment returned true and every result is finite */
+  int fail;                /* VPL_INIT_FAIL_* mask, 0 when ok */
+  double delta_bg[3];      /* applied by the reference before it knows whether the alignment fails: valid either way */
+  double g_linear[3];      /* LinearAlignment's gravity (x.segment<3>(n_state - 4)) and scale */
+  double s_linear;
+  double s;                /* the scale after RefineGravity (x.tail(1) / 100) */
+  double g_refined[3];     /* gravity after RefineGravity, SfM frame */
+  double g[3];             /* ... after the rotation: R0 * g_refined */
+  double vel[VPL_INIT_MAX_FRAMES][3]; /* x.segment<3>(3 f) of the last solve: image frame f's velocity in its own body frame */
+  double pose[VPL_NFRAMES][7];        /* Ps / Rs after the state change, the window's parameter-block layout */
+  double speed_bias[VPL_NFRAMES][9];  /* Vs, the input Bas, Bgs + delta_bg */
+} vpl_init_result;
+/* in [n], out [n].  window_preint: NULL or [n][VPL_NFRAMES], pre_integrations[1..10] after step 3 (entry 0 zeroed);
+ * image_preint: NULL or [n][VPL_INIT_MAX_FRAMES], the re-propagated image pre-integrations 1 .. F-1 (the other entries zeroed).
+ * A sequence that fails (ok = 0) has everything behind the failing stage zeroed; delta_bg, g_linear and s_linear are always set.
+ * Host in, host out: one host-to-device copy, the kernels, one copy back and one synchronisation.
+ * Refused before anything is launched -- VPL_E_INVALID: null arrays, F < 11, key not as described, an interval with
+ * n_samples < 1; VPL_E_CAPACITY: F > VPL_INIT_MAX_FRAMES, n > max_windows.  A non-finite input is not refused: the sequence
+ * comes back with ok = 0 and VPL_INIT_FAIL_NONFINITE. */
+int vpl_init_align_batch(vpl_ctx* ctx, int n, const vpl_init_input* in, const vpl_ba_options* opt, vpl_init_result* out,
+                         vpl_preintegration* window_preint, vpl_preintegration* image_preint);
+/* Host only, no device call: the pre-integration jobs of step 3 for one sequence as vpl_init_align_batch builds them --
+ * jobs[j][3] = (offset, nsamples, acc0_row) for j = 0 .. F-2 the image intervals 1 .. F-1 and j = F-1 .. F+8 the window
+ * intervals 1 .. 10; offset in samples; acc0_row: the sample row whose measurement starts the job (always offset - 1),
+ * -1 = the input's acc0 / gyr0.  jobs needs room for F + 9 rows.  Refusals as above. */
+int vpl_init_debug_jobs(int n_frames, const int* n_samples, const int* key, int* jobs);
+
 /* ---- single-factor batch evaluators ------------------------------------- *
  * Each replaces one CostFunction::Evaluate (signature
  *   bool Evaluate(double const* const* parameters, double* residuals, double** jacobians) const )
@@ -390,6 +454,24 @@ typedef struct vpl_odo_frame {   /* one image of one sequence, as processImage()
 int vpl_odo_set_window(vpl_odo* odo, int seq, const double pose[][7], const double speed_bias[][9], const double ex_pose[7],
                        const vpl_preintegration* preint, const vpl_odo_frame* frames);
 
+/* The session takes its first window from the visual-inertial alignment (vpl_init_align_batch above) instead of from
+ * vpl_odo_set_window: Estimator::visualInitialAlign (estimator.cpp:512-588) for every sequence of the session in one call, with
+ * the results staying on the device.  in [n_seq]: the alignment's input; ex_pose [n_seq][7]: para_Ex_Pose (its rotation is RIC, its
+ * translation should be in.tic); frames [n_seq][11]: the observations of the window's frames (n_*, *_id, *_obs only); out [n_seq].
+ *   - the observations enter the store with pose = (T_key, quat(R_key)), extrinsic = (0, qic) and every depth unset (clearDepth),
+ *     so that the session's point triangulation is triangulate(Ps, TIC_TMP = 0, RIC) at SfM scale (:540-545); no line is touched;
+ *   - the alignment runs (stages 1-4 of vpl_init_align_batch, the same bits);
+ *   - for a sequence with ok: states, the true extrinsic and pre_integrations[1..10] enter the store and every point the solve
+ *     selects is scaled, estimated_depth *= s -- a depth the 0.1 clamp set to init_depth too, as in the reference (:564-570).  The
+ *     sequence then holds a window: no prior, last_P = pose[9], its keyframe decision when the rule is on; in an IMU-enabled session
+ *     the samples of window interval 10 become slot 10's buffer (no vpl_odo_set_imu needed);
+ *   - a sequence without ok ends WITHOUT a window, whatever it held before.
+ * Refusals leave every sequence as it was: those of vpl_init_align_batch and of vpl_odo_set_window, between vpl_odo_solve and
+ * vpl_odo_advance (VPL_E_INVALID), the selected tracks beyond the context's capacities, window interval 10 longer than max_samples
+ * (VPL_E_CAPACITY).  Not on the per-keyframe path: it synchronises and allocates. */
+int vpl_odo_init(vpl_odo* odo, const vpl_init_input* in, const double (*ex_pose)[7], const vpl_odo_frame* frames,
+                 vpl_init_result* out);
+
 typedef struct vpl_odo_result {  /* per sequence */
   double pose[VPL_NFRAMES][7], speed_bias[VPL_NFRAMES][9], ex_pose[7]; /* after double2vector2, BEFORE the slide */
   vpl_solve_report line_report, report; /* onlyLineOpt's, the solve's */
@@ -535,6 +617,8 @@ int vpl_odo_keyframe_imu_auto(vpl_odo* odo, const vpl_odo_imu_frame* next, vpl_o
 /* What a caller may want to look at; none of it is needed to keep going.  Arrays may be NULL (not wanted); the track arrays
  * need room for max_*_tracks entries.  Tracks come in the feature manager's order. */
 int vpl_odo_get_prior(vpl_odo* odo, int seq, vpl_prior* out);   /* n = 0: no prior yet */
+/* the window's states as the store holds them: pose [11][7], speed_bias [11][9], ex_pose [7]; VPL_E_INVALID without a window */
+int vpl_odo_get_states(vpl_odo* odo, int seq, double (*pose)[7], double (*speed_bias)[9], double* ex_pose);
 int vpl_odo_get_tracks(vpl_odo* odo, int seq, int* n_points, int* point_id, int* point_start, int* point_nobs, double* inv_depth,
                        int* n_lines, int* line_id, int* line_start, int* line_nobs, int* line_triangulated, double* line_plk);
 /* Host <-> device traffic of the last keyframe: the new frames' doubles | the integer tables (layout tables of the stages, track

@@ -8,7 +8,11 @@ keyframes per second.  Every C call ends in a stream synchronise, so the host cl
 propagation on the host (not timed: a C++ caller's costs microseconds), vpl_odo_advance; the three C calls are summed.
 --mode rule: what the keyframe rule (vpl_odo_enable_keyframe_rule: one more launch and a 24-byte record per image) costs -- the plain
 sequence through a rule-enabled session and through a plain one, alternating, --repeat times (default there: 3), with explicit
-MARGIN_OLD flags in both so that the two do the same work; medians over keyframes 4..31 of "slide + new frame" and of the keyframe."""
+MARGIN_OLD flags in both so that the two do the same work; medians over keyframes 4..31 of "slide + new frame" and of the keyframe.
+--mode init-align: vpl_init_align_batch (the visual-inertial alignment, once per start of a sequence) for 1 and for --batch
+sequences of 14 and of 40 image frames, pre-integrations read back; median, min and max of 7 calls after one warm-up call.
+--mode init: vpl_odo_init (the session takes its first window from the alignment: observations up, alignment, triangulation, scale)
+for sessions of 1 and of --batch sequences of 14 image frames; the same statistics."""
 import argparse
 import os
 import sys
@@ -89,13 +93,60 @@ def run_imu(M, n_keyframes, halves):
     return acc
 
 
+def run_init_align(n, F):
+    """seconds per vpl_init_align_batch call over n copies of the F-frame input of tests/test_gpu_init_align.py"""
+    import time
+    import init_align_inputs as A
+    opt = v.default_options()
+    q = A.device_input(14, A.KEY14) if F == 14 else A.device_input(40, A.KEY40)
+    ctx = v.Context(device=0, max_windows=n, max_points=8, max_point_obs=64, max_lines=8, max_line_obs=64)
+    ts = []
+    for k in range(8):
+        t0 = time.perf_counter()
+        res, _, _ = ctx.init_align([q] * n, opt)
+        ts.append(time.perf_counter() - t0)
+        assert all(r.ok for r in res)
+    ctx.close()
+    return ts[1:]
+
+
+def run_init(n):
+    """seconds per vpl_odo_init call of a session of n sequences, each the 14-frame input with its observations"""
+    import init_align_inputs as A
+    opt = v.default_options()
+    q = A.device_input(14, A.KEY14)
+    M = A.measurements(14, 77)
+    frames = [S._obs_frame(M, F) for F in A.KEY14]
+    ctx = S._ctxn(n)
+    ses = v.Session(ctx, n_seq=n, opt=opt, init_depth=5.0, line_min_obs=T.LINE_MIN_OBS, max_point_tracks=S.MAX_PT, max_line_tracks=S.MAX_LT)
+    ts = []
+    for k in range(8):
+        res = ses.init([q] * n, [M.ex] * n, [frames] * n)
+        ts.append(ses.last_call_s)
+        assert all(r.ok for r in res)
+    ses.close()
+    ctx.close()
+    return ts[1:]
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--batch-keyframes", type=int, default=12)
-    ap.add_argument("--mode", choices=("plain", "imu", "halves", "rule"), default="plain")
+    ap.add_argument("--mode", choices=("plain", "imu", "halves", "rule", "init-align", "init"), default="plain")
     ap.add_argument("--repeat", type=int, default=1, help="imu / halves: run the sequence this many times, the two modes alternating")
     a = ap.parse_args()
+    if a.mode == "init":
+        for n in (1, a.batch):
+            ts = np.array(run_init(n)) * 1e3
+            print("odo_init F=14 n_seq=%d: median %.3f ms (min %.3f, max %.3f) per call" % (n, np.median(ts), ts.min(), ts.max()))
+        sys.exit(0)
+    if a.mode == "init-align":
+        for F in (14, 40):
+            for n in (1, a.batch):
+                ts = np.array(run_init_align(n, F)) * 1e3
+                print("init_align F=%d n_seq=%d: median %.3f ms (min %.3f, max %.3f) per call" % (F, n, np.median(ts), ts.min(), ts.max()))
+        sys.exit(0)
     if a.mode == "rule":
         for r in range(a.repeat if a.repeat > 1 else 3):
             for name, rule in (("rule", True), ("plain", False)):

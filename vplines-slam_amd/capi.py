@@ -61,6 +61,72 @@ class Prior(C.Structure):
         return np.ctypeslib.as_array(self.r0)[: self.n].copy()
 
 
+INIT_MAX_FRAMES = 40
+INIT_FAIL_GRAVITY, INIT_FAIL_SCALE, INIT_FAIL_REFINED_SCALE, INIT_FAIL_NONFINITE = 1, 2, 4, 8
+
+
+class CInitInput(C.Structure):   # vpl_init_input
+    _fields_ = [("n_frames", C.c_int), ("R", _dp), ("T", _dp), ("n_samples", _ip), ("samples", _dp),
+                ("acc0", C.c_double * 3), ("gyr0", C.c_double * 3), ("lin_ba", _dp), ("lin_bg", _dp),
+                ("key", C.c_int * NF), ("bas", (C.c_double * 3) * NF), ("bgs", (C.c_double * 3) * NF),
+                ("tic", C.c_double * 3)]
+
+
+class InitResult(C.Structure):   # vpl_init_result
+    _fields_ = [("ok", C.c_int), ("fail", C.c_int), ("delta_bg", C.c_double * 3), ("g_linear", C.c_double * 3),
+                ("s_linear", C.c_double), ("s", C.c_double), ("g_refined", C.c_double * 3), ("g", C.c_double * 3),
+                ("vel", (C.c_double * 3) * INIT_MAX_FRAMES), ("pose", (C.c_double * 7) * NF),
+                ("speed_bias", (C.c_double * 9) * NF)]
+
+    def arrays(self):
+        """the array members as numpy copies"""
+        return {f: np.array(getattr(self, f)) for f in ("delta_bg", "g_linear", "g_refined", "g", "vel", "pose", "speed_bias")}
+
+
+class InitInput:
+    """numpy-backed owner of one vpl_init_input: what the caller's SfM and IMU buffers hand to the alignment.  R [F,3,3], T [F,3]
+    = ImageFrame::R / T; n_samples [F] (entry 0 unused), samples [sum,7] = (dt, acc, gyr) of intervals 1..F-1; acc0 / gyr0 the
+    measurement before interval 1; lin_ba / lin_bg [F,3]; key [11]; bas / bgs [11,3]; tic [3]."""
+
+    def __init__(self, R, T, n_samples, samples, acc0, gyr0, lin_ba, lin_bg, key, bas, bgs, tic):
+        self.R = _arr(R, np.float64).reshape(-1, 9).copy()
+        self.n_frames = self.R.shape[0]
+        self.T = _arr(T, np.float64).reshape(-1, 3).copy()
+        self.n_samples = _arr(n_samples, np.int32).copy()
+        self.samples = _arr(samples, np.float64).reshape(-1, 7).copy()
+        self.acc0, self.gyr0 = _arr(acc0, np.float64).copy(), _arr(gyr0, np.float64).copy()
+        self.lin_ba = _arr(lin_ba, np.float64).reshape(-1, 3).copy()
+        self.lin_bg = _arr(lin_bg, np.float64).reshape(-1, 3).copy()
+        self.key = _arr(key, np.int32).copy()
+        self.bas, self.bgs = _arr(bas, np.float64).reshape(NF, 3).copy(), _arr(bgs, np.float64).reshape(NF, 3).copy()
+        self.tic = _arr(tic, np.float64).copy()
+
+    def to_c(self, ci=None):
+        ci = ci if ci is not None else CInitInput()
+        ci.n_frames = self.n_frames
+        ci.R, ci.T, ci.samples = _p(self.R), _p(self.T), _p(self.samples)
+        ci.n_samples = self.n_samples.ctypes.data_as(_ip)
+        ci.lin_ba, ci.lin_bg = _p(self.lin_ba), _p(self.lin_bg)
+        for k in range(3):
+            ci.acc0[k], ci.gyr0[k], ci.tic[k] = self.acc0[k], self.gyr0[k], self.tic[k]
+        for i in range(NF):
+            ci.key[i] = int(self.key[i])
+            for k in range(3):
+                ci.bas[i][k], ci.bgs[i][k] = self.bas[i, k], self.bgs[i, k]
+        return ci
+
+
+def init_debug_jobs(n_samples, key):
+    """vpl_init_debug_jobs (host only): [F + 9, 3] = (offset, nsamples, acc0 row) of the image intervals 1..F-1, then of the window
+    intervals 1..10; the VPL_E_* code instead when the list is refused"""
+    lib = load_hip_library()
+    n_samples, key = _arr(n_samples, np.int32), _arr(key, np.int32)
+    F = len(n_samples)
+    jobs = np.zeros((max(F, 0) + 9, 3), dtype=np.int32)
+    rc = lib.vpl_init_debug_jobs(F, n_samples.ctypes.data_as(_ip), key.ctypes.data_as(_ip), jobs.ctypes.data_as(_ip))
+    return jobs if rc == 0 else rc
+
+
 class CWindow(C.Structure):
     _fields_ = [("pose", (C.c_double * 7) * NF), ("speed_bias", (C.c_double * 9) * NF), ("ex_pose", C.c_double * 7),
                 ("n_points", C.c_int), ("point_start", _ip), ("point_nobs", _ip), ("point_obs", _dp),
@@ -253,6 +319,9 @@ def load_hip_library():
     lib.vpl_last_error.restype = C.c_char_p
     lib.vpl_preintegrate_batch.argtypes = [vp, C.c_int, _ip, _ip, _dp, _dp, _dp, _dp, _dp, C.POINTER(BaOptions),
                                            C.POINTER(Preintegration)]
+    lib.vpl_init_align_batch.argtypes = [vp, C.c_int, C.POINTER(CInitInput), C.POINTER(BaOptions), C.POINTER(InitResult),
+                                         C.POINTER(Preintegration), C.POINTER(Preintegration)]
+    lib.vpl_init_debug_jobs.argtypes = [C.c_int, _ip, _ip, _ip]
     for name in ("vpl_projection_factor_evaluate", "vpl_line_factor_evaluate", "vpl_vp_factor_evaluate"):
         getattr(lib, name).argtypes = [vp, C.c_int, _dp, _dp, C.c_double, _dp, _dp]
     lib.vpl_imu_factor_evaluate.argtypes = [vp, C.c_int, _dp, C.POINTER(Preintegration), C.c_double, _dp, _dp]
@@ -286,10 +355,12 @@ def load_hip_library():
     lib.vpl_odo_destroy.argtypes = [vp]
     lib.vpl_odo_destroy.restype = None
     lib.vpl_odo_set_window.argtypes = [vp, C.c_int, _dp, _dp, _dp, C.POINTER(Preintegration), C.POINTER(OdoFrame)]
+    lib.vpl_odo_init.argtypes = [vp, C.POINTER(CInitInput), _dp, C.POINTER(OdoFrame), C.POINTER(InitResult)]
     lib.vpl_odo_keyframe.argtypes = [vp, C.POINTER(OdoFrame), _ip, C.POINTER(OdoResult)]
     lib.vpl_odo_solve.argtypes = [vp, _ip, C.POINTER(OdoResult)]
     lib.vpl_odo_advance.argtypes = [vp, C.POINTER(OdoFrame), C.POINTER(OdoResult)]
     lib.vpl_odo_get_prior.argtypes = [vp, C.c_int, C.POINTER(Prior)]
+    lib.vpl_odo_get_states.argtypes = [vp, C.c_int, _dp, _dp, _dp]
     lib.vpl_odo_get_tracks.argtypes = [vp, C.c_int, _ip, _ip, _ip, _ip, _dp, _ip, _ip, _ip, _ip, _ip, _dp]
     lib.vpl_odo_enable_imu.argtypes = [vp, C.c_int]
     lib.vpl_odo_set_imu.argtypes = [vp, C.c_int, C.c_int, _dp, _dp, _dp]
@@ -501,6 +572,30 @@ class Context:
                                              _p(samples), _p(acc0), _p(gyr0), _p(ba), _p(bg), C.byref(opt), out)
         self._check(rc, "vpl_preintegrate_batch")
         return out
+
+    def init_align(self, inputs, opt, want_preint=True, check=True):
+        """vpl_init_align_batch over a list of InitInput: the visual-inertial alignment (gyroscope bias, scale, gravity, the state
+        change) of every sequence in one call.  -> (results [n] of InitResult, window pre-integrations [n][11], image
+        pre-integrations [n][INIT_MAX_FRAMES]); the last two None without want_preint.  check=False: a refusal comes back as its
+        VPL_E_* code instead of an exception."""
+        self._settle()
+        n = len(inputs)
+        ci = (CInitInput * n)()
+        for i, q in enumerate(inputs):
+            if isinstance(q, CInitInput):
+                C.memmove(C.byref(ci[i]), C.byref(q), C.sizeof(CInitInput))   # as the caller filled it (tests of the refusals)
+            else:
+                q.to_c(ci[i])
+        res = (InitResult * n)()
+        wpre = ((Preintegration * NF) * n)() if want_preint else None
+        ipre = ((Preintegration * INIT_MAX_FRAMES) * n)() if want_preint else None
+        rc = self.lib.vpl_init_align_batch(self.h, n, ci, C.byref(opt), res,
+                                           C.cast(wpre, C.POINTER(Preintegration)) if want_preint else None,
+                                           C.cast(ipre, C.POINTER(Preintegration)) if want_preint else None)
+        if rc != 0 and not check:
+            return rc
+        self._check(rc, "vpl_init_align_batch")
+        return res, wpre, ipre
 
     # ---- window solve ---------------------------------------------------------------
     def upload(self, windows, opt, chained=False):
@@ -733,6 +828,34 @@ class Session:
         self.ctx._settle()
         self.ctx._check(self.lib.vpl_odo_set_window(self.h, seq, _p(pose), _p(sb), _p(ex), preint, cf), "vpl_odo_set_window")
 
+    def init(self, inputs, ex_pose, frames, check=True):
+        """vpl_odo_init: the session takes its first window from the visual-inertial alignment.  inputs: one InitInput per sequence;
+        ex_pose [n_seq][7]; frames: per sequence its 11 Frames (observations only).  -> one InitResult per sequence; a sequence whose
+        result is not ok holds no window afterwards.  check=False: a refusal comes back as its VPL_E_* code."""
+        n = self.n_seq
+        assert len(inputs) == n and len(frames) == n and all(len(f) == NF for f in frames)
+        ci = (CInitInput * n)()
+        for i, q in enumerate(inputs):
+            if isinstance(q, CInitInput):
+                C.memmove(C.byref(ci[i]), C.byref(q), C.sizeof(CInitInput))
+            else:
+                q.to_c(ci[i])
+        ex = _arr(ex_pose, np.float64).reshape(n, 7)
+        cf = (OdoFrame * (n * NF))()
+        for i, fs in enumerate(frames):
+            for j, f in enumerate(fs):
+                f.to_c(cf[i * NF + j])
+        res = (InitResult * n)()
+        self.ctx._settle()
+        t0 = time.perf_counter()
+        rc = self.lib.vpl_odo_init(self.h, ci, _p(ex), cf, res)
+        self.last_call_s = time.perf_counter() - t0
+        self.last_rc = rc
+        if rc != 0 and not check:
+            return rc
+        self.ctx._check(rc, "vpl_odo_init")
+        return res
+
     def keyframe(self, frames, flags=None):
         """vpl_odo_keyframe: solveOdometry -> removeFailures -> slideWindow(flag) -> the Frames enter slot 10; one
         OdoResult per sequence (states BEFORE the slide)"""
@@ -894,6 +1017,12 @@ class Session:
         out = (Preintegration * NF)()
         self.ctx._check(self.lib.vpl_odo_get_preint(self.h, seq, out), "vpl_odo_get_preint")
         return out
+
+    def get_states(self, seq=0):
+        """vpl_odo_get_states: (pose [11, 7], speed_bias [11, 9], ex_pose [7]) as the store holds them"""
+        pose, sb, ex = np.zeros((NF, 7)), np.zeros((NF, 9)), np.zeros(7)
+        self.ctx._check(self.lib.vpl_odo_get_states(self.h, seq, _p(pose), _p(sb), _p(ex)), "vpl_odo_get_states")
+        return pose, sb, ex
 
     def get_prior(self, seq=0):
         p = Prior()

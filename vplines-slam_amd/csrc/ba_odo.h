@@ -354,6 +354,45 @@ __global__ __launch_bounds__(ODO_THREADS) void k_odo_append(OdoStore S, const do
   }
 }
 
+// ---- vpl_odo_init: the alignment's results enter the store, device to device.  For a sequence the alignment accepted: the
+// states, the true extrinsic and pre_integrations[1..10] -- k_preintegrate's output (pre3w [seq][10], the 15 x 15 jacobian in the
+// sqrt_info slot) in the store's form, as to_dev_preint makes it -- and every point the triangulation selected scaled:
+// estimated_depth *= s (estimator.cpp:564-570), a clamped init_depth included.  sum_dt [seq][11] goes back to the host's book.
+// A sequence that failed is left as the triangulation left it; the host drops its window.
+__global__ __launch_bounds__(ODO_THREADS) void k_odo_init_finish(DevBatch B, OdoStore S, const int* __restrict__ psrc,
+                                                                 const vpl_init_result* __restrict__ res, const DevPreint* __restrict__ pre3w,
+                                                                 const double* __restrict__ ex, double* __restrict__ sum_dt) {
+  const int w = blockIdx.x, tid = threadIdx.x;
+  const vpl_init_result& r = res[w];
+  if (!r.ok) return;
+  const double* rp = &r.pose[0][0];
+  const double* rs = &r.speed_bias[0][0];
+  for (int i = tid; i < 77; i += ODO_THREADS) S.pose[w * 77 + i] = rp[i];
+  for (int i = tid; i < 99; i += ODO_THREADS) S.sb[w * 99 + i] = rs[i];
+  for (int i = tid; i < 7; i += ODO_THREADS) S.ex[w * 7 + i] = ex[w * 7 + i];
+  for (int i = tid; i < NF * ODO_PRE_D; i += ODO_THREADS) {
+    const int f = i / ODO_PRE_D, k = i % ODO_PRE_D;
+    double v = 0.0;                                     // entry 0, and sqrt_info (k_prep writes it)
+    if (f > 0) {
+      const DevPreint& src = pre3w[(size_t)w * (NF - 1) + f - 1];
+      const double* q = reinterpret_cast<const double*>(&src);
+      if (k < 17) v = q[k];
+      else if (k < 17 + 45) {
+        const int b = (k - 17) / 9, e = (k - 17) % 9;   // dp_dba, dp_dbg, dq_dbg, dv_dba, dv_dbg
+        const int r0 = b < 2 ? 0 : b == 2 ? 3 : 6, c0 = (b == 0 || b == 3) ? 9 : 12;
+        v = src.sqrt_info[(r0 + e / 3) * 15 + c0 + e % 3];
+      } else if (k < 17 + 45 + 225) v = src.cov[k - 62];
+      if (k == 0) sum_dt[w * NF + f] = v;
+    } else if (k == 0) sum_dt[w * NF] = 0.0;
+    reinterpret_cast<double*>(S.pre + (size_t)w * NF)[i] = v;
+  }
+  const double s = r.s;
+  for (int p = tid; p < B.nP[w]; p += ODO_THREADS) {
+    const size_t t = (size_t)w * S.maxPT + psrc[(size_t)w * B.maxP + p];
+    S.invd[t] = 1.0 / ((1.0 / S.invd[t]) * s);
+  }
+}
+
 // ---- the IMU side of the new frame (vpl_odo_advance_imu), after k_odo_slide: one wave per sequence, 16 lanes per integration
 // as in k_preintegrate, whose step body it shares (preint_steps).  A / IA: the store and IMU side before the slide (read);
 // D / ID: after it (D as k_odo_slide left it).

@@ -219,6 +219,51 @@ static int odo_decide(vpl_odo* o, int seq0, int n) {
   return VPL_OK;
 }
 
+// the books of a window's eleven frames, built on copies (a refusal leaves the sequence as it was); pd / ld: per frame and
+// observation, its place in the store (track | frame << 20, -1 = ignored)
+static int odo_build_books(vpl_odo* o, const vpl_odo_frame* frames, OdoBook& P, OdoBook& L, std::vector<std::vector<int>>& pd,
+                           std::vector<std::vector<int>>& ld, const char* who) {
+  vpl_ctx* c = o->c;
+  pd.assign(NF, std::vector<int>()); ld.assign(NF, std::vector<int>());
+  for (int f = 0; f < NF; ++f) {
+    if ((int)P.t.size() + odo_count_unknown(P, frames[f].n_points, frames[f].point_id) > o->maxPT ||
+        (int)L.t.size() + odo_count_unknown(L, frames[f].n_lines, frames[f].line_id) > o->maxLT)
+      return fail(c, VPL_E_CAPACITY, std::string(who) + ": more tracks than the session's capacity");
+    pd[f].resize(frames[f].n_points); ld[f].resize(frames[f].n_lines);
+    odo_add_frame(P, f, frames[f].n_points, frames[f].point_id, pd[f].data());
+    odo_add_frame(L, f, frames[f].n_lines, frames[f].line_id, ld[f].data());
+  }
+  return VPL_OK;
+}
+// an image of the sequence's tracks in the store, copied array by array (not on the per-keyframe path): the observations, every
+// depth unset, no line triangulated
+static int odo_upload_tracks(vpl_odo* o, int seq, const OdoBook& P, const OdoBook& L, const std::vector<std::vector<int>>& pd,
+                             const std::vector<std::vector<int>>& ld, const vpl_odo_frame* frames) {
+  vpl_ctx* c = o->c;
+  const OdoStore& S = o->st[o->cur];
+  const size_t nP = P.t.size(), nL = L.t.size();
+  std::vector<double> pobs(std::max<size_t>(nP, 1) * NF * 3, 0.0), lobs(std::max<size_t>(nL, 1) * NF * 8, 0.0), invd(std::max<size_t>(nP, 1), -1.0),
+      plk(std::max<size_t>(nL, 1) * 6, 0.0);
+  std::vector<int> tri(std::max<size_t>(nL, 1), 0);
+  for (int f = 0; f < NF; ++f) {
+    for (int i = 0; i < frames[f].n_points; ++i) {
+      const int e = pd[f][i];
+      if (e >= 0) std::memcpy(&pobs[((size_t)(e & 0xFFFFF) * NF + (e >> 20 & 15)) * 3], frames[f].point_obs + 3 * (size_t)i, 24);
+    }
+    for (int i = 0; i < frames[f].n_lines; ++i) {
+      const int e = ld[f][i];
+      if (e >= 0) std::memcpy(&lobs[((size_t)(e & 0xFFFFF) * NF + (e >> 20 & 15)) * 8], frames[f].line_obs + 8 * (size_t)i, 64);
+    }
+  }
+  const size_t q = seq;
+  HIPCHK(c, hipMemcpy(S.pobs + q * S.maxPT * NF * 3, pobs.data(), nP * NF * 3 * 8, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(S.lobs + q * S.maxLT * NF * 8, lobs.data(), nL * NF * 8 * 8, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(S.invd + q * S.maxPT, invd.data(), nP * 8, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(S.plk + q * S.maxLT * 6, plk.data(), nL * 6 * 8, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(S.tri + q * S.maxLT, tri.data(), nL * 4, hipMemcpyHostToDevice));
+  return VPL_OK;
+}
+
 extern "C" {
 
 int vpl_odo_create(vpl_odo** out, vpl_ctx* c, int n_seq, const vpl_ba_options* opt, double init_depth, int line_min_obs,
@@ -284,41 +329,15 @@ int vpl_odo_set_window(vpl_odo* o, int seq, const double pose[][7], const double
     if (odo_check_frame(odo_obs(frames[f]))) return fail(c, VPL_E_INVALID, "odo_set_window: null observation array");
   // the bookkeeping on a copy: a refusal leaves the sequence as it was
   OdoBook P, L;
-  std::vector<std::vector<int>> pd(NF), ld(NF);
-  for (int f = 0; f < NF; ++f) {
-    if ((int)P.t.size() + odo_count_unknown(P, frames[f].n_points, frames[f].point_id) > o->maxPT ||
-        (int)L.t.size() + odo_count_unknown(L, frames[f].n_lines, frames[f].line_id) > o->maxLT)
-      return fail(c, VPL_E_CAPACITY, "odo_set_window: more tracks than the session's capacity");
-    pd[f].resize(frames[f].n_points); ld[f].resize(frames[f].n_lines);
-    odo_add_frame(P, f, frames[f].n_points, frames[f].point_id, pd[f].data());
-    odo_add_frame(L, f, frames[f].n_lines, frames[f].line_id, ld[f].data());
-  }
+  std::vector<std::vector<int>> pd, ld;
+  { const int rb = odo_build_books(o, frames, P, L, pd, ld, "odo_set_window"); if (rb) return rb; }
   { const int rq = odo_quiesce(o); if (rq) return rq; }
-  // an image of the sequence's part of the store, copied array by array (not on the per-keyframe path)
   const OdoStore& S = o->st[o->cur];
-  const size_t nP = P.t.size(), nL = L.t.size();
-  std::vector<double> pobs(std::max<size_t>(nP, 1) * NF * 3, 0.0), lobs(std::max<size_t>(nL, 1) * NF * 8, 0.0), invd(std::max<size_t>(nP, 1), -1.0),
-      plk(std::max<size_t>(nL, 1) * 6, 0.0);
-  std::vector<int> tri(std::max<size_t>(nL, 1), 0);
-  for (int f = 0; f < NF; ++f) {
-    for (int i = 0; i < frames[f].n_points; ++i) {
-      const int e = pd[f][i];
-      if (e >= 0) std::memcpy(&pobs[((size_t)(e & 0xFFFFF) * NF + (e >> 20 & 15)) * 3], frames[f].point_obs + 3 * (size_t)i, 24);
-    }
-    for (int i = 0; i < frames[f].n_lines; ++i) {
-      const int e = ld[f][i];
-      if (e >= 0) std::memcpy(&lobs[((size_t)(e & 0xFFFFF) * NF + (e >> 20 & 15)) * 8], frames[f].line_obs + 8 * (size_t)i, 64);
-    }
-  }
+  { const int ru = odo_upload_tracks(o, seq, P, L, pd, ld, frames); if (ru) return ru; }
   std::vector<DevPreint> pre(NF);
   std::memset(pre.data(), 0, sizeof(DevPreint) * NF);
   for (int f = 1; f < NF; ++f) to_dev_preint(preint[f], pre[f]);
   const size_t q = seq;
-  HIPCHK(c, hipMemcpy(S.pobs + q * S.maxPT * NF * 3, pobs.data(), nP * NF * 3 * 8, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(S.lobs + q * S.maxLT * NF * 8, lobs.data(), nL * NF * 8 * 8, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(S.invd + q * S.maxPT, invd.data(), nP * 8, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(S.plk + q * S.maxLT * 6, plk.data(), nL * 6 * 8, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(S.tri + q * S.maxLT, tri.data(), nL * 4, hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(S.pose + q * 77, pose, 77 * 8, hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(S.sb + q * 99, speed_bias, 99 * 8, hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(S.ex + q * 7, ex_pose, 7 * 8, hipMemcpyHostToDevice));
@@ -732,6 +751,140 @@ int vpl_odo_set_imu(vpl_odo* o, int seq, int n10, const double* samples10, const
   return VPL_OK;
 }
 
+// ---- the session's first window from the visual-inertial alignment (csrc/init_align_host.h) -------------------------------------
+int vpl_odo_init(vpl_odo* o, const vpl_init_input* in, const double (*ex_pose)[7], const vpl_odo_frame* frames, vpl_init_result* out) {
+  if (!o || !in || !ex_pose || !frames || !out) return VPL_E_INVALID;
+  vpl_ctx* c = o->c;
+  const int nS = o->nS;
+  if (o->solved) return fail(c, VPL_E_INVALID, "odo_init: between vpl_odo_solve and vpl_odo_advance");
+  // 1. every refusal, on copies: the alignment's, the books', the IMU buffer's, the capacities of the triangulation's batch
+  { const int ri = init_check_inputs(c, nS, in); if (ri) return ri; }
+  std::vector<OdoBook> P(nS), L(nS);
+  std::vector<std::vector<std::vector<int>>> pd(nS), ld(nS);
+  std::vector<int> job10(3 * (size_t)nS);
+  for (int w = 0; w < nS; ++w) {
+    const vpl_odo_frame* fw = frames + (size_t)w * NF;
+    for (int f = 0; f < NF; ++f)
+      if (odo_check_frame(odo_obs(fw[f]))) return fail(c, VPL_E_INVALID, "odo_init: null observation array");
+    const int rb = odo_build_books(o, fw, P[w], L[w], pd[w], ld[w], "odo_init");
+    if (rb) return rb;
+    const int F = in[w].n_frames;
+    std::vector<int> jobs((size_t)(F + 9) * 3);
+    init_build_jobs(F, in[w].n_samples, in[w].key, jobs.data());
+    std::memcpy(&job10[3 * (size_t)w], &jobs[3 * (size_t)(F + 8)], 12);   // window interval 10
+    if (o->imu && job10[3 * (size_t)w + 1] > o->max_samples) return fail(c, VPL_E_CAPACITY, "odo_init: window interval 10 holds more IMU samples than max_samples");
+  }
+  for (int w = 0; w < nS; ++w) { std::swap(o->seq[w].P, P[w]); std::swap(o->seq[w].L, L[w]); }
+  odo_select(o);
+  {
+    const DevBatch& B = c->B;
+    bool fits = true;
+    for (int w = 0; w < nS; ++w) {
+      long po = 0, lo = 0;
+      for (int n : o->pnobs[w]) po += n;
+      for (int n : o->lnobs[w]) lo += n;
+      fits = fits && (int)o->pstart[w].size() <= B.maxP && (int)o->lstart[w].size() <= B.maxL && po <= B.maxPO && lo <= B.maxLO;
+    }
+    if (!fits) {
+      for (int w = 0; w < nS; ++w) { std::swap(o->seq[w].P, P[w]); std::swap(o->seq[w].L, L[w]); }
+      odo_select(o);   // the selection of the books that stay
+      return fail(c, VPL_E_CAPACITY, "odo_init: the selected tracks exceed the context's capacities");
+    }
+  }
+  // from here on the sequences are rewritten: one that does not come out aligned holds no window
+  auto drop = [&](int w) {
+    OdoSeq& q = o->seq[w];
+    q.P = OdoBook(); q.L = OdoBook();
+    q.set = false; q.imu_set = false; q.has_prior = false; q.prior = HostTab(); q.dec_set = false; q.failure = 0;
+  };
+  auto drop_all = [&](int rc) { for (int w = 0; w < nS; ++w) drop(w); return rc; };
+  o->solved = false;
+  { const int rq = odo_quiesce(o); if (rq) return drop_all(rq); }
+  const OdoStore S = o->st[o->cur];
+  hipStream_t s = c->stream;
+  // 2. the observations, on the SfM camera frames: pose = (T_key, quat(R_key)), extrinsic = (0, qic), every depth unset
+  for (int w = 0; w < nS; ++w) {
+    const int ru = odo_upload_tracks(o, w, o->seq[w].P, o->seq[w].L, pd[w], ld[w], frames + (size_t)w * NF);
+    if (ru) return drop_all(ru);
+    double pose[NF][7], ex0[7] = {0, 0, 0, ex_pose[w][3], ex_pose[w][4], ex_pose[w][5], ex_pose[w][6]};
+    for (int i = 0; i < NF; ++i) {
+      const double* R = in[w].R + 9 * (size_t)in[w].key[i];
+      const double* T = in[w].T + 3 * (size_t)in[w].key[i];
+      M3 Rm;
+      for (int k = 0; k < 9; ++k) Rm.m[k] = R[k];
+      const Q4 q = mat2q(Rm);
+      pose[i][0] = T[0]; pose[i][1] = T[1]; pose[i][2] = T[2]; pose[i][3] = q.x; pose[i][4] = q.y; pose[i][5] = q.z; pose[i][6] = q.w;
+    }
+    if (hipMemcpy(S.pose + (size_t)w * 77, pose, 77 * 8, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(S.ex + (size_t)w * 7, ex0, 7 * 8, hipMemcpyHostToDevice) != hipSuccess)
+      return drop_all(fail(c, VPL_E_HIP, "odo_init: upload of the SfM frames failed"));
+  }
+  // 3. the alignment, its results staying on the device
+  InitDevice D;
+  const void* owner = &D;
+  std::vector<vpl_init_result> res(nS);
+  std::vector<double> sum_dt((size_t)nS * NF, 0.0);
+  auto run = [&]() -> int {
+    int rc = init_enqueue(c, nS, in, &o->opt, owner, D);
+    if (rc) return rc;
+    // 4. the session's own point triangulation on that store; no line is touched
+    vpl_ba_options topt;
+    vpl_ba_default_options(&topt);
+    topt.marginalization_flag = VPL_MARGIN_NONE;
+    const OdoSrc src = odo_src(o, false);
+    if ((rc = upload_impl(c, nS, o->win.data(), &topt, true, false, &src))) return rc;
+    launch_triangulate(c, nS, true, false, o->init_depth);
+    hipLaunchKernelGGL(k_odo_scatter_tri, dim3(nS), dim3(ODO_THREADS), 0, s, c->B, S, (const int*)o->d_psrc, (const int*)o->d_lsrc,
+                       odo_out_views(o).d_flags);
+    // 5. states, extrinsic, pre-integrations and the scale into the store
+    double* d_ex = nullptr;   // [nS][7] the true extrinsics | [nS][11] sum_dt back
+    HIPCHK(c, dalloc(c, &d_ex, (size_t)nS * (7 + NF), owner));
+    HIPCHK(c, hipMemcpyAsync(d_ex, ex_pose, (size_t)nS * 56, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_odo_init_finish, dim3(nS), dim3(ODO_THREADS), 0, s, c->B, S, (const int*)o->d_psrc,
+                       (const vpl_init_result*)D.results(), (const DevPreint*)(D.pre3() + D.J1), (const double*)d_ex, d_ex + (size_t)nS * 7);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(res.data(), D.results(), (size_t)nS * sizeof(vpl_init_result), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(sum_dt.data(), d_ex + (size_t)nS * 7, (size_t)nS * NF * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    int hits = 0;
+    if ((rc = init_guard_hits(c, owner, &hits))) return rc;
+    return hits ? fail(c, VPL_E_HIP, "odo_init: guard behind " + std::to_string(hits) + " device array(s) overwritten") : VPL_OK;
+  };
+  const int rr = run();
+  dfree_owner(c, owner);
+  if (rr) return drop_all(rr);
+  // 6. the host's side of every sequence
+  for (int w = 0; w < nS; ++w) {
+    out[w] = res[w];
+    if (!res[w].ok) { drop(w); continue; }
+    OdoSeq& Q = o->seq[w];
+    for (int f = 0; f < NF; ++f) Q.sum_dt[f] = sum_dt[(size_t)w * NF + f];
+    Q.prior = HostTab();
+    Q.has_prior = false;
+    Q.set = true;
+    Q.imu_set = false;
+    std::memcpy(Q.last_pose, res[w].pose[NF - 2], 56);
+    Q.failure = 0;
+    Q.dec_set = false;
+    if (o->imu) {   // the samples of window interval 10 are slot 10's buffer, what starts them its linearized_acc / _gyr
+      const int* j = &job10[3 * (size_t)w];
+      const double* first = j[2] < 0 ? nullptr : in[w].samples + 7 * (size_t)j[2];
+      double lin[6];
+      for (int k = 0; k < 3; ++k) { lin[k] = first ? first[1 + k] : in[w].acc0[k]; lin[3 + k] = first ? first[4 + k] : in[w].gyr0[k]; }
+      const OdoImu& m = o->im[o->cur];
+      if (hipMemcpy(m.smp + (size_t)w * m.max * 7, in[w].samples + 7 * (size_t)j[0], (size_t)j[1] * 56, hipMemcpyHostToDevice) != hipSuccess ||
+          hipMemcpy(m.lin + (size_t)w * 6, lin, 48, hipMemcpyHostToDevice) != hipSuccess ||
+          hipMemcpy(m.n + w, &j[1], 4, hipMemcpyHostToDevice) != hipSuccess)
+        return drop_all(fail(c, VPL_E_HIP, "odo_init: upload of the IMU buffer failed"));
+      Q.imu_set = true;
+    }
+  }
+  if (o->rule)
+    for (int w = 0; w < nS; ++w)
+      if (o->seq[w].set) { const int rd = odo_decide(o, w, 1); if (rd) return drop_all(rd); }
+  return VPL_OK;
+}
+
 // ---- the keyframe decision and the failure check ------------------------------------------------------------------------------
 void vpl_odo_default_keyframe_rule(vpl_odo_keyframe_rule* r) {
   if (!r) return;
@@ -852,6 +1005,19 @@ int vpl_odo_get_preint(vpl_odo* o, int seq, vpl_preintegration* out) {
     for (int k = 9; k < 15; ++k) p.jacobian[k * 15 + k] = 1.0;
     std::memcpy(p.covariance, d.cov, sizeof(p.covariance));
   }
+  return VPL_OK;
+}
+
+int vpl_odo_get_states(vpl_odo* o, int seq, double (*pose)[7], double (*speed_bias)[9], double* ex_pose) {
+  if (!o || seq < 0 || seq >= o->nS || !pose || !speed_bias || !ex_pose) return VPL_E_INVALID;
+  vpl_ctx* c = o->c;
+  if (!o->seq[seq].set) return fail(c, VPL_E_INVALID, "odo_get_states: the sequence has no window");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const OdoStore& S = o->st[o->cur];
+  HIPCHK(c, hipMemcpy(pose, S.pose + (size_t)seq * 77, 77 * 8, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(speed_bias, S.sb + (size_t)seq * 99, 99 * 8, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(ex_pose, S.ex + (size_t)seq * 7, 7 * 8, hipMemcpyDeviceToHost));
   return VPL_OK;
 }
 

@@ -3,7 +3,8 @@
 // kernel sequence of one batched solve on the context's stream, unpacks results.
 // One translation unit.  This file: context create / destroy and the setters, pre-integration and the single-factor evaluators,
 // the launch sequences, the window entry points, download and prior fetch, the debug entry points.  Included once each, like the
-// kernel headers: ba_stage.h (staging arena), ba_ctx.h (vpl_ctx), ba_upload.h (the upload), ba_session.h (vpl_odo_*).
+// kernel headers: ba_stage.h (staging arena), ba_ctx.h (vpl_ctx), ba_upload.h (the upload), init_align_host.h (vpl_init_*),
+// ba_session.h (vpl_odo_*).
 // There is no CPU compute path in this library: every entry point that computes launches
 // HIP kernels and reports VPL_E_NODEVICE / VPL_E_HIP when that is impossible.
 #include <hip/hip_runtime.h>
@@ -37,6 +38,7 @@ using namespace vpl;
 #include "ba_stage.h"
 #include "ba_ctx.h"
 #include "ba_upload.h"
+#include "init_align_host.h"
 
 template <typename Launch>
 static int eval_generic(vpl_ctx* c, int n, const double* params, int psz, const double* consts, int csz, int nres,
@@ -199,7 +201,7 @@ static int ctx_init(vpl_ctx* c, int device, int max_windows, int max_points, int
       {(const void*)k_schur_mixed, schur_max}, {(const void*)k_chol, CHOL_SMEM}, {(const void*)k_back, back_max},
       {(const void*)k_step<3, false>, step_max}, {(const void*)k_step<3, true>, step_max}, {(const void*)k_step<5, false>, step_max},
       {(const void*)k_prep, PREP_SMEM}, {(const void*)k_marg<MARG_THREADS>, 159 * 1024}, {(const void*)k_marg<256>, MARG_LDS_SMALL},
-      {(const void*)k_prior_eigen, prior_eig_layout(MAXKEEP).bytes}};
+      {(const void*)k_prior_eigen, prior_eig_layout(MAXKEEP).bytes}, {(const void*)k_init_align, init_lds_bytes(INIT_NMAX)}};
   for (const auto& k : lds)
     if (hipFuncSetAttribute(k.first, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.second) != hipSuccess) return VPL_E_HIP;
   vpl_ba_default_options(&c->opt);
@@ -323,22 +325,12 @@ int vpl_preintegrate_batch(vpl_ctx* c, int n, const int* offset, const int* nsam
   HIPCHK(c, hipMemcpyAsync(d_g.p, gyr0, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(d_ba.p, lin_ba, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(d_bg.p, lin_bg, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  { KTimer t(c, "k_preintegrate");
-    hipLaunchKernelGGL(k_preintegrate, dim3((n + 3) / 4), dim3(64), 0, c->stream, n, (const int*)d_off.p, (const int*)d_ns.p, d_s.d(),
-                       d_a.d(), d_g.d(), d_ba.d(), d_bg.d(), opt->acc_n * opt->acc_n, opt->gyr_n * opt->gyr_n,
-                       opt->acc_w * opt->acc_w, opt->gyr_w * opt->gyr_w, (DevPreint*)d_out.p); }
+  launch_preintegrate(c, n, (const int*)d_off.p, (const int*)d_ns.p, d_s.d(), d_a.d(), d_g.d(), d_ba.d(), d_bg.d(), opt, (DevPreint*)d_out.p);
   HIPCHK(c, hipGetLastError());
   std::vector<DevPreint> h(n);
   HIPCHK(c, hipMemcpyAsync(h.data(), d_out.p, n * sizeof(DevPreint), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  for (int i = 0; i < n; ++i) {
-    vpl_preintegration& o = out[i];
-    o.sum_dt = h[i].sum_dt;
-    for (int k = 0; k < 3; ++k) { o.delta_p[k] = h[i].dp[k]; o.delta_v[k] = h[i].dv[k]; o.linearized_ba[k] = h[i].lba[k]; o.linearized_bg[k] = h[i].lbg[k]; }
-    for (int k = 0; k < 4; ++k) o.delta_q[k] = h[i].dq[k];
-    std::memcpy(o.jacobian, h[i].sqrt_info, sizeof(o.jacobian));   // k_preintegrate carries J out in this slot
-    std::memcpy(o.covariance, h[i].cov, sizeof(o.covariance));
-  }
+  for (int i = 0; i < n; ++i) from_preintegrate_out(h[i], out[i]);
   return VPL_OK;
 }
 
