@@ -303,7 +303,9 @@ int vpl_ba_upload(vpl_ctx* ctx, int n_windows, const vpl_window* windows, const 
  * stages of vpl_ba_solve_odometry upload too): VPL_E_INVALID otherwise. */
 int vpl_ba_upload_chained(vpl_ctx* ctx, int n_windows, const vpl_window* windows, const vpl_ba_options* opt);
 int vpl_ba_solve(vpl_ctx* ctx);           /* enqueue one batched solve of the uploaded windows */
-int vpl_ba_reset_state(vpl_ctx* ctx);     /* restore the uploaded initial states on device (for repeated timing) */
+int vpl_ba_reset_state(vpl_ctx* ctx);     /* restore the uploaded initial states on device (for repeated timing): enqueues
+                                            * nothing -- the next vpl_ba_solve restores as it starts, any other call that reads or
+                                            * writes the states first copies them back */
 int vpl_ba_download(vpl_ctx* ctx, int n_windows, vpl_window* windows, vpl_prior* priors_out,
                     vpl_solve_report* reports);
 int vpl_ctx_synchronize(vpl_ctx* ctx);

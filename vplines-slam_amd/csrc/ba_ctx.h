@@ -9,6 +9,7 @@
 #include "vplines_ba.h"
 #include "ba_types.h"
 #include "ba_stage.h"
+#include "ba_restore.h"
 
 struct vpl_ctx {
   // ---- device, stream, the batch's arrays
@@ -55,8 +56,12 @@ struct vpl_ctx {
   // ---- graph
   // the ~19 launches of one solve as a hipGraph, captured on the first vpl_ba_solve after an upload (the kernel arguments --
   // the batch descriptor by value -- are fixed until the next upload); VPL_BA_GRAPH=0 launches kernel by kernel
-  hipGraphExec_t graph_exec = nullptr;
+  // k_prep's restore mode is one of those arguments: one instance per RestoreMode, each captured on its first use
+  hipGraphExec_t graph_exec[3] = {nullptr, nullptr, nullptr};
   bool use_graph = true;
+  // ---- pending restore (ba_restore.h)
+  int restore_pending = RESTORE_NONE;            // vpl_ba_reset_state was called and nothing has restored the states yet
+  bool restore_fold = true;                      // VPL_BA_RESET_FOLD=0: vpl_ba_reset_state issues its five copies at once (A/B runs, tests)
   // ---- timing
   bool timing = false;
   std::map<std::string, std::pair<double, int>> ktimes;
@@ -80,15 +85,46 @@ struct vpl_ctx {
 };
 
 static void drop_graph(vpl_ctx* c) {
-  if (c->graph_exec) { (void)hipGraphExecDestroy(c->graph_exec); c->graph_exec = nullptr; }
+  for (hipGraphExec_t& g : c->graph_exec)
+    if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+}
+
+// the states of the uploaded batch back to what the upload put there (pose, sb, ex, invd and, RESTORE_LINES, the lines)
+static int restore_states(vpl_ctx* c, int mode) {
+  if (mode == RESTORE_NONE || c->nW < 1) return VPL_OK;
+  const DevBatch& B = c->B;
+  const size_t W = c->nW;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(B.pose, B.pose_0, W * 77 * 8, hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(B.sb, B.sb_0, W * 99 * 8, hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(B.ex, B.ex_0, W * 7 * 8, hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(B.invd, B.invd_0, W * B.maxP * 8, hipMemcpyDeviceToDevice, c->stream));
+  if (mode == RESTORE_LINES) HIPCHK(c, hipMemcpyAsync(B.plk, B.plk_0, W * B.maxL * 6 * 8, hipMemcpyDeviceToDevice, c->stream));
+  return VPL_OK;
+}
+// one call's effect on the pending restore (restore_step, ba_restore.h): issues the copies it asks for; *prep, if given,
+// receives the mode the caller has to hand to k_prep
+static int restore_event(vpl_ctx* c, RestoreEvent ev, int* prep = nullptr) {
+  const RestoreStep s = restore_step(c->restore_pending, ev, c->restore_fold);
+  c->restore_pending = s.pending;
+  if (prep) *prep = s.prep;
+  return restore_states(c, s.flush);
 }
 
 // completes the asynchronous call that is still pending on this context, if any
-static int settle(vpl_ctx* c) {
+static int settle_call(vpl_ctx* c) {
   if (!c || !c->pending) return VPL_OK;
   std::function<int()> fin;
   fin.swap(c->pending);
   return fin();
+}
+// ... and brings the states up to date: what every entry point starts with, except those that deal with the pending restore
+// themselves (vpl_ba_reset_state, vpl_ba_solve, the upload, vpl_ctx_set_stream)
+static int settle(vpl_ctx* c) {
+  if (!c) return VPL_OK;
+  const int rs = settle_call(c);
+  if (rs) return rs;
+  return restore_event(c, RESTORE_EV_OBSERVE);
 }
 // the tail of an entry point: now, or (asynchronous variant) when the caller collects
 static int finish_or_defer(vpl_ctx* c, bool async, std::function<int()> fin) {

@@ -24,27 +24,100 @@ __host__ __device__ constexpr int lin_stage_doubles(int maxL) {   // MFMA stagin
   return m > 4650 + 3570 ? m : 4650 + 3570;              // IMU phase: whitened [J | r] of the ten factors + their J^T J blocks (imuH)
 }
 constexpr int PREP_THREADS = 640;         // ten waves: one IMU factor each, all ten in one round
-// per-wave scratch of the whitening (3 x 225) + the staged prior J0 of the batch's largest prior (capped at PREP_NMAX)
+// per-wave scratch of the whitening (3 x 225) + the staged prior J0 and r0 of the batch's largest prior (capped at PREP_NMAX) +
+// the twelve re-normalised poses (84): 70 KB at n = 45, two work-groups fit a CU's LDS
 inline size_t prep_smem(int max_prior_n) {
   const int ns = max_prior_n < PREP_NMAX ? max_prior_n : PREP_NMAX;
-  return (size_t)((PREP_THREADS / 64) * 675 + ns * ns) * sizeof(double);
+  return (size_t)((PREP_THREADS / 64) * 675 + ns * ns + ns + 84) * sizeof(double);
 }
-constexpr size_t PREP_SMEM = (size_t)((PREP_THREADS / 64) * 675 + PREP_NMAX * PREP_NMAX) * sizeof(double);
+constexpr size_t PREP_SMEM = (size_t)((PREP_THREADS / 64) * 675 + PREP_NMAX * PREP_NMAX + PREP_NMAX + 84) * sizeof(double);
 
 // Every kernel of the solve is a `*_body` device function of (batch, window, dynamic LDS) plus a thin __global__ wrapper.
-__device__ __forceinline__ void prep_body(const DevBatch& B, const int w, double* psm, int nstage) {
+// restore (RestoreMode of ba_restore.h; 0: none): a vpl_ba_reset_state is pending -- the work-group first takes its window's
+// states from the snapshots of the upload: speed/bias, inverse depths and (2) the Pluecker vectors are copied, poses and
+// extrinsic are read from the snapshot where (b) reads them and written where (b) writes anyway.
+__device__ __forceinline__ void prep_body(const DevBatch& B, const int w, double* psm, int nstage, const int restore) {
   const int tid = threadIdx.x;
   const int lane = tid & 63, wv = tid >> 6;
   const int NWV = blockDim.x >> 6;       // 10 waves: one IMU factor each
   double* wsc = psm + wv * 675;          // per-wave scratch: G (225) | X = G^-1 (225) | P = cov^-1 (225)
   double* Jl = psm + NWV * 675;          // prior J0 staged (n * n), room for nstage x nstage
+  double* r0s = Jl + nstage * nstage;    // ... and its r0 (n)
+  double* xq = r0s + nstage;             // the states (b) leaves, for the lines: [NF + 1][7]
+  // the snapshot is requested first of all, two values per thread in registers (the whole of it at the benchmark's 200 points
+  // and 80 lines), and stored behind the request of J0: nothing in this kernel reads the destinations
+  const int nrs = restore ? 99 + B.maxP + (restore > 1 ? 6 * B.maxL : 0) : 0;
+  auto rs_src = [&](int i) -> const double* {
+    return i < 99 ? B.sb_0 + (size_t)w * 99 + i
+                  : i < 99 + B.maxP ? B.invd_0 + (size_t)w * B.maxP + (i - 99) : B.plk_0 + (size_t)w * B.maxL * 6 + (i - 99 - B.maxP);
+  };
+  auto rs_dst = [&](int i) -> double* {
+    return i < 99 ? B.sb + (size_t)w * 99 + i
+                  : i < 99 + B.maxP ? B.invd + (size_t)w * B.maxP + (i - 99) : B.plk + (size_t)w * B.maxL * 6 + (i - 99 - B.maxP);
+  };
+  const int rs1 = tid + (int)blockDim.x;
+  double rv0 = 0.0, rv1 = 0.0;
+  if (tid < nrs) rv0 = *rs_src(tid);
+  if (rs1 < nrs) rv1 = *rs_src(rs1);
   // the prior's J0 is requested first: its round trip runs under the whitening below
   const int n = B.pr_n[w];
   const bool fits = n > 0 && n <= nstage;
   if (fits) {
     const double* J0g = B.pr_J0 + (size_t)w * B.prS;
     for (int idx = tid; idx < n * n; idx += blockDim.x) Jl[idx] = J0g[idx];
+    const double* r0g = B.pr_r0 + (size_t)w * MAXPN;
+    for (int idx = tid; idx < n; idx += blockDim.x) r0s[idx] = r0g[idx];
   }
+  // ... and the start frame and Pluecker vector of this thread's first line (a chain of two round trips where (c) needs them)
+  const int nLw = B.nL[w];
+  const bool orth_in = B.orth_in[w] != 0;
+  // (a restore of the lines: from the snapshot -- the copy to B.plk is another thread's store)
+  const double* plk_in = (restore > 1 ? B.plk_0 : B.plk) + (size_t)w * B.maxL * 6;
+  int s1 = 0;
+  double pl1[6] = {0, 0, 0, 0, 0, 0};
+  if (!orth_in && tid < nLw) {
+    s1 = B.ln_start[(size_t)w * B.maxL + tid];
+#pragma unroll
+    for (int q = 0; q < 6; ++q) pl1[q] = plk_in[tid * 6 + q];
+  }
+  // ... and the covariance of this wave's first IMU factor: its round trip runs under (b) and the barrier
+  double cv[4] = {0, 0, 0, 0};
+  if (1 + wv < NF) {
+    const DevPreint& P1 = B.pre[(size_t)w * NF + 1 + wv];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if (lane + 64 * i < 225) cv[i] = P1.cov[lane + 64 * i];
+  }
+  if (tid < nrs) *rs_dst(tid) = rv0;
+  if (rs1 < nrs) *rs_dst(rs1) = rv1;
+  for (int i = rs1 + (int)blockDim.x; i < nrs; i += blockDim.x) *rs_dst(i) = *rs_src(i);   // (larger contexts)
+  // (b) states: Rs = normalized(q).toRotationMatrix(); para = Quaterniond(Rs)   (vector2double, estimator.cpp:650-705)
+  if (tid < NF + 1) {
+    double* x = tid < NF ? B.pose + ((size_t)w * NF + tid) * 7 : B.ex + (size_t)w * 7;
+    const double* xin = !restore ? x : tid < NF ? B.pose_0 + ((size_t)w * NF + tid) * 7 : B.ex_0 + (size_t)w * 7;
+    const double x0 = xin[0], x1 = xin[1], x2 = xin[2];
+    Q4 q = mat2q(qmat(qnormalized(qpose(xin))));
+    if (tid == 0) {
+      M3 R0 = qmat(qnormalized(qpose(xin)));
+      V3 ypr = R2ypr(R0);
+      double* g = B.gauge + (size_t)w * 4;
+      g[0] = ypr.x; g[1] = x0; g[2] = x1; g[3] = x2;
+      const double* fr = B.fail_ref + (size_t)w * 13;
+      if (fr[0] != 0.0) {   // failure_occur: origin_R0 = R2ypr(last_R0), origin_P0 = last_P0 (estimator.cpp:818-823)
+        M3 Rl;
+        for (int k = 0; k < 9; ++k) Rl.m[k] = fr[4 + k];
+        g[0] = R2ypr(Rl).x; g[1] = fr[1]; g[2] = fr[2]; g[3] = fr[3];
+      }
+    }
+    if (restore) { x[0] = x0; x[1] = x1; x[2] = x2; }
+    x[3] = q.x; x[4] = q.y; x[5] = q.z; x[6] = q.w;
+    // the lines below read the states from LDS, not back from HBM behind the stores
+    double* xo = xq + 7 * tid;
+    xo[0] = x0; xo[1] = x1; xo[2] = x2; xo[3] = q.x; xo[4] = q.y; xo[5] = q.z; xo[6] = q.w;
+  }
+  // the one barrier of the kernel: the states, J0 and r0 in LDS.  (b) sits in front of it and the whitening behind, so that a
+  // wave goes on to its lines and its tiles of the prior when ITS factor is done, not when the slowest wave's is
+  __syncthreads();
   // (a) IMU: sqrt_info = LLT(cov^-1).matrixL().transpose()  (imu_factor.h:68).  cov is SPD: its inverse
   //     is formed from its Cholesky factor (cov = G G^T, cov^-1 = G^-T G^-1), then factored again.
   for (int j = 1 + wv; j < NF; j += NWV) {
@@ -52,7 +125,13 @@ __device__ __forceinline__ void prep_body(const DevBatch& B, const int w, double
     double* G = wsc;
     double* X = wsc + 225;
     double* Pm = wsc + 450;
-    for (int k = lane; k < 225; k += 64) G[k] = P.cov[k];
+    if (j == 1 + wv) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if (lane + 64 * i < 225) G[lane + 64 * i] = cv[i];
+    } else {
+      for (int k = lane; k < 225; k += 64) G[k] = P.cov[k];
+    }
     __builtin_amdgcn_wave_barrier();
     // cov = G G^T and X = G^-1 in one pass: the register tile factorisation carries an identity along (ba_common.h)
     wave_chol16(G, 15, 15, X, lane);
@@ -72,48 +151,34 @@ __device__ __forceinline__ void prep_body(const DevBatch& B, const int w, double
     }
     __builtin_amdgcn_wave_barrier();
   }
-  // (b) states: Rs = normalized(q).toRotationMatrix(); para = Quaterniond(Rs)   (vector2double, estimator.cpp:650-705)
-  if (tid < NF + 1) {
-    double* x = tid < NF ? B.pose + ((size_t)w * NF + tid) * 7 : B.ex + (size_t)w * 7;
-    Q4 q = mat2q(qmat(qnormalized(qpose(x))));
-    if (tid == 0) {
-      M3 R0 = qmat(qnormalized(qpose(x)));
-      V3 ypr = R2ypr(R0);
-      double* g = B.gauge + (size_t)w * 4;
-      g[0] = ypr.x; g[1] = x[0]; g[2] = x[1]; g[3] = x[2];
-      const double* fr = B.fail_ref + (size_t)w * 13;
-      if (fr[0] != 0.0) {   // failure_occur: origin_R0 = R2ypr(last_R0), origin_P0 = last_P0 (estimator.cpp:818-823)
-        M3 Rl;
-        for (int k = 0; k < 9; ++k) Rl.m[k] = fr[4 + k];
-        g[0] = R2ypr(Rl).x; g[1] = fr[1]; g[2] = fr[2]; g[3] = fr[3];
-      }
-    }
-    x[3] = q.x; x[4] = q.y; x[5] = q.z; x[6] = q.w;
-    // the lines below read the states from LDS (wave 0's scratch is free now), not back from HBM behind the stores
-    double* xq = psm + 7 * tid;
-    xq[0] = x[0]; xq[1] = x[1]; xq[2] = x[2]; xq[3] = q.x; xq[4] = q.y; xq[5] = q.z; xq[6] = q.w;
-  }
-  __syncthreads();
-  // (c) lines: world orth from the start-camera-frame Pluecker (getLineOrthVector, feature_manager.cpp:341-365)
-  const int nL = B.orth_in[w] ? 0 : B.nL[w];
-  for (int l = tid; l < nL; l += blockDim.x) {
-    const int s = B.ln_start[(size_t)w * B.maxL + l];
-    const double* ps = psm + 7 * s;
-    const double* ex = psm + 7 * NF;
-    M3 Rs = qmat(qpose(ps)), ric = qmat(qpose(ex));
-    V3 P{ps[0], ps[1], ps[2]}, tic{ex[0], ex[1], ex[2]};
-    V3 twc = P + mul(Rs, tic);
-    M3 Rwc = mul(Rs, ric);
-    const double* pl = B.plk + ((size_t)w * B.maxL + l) * 6;
-    Plk Lc{V3{pl[0], pl[1], pl[2]}, V3{pl[3], pl[4], pl[5]}};
-    Plk Lw = plk_to_pose(Lc, Rwc, twc);
-    plk_to_orth(Lw, B.orth + ((size_t)w * B.maxL + l) * 4);
-  }
-  // world Pluecker coordinates of every line's orthonormal parameters (what the factors evaluate, line_parameterization /
-  // utility orth_to_plk), once per line: a lane writes the parameters above and reads them back itself
-  for (int l = tid; l < B.nL[w]; l += blockDim.x) {
+  // (c) lines: world orth from the start-camera-frame Pluecker (getLineOrthVector, feature_manager.cpp:341-365), unless the
+  // caller uploaded the orthonormal parameters, and their world Pluecker coordinates (what the factors evaluate,
+  // line_parameterization / utility orth_to_plk), once per line.  The parameters stay in registers between the two.
+  for (int l = tid; l < nLw; l += blockDim.x) {
     const size_t li = (size_t)w * B.maxL + l;
-    const Plk Lw = orth_to_plk(B.orth + li * 4);
+    double o4[4];
+    if (!orth_in) {
+      const bool first = l == tid;      // requested at the top
+      const int s = first ? s1 : B.ln_start[li];
+      const double* ps = xq + 7 * s;
+      const double* ex = xq + 7 * NF;
+      M3 Rs = qmat(qpose(ps)), ric = qmat(qpose(ex));
+      V3 P{ps[0], ps[1], ps[2]}, tic{ex[0], ex[1], ex[2]};
+      V3 twc = P + mul(Rs, tic);
+      M3 Rwc = mul(Rs, ric);
+      double pl[6];
+#pragma unroll
+      for (int q = 0; q < 6; ++q) pl[q] = first ? pl1[q] : plk_in[(size_t)l * 6 + q];
+      Plk Lc{V3{pl[0], pl[1], pl[2]}, V3{pl[3], pl[4], pl[5]}};
+      Plk Lw = plk_to_pose(Lc, Rwc, twc);
+      plk_to_orth(Lw, o4);
+      double* og = B.orth + li * 4;
+      og[0] = o4[0]; og[1] = o4[1]; og[2] = o4[2]; og[3] = o4[3];
+    } else {
+      const double* og = B.orth + li * 4;
+      o4[0] = og[0]; o4[1] = og[1]; o4[2] = og[2]; o4[3] = og[3];
+    }
+    const Plk Lw = orth_to_plk(o4);
     double* o = B.lw + li * 6;
     o[0] = Lw.n.x; o[1] = Lw.n.y; o[2] = Lw.n.z; o[3] = Lw.v.x; o[4] = Lw.v.y; o[5] = Lw.v.z;
   }
@@ -121,7 +186,7 @@ __device__ __forceinline__ void prep_body(const DevBatch& B, const int w, double
   if (n > 0) {
     const double* J0 = B.pr_J0 + (size_t)w * B.prS;
     double* H = B.pr_H + (size_t)w * B.prS;
-    const double* Js = fits ? Jl : J0;   // (staged at the top; the barrier after the states made it visible)
+    const double* Js = fits ? Jl : J0;   // (staged at the top; the barrier made it visible)
     if (fits) {
       // on the FP64 matrix cores (round 4): the lower 16 x 16 tiles of J0^T J0 dealt to the waves, K-steps of four rows of J0;
       // lane (kk, m) supplies J0[4 ks + kk][16 t + m] for both operands and holds C[kk + 4 v][m].  One scalar dot product of
@@ -158,11 +223,17 @@ __device__ __forceinline__ void prep_body(const DevBatch& B, const int w, double
     }
     // g0 = J0^T r0: with H it turns the gradient of the prior, J0^T (r0 + J0 dx), into g0 + H dx -- a mat-vec that does not
     // wait for the residual
+    // (r0 from LDS with J0: from HBM the loop paid a round trip per batch of loads)
     for (int c2 = tid; c2 < n; c2 += blockDim.x) {
       double s = 0;
-      const double* r0g = B.pr_r0 + (size_t)w * MAXPN;
+      if (fits) {
 #pragma unroll 8
-      for (int k = 0; k < n; ++k) s += Js[(size_t)k * n + c2] * r0g[k];
+        for (int k = 0; k < n; ++k) s += Jl[k * n + c2] * r0s[k];
+      } else {
+        const double* r0g = B.pr_r0 + (size_t)w * MAXPN;
+#pragma unroll 8
+        for (int k = 0; k < n; ++k) s += J0[(size_t)k * n + c2] * r0g[k];
+      }
       B.pr_g0[(size_t)w * MAXPN + c2] = s;
     }
     if (tid < B.pr_nb[w]) {
@@ -183,9 +254,11 @@ __device__ __forceinline__ void prep_body(const DevBatch& B, const int w, double
     B.tr[w] = t;
   }
 }
-__global__ __launch_bounds__(PREP_THREADS) void k_prep(DevBatch B, int nstage) {
+// 128 VGPRs: one work-group of ten waves per CU, the 512 windows of the benchmark in two rounds.  Held to 96 VGPRs (two
+// work-groups per CU, one round) the kernel spills 38 registers and is slower: 52 against 46 us (profiles/r12)
+__global__ __launch_bounds__(PREP_THREADS) void k_prep(DevBatch B, int nstage, int restore) {
   extern __shared__ double psm[];
-  prep_body(B, blockIdx.x, psm, nstage);
+  prep_body(B, blockIdx.x, psm, nstage, restore);
 }
 
 // ---------------------------------------------------------------------------------------

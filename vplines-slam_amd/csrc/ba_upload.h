@@ -155,7 +155,7 @@ static int upload_check(vpl_ctx* c, int nW, const vpl_window* win, const vpl_ba_
       opt->marginalization_flag != VPL_MARGIN_NONE)
     return fail(c, VPL_E_INVALID, "unknown marginalization_flag");
   HIPCHK(c, hipSetDevice(c->device));
-  { const int rs = settle(c); if (rs) return rs; }   // an asynchronous call whose results have not been collected yet
+  { const int rs = settle_call(c); if (rs) return rs; }   // an asynchronous call whose results have not been collected yet
   // chained: the priors of THIS batch size must be resident, i.e. the context's last upload was solved (or marginalised) with a
   // marginalisation and nothing was uploaded since (any upload rewrites mg_n / mg_nb / mg_kind, the tables of the NEXT prior)
   if (chained && (!c->prior_resident || c->prior_resident_nW != nW))
@@ -495,6 +495,7 @@ static int upload_body(vpl_ctx* c, int nW, const vpl_window* win, const vpl_ba_o
   if (rc) return rc;
   const int prev_prS = c->B.prS;
   c->prior_resident = false;
+  (void)restore_event(c, RESTORE_EV_UPLOAD);   // (issues nothing: the snapshots a pending restore would copy are rewritten below)
   if (c->leg_timing) HIPCHK(c, hipEventRecord(c->leg_ev[0], c->stream));
   drop_graph(c);
   c->upload_open = true;   // from here on a refusal leaves the context with no batch (upload_impl)
@@ -590,16 +591,4 @@ static int upload_impl(vpl_ctx* c, int nW, const vpl_window* win, const vpl_ba_o
     c->upload_open = false;
   }
   return rc;
-}
-
-// the states of the uploaded batch back to what the upload put there (pose, sb, ex, invd and, with `plk`, the lines)
-static int restore_states(vpl_ctx* c, bool plk) {
-  const DevBatch& B = c->B;
-  const size_t W = c->nW;
-  HIPCHK(c, hipMemcpyAsync(B.pose, B.pose_0, W * 77 * 8, hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(B.sb, B.sb_0, W * 99 * 8, hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(B.ex, B.ex_0, W * 7 * 8, hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(B.invd, B.invd_0, W * B.maxP * 8, hipMemcpyDeviceToDevice, c->stream));
-  if (plk) HIPCHK(c, hipMemcpyAsync(B.plk, B.plk_0, W * B.maxL * 6 * 8, hipMemcpyDeviceToDevice, c->stream));
-  return VPL_OK;
 }

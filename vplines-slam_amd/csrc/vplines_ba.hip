@@ -208,6 +208,7 @@ static int ctx_init(vpl_ctx* c, int device, int max_windows, int max_points, int
   if (const char* gv = std::getenv("VPL_BA_GRAPH")) c->use_graph = std::atoi(gv) != 0;
   if (const char* gv = std::getenv("VPL_BA_GENERAL")) c->force_general = std::atoi(gv) != 0;
   if (const char* gv = std::getenv("VPL_BA_STEP_FUSED")) c->step_fused = std::atoi(gv) != 0;
+  if (const char* gv = std::getenv("VPL_BA_RESET_FOLD")) c->restore_fold = std::atoi(gv) != 0;
   if (const char* gv = std::getenv("VPL_BA_SCHUR_WIDE")) { c->schur_wide_all = std::atoi(gv) > 0; c->schur_never_wide = std::atoi(gv) < 0; }
   return VPL_OK;
 }
@@ -234,6 +235,7 @@ void vpl_ctx_destroy(vpl_ctx* c) {
   // (teardown: a failure has nobody to be reported to)
   (void)hipSetDevice(c->device);
   (void)hipDeviceSynchronize();
+  (void)restore_event(c, RESTORE_EV_DESTROY);   // (a pending restore is dropped: nobody can observe the states any more)
   drop_graph(c);
   free_arrays(c);
   c->stage.release();
@@ -245,7 +247,7 @@ int vpl_ctx_set_stream(vpl_ctx* c, void* s) {
   if (!c) return VPL_E_INVALID;
   // what is in flight on the stream so far is completed first (an enqueued call would otherwise be collected behind a
   // synchronisation of the NEW stream, and a later download would not be ordered behind a solve on the old one)
-  const int rs = settle(c);
+  const int rs = settle_call(c);
   if (rs) return rs;
   if (c->stream != (hipStream_t)s) {
     HIPCHK(c, hipSetDevice(c->device));
@@ -254,7 +256,8 @@ int vpl_ctx_set_stream(vpl_ctx* c, void* s) {
   }
   drop_graph(c);
   c->stream = (hipStream_t)s;
-  return VPL_OK;
+  // a pending restore is issued on the NEW stream (everything on the old one has completed; the old one may be gone)
+  return restore_event(c, RESTORE_EV_OBSERVE);
 }
 // the rule that turns the kept block into the next prior (k_marg's pivoted Cholesky, or k_prior_eigen behind it); a call already
 // enqueued is collected first, so that every call runs under the rule in force when it was enqueued
@@ -414,10 +417,12 @@ int vpl_line_orth_plus(vpl_ctx* c, int n, const double* x, const double* delta, 
 }
 
 // ---- window batch: upload (ba_upload.h) / solve / download --------------------------------------------------
+// enqueues nothing (ba_restore.h): the next vpl_ba_solve restores inside k_prep, any other call that touches the states first
+// issues the copies.  VPL_BA_RESET_FOLD=0: the copies at once.
 int vpl_ba_reset_state(vpl_ctx* c) {
-  if (c) { const int rs = settle(c); if (rs) return rs; }
+  if (c) { const int rs = settle_call(c); if (rs) return rs; }
   if (!c || c->nW < 1) return VPL_E_INVALID;
-  return restore_states(c, true);
+  return restore_event(c, RESTORE_EV_RESET);
 }
 
 int vpl_ba_upload(vpl_ctx* c, int nW, const vpl_window* win, const vpl_ba_options* opt) {
@@ -427,10 +432,11 @@ int vpl_ba_upload_chained(vpl_ctx* c, int nW, const vpl_window* win, const vpl_b
   return upload_impl(c, nW, win, opt, false, true);
 }
 
-// k_prep: whitening matrices, q <- Quaterniond(R(q)), the world orth of the lines and J0^T J0 of the incoming prior
-static void launch_prep(vpl_ctx* c, const DevBatch& B, int nw, hipStream_t s) {
+// k_prep: whitening matrices, q <- Quaterniond(R(q)), the world orth of the lines and J0^T J0 of the incoming prior; restore
+// (a RestoreMode): every work-group first takes its window's states from the snapshots of the upload
+static void launch_prep(vpl_ctx* c, const DevBatch& B, int nw, hipStream_t s, int restore = RESTORE_NONE) {
   KTimer t(c, "k_prep");
-  hipLaunchKernelGGL(k_prep, dim3(nw), dim3(PREP_THREADS), prep_smem(c->maxPriorN), s, B, std::min(c->maxPriorN, PREP_NMAX));
+  hipLaunchKernelGGL(k_prep, dim3(nw), dim3(PREP_THREADS), prep_smem(c->maxPriorN), s, B, std::min(c->maxPriorN, PREP_NMAX), restore);
 }
 // the marginalisation of the uploaded flag: k_lin<1|2> linearises its factor subset at the current states, k_marg eliminates
 // and factors the kept block (VPL_PRIOR_EIGEN: k_prior_eigen then replaces the factor by the reference's).  Nothing runs for MARGIN_NONE, nor for MARGIN_SECOND_NEW when every window passes its prior through.
@@ -686,8 +692,8 @@ int vpl_ba_only_line_opt_async(vpl_ctx* c, int nW, vpl_window* win, const vpl_ba
   return only_line_opt_impl(c, nW, win, opt, reports, true);
 }
 
-// The whole solve of the windows [w0, w0 + nw) on stream s
-static void launch_solve(vpl_ctx* c, int w0, int nw, hipStream_t s) {
+// The whole solve of the windows [w0, w0 + nw) on stream s; restore: see launch_prep
+static void launch_solve(vpl_ctx* c, int w0, int nw, hipStream_t s, int restore) {
   DevBatch B = c->B;
   B.ord_it = 0;
   // with kernel timing on, every launch also counts the windows that did work in it (vpl_ba_launch_profile)
@@ -696,7 +702,7 @@ static void launch_solve(vpl_ctx* c, int w0, int nw, hipStream_t s) {
   B.step_fused = c->step_fused && !c->timing;
   if (c->timing) { c->ltimes.clear(); (void)hipMemsetAsync(c->d_act, 0, sizeof(int) * ACT_SLOTS * 4, s); }   // (counts only)
   const dim3 grid(nw);
-  launch_prep(c, B, nw, s);
+  launch_prep(c, B, nw, s, restore);
   ++B.launch;
   { KTimer t(c, "k_lin"); hipLaunchKernelGGL(k_lin2, dim3(16 * ((nw + 7) / 8)), dim3(LIN_THREADS), lin_smem(c->maxP, c->maxL), s, B); }
   ++B.launch;
@@ -745,31 +751,34 @@ static void launch_solve(vpl_ctx* c, int w0, int nw, hipStream_t s) {
 
 // vpl_ba_solve: the kernel-per-phase sequence over the whole batch, asynchronous on the context's stream.
 int vpl_ba_solve(vpl_ctx* c) {
-  if (c) { const int rs = settle(c); if (rs) return rs; }
+  if (c) { const int rs = settle_call(c); if (rs) return rs; }
   if (!c || c->nW < 1) return VPL_E_INVALID;
   HIPCHK(c, hipSetDevice(c->device));
+  int restore = RESTORE_NONE;      // a pending vpl_ba_reset_state: k_prep's work-groups restore their windows
+  { const int rr = restore_event(c, RESTORE_EV_SOLVE, &restore); if (rr) return rr; }
   if (c->opt.marginalization_flag != VPL_MARGIN_NONE) { c->prior_resident = true; c->prior_resident_nW = c->nW; }
   if (c->leg_timing) {
     HIPCHK(c, hipEventRecord(c->leg_ev[2], c->stream));
-    launch_solve(c, 0, c->nW, c->stream);
+    launch_solve(c, 0, c->nW, c->stream, restore);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(c->leg_ev[3], c->stream));
     return VPL_OK;
   }
   if (c->use_graph && !c->timing && c->stream != nullptr) {   // (the legacy default stream cannot be captured)
-    if (!c->graph_exec) {
+    hipGraphExec_t& exec = c->graph_exec[restore];   // (the restore mode is a kernel argument: one instance per mode)
+    if (!exec) {
       hipGraph_t graph = nullptr;
       HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-      launch_solve(c, 0, c->nW, c->stream);
+      launch_solve(c, 0, c->nW, c->stream, restore);
       HIPCHK(c, hipStreamEndCapture(c->stream, &graph));
-      hipError_t e = hipGraphInstantiate(&c->graph_exec, graph, nullptr, nullptr, 0);
+      hipError_t e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
       (void)hipGraphDestroy(graph);   // (the instance does not need it)
-      if (e != hipSuccess) { c->graph_exec = nullptr; return fail(c, VPL_E_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e)); }
+      if (e != hipSuccess) { exec = nullptr; return fail(c, VPL_E_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e)); }
     }
-    HIPCHK(c, hipGraphLaunch(c->graph_exec, c->stream));
+    HIPCHK(c, hipGraphLaunch(exec, c->stream));
     return VPL_OK;
   }
-  launch_solve(c, 0, c->nW, c->stream);
+  launch_solve(c, 0, c->nW, c->stream, restore);
   HIPCHK(c, hipGetLastError());
   return VPL_OK;
 }
@@ -975,7 +984,7 @@ int vpl_ba_solve_windows(vpl_ctx* c, int nW, vpl_window* win, const vpl_ba_optio
 // -- after this restore -- the states k_prep re-normalised in place.  Same bits as the four-stage call.
 static int reuse_line_opt_batch(vpl_ctx* c) {
   HIPCHK(c, hipMemsetAsync(c->B.ln_removed, 0, (size_t)c->nW * c->B.maxL * 4, c->stream));
-  return restore_states(c, false);
+  return restore_event(c, RESTORE_EV_REUSE);
 }
 
 // Estimator::solveOdometry (estimator.cpp:624-648) for a batch, in one call: triangulate || (triangulateLine -> onlyLineOpt)
