@@ -649,6 +649,29 @@ int vpl_odo_debug_tracks(int max_tracks, int n_steps, const int* flag, const int
 int vpl_odo_debug_parallax_list(int max_tracks, int n_steps, const int* flag, const int* n_ids, const int* ids,
                                 const unsigned char* erase, int* n_list, int* list, int* last_track_num);
 
+/* ---- read-out of one window's linearisation and trust-region step (tests/test_gpu_step_kernels.py) ------------------------ *
+ * Debug access to the buffers the step kernels read and write, for window `window` of the uploaded batch.  Both calls complete
+ * whatever is enqueued on the context, wait for its stream, copy device buffers and launch nothing.  The window's full index
+ * has n = 171 + n_points + 4 n_lines entries: the cam dims (frame f: pose 15 f + 0..5, speed/bias 15 f + 6..14; extrinsic
+ * 165..170), the inverse depths in the window's track order, the orthonormal line parameters in fours -- of the lines that
+ * travelled: device line l is the caller's line line_index[l] (untriangulated lines take no part in a solve).  Both return n,
+ * or a VPL_E_* code.
+ * vpl_ba_debug_linearization: H [n][n] (dense, symmetric: the packed camera Hessian, the landmark blocks and the compact W rows
+ * expanded on the host) and g [n] of the last linearisation; the current states x_pose [11][7], x_speed_bias [11][9],
+ * x_ex_pose [7], x_inv_depth [n_points], x_line_orth [n_lines][4] (world frame) and the cost at x.  With H or g NULL only the
+ * counts and line_index (n_lines entries, may be NULL) are written: call it once to size the arrays.
+ * vpl_ba_debug_step: jacobi scale, diagonal, scaled gradient and Gauss-Newton step of the last iteration ([n] each);
+ * tr14 = radius, mu, alpha, a1 (|gradient|^2), a2 (|gn|^2), a3 (gradient . gn), model_cost_change, dogleg_step_norm, step_norm,
+ * x_norm, iter, status, num_successful, step_valid (1 between the step kernel and k_cost, which clears it: 0 after a solve);
+ * path (0: k_schur / k_chol / k_back, 1: k_solve for the whole solve,
+ * 2: k_solve for this iteration) and the candidate states, shaped like x_*.  Any output pointer may be NULL. */
+int vpl_ba_debug_linearization(vpl_ctx* ctx, int window, int* n_points, int* n_lines, int* line_index, double* H, double* g,
+                               double* x_pose, double* x_speed_bias, double* x_ex_pose, double* x_inv_depth, double* x_line_orth,
+                               double* x_cost);
+int vpl_ba_debug_step(vpl_ctx* ctx, int window, double* scale, double* diag, double* grad, double* gn, double* tr14, int* path,
+                      double* cand_pose, double* cand_speed_bias, double* cand_ex_pose, double* cand_inv_depth,
+                      double* cand_line_orth);
+
 /* ---- instrumentation (bench.py) ------------------------------------------ */
 /* Per-kernel device time of the last solve measured with hipEvents on the
  * context's stream. names/ms arrays of length *count on input; count updated. */

@@ -383,6 +383,8 @@ def load_hip_library():
     lib.vpl_failure_detection.argtypes = [C.POINTER(FailureLimits), _dp, _dp, _dp]
     lib.vpl_odo_debug_parallax_list.argtypes = [C.c_int, C.c_int, _ip, _ip, _ip, C.POINTER(C.c_ubyte), _ip, _ip, _ip]
     lib.vpl_ba_debug_marg_Ab.argtypes = [vp, C.c_int, _dp, _dp]
+    lib.vpl_ba_debug_linearization.argtypes = [vp, C.c_int, _ip, _ip, _ip] + [_dp] * 8
+    lib.vpl_ba_debug_step.argtypes = [vp, C.c_int] + [_dp] * 5 + [_ip] + [_dp] * 5
     lib.vpl_ba_debug_allocs.argtypes = [vp, _llp, _llp]
     lib.vpl_ba_debug_psd_factor.argtypes = [vp, C.c_int, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _ip, _ip, _dp, _dp]
     _hip = lib
@@ -444,6 +446,54 @@ class Context:
             return rc
         return [(int(rank[i]), perm[i, : ns[i]].copy(), J0[i, : ns[i] * ns[i]].reshape(ns[i], ns[i]).copy(), r0[i, : ns[i]].copy())
                 for i in range(N)]
+
+    TR_FIELDS = ("radius", "mu", "alpha", "a1", "a2", "a3", "model_cost_change", "dogleg_step_norm", "step_norm", "x_norm",
+                 "iter", "status", "num_successful", "step_valid")      # tr14 of vpl_ba_debug_step, the last four integers
+
+    def _debug_counts(self, w):
+        nP, nL = C.c_int(0), C.c_int(0)
+        n = self.lib.vpl_ba_debug_linearization(self.h, w, C.byref(nP), C.byref(nL), *([None] * 9))
+        if n < 0:
+            self._check(n, "vpl_ba_debug_linearization")
+        return n, nP.value, nL.value
+
+    def debug_linearization(self, w):
+        """vpl_ba_debug_linearization: the linearisation of window w of the uploaded batch as the step kernels read it.  -> dict:
+        n, n_points, n_lines, line_index [n_lines] (the caller's index of every device line), H [n, n], g [n] over the window's
+        full index (171 cam dims | inverse depths | line dims in fours), the current states pose [11, 7], speed_bias [11, 9],
+        ex_pose [7], inv_depth [n_points], line_orth [n_lines, 4] and x_cost."""
+        self._settle()
+        n, nP, nL = self._debug_counts(w)
+        idx = np.zeros(max(nL, 1), np.int32)
+        H, g = np.zeros((n, n)), np.zeros(n)
+        pose, sb, ex = np.zeros((NF, 7)), np.zeros((NF, 9)), np.zeros(7)
+        invd, orth, cost = np.zeros(max(nP, 1)), np.zeros((max(nL, 1), 4)), np.zeros(1)
+        rc = self.lib.vpl_ba_debug_linearization(self.h, w, None, None, idx.ctypes.data_as(_ip), _p(H), _p(g), _p(pose), _p(sb),
+                                                 _p(ex), _p(invd), _p(orth), _p(cost))
+        if rc != n:
+            self._check(rc if rc < 0 else -1, "vpl_ba_debug_linearization")
+        return dict(n=n, n_points=nP, n_lines=nL, line_index=idx[:nL].copy(), H=H, g=g, pose=pose, speed_bias=sb, ex_pose=ex,
+                    inv_depth=invd[:nP].copy(), line_orth=orth[:nL].copy(), x_cost=float(cost[0]))
+
+    def debug_step(self, w):
+        """vpl_ba_debug_step: the step of the last iteration of window w.  -> dict: n, scale / diag / grad / gn [n], the TR_FIELDS
+        of the trust-region state (floats, the last four ints), path, and the candidate states pose_c [11, 7], speed_bias_c
+        [11, 9], ex_pose_c [7], inv_depth_c [n_points], line_orth_c [n_lines, 4]."""
+        self._settle()
+        n, nP, nL = self._debug_counts(w)
+        scale, diag, grad, gn = (np.zeros(n) for _ in range(4))
+        tr, path = np.zeros(14), C.c_int(-1)
+        pose, sb, ex = np.zeros((NF, 7)), np.zeros((NF, 9)), np.zeros(7)
+        invd, orth = np.zeros(max(nP, 1)), np.zeros((max(nL, 1), 4))
+        rc = self.lib.vpl_ba_debug_step(self.h, w, _p(scale), _p(diag), _p(grad), _p(gn), _p(tr), C.byref(path), _p(pose), _p(sb),
+                                        _p(ex), _p(invd), _p(orth))
+        if rc != n:
+            self._check(rc if rc < 0 else -1, "vpl_ba_debug_step")
+        out = dict(n=n, scale=scale, diag=diag, grad=grad, gn=gn, path=path.value, pose_c=pose, speed_bias_c=sb, ex_pose_c=ex,
+                   inv_depth_c=invd[:nP].copy(), line_orth_c=orth[:nL].copy())
+        for k, f in enumerate(self.TR_FIELDS):
+            out[f] = float(tr[k]) if k < 10 else int(tr[k])
+        return out
 
     def close(self):
         if self.h:

@@ -1053,6 +1053,149 @@ int vpl_ba_debug_marg_Ab(vpl_ctx* c, int w, double* A, double* b) {
   return n;
 }
 
+// Debug/test access to what the trust-region step kernels read and write for ONE window of the uploaded batch (tests/
+// test_gpu_step_kernels.py): both calls complete whatever is enqueued on the context, wait for its stream, copy device
+// buffers and launch nothing.  Full index of the window: 171 cam dims | nP inverse depths | 4 nL line dims -- the window's own
+// counts, not the context's strides; device line l is the caller's line line_index[l] (untriangulated lines do not travel).
+static int debug_window_ready(vpl_ctx* c, int w) {
+  if (!c) return VPL_E_INVALID;
+  const int rs = settle(c);
+  if (rs) return rs;
+  if (c->upload_open || w < 0 || w >= c->nW || (size_t)w >= c->h_nP.size() || (size_t)w >= c->h_lmap.size())
+    return fail(c, VPL_E_INVALID, "debug read-out: no such window in the uploaded batch");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return VPL_OK;
+}
+static hipError_t debug_fetch_d(std::vector<double>& dst, const double* src, size_t n) {
+  dst.assign(n ? n : 1, 0.0);
+  return n ? hipMemcpy(dst.data(), src, n * 8, hipMemcpyDeviceToHost) : hipSuccess;
+}
+static hipError_t debug_fetch_i(std::vector<int>& dst, const int* src, size_t n) {
+  dst.assign(n ? n : 1, 0);
+  return n ? hipMemcpy(dst.data(), src, n * 4, hipMemcpyDeviceToHost) : hipSuccess;
+}
+// the five state arrays of window w (x: B.pose ..., the candidate: B.pose_c ...) in the window's own counts
+static int debug_states(vpl_ctx* c, int w, int nP, int nL, const double* dpose, const double* dsb, const double* dex,
+                        const double* dinvd, const double* dorth, double* pose, double* sb, double* ex, double* invd, double* orth) {
+  const DevBatch& B = c->B;
+  if (pose) HIPCHK(c, hipMemcpy(pose, dpose + (size_t)w * 77, 77 * 8, hipMemcpyDeviceToHost));
+  if (sb) HIPCHK(c, hipMemcpy(sb, dsb + (size_t)w * 99, 99 * 8, hipMemcpyDeviceToHost));
+  if (ex) HIPCHK(c, hipMemcpy(ex, dex + (size_t)w * 7, 7 * 8, hipMemcpyDeviceToHost));
+  if (invd && nP) HIPCHK(c, hipMemcpy(invd, dinvd + (size_t)w * B.maxP, (size_t)nP * 8, hipMemcpyDeviceToHost));
+  if (orth && nL) HIPCHK(c, hipMemcpy(orth, dorth + (size_t)w * B.maxL * 4, (size_t)nL * 4 * 8, hipMemcpyDeviceToHost));
+  return VPL_OK;
+}
+// a vector over the context's full index [171 | maxP | 4 maxL] -> the window's [171 | nP | 4 nL]
+static int debug_full_vector(vpl_ctx* c, int w, int nP, int nL, const double* dsrc, double* out) {
+  if (!out) return VPL_OK;
+  const DevBatch& B = c->B;
+  const double* src = dsrc + (size_t)w * B.nfull;
+  HIPCHK(c, hipMemcpy(out, src, NC * 8, hipMemcpyDeviceToHost));
+  if (nP) HIPCHK(c, hipMemcpy(out + NC, src + NC, (size_t)nP * 8, hipMemcpyDeviceToHost));
+  if (nL) HIPCHK(c, hipMemcpy(out + NC + nP, src + NC + B.maxP, (size_t)nL * 4 * 8, hipMemcpyDeviceToHost));
+  return VPL_OK;
+}
+
+// The linearisation k_lin left for window w, expanded on the host into the dense symmetric H [n][n] and g [n] over the full
+// index: the packed camera Hessian, the diagonal landmark blocks, and the compact W rows of every landmark spread over the
+// camera columns of the frames they cover (wcol, vis2cam).  Slots of a compact row that no factor writes are read like every
+// other: the step kernels read them too.  x_*: the current states, x_cost: TrState::x_cost.  Returns n; H = NULL: only the
+// counts (n_points, n_lines) and n, nothing is read from the device.
+int vpl_ba_debug_linearization(vpl_ctx* c, int w, int* n_points, int* n_lines, int* line_index, double* H, double* g,
+                               double* x_pose, double* x_speed_bias, double* x_ex_pose, double* x_inv_depth, double* x_line_orth,
+                               double* x_cost) {
+  const int rc = debug_window_ready(c, w);
+  if (rc) return rc;
+  const DevBatch& B = c->B;
+  const int nP = c->h_nP[w], nL = (int)c->h_lmap[w].size();
+  const int n = NC + nP + 4 * nL;
+  if (nP < 0 || nP > B.maxP || nL > B.maxL) return fail(c, VPL_E_INVALID, "debug read-out: counts outside the context's capacity");
+  if (n_points) *n_points = nP;
+  if (n_lines) *n_lines = nL;
+  if (line_index) for (int l = 0; l < nL; ++l) line_index[l] = c->h_lmap[w][l];
+  if (!H || !g) return n;
+  const int WS = B.WS;
+  std::vector<double> Hcc, gc, Hpp, gp, Wp, Hll, gl, Wl;
+  std::vector<int> ps, ls;
+  HIPCHK(c, debug_fetch_d(Hcc, B.Hcc + (size_t)w * NCP, NCP));
+  HIPCHK(c, debug_fetch_d(gc, B.gc + (size_t)w * NC, NC));
+  HIPCHK(c, debug_fetch_d(Hpp, B.Hpp + (size_t)w * B.maxP, nP));
+  HIPCHK(c, debug_fetch_d(gp, B.gp + (size_t)w * B.maxP, nP));
+  HIPCHK(c, debug_fetch_d(Wp, B.Wp + (size_t)w * B.maxP * WS, (size_t)nP * WS));
+  HIPCHK(c, debug_fetch_d(Hll, B.Hll + (size_t)w * B.maxL * 16, (size_t)nL * 16));
+  HIPCHK(c, debug_fetch_d(gl, B.gl + (size_t)w * B.maxL * 4, (size_t)nL * 4));
+  HIPCHK(c, debug_fetch_d(Wl, B.Wl + (size_t)w * B.maxL * 4 * WS, (size_t)nL * 4 * WS));
+  HIPCHK(c, debug_fetch_i(ps, B.pt_start + (size_t)w * B.maxP, nP));
+  HIPCHK(c, debug_fetch_i(ls, B.ln_start + (size_t)w * B.maxL, nL));
+  std::fill(H, H + (size_t)n * n, 0.0);
+  auto put = [&](int r, int k, double v) { H[(size_t)r * n + k] = v; H[(size_t)k * n + r] = v; };
+  for (int r = 0; r < NC; ++r) {
+    g[r] = gc[r];
+    for (int k = 0; k <= r; ++k) put(r, k, Hcc[tri(r, k)]);
+  }
+  for (int p = 0; p < nP; ++p) {
+    const int k = NC + p;
+    g[k] = gp[p];
+    H[(size_t)k * n + k] = Hpp[p];
+    if (ps[p] < 0 || ps[p] >= NF) return fail(c, VPL_E_INVALID, "debug read-out: start frame of a point track outside the window");
+    for (int v = 0; v < NV; ++v) {
+      const int cc = wcol(v, ps[p], WS);
+      if (cc >= 0) put(vis2cam(v), k, Wp[(size_t)p * WS + cc]);
+    }
+  }
+  for (int l = 0; l < nL; ++l) {
+    if (ls[l] < 0 || ls[l] >= NF) return fail(c, VPL_E_INVALID, "debug read-out: start frame of a line track outside the window");
+    for (int a = 0; a < 4; ++a) {
+      const int k = NC + nP + 4 * l + a;
+      g[k] = gl[4 * l + a];
+      for (int b = 0; b < 4; ++b) H[(size_t)k * n + NC + nP + 4 * l + b] = Hll[16 * l + 4 * a + b];
+      for (int v = 0; v < NV; ++v) {
+        const int cc = wcol(v, ls[l], WS);
+        if (cc >= 0) put(vis2cam(v), k, Wl[((size_t)l * 4 + a) * WS + cc]);
+      }
+    }
+  }
+  const int rs = debug_states(c, w, nP, nL, B.pose, B.sb, B.ex, B.invd, B.orth, x_pose, x_speed_bias, x_ex_pose, x_inv_depth, x_line_orth);
+  if (rs) return rs;
+  if (x_cost) {
+    TrState t;
+    HIPCHK(c, hipMemcpy(&t, B.tr + w, sizeof(t), hipMemcpyDeviceToHost));
+    *x_cost = t.x_cost;
+  }
+  return n;
+}
+
+// The step the kernels of the last iteration computed for window w: jacobi scale, diagonal_, gradient_ and the Gauss-Newton step
+// over the full index ([n] each, n as above), the trust-region state as 14 doubles (radius, mu, alpha, a1, a2, a3,
+// model_cost_change, dogleg_step_norm, step_norm, x_norm, iter, status, num_successful, step_valid), the window's path flag
+// and the candidate states.  Returns n.
+int vpl_ba_debug_step(vpl_ctx* c, int w, double* scale, double* diag, double* grad, double* gn, double* tr14, int* path,
+                      double* cand_pose, double* cand_speed_bias, double* cand_ex_pose, double* cand_inv_depth,
+                      double* cand_line_orth) {
+  const int rc = debug_window_ready(c, w);
+  if (rc) return rc;
+  const DevBatch& B = c->B;
+  const int nP = c->h_nP[w], nL = (int)c->h_lmap[w].size();
+  if (nP < 0 || nP > B.maxP || nL > B.maxL) return fail(c, VPL_E_INVALID, "debug read-out: counts outside the context's capacity");
+  int rs = debug_full_vector(c, w, nP, nL, B.scale, scale);
+  if (!rs) rs = debug_full_vector(c, w, nP, nL, B.diag, diag);
+  if (!rs) rs = debug_full_vector(c, w, nP, nL, B.grad, grad);
+  if (!rs) rs = debug_full_vector(c, w, nP, nL, B.gn, gn);
+  if (rs) return rs;
+  if (tr14) {
+    TrState t;
+    HIPCHK(c, hipMemcpy(&t, B.tr + w, sizeof(t), hipMemcpyDeviceToHost));
+    const double v[14] = {t.radius, t.mu, t.alpha, t.a1, t.a2, t.a3, t.model_cost_change, t.dogleg_step_norm, t.step_norm, t.x_norm,
+                          (double)t.iter, (double)t.status, (double)t.num_successful, (double)t.step_valid};
+    std::memcpy(tr14, v, sizeof(v));
+  }
+  if (path) HIPCHK(c, hipMemcpy(path, B.path + w, 4, hipMemcpyDeviceToHost));
+  rs = debug_states(c, w, nP, nL, B.pose_c, B.sb_c, B.ex_c, B.invd_c, B.orth_c, cand_pose, cand_speed_bias, cand_ex_pose,
+                    cand_inv_depth, cand_line_orth);
+  return rs ? rs : NC + nP + 4 * nL;
+}
+
 // Debug/test access to the pivoted Cholesky factorisations of ba_marg.h on caller-supplied matrices (k_psd_factor): n_cases
 // work-groups in one launch.  form 0: psd_pivoted_cholesky_wave<16> (256 threads, n <= 16); 1: _wave<48> (256 or 512, n <= 48);
 // 2: _wave4<19, 4> (512, n <= 76: on fewer than eight waves it would wait out its poll limit); 3: the work-group version (256 or
