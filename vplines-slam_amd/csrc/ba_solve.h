@@ -12,6 +12,7 @@
 //    FunctionToleranceReached, IsStepSuccessful, HandleSuccessfulStep, HandleUnsuccessfulStep}).
 #pragma once
 #include "ba_common.h"
+#include "ba_trust.h"
 
 namespace vpl {
 
@@ -23,11 +24,6 @@ constexpr int NAP = NTILES * 256;            // tile-major lower storage of the 
 constexpr int TK = 16;                       // rows of the landmark tile staged per pass
 constexpr int TW = NV + 1;                   // tile width: 72 vis dims + rhs column
 constexpr int NB3 = 25;                      // 3-wide output blocks over the 73(+2 pad) tile columns
-
-// ceres defaults (solver.h, 1.12)
-constexpr double kMinDiag = 1e-6, kMaxDiag = 1e32, kMaxMu = 1.0, kMuIncrease = 10.0;
-constexpr double kMinRelDecrease = 1e-3, kFuncTol = 1e-6, kParamTol = 1e-8, kMinRadius = 1e-32;
-constexpr int kMaxInvalid = 5;
 
 __device__ __forceinline__ int tcol2row(int a) { return a < NV ? vis2cam(a) : NC; }
 // Offset of element (r, c) inside a 16x16 tile.  Rows are XOR-swizzled: a column read by 16 lanes (the MFMA operands,
@@ -220,25 +216,6 @@ constexpr int CW = 80;             // staged row width (doubles)
 constexpr int CROWS = 64;          // landmark rows per staged chunk
 constexpr int NCT = 15;            // lower tiles of the 5x5 compact tile grid
 
-__device__ __forceinline__ void chol4(double* A, bool& ok) {   // packed lower 4x4, in place
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    double d = A[tri(j, j)];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) if (k < j) d -= A[tri(j, k)] * A[tri(j, k)];
-    if (!(d > 0.0)) { ok = false; d = 1.0; }
-    d = sqrt(d);
-    A[tri(j, j)] = d;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) if (i > j) {
-      double s2 = A[tri(i, j)];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) if (k < j) s2 -= A[tri(i, k)] * A[tri(j, k)];
-      A[tri(i, j)] = s2 / d;
-    }
-  }
-}
-
 // (returns whether the window took this path)
 __device__ __forceinline__ bool solve_body(const DevBatch& B, const int w, double* sm) {
   const int tid = threadIdx.x, T = SOLVE_THREADS;
@@ -283,98 +260,12 @@ __device__ __forceinline__ bool solve_body(const DevBatch& B, const int w, doubl
   VPL_STAMP(B, w, 0);
   if (!reuse0) {
     // ---- jacobi scaling (iteration 0 only), diagonal_, gradient_ --------------------------
-    const bool first = (tr->iter == 0);
-    // What the scaling works out for the landmarks (scale, diagonal, gradient, and their H blocks) is also left in LDS, in the
-    // space of the staging buffers (free until the first chunk is staged): the landmark constants of the first factorisation
-    // attempt read it there instead of loading back from HBM what was stored a moment ago.  A retry with a larger mu reloads.
+    // The landmark constants it leaves in LDS take the space of the staging buffers (free until the first chunk is staged):
+    // the first factorisation attempt reads them there.  A retry with a larger mu reloads from HBM.
     double* kP = S;                          // nP x 4: s, d, g, H_pp
     double* kL = S + 4 * B.maxP;             // nL x 28: s(4), d(4), g(4), H_ll(16)
     double a1 = 0.0, q = 0.0;
-    // The inputs of this thread's first point and first line are requested BEFORE the camera entries are worked out and
-    // stored: the three loops below otherwise pay three global round trips back to back (the compiler may not move the
-    // later loops' loads above the earlier loops' stores).  Same arithmetic, same order.
-    double pre_hp = 0.0, pre_sp = 0.0, pre_gp = 0.0, pre_Hl[16], pre_sl[4], pre_gl[4];
-    if (tid < nP) {
-      const size_t pi = (size_t)w * B.maxP + tid;
-      pre_hp = B.Hpp[pi]; pre_gp = B.gp[pi];
-      if (!first) pre_sp = gscale[LP + tid];
-    }
-#pragma unroll
-    for (int k = 0; k < 16; ++k) pre_Hl[k] = 0.0;
-#pragma unroll
-    for (int a = 0; a < 4; ++a) { pre_sl[a] = 0.0; pre_gl[a] = 0.0; }
-    if (tid < nL) {
-      const size_t li = (size_t)w * B.maxL + tid;
-#pragma unroll
-      for (int k = 0; k < 16; ++k) pre_Hl[k] = B.Hll[li * 16 + k];
-#pragma unroll
-      for (int a = 0; a < 4; ++a) {
-        pre_gl[a] = B.gl[li * 4 + a];
-        if (!first) pre_sl[a] = gscale[LL + 4 * tid + a];
-      }
-    }
-    for (int c = tid; c < 176; c += T) {
-      double s = 0.0, d = 1.0, g = 0.0;
-      if (c < NC) {
-        const double h = Hcc[tri(c, c)];
-        s = first ? 1.0 / (1.0 + sqrt(h)) : gscale[c];
-        if (first) gscale[c] = s;
-        d = sqrt(fmin(fmax(s * s * h, kMinDiag), kMaxDiag));
-        g = s * gc[c] / d;
-        gdiag[c] = d; ggrad[c] = g;
-        a1 += g * g;
-      }
-      sc[c] = s; dg[c] = d;
-      uc[c] = s * g / d;   // unscaled-space vector of gradient_/diagonal_
-    }
-    for (int p = tid; p < nP; p += T) {
-      const size_t pi = (size_t)w * B.maxP + p;
-      const bool pre = p == tid;   // this thread's first point was requested together with its camera entry (above)
-      const double h = pre ? pre_hp : B.Hpp[pi];
-      const double s = first ? 1.0 / (1.0 + sqrt(h)) : (pre ? pre_sp : gscale[LP + p]);
-      if (first) gscale[LP + p] = s;
-      const double d = sqrt(fmin(fmax(s * s * h, kMinDiag), kMaxDiag));
-      const double g = s * (pre ? pre_gp : B.gp[pi]) / d;
-      gdiag[LP + p] = d; ggrad[LP + p] = g;
-      kP[4 * p] = s; kP[4 * p + 1] = d; kP[4 * p + 2] = g; kP[4 * p + 3] = h;
-      a1 += g * g;
-      const double u = s * g / d;
-      q += u * h * u;
-    }
-    for (int l = tid; l < nL; l += T) {
-      const size_t li = (size_t)w * B.maxL + l;
-      const bool pre = l == tid;
-      double Hl[16], sl4[4], gl4[4];
-#pragma unroll
-      for (int k = 0; k < 16; ++k) Hl[k] = pre ? pre_Hl[k] : B.Hll[li * 16 + k];
-#pragma unroll
-      for (int a = 0; a < 4; ++a) {
-        sl4[a] = first ? 0.0 : (pre ? pre_sl[a] : gscale[LL + 4 * l + a]);
-        gl4[a] = pre ? pre_gl[a] : B.gl[li * 4 + a];
-      }
-      double u[4];
-#pragma unroll
-      for (int a = 0; a < 4; ++a) {
-        const double h = Hl[5 * a];
-        const double s = first ? 1.0 / (1.0 + sqrt(h)) : sl4[a];
-        if (first) gscale[LL + 4 * l + a] = s;
-        const double d = sqrt(fmin(fmax(s * s * h, kMinDiag), kMaxDiag));
-        const double g = s * gl4[a] / d;
-        gdiag[LL + 4 * l + a] = d; ggrad[LL + 4 * l + a] = g;
-        kL[28 * l + a] = s; kL[28 * l + 4 + a] = d; kL[28 * l + 8 + a] = g;
-        a1 += g * g;
-        u[a] = s * g / d;
-      }
-#pragma unroll
-      for (int k = 0; k < 16; ++k) kL[28 * l + 12 + k] = Hl[k];
-#pragma unroll
-      for (int a = 0; a < 4; ++a) {
-        double hu = 0;
-#pragma unroll
-        for (int b = 0; b < 4; ++b) hu += Hl[4 * a + b] * u[b];
-        q += u[a] * hu;
-      }
-    }
+    scale_and_gradient<T, true>(B, w, tr->iter == 0, kP, kL, uc, sc, dg, a1, q);
     a1 = block_sum(a1, red);
     q = block_sum(q, red);
     VPL_STAMP(B, w, 1);
@@ -409,8 +300,6 @@ __device__ __forceinline__ bool solve_body(const DevBatch& B, const int w, doubl
       // C C^T -> C to lch (the back substitution reads it) and, pre-divided, to LDS.  ONE pass per landmark kind, every
       // HBM operand requested before the arithmetic: as two passes with the row scale / factor handed over through HBM the
       // second one waited for the first one's stores and then for its own loads.
-      const double* kP = S;                  // (see the scaling phase)
-      const double* kL = S + 4 * B.maxP;
       for (int p = tid; p < nP; p += T) {
         const size_t pi = (size_t)w * B.maxP + p;
         double s, d, g, h;
@@ -437,36 +326,7 @@ __device__ __forceinline__ bool solve_body(const DevBatch& B, const int w, doubl
           for (int a = 0; a < 4; ++a) { s4[a] = gscale[LL + 4 * l + a]; d4[a] = gdiag[LL + 4 * l + a]; g4[a] = ggrad[LL + 4 * l + a]; }
         }
         double A[10];
-        int t = 0;
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-          for (int b = 0; b < 4; ++b) if (b <= a) {
-            A[t] = s4[a] * s4[b] * Hl[4 * a + b];
-            if (a == b) A[t] += mu * d4[a] * d4[a];
-            ++t;
-          }
-        bool ok = true;
-        chol4(A, ok);
-        if (!ok) flag[0] = 1;
-        double us[4];
-#pragma unroll
-        for (int k = 0; k < 10; ++k) { lch[l * 10 + k] = A[k]; lC[l * 10 + k] = A[k]; }
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-          const double rd = 1.0 / A[tri(a, a)];
-          lS[4 * l + a] = s4[a] * rd;   // x_a = (s_a w_a - sum_q C_aq x_q) / C_aa = lS_a w_a - sum_q (C_aq / C_aa) x_q
-          us[a] = g4[a] / d4[a];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) if (q < a) lC[l * 10 + tri(a, q)] = A[tri(a, q)] * rd;
-        }
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-          double s2 = 0;
-#pragma unroll
-          for (int q = 0; q < 4; ++q) if (q >= a) s2 += A[tri(q, a)] * us[q];
-          lE[4 * l + a] = s2;
-        }
+        if (!line_block(s4, d4, g4, Hl, mu, l, lch, lC, lS, lE, A)) flag[0] = 1;
       }
       __syncthreads();
       // Loads first, arithmetic and LDS stores after: a loop that stores each element before loading the next one
@@ -661,17 +521,8 @@ __device__ __forceinline__ bool solve_body(const DevBatch& B, const int w, doubl
       break;
     }
     if (!solved) {
-      // every mu < 1 failed: invalid step (TrustRegionMinimizer::HandleInvalidStep)
-      if (tid == 0) {
-        tr->mu = mu;
-        tr->step_valid = 0;
-        tr->iter += 1;
-        tr->num_invalid += 1;
-        if (tr->num_invalid >= kMaxInvalid) { tr->status = 2; tr->iter -= 1; }   // FAILURE breaks before the iteration is recorded
-        else if (tr->iter >= B.opt.num_iterations) tr->status = 3;
-        tr->mu *= kMuIncrease;   // StepIsInvalid
-        tr->reuse = 0;
-      }
+      // every mu < 1 failed: invalid step
+      if (tid == 0) { tr->mu = mu; handle_invalid_step(B, tr); }
       return true;
     }
     VPL_STAMP(B, w, 4);
@@ -690,118 +541,11 @@ __device__ __forceinline__ bool solve_body(const DevBatch& B, const int w, doubl
     }
     __syncthreads();
     VPL_STAMP(B, w, 8);
-    // ---- landmark back substitution y_l = A_l^-1 S_l (g_l - W_l S_c y_c): 8 lanes per landmark row so
-    //      that every 72-wide row of W is read as one contiguous 576-byte segment
-    {
-      const int sub = lane & 7, grp = tid >> 3;   // 64 row groups per pass
-      const int nblk = WS / 6;
-      for (int p0 = 0; p0 < nP; p0 += 2 * (T / 8)) {   // two row groups per trip: their loads are in flight together
-        double wyv[2] = {0.0, 0.0}, sv[2], dv[2], hv[2], gv2[2], grv[2];
-        size_t piv[2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const int p = p0 + h * (T / 8) + grp;
-          piv[h] = (size_t)w * B.maxP + (p < nP ? p : 0);
-          sv[h] = dv[h] = 1.0; hv[h] = gv2[h] = grv[h] = 0.0;
-          if (p < nP) {
-            // compact row: 6-blocks of the frames start .. start + maxTrack - 1, then the extrinsic block
-            const int s0 = pSt[p];
-            for (int blk = sub; blk < nblk; blk += 8) {
-              const bool exb = blk == nblk - 1;
-              const int vb = exb ? 66 : 6 * (s0 + blk);
-              if (!exb && vb >= 66) continue;               // slot of a frame past the window
-              const double* Wr = B.Wp + piv[h] * WS + 6 * blk;
-#pragma unroll
-              for (int k = 0; k < 6; ++k) wyv[h] += Wr[k] * uc[vis2cam(vb + k)];
-            }
-            if (sub == 0) {
-              sv[h] = gscale[LP + p]; dv[h] = gdiag[LP + p]; hv[h] = B.Hpp[piv[h]]; gv2[h] = B.gp[piv[h]];
-              grv[h] = ggrad[LP + p];
-            }
-          }
-        }
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const int p = p0 + h * (T / 8) + grp;
-          double wy = wyv[h];
-          wy += __shfl_xor(wy, 1, 64); wy += __shfl_xor(wy, 2, 64); wy += __shfl_xor(wy, 4, 64);
-          if (p < nP && sub == 0) {
-            const double s = sv[h], d = dv[h];
-            const double Al = s * s * hv[h] + mu * d * d;
-            const double y = s * (gv2[h] - wy) / Al;
-            const double gnv = -d * y;
-            ggn[LP + p] = gnv; lgn[LP + p] = gnv;
-            a2 += gnv * gnv;
-            a3 += grv[h] * gnv;
-          }
-        }
-      }
-      VPL_STAMP(B, w, 9);
-      // lines: NLH row groups per trip, each row's W entries and g_l requested together; the rows' right-hand sides
-      // s (g_l - W_l u_c) go to LDS (the reduced system's space is free by now) and ONE pass with a lane per line does the
-      // 4x4 triangular solves -- done by the leader lane of each group they were a chain of 8 divisions per 64 rows
-      double* lrhs = S;
-      constexpr int NLH = 3;
-      for (int r0 = 0; r0 < 4 * nL; r0 += NLH * (T / 8)) {
-        double wyv[NLH], glv[NLH];
-#pragma unroll
-        for (int h = 0; h < NLH; ++h) {
-          const int r = r0 + h * (T / 8) + grp, l = r >> 2, a = r & 3;
-          wyv[h] = 0.0; glv[h] = 0.0;
-          if (l < nL) {
-            const size_t li = (size_t)w * B.maxL + l;
-            const int s0 = lSt[l];
-            for (int blk = sub; blk < nblk; blk += 8) {
-              const bool exb = blk == nblk - 1;
-              const int vb = exb ? 66 : 6 * (s0 + blk);
-              if (!exb && vb >= 66) continue;
-              const double* Wr = B.Wl + (li * 4 + a) * WS + 6 * blk;
-#pragma unroll
-              for (int k = 0; k < 6; ++k) wyv[h] += Wr[k] * uc[vis2cam(vb + k)];
-            }
-            if (sub == 0) glv[h] = B.gl[li * 4 + a];
-          }
-        }
-#pragma unroll
-        for (int h = 0; h < NLH; ++h) {
-          const int r = r0 + h * (T / 8) + grp;
-          double wy = wyv[h];
-          wy += __shfl_xor(wy, 1, 64); wy += __shfl_xor(wy, 2, 64); wy += __shfl_xor(wy, 4, 64);
-          if (r < 4 * nL && sub == 0) lrhs[r] = gscale[LL + r] * (glv[h] - wy);
-        }
-      }
-      __syncthreads();
-      for (int l = tid; l < nL; l += T) {
-        double C[10], t4[4], gd4[4], gr4[4];   // the factor, diagonal and gradient come from HBM: one batch, before the chain
-#pragma unroll
-        for (int k = 0; k < 10; ++k) C[k] = lch[l * 10 + k];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { gd4[k] = gdiag[LL + 4 * l + k]; gr4[k] = ggrad[LL + 4 * l + k]; }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) t4[k] = lrhs[4 * l + k];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          double s2 = t4[k];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) if (j < k) s2 -= C[tri(k, j)] * t4[j];
-          t4[k] = s2 / C[tri(k, k)];
-        }
-#pragma unroll
-        for (int k = 3; k >= 0; --k) {
-          double s2 = t4[k];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) if (j > k) s2 -= C[tri(j, k)] * t4[j];
-          t4[k] = s2 / C[tri(k, k)];
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const double gnv = -gd4[k] * t4[k];
-          ggn[LL + 4 * l + k] = gnv; lgn[LL + 4 * l + k] = gnv;
-          a2 += gnv * gnv;
-          a3 += gr4[k] * gnv;
-        }
-      }
-    }
+    // ---- landmark back substitution y_l = A_l^-1 S_l (g_l - W_l S_c y_c); the lines' right-hand sides go to S (the reduced
+    //      system's space is free by now)
+    back_substitute_points<T, 2, true>(B, w, mu, uc, pSt, lgn, a2, a3);
+    VPL_STAMP(B, w, 9);
+    back_substitute_lines<T, 3, true>(B, w, uc, lSt, S, lgn, a2, a3);
     VPL_STAMP(B, w, 10);
     a2 = block_sum(a2, red);
     a3 = block_sum(a3, red);
@@ -815,113 +559,12 @@ __device__ __forceinline__ bool solve_body(const DevBatch& B, const int w, doubl
   }
 
   VPL_STAMP(B, w, 6);
-  // ---- DoglegStrategy::ComputeTraditionalDoglegStep ---------------------------------------------
-  const double radius = tr->radius, alpha = tr->alpha, a1 = tr->a1, a2 = tr->a2, a3 = tr->a3, mu = tr->mu;
-  const double gradient_norm = sqrt(a1), gauss_newton_norm = sqrt(a2);
-  double c1, c2, dnorm;   // step (scaled space, before /diag) = -c1 * gradient_ + c2 * gauss_newton_step
-  if (gauss_newton_norm <= radius) {
-    c1 = 0.0; c2 = 1.0; dnorm = gauss_newton_norm;
-  } else if (gradient_norm * alpha >= radius) {
-    c1 = radius / gradient_norm; c2 = 0.0; dnorm = radius;
-  } else {
-    const double b_dot_a = -alpha * a3;
-    const double a_sq = (alpha * gradient_norm) * (alpha * gradient_norm);
-    const double bma = a_sq - 2 * b_dot_a + a2;
-    const double c = b_dot_a - a_sq;
-    const double d = sqrt(c * c + bma * (radius * radius - a_sq));
-    const double beta = (c <= 0) ? (d - c) / bma : (radius * radius - a_sq) / (d + c);
-    c1 = alpha * (1.0 - beta); c2 = beta;
-    dnorm = sqrt(c1 * c1 * a1 - 2.0 * c1 * c2 * a3 + c2 * c2 * a2);
-  }
-  // model_cost_change = -(step^T gs + 1/2 step^T Hs step) with Hs y = gs - mu D^2 y folded in
-  //   step = -c1 v - c2 y,  v = gradient_/diag, y = -gn/diag
-  const double q_cauchy = a1 / alpha;                 // v^T Hs v
-  const double sg = -c1 * a1 + c2 * a3;               // step^T gs
-  const double vHy = a1 + mu * a3;
-  const double yHy = -a3 - mu * a2;
-  const double sHs = c1 * c1 * q_cauchy + 2.0 * c1 * c2 * vHy + c2 * c2 * yHy;
-  const double model_cost_change = -(sg + 0.5 * sHs);
-  const bool valid = model_cost_change > 0.0;
-
-  if (!valid) {
-    if (tid == 0) {
-      tr->step_valid = 0;
-      tr->iter += 1;
-      tr->num_invalid += 1;
-      if (tr->num_invalid >= kMaxInvalid) { tr->status = 2; tr->iter -= 1; }   // FAILURE breaks before the iteration is recorded
-      else if (tr->iter >= B.opt.num_iterations) tr->status = 3;
-      tr->mu *= kMuIncrease;
-      tr->reuse = 0;
-    }
-    return true;
-  }
-
-  // ---- delta = step * jacobi scale; candidate = Plus(x, delta) -----------------------------------
-  const int nfull_used = NC + B.maxP + 4 * nL;
-  for (int k = tid; k < nfull_used; k += T) {
-    const bool live = k < NC || (k >= LP && k < LP + nP) || k >= LL;
-    if (live) gdelta[k] = gscale[k] * (-c1 * ggrad[k] + c2 * (reuse0 ? ggn[k] : lgn[k])) / gdiag[k];   // (a re-used step comes from HBM)
-  }
-  __syncthreads();
-  double sn = 0.0, xn = 0.0;
-  const bool ex_free = B.opt.estimate_extrinsic != 0;
-  if (tid < NF + 1) {
-    const bool isex = tid == NF;
-    const double* x = isex ? B.ex + (size_t)w * 7 : B.pose + ((size_t)w * NF + tid) * 7;
-    double* xc = isex ? B.ex_c + (size_t)w * 7 : B.pose_c + ((size_t)w * NF + tid) * 7;
-    if (isex && !ex_free) {
-      for (int k = 0; k < 7; ++k) xc[k] = x[k];
-    } else {
-      double out[7];
-      pose_plus(x, gdelta + (isex ? 165 : 15 * tid), out);
-      for (int k = 0; k < 7; ++k) { xc[k] = out[k]; sn += (x[k] - out[k]) * (x[k] - out[k]); xn += x[k] * x[k]; }
-    }
-  } else if (tid >= 64 && tid < 64 + NF) {
-    const int f = tid - 64;
-    const double* x = B.sb + ((size_t)w * NF + f) * 9;
-    double* xc = B.sb_c + ((size_t)w * NF + f) * 9;
-    for (int k = 0; k < 9; ++k) {
-      const double d = gdelta[15 * f + 6 + k];
-      xc[k] = x[k] + d;
-      sn += d * d; xn += x[k] * x[k];
-    }
-  }
-  for (int p = tid; p < nP; p += T) {
-    const size_t pi = (size_t)w * B.maxP + p;
-    const double d = gdelta[LP + p];
-    B.invd_c[pi] = B.invd[pi] + d;
-    sn += d * d; xn += B.invd[pi] * B.invd[pi];
-  }
-  for (int l = tid; l < nL; l += T) {
-    const size_t li = (size_t)w * B.maxL + l;
-    double out[4];
-    line_orth_plus(B.orth + li * 4, gdelta + LL + 4 * l, out);
-    for (int k = 0; k < 4; ++k) {
-      const double x = B.orth[li * 4 + k];
-      B.orth_c[li * 4 + k] = out[k];
-      sn += (x - out[k]) * (x - out[k]); xn += x * x;
-    }
-    const Plk Lc_ = orth_to_plk(out);     // the candidate's world Pluecker line, once per line (B.lw_c)
-    double* lwc = B.lw_c + li * 6;
-    lwc[0] = Lc_.n.x; lwc[1] = Lc_.n.y; lwc[2] = Lc_.n.z; lwc[3] = Lc_.v.x; lwc[4] = Lc_.v.y; lwc[5] = Lc_.v.z;
-  }
-  sn = block_sum(sn, red);
-  xn = block_sum(xn, red);
-  VPL_STAMP(B, w, 7);
-  if (tid == 0) {
-    tr->dogleg_step_norm = dnorm;
-    tr->model_cost_change = model_cost_change;
-    tr->step_norm = sqrt(sn);
-    tr->x_norm = sqrt(xn);
-    tr->step_valid = 1;
-    tr->num_invalid = 0;
-  }
+  dogleg_step_and_candidate<T>(B, w, reuse0, lgn, gdelta, red);
   return true;
 }
 __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(DevBatch B) {
   extern __shared__ double sm[];
-  // the list k_cost of THIS iteration fills is emptied here (k_cost runs after this whole kernel)
-  if (blockIdx.x == 0 && threadIdx.x == 0) { B.ord_cnt[2 * ((B.ord_it + 1) & 1)] = 0; B.ord_cnt[2 * ((B.ord_it + 1) & 1) + 1] = 0; }
+  empty_next_order(B);
   const int w = ordered_window(B);
   const bool took = solve_body(B, w, sm);
   // After k_step (B.step_fused) this kernel is the last reader of B.path in the iteration: a flag raised for this iteration

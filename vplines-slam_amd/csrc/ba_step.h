@@ -13,11 +13,11 @@
 //            [72 pose / extrinsic dims | speed/bias 0 | speed/bias 5 | rhs] = 91 rows = 6 tile columns instead of 11.
 //   k_back   (~16 KB LDS)  landmark back-substitution, dogleg step, model cost change, candidate x (Plus).
 //
-// Any elimination order gives the same Gauss-Newton step up to rounding; the arithmetic per entry is
-// the one of ba_solve.h.  Windows the fast path does not cover -- a prior that holds a speed/bias block of another frame
-// than 0, a factorisation that failed and is retried with a larger mu (ceres' LINEAR_SOLVER_FAILURE loop) -- are flagged in
-// B.path and take k_solve (ba_solve.h), which is launched after k_step (three launches: between k_chol and k_back) and leaves
-// at once for everybody else.
+// Any elimination order gives the same Gauss-Newton step up to rounding; the pieces of the step that
+// do not depend on it are shared with the general path (ba_trust.h).  Windows the fast path does not cover -- a prior that
+// holds a speed/bias block of another frame than 0, a factorisation that failed and is retried with a larger mu (ceres'
+// LINEAR_SOLVER_FAILURE loop) -- are flagged in B.path and take k_solve (ba_solve.h), which is launched after k_step (three
+// launches: between k_chol and k_back) and leaves at once for everybody else.
 // Restates ceres-solver 1.12 DoglegStrategy::ComputeStep / SchurEliminator / TrustRegionMinimizer (third party, absent
 // from the reference tree) for the configuration at vins_estimator/src/estimator.cpp:1207-1215.
 #pragma once
@@ -215,103 +215,15 @@ __device__ __forceinline__ void schur_body(const DevBatch& B, const int w, doubl
     const int4* ktab = (const int4*)B.sk_tab + (size_t)w * B.maxKS;
     for (int k = tid; k < B.maxKS; k += T) etab[k] = ktab[k];
   }
-  const size_t fb = (size_t)w * B.nfull;
-  double* gscale = B.scale + fb;
-  double* gdiag = B.diag + fb;
-  double* ggrad = B.grad + fb;
   const double* Hcc = B.Hcc + (size_t)w * NCP;
-  const double* gc = B.gc + (size_t)w * NC;
   double* lch = B.lchol + (size_t)w * B.maxL * 10;
-  const int LP = NC, LL = NC + B.maxP;
   if (tid == 0) { flag[0] = 0; tick[0] = 0; }
   const double mu = tr->mu;
   const bool first = (tr->iter == 0);
   VPL_STAMP(B, w, 0);
-  // ---- jacobi scaling (iteration 0 only), diagonal_, gradient_  (same arithmetic as ba_solve.h) ----
+  // ---- jacobi scaling (iteration 0 only), diagonal_, gradient_ ----
   double a1 = 0.0, q = 0.0;
-  {
-    double pre_hp = 0.0, pre_sp = 0.0, pre_gp = 0.0, pre_Hl[16], pre_sl[4], pre_gl[4];
-    if (tid < nP) {
-      const size_t pi = (size_t)w * B.maxP + tid;
-      pre_hp = B.Hpp[pi]; pre_gp = B.gp[pi];
-      if (!first) pre_sp = gscale[LP + tid];
-    }
-#pragma unroll
-    for (int k = 0; k < 16; ++k) pre_Hl[k] = 0.0;
-#pragma unroll
-    for (int a = 0; a < 4; ++a) { pre_sl[a] = 0.0; pre_gl[a] = 0.0; }
-    if (tid < nL) {
-      const size_t li = (size_t)w * B.maxL + tid;
-#pragma unroll
-      for (int k = 0; k < 16; ++k) pre_Hl[k] = B.Hll[li * 16 + k];
-#pragma unroll
-      for (int a = 0; a < 4; ++a) {
-        pre_gl[a] = B.gl[li * 4 + a];
-        if (!first) pre_sl[a] = gscale[LL + 4 * tid + a];
-      }
-    }
-    for (int c = tid; c < 176; c += T) {
-      double s = 0.0, d = 1.0, g = 0.0;
-      if (c < NC) {
-        const double h = Hcc[tri(c, c)];
-        s = first ? 1.0 / (1.0 + sqrt(h)) : gscale[c];
-        if (first) gscale[c] = s;
-        d = sqrt(fmin(fmax(s * s * h, kMinDiag), kMaxDiag));
-        g = s * gc[c] / d;
-        gdiag[c] = d; ggrad[c] = g;
-        a1 += g * g;
-      }
-      uc[c] = s * g / d;
-    }
-    for (int p = tid; p < nP; p += T) {
-      const size_t pi = (size_t)w * B.maxP + p;
-      const bool pre = p == tid;
-      const double h = pre ? pre_hp : B.Hpp[pi];
-      const double s = first ? 1.0 / (1.0 + sqrt(h)) : (pre ? pre_sp : gscale[LP + p]);
-      if (first) gscale[LP + p] = s;
-      const double d = sqrt(fmin(fmax(s * s * h, kMinDiag), kMaxDiag));
-      const double g = s * (pre ? pre_gp : B.gp[pi]) / d;
-      gdiag[LP + p] = d; ggrad[LP + p] = g;
-      kP[4 * p] = s; kP[4 * p + 1] = d; kP[4 * p + 2] = g; kP[4 * p + 3] = h;
-      a1 += g * g;
-      const double u = s * g / d;
-      q += u * h * u;
-    }
-    for (int l = tid; l < nL; l += T) {
-      const size_t li = (size_t)w * B.maxL + l;
-      const bool pre = l == tid;
-      double Hl[16], sl4[4], gl4[4];
-#pragma unroll
-      for (int k = 0; k < 16; ++k) Hl[k] = pre ? pre_Hl[k] : B.Hll[li * 16 + k];
-#pragma unroll
-      for (int a = 0; a < 4; ++a) {
-        sl4[a] = first ? 0.0 : (pre ? pre_sl[a] : gscale[LL + 4 * l + a]);
-        gl4[a] = pre ? pre_gl[a] : B.gl[li * 4 + a];
-      }
-      double u[4];
-#pragma unroll
-      for (int a = 0; a < 4; ++a) {
-        const double h = Hl[5 * a];
-        const double s = first ? 1.0 / (1.0 + sqrt(h)) : sl4[a];
-        if (first) gscale[LL + 4 * l + a] = s;
-        const double d = sqrt(fmin(fmax(s * s * h, kMinDiag), kMaxDiag));
-        const double g = s * gl4[a] / d;
-        gdiag[LL + 4 * l + a] = d; ggrad[LL + 4 * l + a] = g;
-        kL[28 * l + a] = s; kL[28 * l + 4 + a] = d; kL[28 * l + 8 + a] = g;
-        a1 += g * g;
-        u[a] = s * g / d;
-      }
-#pragma unroll
-      for (int k = 0; k < 16; ++k) kL[28 * l + 12 + k] = Hl[k];
-#pragma unroll
-      for (int a = 0; a < 4; ++a) {
-        double hu = 0;
-#pragma unroll
-        for (int b = 0; b < 4; ++b) hu += Hl[4 * a + b] * u[b];
-        q += u[a] * hu;
-      }
-    }
-  }
+  scale_and_gradient<T, false>(B, w, first, kP, kL, uc, nullptr, nullptr, a1, q);
   __syncthreads();   // uc, kP, kL complete
   // camera part of the Cauchy denominator u^T Hcc u over the entries the factors can fill (B.nz_tab: 6147 of the 14706 of the
   // packed triangle; everything else is a structural zero on this path), 12 loads in flight per thread
@@ -356,36 +268,7 @@ __device__ __forceinline__ void schur_body(const DevBatch& B, const int w, doubl
 #pragma unroll
     for (int k = 0; k < 16; ++k) Hl[k] = kL[28 * l + 12 + k];
     double A[10];
-    int t = 0;
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int b = 0; b < 4; ++b) if (b <= a) {
-        A[t] = s4[a] * s4[b] * Hl[4 * a + b];
-        if (a == b) A[t] += mu * d4[a] * d4[a];
-        ++t;
-      }
-    bool ok = true;
-    chol4(A, ok);
-    if (!ok) flag[0] = 1;
-    double us[4];
-#pragma unroll
-    for (int k = 0; k < 10; ++k) { lch[l * 10 + k] = A[k]; lC[l * 10 + k] = A[k]; }
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      const double rd = 1.0 / A[tri(a, a)];
-      lS[4 * l + a] = s4[a] * rd;
-      us[a] = g4[a] / d4[a];
-#pragma unroll
-      for (int qd = 0; qd < 4; ++qd) if (qd < a) lC[l * 10 + tri(a, qd)] = A[tri(a, qd)] * rd;
-    }
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      double s2 = 0;
-#pragma unroll
-      for (int qd = 0; qd < 4; ++qd) if (qd >= a) s2 += A[tri(qd, a)] * us[qd];
-      lE[4 * l + a] = s2;
-    }
+    if (!line_block(s4, d4, g4, Hl, mu, l, lch, lC, lS, lE, A)) flag[0] = 1;
     {   // x_g = C^-1 S g_l by the same forward substitution the rows of W go through (g_l = g~ d / s)
       double xg[4];
 #pragma unroll
@@ -639,13 +522,12 @@ __device__ __forceinline__ void schur_body(const DevBatch& B, const int w, doubl
 template <int NTC>
 __global__ __launch_bounds__(SCHUR_THREADS, 2) void k_schur(DevBatch B) {
   extern __shared__ double sm[];
-  // the list k_cost of THIS iteration fills is emptied here (k_cost runs after this whole kernel)
-  if (blockIdx.x == 0 && threadIdx.x == 0) { B.ord_cnt[2 * ((B.ord_it + 1) & 1)] = 0; B.ord_cnt[2 * ((B.ord_it + 1) & 1) + 1] = 0; }
+  empty_next_order(B);
   schur_body<NTC>(B, ordered_window(B), sm);
 }
 __global__ __launch_bounds__(SCHUR_THREADS, 2) void k_schur_mixed(DevBatch B) {
   extern __shared__ double sm[];
-  if (blockIdx.x == 0 && threadIdx.x == 0) { B.ord_cnt[2 * ((B.ord_it + 1) & 1)] = 0; B.ord_cnt[2 * ((B.ord_it + 1) & 1) + 1] = 0; }
+  empty_next_order(B);
   schur_body<3, true>(B, ordered_window(B), sm);
 }
 inline size_t schur_smem(int maxP, int maxL, int ntc = 5) {
@@ -1025,14 +907,13 @@ constexpr size_t CHOL_SMEM = (size_t)(((XROWS_A + XROWS_B) * XLD > DNAP ? (XROWS
 // ---------------------------------------------------------------------------------------------------------------------
 // k_back : landmark back-substitution y_l = A_l^-1 S_l (g_l - W_l S_c y_c), then DoglegStrategy::ComputeTraditionalDoglegStep,
 // the model cost change and the candidate x (+) delta -- for a window that re-uses the Gauss-Newton step of a rejected
-// iteration only the latter (the arithmetic is the one of ba_solve.h).
+// iteration only the latter.
 // ---------------------------------------------------------------------------------------------------------------------
 // FUSED (k_step): k_solve runs AFTER this body and is the flag's last reader -- a window of the general path leaves without
 // touching B.path, k_solve takes a one-iteration flag down itself.
 template <bool FUSED = false>
 __device__ __forceinline__ void back_body(const DevBatch& B, const int w, double* sm) {
   const int tid = threadIdx.x, T = BACK_THREADS;
-  const int lane = tid & 63;
   TrState* tr = &B.tr[w];
   if (tr->status != 0) return;
   const int path = B.path[w];
@@ -1043,7 +924,6 @@ __device__ __forceinline__ void back_body(const DevBatch& B, const int w, double
     return;
   }
   const int nP = B.nP[w], nL = B.nL[w];
-  const int WS = B.WS;
   double* uc = sm;                       // 176 S_c y_c
   double* lrhs = uc + 176;               // 4 maxL
   double* lgn = lrhs + 4 * B.maxL;       // nfull Gauss-Newton step (scaled space)
@@ -1051,13 +931,7 @@ __device__ __forceinline__ void back_body(const DevBatch& B, const int w, double
   double* red = gdelta + B.nfull;        // 24
   int* pSt = (int*)(red + 24);
   int* lSt = pSt + B.maxP;
-  const size_t fb = (size_t)w * B.nfull;
-  const double* gscale = B.scale + fb;
-  const double* gdiag = B.diag + fb;
-  const double* ggrad = B.grad + fb;
-  double* ggn = B.gn + fb;
-  const double* lch = B.lchol + (size_t)w * B.maxL * 10;
-  const int LP = NC, LL = NC + B.maxP;
+  double* ggn = B.gn + (size_t)w * B.nfull;
   const bool reuse0 = tr->reuse != 0;
   count_active(B, reuse0 ? 2 : 1);
   VPL_STAMP(B, w, 5);
@@ -1069,111 +943,8 @@ __device__ __forceinline__ void back_body(const DevBatch& B, const int w, double
     for (int c = tid; c < NC; c += T) lgn[c] = ggn[c];
     __syncthreads();
     double a2 = 0.0, a3 = 0.0;
-    {
-      const int sub = lane & 7, grp = tid >> 3;   // 64 row groups per pass
-      const int nblk = WS / 6;
-      constexpr int NPH = 4;   // row groups per trip: their loads are in flight together
-      for (int p0 = 0; p0 < nP; p0 += NPH * (T / 8)) {
-        double wyv[NPH], sv[NPH], dv[NPH], hv[NPH], gv2[NPH], grv[NPH];
-        size_t piv[NPH];
-#pragma unroll
-        for (int h = 0; h < NPH; ++h) {
-          const int p = p0 + h * (T / 8) + grp;
-          piv[h] = (size_t)w * B.maxP + (p < nP ? p : 0);
-          wyv[h] = 0.0; sv[h] = dv[h] = 1.0; hv[h] = gv2[h] = grv[h] = 0.0;
-          if (p < nP) {
-            const int s0 = pSt[p];
-            for (int blk = sub; blk < nblk; blk += 8) {
-              const bool exb = blk == nblk - 1;
-              const int vb = exb ? 66 : 6 * (s0 + blk);
-              if (!exb && vb >= 66) continue;
-              const double* Wr = B.Wp + piv[h] * WS + 6 * blk;
-#pragma unroll
-              for (int k = 0; k < 6; ++k) wyv[h] += Wr[k] * uc[vb + k];
-            }
-            if (sub == 0) {
-              sv[h] = gscale[LP + p]; dv[h] = gdiag[LP + p]; hv[h] = B.Hpp[piv[h]]; gv2[h] = B.gp[piv[h]];
-              grv[h] = ggrad[LP + p];
-            }
-          }
-        }
-#pragma unroll
-        for (int h = 0; h < NPH; ++h) {
-          const int p = p0 + h * (T / 8) + grp;
-          double wy = wyv[h];
-          wy += __shfl_xor(wy, 1, 64); wy += __shfl_xor(wy, 2, 64); wy += __shfl_xor(wy, 4, 64);
-          if (p < nP && sub == 0) {
-            const double s = sv[h], d = dv[h];
-            const double Al = s * s * hv[h] + mu * d * d;
-            const double y = s * (gv2[h] - wy) / Al;
-            const double gnv = -d * y;
-            ggn[LP + p] = gnv; lgn[LP + p] = gnv;
-            a2 += gnv * gnv;
-            a3 += grv[h] * gnv;
-          }
-        }
-      }
-      constexpr int NLH = 5;
-      for (int r0 = 0; r0 < 4 * nL; r0 += NLH * (T / 8)) {
-        double wyv[NLH], glv[NLH];
-#pragma unroll
-        for (int h = 0; h < NLH; ++h) {
-          const int r = r0 + h * (T / 8) + grp, l = r >> 2, a = r & 3;
-          wyv[h] = 0.0; glv[h] = 0.0;
-          if (l < nL) {
-            const size_t li = (size_t)w * B.maxL + l;
-            const int s0 = lSt[l];
-            for (int blk = sub; blk < nblk; blk += 8) {
-              const bool exb = blk == nblk - 1;
-              const int vb = exb ? 66 : 6 * (s0 + blk);
-              if (!exb && vb >= 66) continue;
-              const double* Wr = B.Wl + (li * 4 + a) * WS + 6 * blk;
-#pragma unroll
-              for (int k = 0; k < 6; ++k) wyv[h] += Wr[k] * uc[vb + k];
-            }
-            if (sub == 0) glv[h] = B.gl[li * 4 + a];
-          }
-        }
-#pragma unroll
-        for (int h = 0; h < NLH; ++h) {
-          const int r = r0 + h * (T / 8) + grp;
-          double wy = wyv[h];
-          wy += __shfl_xor(wy, 1, 64); wy += __shfl_xor(wy, 2, 64); wy += __shfl_xor(wy, 4, 64);
-          if (r < 4 * nL && sub == 0) lrhs[r] = gscale[LL + r] * (glv[h] - wy);
-        }
-      }
-      __syncthreads();
-      for (int l = tid; l < nL; l += T) {
-        double C[10], t4[4], gd4[4], gr4[4];
-#pragma unroll
-        for (int k = 0; k < 10; ++k) C[k] = lch[l * 10 + k];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { gd4[k] = gdiag[LL + 4 * l + k]; gr4[k] = ggrad[LL + 4 * l + k]; }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) t4[k] = lrhs[4 * l + k];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          double s2 = t4[k];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) if (j < k) s2 -= C[tri(k, j)] * t4[j];
-          t4[k] = s2 / C[tri(k, k)];
-        }
-#pragma unroll
-        for (int k = 3; k >= 0; --k) {
-          double s2 = t4[k];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) if (j > k) s2 -= C[tri(j, k)] * t4[j];
-          t4[k] = s2 / C[tri(k, k)];
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const double gnv = -gd4[k] * t4[k];
-          ggn[LL + 4 * l + k] = gnv; lgn[LL + 4 * l + k] = gnv;
-          a2 += gnv * gnv;
-          a3 += gr4[k] * gnv;
-        }
-      }
-    }
+    back_substitute_points<T, 4, false>(B, w, mu, uc, pSt, lgn, a2, a3);
+    back_substitute_lines<T, 5, false>(B, w, uc, lSt, lrhs, lgn, a2, a3);
     a2 = block_sum(a2, red);
     a3 = block_sum(a3, red);
     if (tid == 0) {
@@ -1184,102 +955,7 @@ __device__ __forceinline__ void back_body(const DevBatch& B, const int w, double
     __syncthreads();
   }
   VPL_STAMP(B, w, 6);
-  // ---- DoglegStrategy::ComputeTraditionalDoglegStep ---------------------------------------------
-  const double radius = tr->radius, alpha = tr->alpha, a1 = tr->a1, a2 = tr->a2, a3 = tr->a3, mu = tr->mu;
-  const double gradient_norm = sqrt(a1), gauss_newton_norm = sqrt(a2);
-  double c1, c2, dnorm;
-  if (gauss_newton_norm <= radius) {
-    c1 = 0.0; c2 = 1.0; dnorm = gauss_newton_norm;
-  } else if (gradient_norm * alpha >= radius) {
-    c1 = radius / gradient_norm; c2 = 0.0; dnorm = radius;
-  } else {
-    const double b_dot_a = -alpha * a3;
-    const double a_sq = (alpha * gradient_norm) * (alpha * gradient_norm);
-    const double bma = a_sq - 2 * b_dot_a + a2;
-    const double c = b_dot_a - a_sq;
-    const double d = sqrt(c * c + bma * (radius * radius - a_sq));
-    const double beta = (c <= 0) ? (d - c) / bma : (radius * radius - a_sq) / (d + c);
-    c1 = alpha * (1.0 - beta); c2 = beta;
-    dnorm = sqrt(c1 * c1 * a1 - 2.0 * c1 * c2 * a3 + c2 * c2 * a2);
-  }
-  const double q_cauchy = a1 / alpha;
-  const double sg = -c1 * a1 + c2 * a3;
-  const double vHy = a1 + mu * a3;
-  const double yHy = -a3 - mu * a2;
-  const double sHs = c1 * c1 * q_cauchy + 2.0 * c1 * c2 * vHy + c2 * c2 * yHy;
-  const double model_cost_change = -(sg + 0.5 * sHs);
-  const bool valid = model_cost_change > 0.0;
-  if (!valid) {
-    if (tid == 0) {
-      tr->step_valid = 0;
-      tr->iter += 1;
-      tr->num_invalid += 1;
-      if (tr->num_invalid >= kMaxInvalid) { tr->status = 2; tr->iter -= 1; }
-      else if (tr->iter >= B.opt.num_iterations) tr->status = 3;
-      tr->mu *= kMuIncrease;
-      tr->reuse = 0;
-    }
-    return;
-  }
-  const int nfull_used = NC + B.maxP + 4 * nL;
-  for (int k = tid; k < nfull_used; k += T) {
-    const bool live = k < NC || (k >= LP && k < LP + nP) || k >= LL;
-    if (live) gdelta[k] = gscale[k] * (-c1 * ggrad[k] + c2 * (reuse0 ? ggn[k] : lgn[k])) / gdiag[k];
-  }
-  __syncthreads();
-  double sn = 0.0, xn = 0.0;
-  const bool ex_free = B.opt.estimate_extrinsic != 0;
-  if (tid < NF + 1) {
-    const bool isex = tid == NF;
-    const double* x = isex ? B.ex + (size_t)w * 7 : B.pose + ((size_t)w * NF + tid) * 7;
-    double* xc = isex ? B.ex_c + (size_t)w * 7 : B.pose_c + ((size_t)w * NF + tid) * 7;
-    if (isex && !ex_free) {
-      for (int k = 0; k < 7; ++k) xc[k] = x[k];
-    } else {
-      double out[7];
-      pose_plus(x, gdelta + (isex ? 165 : 15 * tid), out);
-      for (int k = 0; k < 7; ++k) { xc[k] = out[k]; sn += (x[k] - out[k]) * (x[k] - out[k]); xn += x[k] * x[k]; }
-    }
-  } else if (tid >= 64 && tid < 64 + NF) {
-    const int f = tid - 64;
-    const double* x = B.sb + ((size_t)w * NF + f) * 9;
-    double* xc = B.sb_c + ((size_t)w * NF + f) * 9;
-    for (int k = 0; k < 9; ++k) {
-      const double d = gdelta[15 * f + 6 + k];
-      xc[k] = x[k] + d;
-      sn += d * d; xn += x[k] * x[k];
-    }
-  }
-  for (int p = tid; p < nP; p += T) {
-    const size_t pi = (size_t)w * B.maxP + p;
-    const double d = gdelta[LP + p];
-    B.invd_c[pi] = B.invd[pi] + d;
-    sn += d * d; xn += B.invd[pi] * B.invd[pi];
-  }
-  for (int l = tid; l < nL; l += T) {
-    const size_t li = (size_t)w * B.maxL + l;
-    double out[4];
-    line_orth_plus(B.orth + li * 4, gdelta + LL + 4 * l, out);
-    for (int k = 0; k < 4; ++k) {
-      const double x = B.orth[li * 4 + k];
-      B.orth_c[li * 4 + k] = out[k];
-      sn += (x - out[k]) * (x - out[k]); xn += x * x;
-    }
-    const Plk Lc_ = orth_to_plk(out);     // the candidate's world Pluecker line, once per line (B.lw_c)
-    double* lwc = B.lw_c + li * 6;
-    lwc[0] = Lc_.n.x; lwc[1] = Lc_.n.y; lwc[2] = Lc_.n.z; lwc[3] = Lc_.v.x; lwc[4] = Lc_.v.y; lwc[5] = Lc_.v.z;
-  }
-  sn = block_sum(sn, red);
-  xn = block_sum(xn, red);
-  VPL_STAMP(B, w, 7);
-  if (tid == 0) {
-    tr->dogleg_step_norm = dnorm;
-    tr->model_cost_change = model_cost_change;
-    tr->step_norm = sqrt(sn);
-    tr->x_norm = sqrt(xn);
-    tr->step_valid = 1;
-    tr->num_invalid = 0;
-  }
+  dogleg_step_and_candidate<T>(B, w, reuse0, lgn, gdelta, red);
 }
 #ifndef VPL_BACK_WAVES
 #define VPL_BACK_WAVES 2          // A/B switch: waves per SIMD the register allocation of k_back is held to
@@ -1306,8 +982,7 @@ static_assert(SCHUR_THREADS == CHOL_THREADS && CHOL_THREADS == BACK_THREADS, "k_
 template <int NTC, bool MIXED>
 __global__ __launch_bounds__(SCHUR_THREADS, 2) void k_step(DevBatch B) {
   extern __shared__ double sm[];
-  // the list k_cost of THIS iteration fills is emptied here (k_cost runs after this whole kernel)
-  if (blockIdx.x == 0 && threadIdx.x == 0) { B.ord_cnt[2 * ((B.ord_it + 1) & 1)] = 0; B.ord_cnt[2 * ((B.ord_it + 1) & 1) + 1] = 0; }
+  empty_next_order(B);
   const int w = ordered_window(B);
   schur_body<NTC, MIXED>(B, w, sm);
   __syncthreads();

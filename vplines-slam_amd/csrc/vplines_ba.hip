@@ -706,26 +706,25 @@ static void launch_solve(vpl_ctx* c, int w0, int nw, hipStream_t s, int restore)
   ++B.launch;
   { KTimer t(c, "k_lin"); hipLaunchKernelGGL(k_lin2, dim3(16 * ((nw + 7) / 8)), dim3(LIN_THREADS), lin_smem(c->maxP, c->maxL), s, B); }
   ++B.launch;
+  // The shape of the landmark elimination: three column tiles when every compact row fits them; for rows wider than 6 frames
+  // all five, or (few long tracks) the mixed form: narrow view for the entries of short tracks, all tiles for the flagged ones.
+  const bool narrow = B.WS + 2 <= 48, wide = !narrow && (c->schur_wide_all || (c->schur_mostly_wide && !c->schur_never_wide));
+  const int ntc = wide ? 5 : 3;
+  void (*const kstep)(DevBatch) = narrow ? k_step<3, false> : wide ? k_step<5, false> : k_step<3, true>;
+  void (*const kschur)(DevBatch) = narrow ? k_schur<3> : wide ? k_schur<5> : k_schur_mixed;
   for (int it = 0; it < c->opt.num_iterations; ++it) {
     B.ord_it = it;      // k_solve / k_cost of iteration `it` walk order[it & 1]; k_cost fills order[(it + 1) & 1]
     // the step: landmark elimination -> reduced camera system -> landmark back-substitution + dogleg + candidate; the general
     // path (windows flagged in B.path only) after it, or before the back-substitution in the three-launch form.
     // One launch (k_step) unless the solve is timed kernel by kernel: the timing mode attributes time and active windows
     // per phase (vpl_ba_launch_profile) and issues the same bodies as three launches -- the same bits.
-    const bool wide = c->schur_wide_all || (c->schur_mostly_wide && !c->schur_never_wide);
     if (B.step_fused) {
-      if (B.WS + 2 <= 48) hipLaunchKernelGGL((k_step<3, false>), grid, dim3(SCHUR_THREADS), step_smem(B.maxP, B.maxL, 3), s, B);
-      else if (wide) hipLaunchKernelGGL((k_step<5, false>), grid, dim3(SCHUR_THREADS), step_smem(B.maxP, B.maxL, 5), s, B);
-      // rows wider than 6 frames: narrow view for the entries of short tracks, all tiles for the flagged ones (round 4)
-      else hipLaunchKernelGGL((k_step<3, true>), grid, dim3(SCHUR_THREADS), step_smem(B.maxP, B.maxL, 3), s, B);
+      hipLaunchKernelGGL(kstep, grid, dim3(SCHUR_THREADS), step_smem(B.maxP, B.maxL, ntc), s, B);
       ++B.launch;
       hipLaunchKernelGGL(k_solve, grid, dim3(SOLVE_THREADS), solve_smem(B.maxP, B.maxL), s, B);
       ++B.launch;
     } else {
-      { KTimer t(c, "k_schur");
-        if (B.WS + 2 <= 48) hipLaunchKernelGGL(k_schur<3>, grid, dim3(SCHUR_THREADS), schur_smem(B.maxP, B.maxL, 3), s, B);
-        else if (wide) hipLaunchKernelGGL(k_schur<5>, grid, dim3(SCHUR_THREADS), schur_smem(B.maxP, B.maxL, 5), s, B);
-        else hipLaunchKernelGGL(k_schur_mixed, grid, dim3(SCHUR_THREADS), schur_smem(B.maxP, B.maxL, 3), s, B); }
+      { KTimer t(c, "k_schur"); hipLaunchKernelGGL(kschur, grid, dim3(SCHUR_THREADS), schur_smem(B.maxP, B.maxL, ntc), s, B); }
       ++B.launch;
       { KTimer t(c, "k_chol"); hipLaunchKernelGGL(k_chol, grid, dim3(CHOL_THREADS), CHOL_SMEM, s, B); }
       ++B.launch;
