@@ -288,6 +288,563 @@ inline void lin_asm_entry(int r, int c, int* out) {
   out[1] = r | c << 8;
 }
 
+
+// ---------------------------------------------------------------------------------------
+// k_lin's dynamic LDS is carved at the top of lin_body (the host sizes it: lin_smem_base / lin_prh_n / lin_smem below); the
+// phases take the arrays they use.  [imuJ | imur] is one region with three tenants in turn: the MFMA staging of the point phase
+// (8 waves x 32 rows x 20 doubles), the wave-private partial sums + per-track accumulators of the line phase (8 x LIN_HW + 38
+// maxL), the whitened IMU Jacobians (the assembly reads them).  The tenants' own arrays, by the region's base imuJ:
+// point phase, from the start of the kernel (nothing before it touches the region): wave wvi's staging tile ...
+__device__ __forceinline__ double* lin_pt_stage(double* imuJ, int wvi) { return imuJ + wvi * (32 * STG_LD); }
+// ... and, in the part the tiles leave free, the second commit chain's copy of Hv | gv: zeroed by waves 4..7 in front of the
+// barrier inside the point phase, folded into Hv | gv (lin_points_fold) behind the barrier that ends the point phase
+__device__ __forceinline__ double* lin_Hv2(double* imuJ) { return imuJ + LIN_STAGE; }
+// line phase, from the barrier behind lin_points_out ("staging space is handed over") to the one behind lin_lines_out: wave
+// wvi's partial sums Hw (LIN_HW doubles) and the per-track accumulators lacc (38 per line)
+__device__ __forceinline__ double* lin_ln_Hw(double* imuJ, int wvi) { return imuJ + wvi * LIN_HW; }
+__device__ __forceinline__ double* lin_ln_acc(double* imuJ) { return imuJ + 8 * LIN_HW; }
+// IMU phase, from the barrier behind lin_lines_out ("the staging region goes to the IMU phase") to the end of the kernel:
+// imuJ and imur themselves and, behind them, the J^T J blocks of the factors for the assembly
+__device__ __forceinline__ double* lin_imuH(double* imuJ) { return imuJ + 4650; }
+
+// The prior phase gives one lane to each kept block (tid < nb): its entry of the block table and its linearisation point are
+// requested with the states, at the top of the kernel ...  (cost_body, ba_solve.h, has the same text inline: through these
+// two functions k_cost spills two more registers inside its 128)
+struct PriorBlock {
+  int kind = 0, fr = 0, idx = 0;
+  double x0[9];
+};
+__device__ __forceinline__ void prior_block_request(const DevBatch& B, const int w, const int tid, const int nb, PriorBlock& b) {
+  if (tid < nb) {
+    b.kind = B.pr_kind[(size_t)w * MAXPB + tid]; b.fr = B.pr_frame[(size_t)w * MAXPB + tid]; b.idx = B.pr_idx[(size_t)w * MAXPB + tid];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) b.x0[k] = B.pr_x0[((size_t)w * MAXPB + tid) * 9 + k];
+  }
+}
+// ... and its dx goes to prdx once the states are in LDS (xp: the poses and the extrinsic, xs: speed/bias)
+__device__ __forceinline__ void prior_block_dx_store(const PriorBlock& b, const int tid, const int nb, const double* xp, const double* xs,
+                                                     double* prdx) {
+  if (tid < nb) {
+    const double* x = b.kind == 0 ? xp + 7 * b.fr : b.kind == 1 ? xs + 9 * b.fr : xp + 77;
+    double dx[9];
+    prior_block_dx(b.kind, x, b.x0, dx);
+    const int ls = b.kind == 1 ? 9 : 6;
+    for (int k = 0; k < ls; ++k) prdx[b.idx + k] = dx[k];
+  }
+}
+// What the prior phase asks for while the states are staged, one round trip ahead of its use: this lane's kept block (lanes
+// tid < nb), its entry of the index map (tid < n), and of row tid >> 3 of J0 and H = J0^T J0 the columns (tid & 7) + 8 q,
+// q < LIN_PJ; r0 and g0 of that row in its first lane
+constexpr int LIN_PJ = 6;
+struct PriorRegs {
+  int n = 0, nb = 0;
+  PriorBlock blk;
+  int pmap = -1;
+  double j0[LIN_PJ], hv[LIN_PJ], r0 = 0.0, g0 = 0.0;
+};
+// the static table entries of a thread's packed entries of Hcc (e = u T + tid): lin_asm_request -> lin_assemble
+constexpr int LIN_ASM_PER_THREAD = (NCP + LIN_THREADS - 1) / LIN_THREADS;
+
+// ---- the phases of lin_body, in the order it calls them ---------------------------------------------------------------
+// stage: zeroing, states and pre-integrations to LDS; the prior's requests
+template <int ROLE>
+__device__ __forceinline__ void lin_stage(const DevBatch& B, const int w, double* sm, double* xp, double* xs, double* pacc, const int PST, double* plds,
+                                             int* invmap, int* tick, PriorRegs& P) {
+  constexpr bool DO_PTS = ROLE != 2, DO_REST = ROLE != 1;
+  const int tid = threadIdx.x, T = LIN_THREADS;
+  for (int i = tid; i < HV_DOUBLES + NV; i += T) sm[i] = 0.0;
+  if (DO_PTS) for (int i = tid; i < 14 * PST; i += T) pacc[i] = 0.0;
+  for (int i = tid; i < 84; i += T) xp[i] = i < 77 ? B.pose[(size_t)w * 77 + i] : B.ex[(size_t)w * 7 + (i - 77)];
+  if (DO_REST) {
+    for (int i = tid; i < 99; i += T) xs[i] = B.sb[(size_t)w * 99 + i];
+    for (int i = tid; i < 10 * PRE_LDS; i += T) {   // (the IMU phase is then free of global round trips)
+      const int f = i / PRE_LDS;
+      plds[i] = ((const double*)&B.pre[(size_t)w * NF + f + 1])[i - PRE_LDS * f];
+    }
+  }
+  for (int i = tid; i < NC; i += T) invmap[i] = -1;
+  if (tid < 5) tick[tid] = 0;
+  // The prior's inputs are requested HERE, with the states: its block table and linearisation point (one lane per block), the
+  // index map, and this lane's part of the rows of J0 and H = J0^T J0 (eight lanes per row, the first LIN_PJ columns of
+  // each) -- the phase was three dependent round trips (table -> barrier -> rows), each ~3 k cycles with every CU in it.
+  P.n = DO_REST ? B.pr_n[w] : 0; P.nb = P.n > 0 ? B.pr_nb[w] : 0;
+  const int n = P.n;
+  const int prow = tid >> 3, psub = tid & 7;
+  prior_block_request(B, w, tid, P.nb, P.blk);
+  if (tid < n) P.pmap = B.pr_map[(size_t)w * MAXPN + tid];
+  {
+    const double* J0 = B.pr_J0 + (size_t)w * B.prS;
+    const double* Hp = B.pr_H + (size_t)w * B.prS;
+#pragma unroll
+    for (int q = 0; q < LIN_PJ; ++q) {
+      const int c = psub + 8 * q;
+      const bool in = prow < n && c < n;
+      P.j0[q] = in ? J0[(size_t)prow * n + c] : 0.0;
+      P.hv[q] = in ? Hp[(size_t)prow * n + c] : 0.0;
+    }
+    if (prow < n && psub == 0) { P.r0 = B.pr_r0[(size_t)w * MAXPN + prow]; P.g0 = B.pr_g0[(size_t)w * MAXPN + prow]; }
+  }
+}
+
+// ---- prior: r = r0 + J0 dx ; g = J0^T r -------------------------------------------
+// PriorRegs -> prdx, invmap, prr, prg, prH; this thread's share of the cost
+__device__ __forceinline__ void lin_prior(const DevBatch& B, const int w, const double* xp, const double* xs, double* prdx, double* prr, double* prg,
+                                             double* prH, const int PRH_N, int* invmap, const PriorRegs& P, double& cost) {
+  const int tid = threadIdx.x, T = LIN_THREADS;
+  const int n = P.n;
+  const int prow = tid >> 3, psub = tid & 7;
+  double r0r = P.r0, g0r = P.g0;
+  if (n > 0) {
+    prior_block_dx_store(P.blk, tid, P.nb, xp, xs, prdx);
+    if (tid < n) invmap[P.pmap] = tid;
+    for (int i = tid + T; i < n; i += T) invmap[B.pr_map[(size_t)w * MAXPN + i]] = i;
+    __syncthreads();
+    const double* J0 = B.pr_J0 + (size_t)w * B.prS;
+    // r = r0 + J0 dx and g = J0^T r = g0 + H dx (H = J0^T J0, g0 = J0^T r0 from k_prep) in ONE pass: eight lanes per row
+    const double* Hp = B.pr_H + (size_t)w * B.prS;
+    for (int r = prow; r < n; r += T >> 3) {
+      const bool first = r == prow;
+      double s = 0, sg = 0;
+      if (first) {
+#pragma unroll
+        for (int q = 0; q < LIN_PJ; ++q) {
+          const int c = psub + 8 * q;
+          if (c < n) {
+            const double dxc = prdx[c];
+            s += P.j0[q] * dxc;
+            sg += P.hv[q] * dxc;
+            if (n <= PRH_N && c <= r) prH[r * (r + 1) / 2 + c] = P.hv[q];   // kept for the assembly
+          }
+        }
+      }
+      for (int c = psub + (first ? 8 * LIN_PJ : 0); c < n; c += 8) {
+        const double dxc = prdx[c];
+        const double hrc = Hp[(size_t)r * n + c];
+        s += J0[(size_t)r * n + c] * dxc;
+        sg += hrc * dxc;
+        if (n <= PRH_N && c <= r) prH[r * (r + 1) / 2 + c] = hrc;
+      }
+      s += __shfl_xor(s, 1, 64); s += __shfl_xor(s, 2, 64); s += __shfl_xor(s, 4, 64);
+      sg += __shfl_xor(sg, 1, 64); sg += __shfl_xor(sg, 2, 64); sg += __shfl_xor(sg, 4, 64);
+      if (psub == 0) {
+        if (!first) { r0r = B.pr_r0[(size_t)w * MAXPN + r]; g0r = B.pr_g0[(size_t)w * MAXPN + r]; }
+        s += r0r;
+        prr[r] = s;
+        prg[r] = sg + g0r;
+        cost += 0.5 * s * s;
+      }
+    }
+  }
+}
+
+// zero the W rows first where some slot is not written by a factor (shorter tracks, erased lines, the start-frame
+// slot of the lines in the marginalisation pass); uniform track lengths need no fill in the solve
+template <int MODE, int ROLE>
+__device__ __forceinline__ void lin_clear_w(const DevBatch& B, const int w, const int nP, const int nL) {
+  constexpr bool MARG = MODE != 0;
+  constexpr bool DO_PTS = ROLE != 2, DO_REST = ROLE != 1;
+  const int tid = threadIdx.x, T = LIN_THREADS;
+  const int WS = B.WS;
+  if (B.wfill) {
+    // (the marginalisation pass only ever reads the rows of the tracks that start in frame 0)
+    double* Wp0 = B.Wp + (size_t)w * B.maxP * WS;
+    if (DO_PTS)
+      for (int i = tid; i < nP * WS; i += T)
+        if (!MARG || B.pt_start[(size_t)w * B.maxP + i / WS] == 0) Wp0[i] = 0.0;
+    double* Wl0 = B.Wl + (size_t)w * B.maxL * 4 * WS;
+    if (DO_REST)
+      for (int i = tid; i < nL * 4 * WS; i += T)
+        if (!MARG || B.ln_start[(size_t)w * B.maxL + i / (4 * WS)] == 0) Wl0[i] = 0.0;
+  } else if (MARG) {
+    // uniform tracks: the one slot no factor writes is the start-frame block of the lines (their start observation is
+    // skipped in this pass) -- 24 entries per line, not the 13 k entries of all rows
+    double* Wl0 = B.Wl + (size_t)w * B.maxL * 4 * WS;
+    for (int i = tid; i < nL * 24; i += T) {
+      const int l = i / 24, e = i - 24 * l;
+      if (B.ln_start[(size_t)w * B.maxL + l] == 0) Wl0[(l * 4 + e / 6) * WS + e % 6] = 0.0;
+    }
+  }
+}
+
+// points out: the second commit chain's copy into Hv | gv (Hv | gv are contiguous) ...
+__device__ __forceinline__ void lin_points_fold(double* sm, double* imuJ) {
+  const int tid = threadIdx.x, T = LIN_THREADS;
+  for (int i = tid; i < HV_DOUBLES + NV; i += T) sm[i] += lin_Hv2(imuJ)[i];
+}
+// ... and the per-track sums out of LDS
+__device__ __forceinline__ void lin_points_out(const DevBatch& B, const int w, const double* pacc, const int PST, const int nP) {
+  const int tid = threadIdx.x, T = LIN_THREADS;
+  const int WS = B.WS;
+  for (int p = tid; p < nP; p += T) {
+    const size_t pi = (size_t)w * B.maxP + p;
+    const double* pa = pacc + p;
+    double* Wrow = B.Wp + pi * WS;
+    B.Hpp[pi] = pa[0];
+    B.gp[pi] = pa[PST];
+#pragma unroll
+    for (int a = 0; a < 6; ++a) { Wrow[a] = pa[(2 + a) * PST]; Wrow[WS - 6 + a] = pa[(8 + a) * PST]; }
+  }
+}
+
+// hand-over out (ROLE 1): Hv | gv and the cost of the point factors -> B.lin_part, B.lin_flag
+__device__ __forceinline__ void lin_handover_out(const DevBatch& B, const int w, const double* sm, const double cost_pts) {
+  const int tid = threadIdx.x, T = LIN_THREADS;
+  // this work-group's part of the visual Hessian / gradient and of the cost go to the window's other work-group with
+  // device-coherent stores (agent scope: global_store ... sc1, written through to the L2 both work-groups share -- they sit
+  // on the same XCD).  RELEASE, spelled out: every thread waits until ITS stores have been acknowledged (s_waitcnt
+  // vmcnt(0): on gfx9 stores count in vmcnt, and a write-through store is acknowledged by the L2), THEN the barrier, THEN
+  // the flag.  s_barrier alone does not wait for outstanding stores (the payload of another wave could still
+  // be on its way to a different L2 channel when the flag landed).  __builtin_amdgcn_fence(release, "agent") would do the
+  // wait too but adds buffer_wbl2 sc1, a write-back of the whole L2 per wave that every work-group of the XCD pays for
+  // (measured in round 3: 490 us against 270 for the 512-window launch); with write-through stores there is nothing
+  // to write back.
+  double* part = B.lin_part + (size_t)w * LIN_PART;
+  for (int i = tid; i < HV_DOUBLES + NV; i += T) __hip_atomic_store(&part[i], sm[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (tid == 0) __hip_atomic_store(&part[HV_DOUBLES + NV], cost_pts, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0) (expcnt 7, lgkmcnt 15: not waited for)
+  __syncthreads();
+  if (tid == 0) __hip_atomic_store(&B.lin_flag[w], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// lines out: lacc -> Hll, gl, the extrinsic columns of Wl; the eight Hw -> Hv, gv
+__device__ __forceinline__ void lin_lines_out(const DevBatch& B, const int w, double* Hv, double* gv, double* imuJ, const int nL) {
+  const int tid = threadIdx.x, T = LIN_THREADS;
+  const int WS = B.WS;
+  // per-line results out of the LDS accumulators
+  {
+    const double* lacc = lin_ln_acc(imuJ);
+    for (int l = tid; l < nL; l += T) {
+      const size_t li = (size_t)w * B.maxL + l;
+      const double* la = lacc + l * 38;
+      double* Hl = B.Hll + li * 16;
+      int t = 0;
+#pragma unroll
+      for (int a = 0; a < 4; ++a) {
+        B.gl[li * 4 + a] = la[10 + a];
+#pragma unroll
+        for (int c2 = 0; c2 <= a; ++c2, ++t) { Hl[4 * a + c2] = la[t]; Hl[4 * c2 + a] = la[t]; }
+#pragma unroll
+        for (int c2 = 0; c2 < 6; ++c2) B.Wl[(li * 4 + a) * WS + WS - 6 + c2] = la[14 + 6 * a + c2];
+      }
+    }
+  }
+  // fold the eight partial sums into the LDS Hessian / gradient, one thread per entry, waves in order
+  for (int e = tid; e < LIN_HW; e += T) {
+    double v = 0.0;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) v += lin_ln_Hw(imuJ, q)[e];
+    if (e < 693) {
+      const int f = e / 63, q = e - 63 * f;
+      if (q < 21) {
+        int a, c2;
+        tri_decode(q, a, c2);
+        Hv[hvi(6 * f + a, 6 * f + c2)] += v;
+      } else if (q < 57) {
+        const int a = (q - 21) / 6, c2 = (q - 21) % 6;
+        Hv[hvi(66 + a, 6 * f + c2)] += v;
+      } else {
+        gv[6 * f + (q - 57)] += v;
+      }
+    } else if (e < 714) {
+      int a, c2;
+      tri_decode(e - 693, a, c2);
+      Hv[hvi(66 + a, 66 + c2)] += v;
+    } else {
+      gv[66 + (e - 714)] += v;
+    }
+  }
+}
+
+// ---- IMU factors: raw residual / Jacobian per factor, then cooperative whitening ------
+// states, plds -> sa (requested here, consumed by lin_imu_whiten), imuact, raw imuJ | imur
+template <int MODE>
+__device__ __forceinline__ void lin_imu_raw(const DevBatch& B, const int w, const double* xp, const double* xs, const double* plds, double* imuJ, double* imur,
+                                               int* imuact, double (&sa)[2][4]) {
+  constexpr bool MARG = MODE != 0;
+  constexpr bool PRIOR_ONLY = MODE == 2;
+  const int tid = threadIdx.x, T = LIN_THREADS, lane = tid & 63;
+  for (int i = tid; i < 4650; i += T) imuJ[i] = 0.0;   // [imuJ | imur]: by everybody, not 450 stores by each of the ten lanes below
+  // S^T of this wave's factors as the A operand of the whitening (A[k][i] = S[i][k]), requested before the raw evaluation
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int f = (tid >> 6) + 8 * q;
+    const double* S = B.pre[(size_t)w * NF + (f < 10 ? f : 0) + 1].sqrt_info;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      const int k = 4 * ks + (lane >> 4), i = lane & 15;
+      sa[q][ks] = (f < 10 && i < 15 && k < 15 && k >= i) ? S[i * 15 + k] : 0.0;
+    }
+  }
+  __syncthreads();
+  // raw residual by ten lanes of wave 0, raw Jacobian by ten lanes of wave 1 (each is one long dependent chain)
+  if ((tid & 63) < 10 && tid < 128) {
+    const int f = tid & 63, j = f + 1;
+    const DevPreint& dp = *(const DevPreint*)(plds + PRE_LDS * f);   // (only the staged leading part is read)
+    bool act = MARG ? (j == 1 && dp.sum_dt < 10.0) : !(dp.sum_dt > 10.0);   // estimator.cpp:1088, :1261
+    if (PRIOR_ONLY) act = false;
+    if (tid < 64) imuact[f] = act ? 1 : 0;
+    if (act) {
+      PreInt p = load_preint(dp);
+      if (tid < 64) {
+        imu_residual_raw(p, xp + 7 * (j - 1), xs + 9 * (j - 1), xp + 7 * j, xs + 9 * j, B.opt.g_norm, imur + 15 * f);
+      } else {
+        ImuJac JB = imu_jacobian_raw(p, xp + 7 * (j - 1), xs + 9 * (j - 1), xp + 7 * j, xs + 9 * j, B.opt.g_norm);
+        imu_jac_dense(JB, imuJ + 450 * f);
+      }
+    }
+  }
+}
+// the static table entries of this thread's packed entries (e = u T + tid): one batch of loads, requested before the
+// whitening
+__device__ __forceinline__ void lin_asm_request(const DevBatch& B, int2 (&asmd)[LIN_ASM_PER_THREAD]) {
+  const int tid = threadIdx.x, T = LIN_THREADS;
+#pragma unroll
+  for (int u = 0; u < LIN_ASM_PER_THREAD; ++u) {
+    const int e = u * T + tid;
+    asmd[u] = ((const int2*)B.asm_tab)[e < NCP ? e : 0];
+  }
+}
+// Whitening J <- S J (S upper triangular 15 x 15, [J | r] 15 x 31) and the factor's J^T J on the FP64 matrix cores: one
+// wave per factor (waves 0 and 1 take two).  C[i][j] = sum_k A[k][i] B[k][j]: the A lane (kk, m) supplies A[4 ks + kk][m],
+// the B lane B[4 ks + kk][m], the accumulator lane (kk, m) holds C[kk + 4 v][m].  The 3570 entries of the 11 diagonal
+// 15 x 15 blocks (lower triangles) and 10 sub-diagonal blocks go to imuH for the assembly: a frame's diagonal block is
+// (term of the factor that ends in it) + (term of the factor that starts in it), in that order -- stored, barrier, added.
+__device__ __forceinline__ void lin_imu_whiten(double* imuJ, double* imur, const int* imuact, const double (&sa)[2][4]) {
+  const int tid = threadIdx.x, T = LIN_THREADS, lane = tid & 63;
+  double* imuH = lin_imuH(imuJ);
+  const int wvi = tid >> 6, m16 = lane & 15, kk = lane >> 4;
+  v4d_lin cd[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};        // (0..14)^2 part of this wave's factors, added after the barrier
+  for (int i = tid; i < 120; i += T) imuH[i] = 0.0;    // frame 0 has no factor ending in it
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int f = wvi + 8 * q;
+    if (f >= 10) break;
+    double* J = imuJ + 450 * f;
+    double* rr = imur + 15 * f;
+    const bool on = imuact[f] != 0;
+    v4d_lin jw[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct) {
+      const int c = 16 * ct + m16;
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        const int k = 4 * ks + kk;
+        const double bv = k < 15 ? (c < 30 ? J[k * 30 + c] : (c == 30 ? rr[k] : 0.0)) : 0.0;
+        jw[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(on ? sa[q][ks] : 0.0, bv, jw[ct], 0, 0, 0);
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (on) {
+#pragma unroll
+      for (int ct = 0; ct < 2; ++ct) {
+        const double vals[4] = {jw[ct].x, jw[ct].y, jw[ct].z, jw[ct].w};
+        const int c = 16 * ct + m16;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          const int r = kk + 4 * v;
+          if (r < 15) {
+            if (c < 30) J[r * 30 + c] = vals[v];
+            else if (c == 30) rr[r] = vals[v];
+          }
+        }
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    // J^T J: tiles (0,0), (1,0), (1,1) of the 30 x 30 product
+    v4d_lin c00 = {0, 0, 0, 0}, c10 = {0, 0, 0, 0}, c11 = {0, 0, 0, 0};
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      const int k = 4 * ks + kk;
+      const double lo = k < 15 ? J[k * 30 + m16] : 0.0;
+      const double hi = (k < 15 && m16 < 14) ? J[k * 30 + 16 + m16] : 0.0;
+      c00 = __builtin_amdgcn_mfma_f64_16x16x4f64(lo, lo, c00, 0, 0, 0);
+      c10 = __builtin_amdgcn_mfma_f64_16x16x4f64(hi, lo, c10, 0, 0, 0);
+      c11 = __builtin_amdgcn_mfma_f64_16x16x4f64(hi, hi, c11, 0, 0, 0);
+    }
+    // entry (i, j) of the product, i >= j: i, j < 15 -> diagonal block of frame f (held back); i >= 15 > j -> the
+    // sub-diagonal block (f + 1, f); both >= 15 -> diagonal block of frame f + 1 (stored now)
+    {
+      const double v00[4] = {c00.x, c00.y, c00.z, c00.w}, v10[4] = {c10.x, c10.y, c10.z, c10.w}, v11[4] = {c11.x, c11.y, c11.z, c11.w};
+      double keep[4] = {0, 0, 0, 0};
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        const int i0 = kk + 4 * v, j0 = m16;                  // tile (0,0)
+        if (i0 < 15 && j0 < 15) keep[v] = v00[v];             // (all of it is block (f, f); the row-15 entries go with tile (1,0))
+        const int i1 = 16 + kk + 4 * v;                       // tiles (1,0) and (1,1): product rows 16..31
+        if (i1 < 30) {
+          if (j0 < 15) imuH[11 * 120 + 225 * f + 15 * (i1 - 15) + j0] = v10[v];
+          else imuH[120 * (f + 1) + (i1 - 15) * (i1 - 14) / 2 + 0] = v10[v];                     // (i1, 15): column 0 of block (f+1, f+1)
+          const int j1 = 16 + m16;
+          if (j1 < 30 && j1 <= i1) imuH[120 * (f + 1) + (i1 - 15) * (i1 - 14) / 2 + (j1 - 15)] = v11[v];
+        }
+        if (i0 == 15) {                                       // product row 15 sits in tile (0,0) / its column 15
+          if (j0 < 15) imuH[11 * 120 + 225 * f + j0] = v00[v];
+          else imuH[120 * (f + 1)] = v00[v];                  // (15, 15)
+        }
+      }
+      cd[q] = v4d_lin{keep[0], keep[1], keep[2], keep[3]};
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int f = wvi + 8 * q;
+    if (f >= 10) break;
+    const double keep[4] = {cd[q].x, cd[q].y, cd[q].z, cd[q].w};
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      const int i0 = kk + 4 * v, j0 = m16;
+      if (i0 < 15 && j0 <= i0) imuH[120 * f + i0 * (i0 + 1) / 2 + j0] += keep[v];
+    }
+  }
+}
+__device__ __forceinline__ void lin_imu_cost(const double* imur, const int* imuact, double& cost) {
+  const int tid = threadIdx.x;
+  if (tid < 10 && imuact[tid]) {
+    double s = 0;
+    for (int k = 0; k < 15; ++k) s += imur[15 * tid + k] * imur[15 * tid + k];
+    cost += 0.5 * s;
+  }
+}
+
+// hand-over in (ROLE 2): B.lin_flag, B.lin_part -> Hv | gv, thread 0's cost
+__device__ __forceinline__ void lin_handover_in(const DevBatch& B, const int w, double* sm, double& cost) {
+  const int tid = threadIdx.x, T = LIN_THREADS;
+  // the point factors' part (the other work-group of this window): Hv = (lines) + (points), gv likewise -- the sum the
+  // single work-group forms, in the other order of its two terms
+  // ACQUIRE, spelled out: the flag is polled with agent-scope loads (sc1: served by the L2, never by this CU's vector
+  // cache); the payload loads below are agent-scope loads too, issued after the barrier that follows the successful
+  // poll (a wave issues its memory instructions in order and none of them before s_barrier completes), so they reach the
+  // L2 after the flag store did -- and the writer's stores were acknowledged by that L2 before the flag was written.
+  // No buffer_inv is needed because no load of this payload may hit the vector cache.
+  if (tid == 0) {
+    while (__hip_atomic_load(&B.lin_flag[w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 1) __builtin_amdgcn_s_sleep(32);
+    __hip_atomic_store(&B.lin_flag[w], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __syncthreads();
+  const double* part = B.lin_part + (size_t)w * LIN_PART;
+  for (int i = tid; i < HV_DOUBLES + NV; i += T) sm[i] += __hip_atomic_load(&part[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (tid == 0) cost += __hip_atomic_load(&part[HV_DOUBLES + NV], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __syncthreads();
+}
+
+// ---- assemble the packed cam Hessian and gradient in HBM -----------------------------------
+// Hv, gv, imuH, imuJ | imur, prH, prg, invmap, asmd -> Hcc in one pass, the third pass for n > PRH_N, gc
+__device__ __forceinline__ void lin_assemble(const DevBatch& B, const int w, const double* Hv, const double* gv, double* imuJ, const double* imur,
+                                                const double* prg, const double* prH, const int PRH_N, const int* invmap,
+                                                const int* imuact, const int n, const bool ex_free,
+                                                const int2 (&asmd)[LIN_ASM_PER_THREAD]) {
+  const int tid = threadIdx.x, T = LIN_THREADS;
+  const double* const imuH = lin_imuH(imuJ);
+  double* Hout = B.Hcc + (size_t)w * NCP;
+  const double* pH = B.pr_H + (size_t)w * B.prS;
+  // Every entry is stored ONCE, with its three sources summed in registers: adding to what an earlier pass had stored
+  // is a global read-modify-write, i.e. a full round trip (~3 k cycles with all CUs in this phase) behind every store.
+  // (1) the 3570 entries the IMU factors touch (11 diagonal 15x15 blocks, 10 sub-diagonal ones), each summing its one or
+  // two J^T J terms, go to LDS; (2) rows to waves, columns to lanes: visual block + IMU block + prior (J0^T J0 staged in LDS
+  // by the prior phase), coalesced stores, no index decoding beyond c / 15.  Priors larger than PRH_N (none in the
+  // reference's windows) take a third pass that adds their entries in HBM.
+  VPL_STAMP(B, w, 26);
+  const bool prior_lds = n > 0 && n <= PRH_N;
+  {
+    // flat over the packed triangle: fully coalesced stores; the table entries were requested before the IMU blocks
+#pragma unroll
+    for (int u = 0; u < LIN_ASM_PER_THREAD; ++u) {
+      const int e = u * T + tid;
+      if (e >= NCP) continue;
+      const int hv = asmd[u].x & 0xffff, im = asmd[u].x >> 16, r = asmd[u].y & 255, c = asmd[u].y >> 8;
+      // branch-free: every source is read (clamped index) and selected, so that the LDS reads of many entries overlap
+      const double vh = Hv[hv ? hv - 1 : 0], vi = imuH[im ? im - 1 : 0];
+      const int ir = prior_lds ? invmap[r] : -1, ic = prior_lds ? invmap[c] : -1;
+      const bool hp = ir >= 0 && ic >= 0;
+      const int hi_ = ic > ir ? ic : ir, lo_ = ic > ir ? ir : ic;
+      const double vp = prH[hp ? hi_ * (hi_ + 1) / 2 + lo_ : 0];
+      double v = hv ? vh : 0.0;
+      v += im ? vi : 0.0;
+      v += hp ? vp : 0.0;
+      if (!ex_free && r >= 165) v = 0.0;
+      Hout[e] = v;
+    }
+  }
+  VPL_STAMP(B, w, 27);
+  if (n > PRH_N) {
+    __syncthreads();
+    const int np = n * (n + 1) / 2;
+    for (int base = 0; base < np; base += 4 * T) {
+      double ph[4];
+      int tr_[4], tc_[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int e = base + u * T + tid;
+        ph[u] = 0.0; tr_[u] = -1; tc_[u] = 0;
+        if (e < np) {
+          int i, j;
+          tri_decode(e, i, j);
+          ph[u] = pH[(size_t)i * n + j];
+          const int ri = B.pr_map[(size_t)w * MAXPN + i], rj = B.pr_map[(size_t)w * MAXPN + j];
+          tr_[u] = ri > rj ? ri : rj;
+          tc_[u] = ri > rj ? rj : ri;
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (tr_[u] >= 0 && (ex_free || tr_[u] < 165)) Hout[(size_t)tr_[u] * (tr_[u] + 1) / 2 + tc_[u]] += ph[u];
+    }
+  }
+  for (int r = tid; r < NC; r += T) {
+    double v = 0.0;
+    const int vr = cam2vis(r);
+    if (vr >= 0) v += gv[vr];
+    if (r < 165) {
+      const int fr = r / 15;
+      if (fr >= 1 && imuact[fr - 1]) {
+        const double* J = imuJ + 450 * (fr - 1);
+        const double* rr = imur + 15 * (fr - 1);
+        const int a = r - 15 * (fr - 1);
+        double s = 0;
+#pragma unroll
+        for (int k = 0; k < 15; ++k) s += J[k * 30 + a] * rr[k];
+        v += s;
+      }
+      if (fr < 10 && imuact[fr]) {
+        const double* J = imuJ + 450 * fr;
+        const double* rr = imur + 15 * fr;
+        const int a = r - 15 * fr;
+        double s = 0;
+#pragma unroll
+        for (int k = 0; k < 15; ++k) s += J[k * 30 + a] * rr[k];
+        v += s;
+      }
+    }
+    if (n > 0 && invmap[r] >= 0) v += prg[invmap[r]];
+    if (!ex_free && r >= 165) v = 0.0;
+    B.gc[(size_t)w * NC + r] = v;
+  }
+}
+
+// finish: block sum, TrState, the NaN rule
+template <int MODE>
+__device__ __forceinline__ void lin_finish(TrState* tr, double* red, double cost) {
+  constexpr bool MARG = MODE != 0;
+  const int tid = threadIdx.x;
+  cost = block_sum(cost, red);
+  if (tid == 0 && !MARG) {
+    tr->x_cost = cost;
+    if (tr->iter == 0) tr->initial_cost = cost;
+    tr->fresh_lin = 1;
+    // A NaN / inf among the inputs: ceres' evaluator rejects the initial point ("Initial residual and Jacobian evaluation
+    // failed", trust_region_minimizer.cc IterationZero) and Solve returns FAILURE with an empty iteration list -- the
+    // reference goes on to double2vector2 and the marginalisation with the states as they were.  Reported the same way:
+    // termination 2, iterations = successful steps = -1 (size of the list - 1), costs 0; every later kernel of the solve
+    // leaves a window whose status is set.
+    if (tr->iter == 0 && tr->num_successful == 0 && !isfinite(cost)) {
+      tr->status = 2; tr->iter = -1; tr->num_successful = -1; tr->x_cost = 0.0; tr->initial_cost = 0.0;
+    }
+  }
+}
+
 // MODE 0: solve linearisation; 1: MARGIN_OLD assembly (prior + IMU(0,1) + landmarks that start in frame 0);
 // 2: MARGIN_SECOND_NEW assembly (the prior alone, estimator.cpp:1387-1405)
 // ROLE 0: the whole linearisation in one work-group (the marginalisation passes).  The solve pass runs as TWO work-groups per
@@ -297,6 +854,12 @@ inline void lin_asm_entry(int r, int c, int* out) {
 // of the others was rejected) more than half of the CUs were idle while one work-group per window walked the phases one
 // after the other; with every CU busy the split costs nothing (the same work in twice as many work-groups).  ROLE 2's
 // work-group follows ROLE 1's in dispatch order, so the one it waits for is always resident or done.
+// The body is the list of the phases above, with the barriers between them.  Which pass runs what:
+//   <0,0> (solve, one work-group)   every phase
+//   <0,1> (solve, point factors)    stage, clear W (lin_clear_w takes ROLE: the points' rows), points, points out, hand-over out
+//   <0,2> (solve, the rest)         stage, prior, clear W (the lines' rows), lines, IMU, hand-over in, assemble, finish
+//   <1,0> (MARGIN_OLD)              every phase on the factor subset; no point cost, nothing for TrState
+//   <2,0> (MARGIN_SECOND_NEW)       every phase, the point, line and IMU phases on empty tables
 template <int MODE, int ROLE>
 __device__ __forceinline__ void lin_body(const DevBatch& B, const int w, double* sm) {
   constexpr bool MARG = MODE != 0;
@@ -336,132 +899,23 @@ __device__ __forceinline__ void lin_body(const DevBatch& B, const int w, double*
   const int nP = B.nP[w], nL = B.nL[w];
   // the marginalisation evaluates every block, constant or not (marginalization_factor.cpp:3-69)
   const bool ex_free = MARG || B.opt.estimate_extrinsic != 0;
-  for (int i = tid; i < HV_DOUBLES + NV; i += T) sm[i] = 0.0;
-  if (DO_PTS) for (int i = tid; i < 14 * PST; i += T) pacc[i] = 0.0;
-  for (int i = tid; i < 84; i += T) xp[i] = i < 77 ? B.pose[(size_t)w * 77 + i] : B.ex[(size_t)w * 7 + (i - 77)];
-  if (DO_REST) {
-    for (int i = tid; i < 99; i += T) xs[i] = B.sb[(size_t)w * 99 + i];
-    for (int i = tid; i < 10 * PRE_LDS; i += T) {   // (the IMU phase is then free of global round trips)
-      const int f = i / PRE_LDS;
-      plds[i] = ((const double*)&B.pre[(size_t)w * NF + f + 1])[i - PRE_LDS * f];
-    }
-  }
-  for (int i = tid; i < NC; i += T) invmap[i] = -1;
-  if (tid < 5) tick[tid] = 0;
-  // The prior's inputs are requested HERE, with the states: its block table and linearisation point (one lane per block), the
-  // index map, and this lane's part of the rows of J0 and H = J0^T J0 (eight lanes per row, the first LIN_PJ columns of
-  // each) -- the phase was three dependent round trips (table -> barrier -> rows), each ~3 k cycles with every CU in it.
-  constexpr int LIN_PJ = 6;
-  const int n = DO_REST ? B.pr_n[w] : 0, nb = n > 0 ? B.pr_nb[w] : 0;
-  const int prow = tid >> 3, psub = tid & 7;
-  int pkind = 0, pfr = 0, pidx = 0, pmap = -1;
-  double px0[9], pj0[LIN_PJ], phv[LIN_PJ], r0r = 0.0, g0r = 0.0;
-  if (tid < nb) {
-    pkind = B.pr_kind[(size_t)w * MAXPB + tid]; pfr = B.pr_frame[(size_t)w * MAXPB + tid]; pidx = B.pr_idx[(size_t)w * MAXPB + tid];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) px0[k] = B.pr_x0[((size_t)w * MAXPB + tid) * 9 + k];
-  }
-  if (tid < n) pmap = B.pr_map[(size_t)w * MAXPN + tid];
-  {
-    const double* J0 = B.pr_J0 + (size_t)w * B.prS;
-    const double* Hp = B.pr_H + (size_t)w * B.prS;
-#pragma unroll
-    for (int q = 0; q < LIN_PJ; ++q) {
-      const int c = psub + 8 * q;
-      const bool in = prow < n && c < n;
-      pj0[q] = in ? J0[(size_t)prow * n + c] : 0.0;
-      phv[q] = in ? Hp[(size_t)prow * n + c] : 0.0;
-    }
-    if (prow < n && psub == 0) { r0r = B.pr_r0[(size_t)w * MAXPN + prow]; g0r = B.pr_g0[(size_t)w * MAXPN + prow]; }
-  }
+  PriorRegs P;
+  lin_stage<ROLE>(B, w, sm, xp, xs, pacc, PST, plds, invmap, tick, P);
   __syncthreads();
   double cost = 0.0;
   VPL_STAMP(B, w, 16);
-
-  // ---- prior: r = r0 + J0 dx ; g = J0^T r -------------------------------------------
-  if (n > 0) {
-    if (tid < nb) {
-      const double* x = pkind == 0 ? xp + 7 * pfr : pkind == 1 ? xs + 9 * pfr : xp + 77;
-      double dx[9];
-      prior_block_dx(pkind, x, px0, dx);
-      int ls = pkind == 1 ? 9 : 6;
-      for (int k = 0; k < ls; ++k) prdx[pidx + k] = dx[k];
-    }
-    if (tid < n) invmap[pmap] = tid;
-    for (int i = tid + T; i < n; i += T) invmap[B.pr_map[(size_t)w * MAXPN + i]] = i;
-    __syncthreads();
-    const double* J0 = B.pr_J0 + (size_t)w * B.prS;
-    // r = r0 + J0 dx and g = J0^T r = g0 + H dx (H = J0^T J0, g0 = J0^T r0 from k_prep) in ONE pass: eight lanes per row
-    const double* Hp = B.pr_H + (size_t)w * B.prS;
-    for (int r = prow; r < n; r += T >> 3) {
-      const bool first = r == prow;
-      double s = 0, sg = 0;
-      if (first) {
-#pragma unroll
-        for (int q = 0; q < LIN_PJ; ++q) {
-          const int c = psub + 8 * q;
-          if (c < n) {
-            const double dxc = prdx[c];
-            s += pj0[q] * dxc;
-            sg += phv[q] * dxc;
-            if (n <= PRH_N && c <= r) prH[r * (r + 1) / 2 + c] = phv[q];   // kept for the assembly
-          }
-        }
-      }
-      for (int c = psub + (first ? 8 * LIN_PJ : 0); c < n; c += 8) {
-        const double dxc = prdx[c];
-        const double hrc = Hp[(size_t)r * n + c];
-        s += J0[(size_t)r * n + c] * dxc;
-        sg += hrc * dxc;
-        if (n <= PRH_N && c <= r) prH[r * (r + 1) / 2 + c] = hrc;
-      }
-      s += __shfl_xor(s, 1, 64); s += __shfl_xor(s, 2, 64); s += __shfl_xor(s, 4, 64);
-      sg += __shfl_xor(sg, 1, 64); sg += __shfl_xor(sg, 2, 64); sg += __shfl_xor(sg, 4, 64);
-      if (psub == 0) {
-        if (!first) { r0r = B.pr_r0[(size_t)w * MAXPN + r]; g0r = B.pr_g0[(size_t)w * MAXPN + r]; }
-        s += r0r;
-        prr[r] = s;
-        prg[r] = sg + g0r;
-        cost += 0.5 * s * s;
-      }
-    }
-  }
-
+  if (DO_REST) lin_prior(B, w, xp, xs, prdx, prr, prg, prH, PRH_N, invmap, P, cost);   // (one barrier inside: prdx, invmap)
   double costp = 0.0;      // this thread's share of the point factors' cost, kept apart from the rest (see below)
   VPL_STAMP(B, w, 18);
+  lin_clear_w<MODE, ROLE>(B, w, nP, nL);
+  __syncthreads();
+  VPL_STAMP(B, w, 23);
+  // ---- phase: points, inline (as a function of its own it costs spilled registers: profiles/r14)
   // ---- visual factors ----------------------------------------------------------------------
   // Wave-uniform rounds: in every round each lane linearises (at most) one factor; the extrinsic
   // block, which every factor touches, is reduced across the wave with DPP/shuffles and added once
   // per wave, the pose blocks go to the LDS Hessian with ds_add_f64, landmark-local sums stay in
   // registers (points: one lane per track) or in LDS accumulators (lines: one lane per observation).
-  const double* xe = xp + 77;
-  const double hub = B.opt.huber_delta;
-  const int lane = tid & 63;
-  // zero the W rows first where some slot is not written by a factor (shorter tracks, erased lines, the start-frame
-  // slot of the lines in the marginalisation pass); uniform track lengths need no fill in the solve
-  const int WS = B.WS;
-  if (B.wfill) {
-    // (the marginalisation pass only ever reads the rows of the tracks that start in frame 0)
-    double* Wp0 = B.Wp + (size_t)w * B.maxP * WS;
-    if (DO_PTS)
-      for (int i = tid; i < nP * WS; i += T)
-        if (!MARG || B.pt_start[(size_t)w * B.maxP + i / WS] == 0) Wp0[i] = 0.0;
-    double* Wl0 = B.Wl + (size_t)w * B.maxL * 4 * WS;
-    if (DO_REST)
-      for (int i = tid; i < nL * 4 * WS; i += T)
-        if (!MARG || B.ln_start[(size_t)w * B.maxL + i / (4 * WS)] == 0) Wl0[i] = 0.0;
-  } else if (MARG) {
-    // uniform tracks: the one slot no factor writes is the start-frame block of the lines (their start observation is
-    // skipped in this pass) -- 24 entries per line, not the 13 k entries of all rows
-    double* Wl0 = B.Wl + (size_t)w * B.maxL * 4 * WS;
-    for (int i = tid; i < nL * 24; i += T) {
-      const int l = i / 24, e = i - 24 * l;
-      if (B.ln_start[(size_t)w * B.maxL + l] == 0) Wl0[(l * 4 + e / 6) * WS + e % 6] = 0.0;
-    }
-  }
-  __syncthreads();
-
-  VPL_STAMP(B, w, 23);
   // points: the work unit is (start frame s, observation index k, <= 16 of the tracks that start in s and are seen at k).
   // Inside a unit every lane works on the same pair of frames (s, j = s + k), so the 6x6 blocks a point factor touches are
   // uniform over its lanes and the sum of J^T [J | r] over them is a rank-2n update: the lanes stage their two Jacobian rows
@@ -472,12 +926,17 @@ __device__ __forceinline__ void lin_body(const DevBatch& B, const int w, double*
   // entries with the sign flipped.  The host packs the units into quarter-wave slots (pu_lane / pu_sub): a full unit takes
   // a slot, small ones share one -- 200 tracks x 5 factors are 60 full units + 30 of two tracks = 64 slots = 2 rounds of
   // the 8 waves.
+  // lane / unit tables -> Wp, pacc, both commit chains; this thread's share of the point factors' cost
   if (DO_PTS) {
+    const double* xe = xp + 77;
+    const double hub = B.opt.huber_delta;
+    const int lane = tid & 63;
+    const int WS = B.WS;
     const int wvi = tid >> 6, nwv = T >> 6;
     const int nRounds = PRIOR_ONLY ? 0 : (MARG ? B.pu_cnt0[w] : B.pu_cnt[w]);
     const int2* plane = (const int2*)B.pu_lane + (size_t)w * B.maxPR * 512;
     const int* psub = B.pu_sub + (size_t)w * B.maxPR * 512;
-    double* stg = imuJ + wvi * (32 * STG_LD);              // this wave's staging tile: 32 rows x 20 (stride STG_LD)
+    double* stg = lin_pt_stage(imuJ, wvi);               // this wave's staging tile: 32 rows x 20 (stride STG_LD)
     const int m16 = lane & 15, kk = lane >> 4;
     const int b_cls = m16 < 6 ? 0 : (m16 < 9 ? 1 : (m16 < 15 ? 2 : 3));       // tile column of this lane: block (s | j | extrinsic | residual)
     const int b_off = m16 < 6 ? m16 : (m16 < 9 ? m16 - 3 : m16 - 9);        // and offset inside the 6-wide block
@@ -488,9 +947,9 @@ __device__ __forceinline__ void lin_body(const DevBatch& B, const int w, double*
     // Two commit chains run side by side: waves 0..3 add into Hv / gv, waves 4..7 into a second copy that lives in the
     // part of the staging region the MFMA tiles leave free; the copy is folded into Hv after the phase.
     const int half = wvi >= nwv / 2 ? 1 : 0, wih = wvi - half * (nwv / 2);
-    double* HvC = half ? imuJ + LIN_STAGE : Hv;
-    double* gvC = half ? imuJ + LIN_STAGE + HV_DOUBLES : gv;
-    if (half) for (int i = tid - T / 2; i < HV_DOUBLES + NV; i += T / 2) imuJ[LIN_STAGE + i] = 0.0;
+    double* HvC = half ? lin_Hv2(imuJ) : Hv;
+    double* gvC = half ? lin_Hv2(imuJ) + HV_DOUBLES : gv;
+    if (half) for (int i = tid - T / 2; i < HV_DOUBLES + NV; i += T / 2) lin_Hv2(imuJ)[i] = 0.0;
     __syncthreads();
     auto ticket_wait = [&](int which, int seq) {
       while (__hip_atomic_load(&tick[which], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != seq) {}
@@ -600,8 +1059,6 @@ __device__ __forceinline__ void lin_body(const DevBatch& B, const int w, double*
         }
       }
       const unsigned long long actmask = __ballot(act);
-      // per-track sums over k: a track's factors sit in different units, i.e. in different waves -- one chain over all
-      // waves; two lanes of a wave may hold the same track with different k: atomic adds, lane order
       PT_LAP(0);
       // Per-track sums over k (H_ll, g_l, W_s, W_ext): a track's factors sit in different units, but (host packing) all in
       // the same half of the work-group: one chain over the half's four waves orders the LDS adds (tick[3 + half]); two
@@ -678,20 +1135,13 @@ __device__ __forceinline__ void lin_body(const DevBatch& B, const int w, double*
     if (lane == 0 && wvi == 0)
       for (int a = 0; a < 6; ++a) B.dbg[(size_t)w * 64 + 44 + a] = pt_t[a];
 #endif
+#undef PT_LAP
   }
   __syncthreads();
   VPL_STAMP(B, w, 51);
-  if (DO_PTS) for (int i = tid; i < HV_DOUBLES + NV; i += T) sm[i] += imuJ[LIN_STAGE + i];   // second commit chain's copy (Hv | gv are contiguous)
+  if (DO_PTS) lin_points_fold(sm, imuJ);
   VPL_STAMP(B, w, 50);
-  if (DO_PTS) for (int p = tid; p < nP; p += T) {   // per-track sums out of LDS
-    const size_t pi = (size_t)w * B.maxP + p;
-    const double* pa = pacc + p;
-    double* Wrow = B.Wp + pi * WS;
-    B.Hpp[pi] = pa[0];
-    B.gp[pi] = pa[PST];
-#pragma unroll
-    for (int a = 0; a < 6; ++a) { Wrow[a] = pa[(2 + a) * PST]; Wrow[WS - 6 + a] = pa[(8 + a) * PST]; }
-  }
+  if (DO_PTS) lin_points_out(B, w, pacc, PST, nP);
   VPL_STAMP(B, w, 55);
   __syncthreads();   // staging space is handed over to the IMU / line phases
   VPL_STAMP(B, w, 24);
@@ -702,24 +1152,11 @@ __device__ __forceinline__ void lin_body(const DevBatch& B, const int w, double*
     cost_pts = block_sum(costp, red);
   }
   if (ROLE == 1) {
-    // this work-group's part of the visual Hessian / gradient and of the cost go to the window's other work-group with
-    // device-coherent stores (agent scope: global_store ... sc1, written through to the L2 both work-groups share -- they sit
-    // on the same XCD).  RELEASE, spelled out: every thread waits until ITS stores have been acknowledged (s_waitcnt
-    // vmcnt(0): on gfx9 stores count in vmcnt, and a write-through store is acknowledged by the L2), THEN the barrier, THEN
-    // the flag.  s_barrier alone does not wait for outstanding stores (the payload of another wave could still
-    // be on its way to a different L2 channel when the flag landed).  __builtin_amdgcn_fence(release, "agent") would do the
-    // wait too but adds buffer_wbl2 sc1, a write-back of the whole L2 per wave that every work-group of the XCD pays for
-    // (measured in round 3: 490 us against 270 for the 512-window launch); with write-through stores there is nothing
-    // to write back.
-    double* part = B.lin_part + (size_t)w * LIN_PART;
-    for (int i = tid; i < HV_DOUBLES + NV; i += T) __hip_atomic_store(&part[i], sm[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (tid == 0) __hip_atomic_store(&part[HV_DOUBLES + NV], cost_pts, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0) (expcnt 7, lgkmcnt 15: not waited for)
-    __syncthreads();
-    if (tid == 0) __hip_atomic_store(&B.lin_flag[w], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    lin_handover_out(B, w, sm, cost_pts);
     return;
   }
   VPL_STAMP(B, w, 22);
+  // ---- phase: lines, inline (as a function of its own it costs spilled registers: profiles/r14)
   // ---- lines -----------------------------------------------------------------------------------------------------
   // One lane per (track, observation), laid out by the host table ll_tab: every wave holds WHOLE tracks, k-major --
   // lane = k * NLW + i for observation k of the wave's i-th line.  Every LDS accumulator of this phase is touched by ONE
@@ -728,11 +1165,16 @@ __device__ __forceinline__ void lin_body(const DevBatch& B, const int w, double*
   // Hessian in fixed order after the phase.  The adds of one wave reach the LDS in program order (and the lanes of one
   // instruction in lane order), so the sums -- and with them the whole solve -- are the same bits on every run; the
   // cross-wave ds_add_f64 of round 1 made two solves of identical inputs differ by 1e-9 .. 1e-6 m.
+  // lw, observations -> Wl, the per-track sums lacc, the waves' partial sums Hw; this thread's share of the cost
   {
+    const double* xe = xp + 77;
+    const double hub = B.opt.huber_delta;
+    const int lane = tid & 63;
+    const int WS = B.WS;
     const int NLW = B.llNLW, KL = B.llK;
     const int wvi = tid >> 6;
-    double* Hw = imuJ + wvi * LIN_HW;
-    double* lacc = imuJ + 8 * LIN_HW;                    // maxL * 38 per-track accumulators
+    double* Hw = lin_ln_Hw(imuJ, wvi);
+    double* lacc = lin_ln_acc(imuJ);                    // maxL * 38 per-track accumulators
     for (int i = lane; i < LIN_HW; i += 64) Hw[i] = 0.0;
     for (int i = tid; i < nL * 38; i += T) lacc[i] = 0.0;
     __syncthreads();
@@ -842,318 +1284,27 @@ __device__ __forceinline__ void lin_body(const DevBatch& B, const int w, double*
     }
   }
   __syncthreads();
-  // per-line results out of the LDS accumulators
-  {
-    const double* lacc = imuJ + 8 * LIN_HW;
-    for (int l = tid; l < nL; l += T) {
-      const size_t li = (size_t)w * B.maxL + l;
-      const double* la = lacc + l * 38;
-      double* Hl = B.Hll + li * 16;
-      int t = 0;
-#pragma unroll
-      for (int a = 0; a < 4; ++a) {
-        B.gl[li * 4 + a] = la[10 + a];
-#pragma unroll
-        for (int c2 = 0; c2 <= a; ++c2, ++t) { Hl[4 * a + c2] = la[t]; Hl[4 * c2 + a] = la[t]; }
-#pragma unroll
-        for (int c2 = 0; c2 < 6; ++c2) B.Wl[(li * 4 + a) * WS + WS - 6 + c2] = la[14 + 6 * a + c2];
-      }
-    }
-  }
-  // fold the eight partial sums into the LDS Hessian / gradient, one thread per entry, waves in order
-  for (int e = tid; e < LIN_HW; e += T) {
-    double v = 0.0;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) v += imuJ[q * LIN_HW + e];
-    if (e < 693) {
-      const int f = e / 63, q = e - 63 * f;
-      if (q < 21) {
-        int a, c2;
-        tri_decode(q, a, c2);
-        Hv[hvi(6 * f + a, 6 * f + c2)] += v;
-      } else if (q < 57) {
-        const int a = (q - 21) / 6, c2 = (q - 21) % 6;
-        Hv[hvi(66 + a, 6 * f + c2)] += v;
-      } else {
-        gv[6 * f + (q - 57)] += v;
-      }
-    } else if (e < 714) {
-      int a, c2;
-      tri_decode(e - 693, a, c2);
-      Hv[hvi(66 + a, 66 + c2)] += v;
-    } else {
-      gv[66 + (e - 714)] += v;
-    }
-  }
+  lin_lines_out(B, w, Hv, gv, imuJ, nL);
   __syncthreads();   // the staging region goes to the IMU phase
   VPL_STAMP(B, w, 25);
-  // ---- IMU factors: raw residual / Jacobian per factor, then cooperative whitening ------
-  for (int i = tid; i < 4650; i += T) imuJ[i] = 0.0;   // [imuJ | imur]: by everybody, not 450 stores by each of the ten lanes below
-  // S^T of this wave's factors as the A operand of the whitening (A[k][i] = S[i][k]), requested before the raw evaluation
-  double sa[2][4];
-#pragma unroll
-  for (int q = 0; q < 2; ++q) {
-    const int f = (tid >> 6) + 8 * q;
-    const double* S = B.pre[(size_t)w * NF + (f < 10 ? f : 0) + 1].sqrt_info;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      const int k = 4 * ks + (lane >> 4), i = lane & 15;
-      sa[q][ks] = (f < 10 && i < 15 && k < 15 && k >= i) ? S[i * 15 + k] : 0.0;
-    }
-  }
-  __syncthreads();
-  // raw residual by ten lanes of wave 0, raw Jacobian by ten lanes of wave 1 (each is one long dependent chain)
-  if ((tid & 63) < 10 && tid < 128) {
-    const int f = tid & 63, j = f + 1;
-    const DevPreint& dp = *(const DevPreint*)(plds + PRE_LDS * f);   // (only the staged leading part is read)
-    bool act = MARG ? (j == 1 && dp.sum_dt < 10.0) : !(dp.sum_dt > 10.0);   // estimator.cpp:1088, :1261
-    if (PRIOR_ONLY) act = false;
-    if (tid < 64) imuact[f] = act ? 1 : 0;
-    if (act) {
-      PreInt p = load_preint(dp);
-      if (tid < 64) {
-        imu_residual_raw(p, xp + 7 * (j - 1), xs + 9 * (j - 1), xp + 7 * j, xs + 9 * j, B.opt.g_norm, imur + 15 * f);
-      } else {
-        ImuJac JB = imu_jacobian_raw(p, xp + 7 * (j - 1), xs + 9 * (j - 1), xp + 7 * j, xs + 9 * j, B.opt.g_norm);
-        imu_jac_dense(JB, imuJ + 450 * f);
-      }
-    }
-  }
+  double sa[2][4];                       // S^T of this wave's IMU factors: lin_imu_raw -> lin_imu_whiten
+  lin_imu_raw<MODE>(B, w, xp, xs, plds, imuJ, imur, imuact, sa);   // (one barrier inside: [imuJ | imur] zeroed)
   __syncthreads();
   VPL_STAMP(B, w, 28);
-  // the static table entries of this thread's packed entries (e = u T + tid): one batch of loads, requested before the
-  // whitening
-  constexpr int ASM_PER_THREAD = (NCP + LIN_THREADS - 1) / LIN_THREADS;
-  int2 asmd[ASM_PER_THREAD];
-#pragma unroll
-  for (int u = 0; u < ASM_PER_THREAD; ++u) {
-    const int e = u * T + tid;
-    asmd[u] = ((const int2*)B.asm_tab)[e < NCP ? e : 0];
-  }
-  // Whitening J <- S J (S upper triangular 15 x 15, [J | r] 15 x 31) and the factor's J^T J on the FP64 matrix cores: one
-  // wave per factor (waves 0 and 1 take two).  C[i][j] = sum_k A[k][i] B[k][j]: the A lane (kk, m) supplies A[4 ks + kk][m],
-  // the B lane B[4 ks + kk][m], the accumulator lane (kk, m) holds C[kk + 4 v][m].  The 3570 entries of the 11 diagonal
-  // 15 x 15 blocks (lower triangles) and 10 sub-diagonal blocks go to imuH for the assembly: a frame's diagonal block is
-  // (term of the factor that ends in it) + (term of the factor that starts in it), in that order -- stored, barrier, added.
-  double* imuH = imuJ + 4650;
-  {
-    const int wvi = tid >> 6, m16 = lane & 15, kk = lane >> 4;
-    v4d_lin cd[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};        // (0..14)^2 part of this wave's factors, added after the barrier
-    for (int i = tid; i < 120; i += T) imuH[i] = 0.0;    // frame 0 has no factor ending in it
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int f = wvi + 8 * q;
-      if (f >= 10) break;
-      double* J = imuJ + 450 * f;
-      double* rr = imur + 15 * f;
-      const bool on = imuact[f] != 0;
-      v4d_lin jw[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
-#pragma unroll
-      for (int ct = 0; ct < 2; ++ct) {
-        const int c = 16 * ct + m16;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-          const int k = 4 * ks + kk;
-          const double bv = k < 15 ? (c < 30 ? J[k * 30 + c] : (c == 30 ? rr[k] : 0.0)) : 0.0;
-          jw[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(on ? sa[q][ks] : 0.0, bv, jw[ct], 0, 0, 0);
-        }
-      }
-      __builtin_amdgcn_wave_barrier();
-      if (on) {
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct) {
-          const double vals[4] = {jw[ct].x, jw[ct].y, jw[ct].z, jw[ct].w};
-          const int c = 16 * ct + m16;
-#pragma unroll
-          for (int v = 0; v < 4; ++v) {
-            const int r = kk + 4 * v;
-            if (r < 15) {
-              if (c < 30) J[r * 30 + c] = vals[v];
-              else if (c == 30) rr[r] = vals[v];
-            }
-          }
-        }
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-      // J^T J: tiles (0,0), (1,0), (1,1) of the 30 x 30 product
-      v4d_lin c00 = {0, 0, 0, 0}, c10 = {0, 0, 0, 0}, c11 = {0, 0, 0, 0};
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        const int k = 4 * ks + kk;
-        const double lo = k < 15 ? J[k * 30 + m16] : 0.0;
-        const double hi = (k < 15 && m16 < 14) ? J[k * 30 + 16 + m16] : 0.0;
-        c00 = __builtin_amdgcn_mfma_f64_16x16x4f64(lo, lo, c00, 0, 0, 0);
-        c10 = __builtin_amdgcn_mfma_f64_16x16x4f64(hi, lo, c10, 0, 0, 0);
-        c11 = __builtin_amdgcn_mfma_f64_16x16x4f64(hi, hi, c11, 0, 0, 0);
-      }
-      // entry (i, j) of the product, i >= j: i, j < 15 -> diagonal block of frame f (held back); i >= 15 > j -> the
-      // sub-diagonal block (f + 1, f); both >= 15 -> diagonal block of frame f + 1 (stored now)
-      {
-        const double v00[4] = {c00.x, c00.y, c00.z, c00.w}, v10[4] = {c10.x, c10.y, c10.z, c10.w}, v11[4] = {c11.x, c11.y, c11.z, c11.w};
-        double keep[4] = {0, 0, 0, 0};
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-          const int i0 = kk + 4 * v, j0 = m16;                  // tile (0,0)
-          if (i0 < 15 && j0 < 15) keep[v] = v00[v];             // (all of it is block (f, f); the row-15 entries go with tile (1,0))
-          const int i1 = 16 + kk + 4 * v;                       // tiles (1,0) and (1,1): product rows 16..31
-          if (i1 < 30) {
-            if (j0 < 15) imuH[11 * 120 + 225 * f + 15 * (i1 - 15) + j0] = v10[v];
-            else imuH[120 * (f + 1) + (i1 - 15) * (i1 - 14) / 2 + 0] = v10[v];                     // (i1, 15): column 0 of block (f+1, f+1)
-            const int j1 = 16 + m16;
-            if (j1 < 30 && j1 <= i1) imuH[120 * (f + 1) + (i1 - 15) * (i1 - 14) / 2 + (j1 - 15)] = v11[v];
-          }
-          if (i0 == 15) {                                       // product row 15 sits in tile (0,0) / its column 15
-            if (j0 < 15) imuH[11 * 120 + 225 * f + j0] = v00[v];
-            else imuH[120 * (f + 1)] = v00[v];                  // (15, 15)
-          }
-        }
-        cd[q] = v4d_lin{keep[0], keep[1], keep[2], keep[3]};
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int f = wvi + 8 * q;
-      if (f >= 10) break;
-      const double keep[4] = {cd[q].x, cd[q].y, cd[q].z, cd[q].w};
-#pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        const int i0 = kk + 4 * v, j0 = m16;
-        if (i0 < 15 && j0 <= i0) imuH[120 * f + i0 * (i0 + 1) / 2 + j0] += keep[v];
-      }
-    }
-  }
+  int2 asmd[LIN_ASM_PER_THREAD];         // lin_asm_request -> lin_assemble: in flight under the whitening
+  lin_asm_request(B, asmd);
+  lin_imu_whiten(imuJ, imur, imuact, sa);   // (one barrier inside: in front of the held-back diagonal adds)
   __syncthreads();
-  if (tid < 10 && imuact[tid]) {
-    double s = 0;
-    for (int k = 0; k < 15; ++k) s += imur[15 * tid + k] * imur[15 * tid + k];
-    cost += 0.5 * s;
-  }
-
-
+  lin_imu_cost(imur, imuact, cost);
   if (ROLE == 2) {
-    // the point factors' part (the other work-group of this window): Hv = (lines) + (points), gv likewise -- the sum the
-    // single work-group forms, in the other order of its two terms
-    // ACQUIRE, spelled out: the flag is polled with agent-scope loads (sc1: served by the L2, never by this CU's vector
-    // cache); the payload loads below are agent-scope loads too, issued after the barrier that follows the successful
-    // poll (a wave issues its memory instructions in order and none of them before s_barrier completes), so they reach the
-    // L2 after the flag store did -- and the writer's stores were acknowledged by that L2 before the flag was written.
-    // No buffer_inv is needed because no load of this payload may hit the vector cache.
-    if (tid == 0) {
-      while (__hip_atomic_load(&B.lin_flag[w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 1) __builtin_amdgcn_s_sleep(32);
-      __hip_atomic_store(&B.lin_flag[w], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    const double* part = B.lin_part + (size_t)w * LIN_PART;
-    for (int i = tid; i < HV_DOUBLES + NV; i += T) sm[i] += __hip_atomic_load(&part[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (tid == 0) cost += __hip_atomic_load(&part[HV_DOUBLES + NV], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
+    lin_handover_in(B, w, sm, cost);
   } else if (!MARG) {
     if (tid == 0) cost += cost_pts;
   }
   VPL_STAMP(B, w, 20);
-  // ---- assemble the packed cam Hessian and gradient in HBM -----------------------------------
-  double* Hout = B.Hcc + (size_t)w * NCP;
-  const double* pH = B.pr_H + (size_t)w * B.prS;
-  // Every entry is stored ONCE, with its three sources summed in registers: adding to what an earlier pass had stored
-  // is a global read-modify-write, i.e. a full round trip (~3 k cycles with all CUs in this phase) behind every store.
-  // (1) the 3570 entries the IMU factors touch (11 diagonal 15x15 blocks, 10 sub-diagonal ones), each summing its one or
-  // two J^T J terms, go to LDS; (2) rows to waves, columns to lanes: visual block + IMU block + prior (J0^T J0 staged in LDS
-  // by the prior phase), coalesced stores, no index decoding beyond c / 15.  Priors larger than PRH_N (none in the
-  // reference's windows) take a third pass that adds their entries in HBM.
-  VPL_STAMP(B, w, 26);
-  const bool prior_lds = n > 0 && n <= PRH_N;
-  {
-    // flat over the packed triangle: fully coalesced stores; the table entries were requested before the IMU blocks
-#pragma unroll
-    for (int u = 0; u < ASM_PER_THREAD; ++u) {
-      const int e = u * T + tid;
-      if (e >= NCP) continue;
-      const int hv = asmd[u].x & 0xffff, im = asmd[u].x >> 16, r = asmd[u].y & 255, c = asmd[u].y >> 8;
-      // branch-free: every source is read (clamped index) and selected, so that the LDS reads of many entries overlap
-      const double vh = Hv[hv ? hv - 1 : 0], vi = imuH[im ? im - 1 : 0];
-      const int ir = prior_lds ? invmap[r] : -1, ic = prior_lds ? invmap[c] : -1;
-      const bool hp = ir >= 0 && ic >= 0;
-      const int hi_ = ic > ir ? ic : ir, lo_ = ic > ir ? ir : ic;
-      const double vp = prH[hp ? hi_ * (hi_ + 1) / 2 + lo_ : 0];
-      double v = hv ? vh : 0.0;
-      v += im ? vi : 0.0;
-      v += hp ? vp : 0.0;
-      if (!ex_free && r >= 165) v = 0.0;
-      Hout[e] = v;
-    }
-  }
-  VPL_STAMP(B, w, 27);
-  if (n > PRH_N) {
-    __syncthreads();
-    const int np = n * (n + 1) / 2;
-    for (int base = 0; base < np; base += 4 * T) {
-      double ph[4];
-      int tr_[4], tc_[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int e = base + u * T + tid;
-        ph[u] = 0.0; tr_[u] = -1; tc_[u] = 0;
-        if (e < np) {
-          int i, j;
-          tri_decode(e, i, j);
-          ph[u] = pH[(size_t)i * n + j];
-          const int ri = B.pr_map[(size_t)w * MAXPN + i], rj = B.pr_map[(size_t)w * MAXPN + j];
-          tr_[u] = ri > rj ? ri : rj;
-          tc_[u] = ri > rj ? rj : ri;
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        if (tr_[u] >= 0 && (ex_free || tr_[u] < 165)) Hout[(size_t)tr_[u] * (tr_[u] + 1) / 2 + tc_[u]] += ph[u];
-    }
-  }
-  for (int r = tid; r < NC; r += T) {
-    double v = 0.0;
-    const int vr = cam2vis(r);
-    if (vr >= 0) v += gv[vr];
-    if (r < 165) {
-      const int fr = r / 15;
-      if (fr >= 1 && imuact[fr - 1]) {
-        const double* J = imuJ + 450 * (fr - 1);
-        const double* rr = imur + 15 * (fr - 1);
-        const int a = r - 15 * (fr - 1);
-        double s = 0;
-#pragma unroll
-        for (int k = 0; k < 15; ++k) s += J[k * 30 + a] * rr[k];
-        v += s;
-      }
-      if (fr < 10 && imuact[fr]) {
-        const double* J = imuJ + 450 * fr;
-        const double* rr = imur + 15 * fr;
-        const int a = r - 15 * fr;
-        double s = 0;
-#pragma unroll
-        for (int k = 0; k < 15; ++k) s += J[k * 30 + a] * rr[k];
-        v += s;
-      }
-    }
-    if (n > 0 && invmap[r] >= 0) v += prg[invmap[r]];
-    if (!ex_free && r >= 165) v = 0.0;
-    B.gc[(size_t)w * NC + r] = v;
-  }
+  lin_assemble(B, w, Hv, gv, imuJ, imur, prg, prH, PRH_N, invmap, imuact, P.n, ex_free, asmd);   // (one barrier inside, for n > PRH_N)
   VPL_STAMP(B, w, 21);
-  cost = block_sum(cost, red);
-  if (tid == 0 && !MARG) {
-    tr->x_cost = cost;
-    if (tr->iter == 0) tr->initial_cost = cost;
-    tr->fresh_lin = 1;
-    // A NaN / inf among the inputs: ceres' evaluator rejects the initial point ("Initial residual and Jacobian evaluation
-    // failed", trust_region_minimizer.cc IterationZero) and Solve returns FAILURE with an empty iteration list -- the
-    // reference goes on to double2vector2 and the marginalisation with the states as they were.  Reported the same way:
-    // termination 2, iterations = successful steps = -1 (size of the list - 1), costs 0; every later kernel of the solve
-    // leaves a window whose status is set.
-    if (tr->iter == 0 && tr->num_successful == 0 && !isfinite(cost)) {
-      tr->status = 2; tr->iter = -1; tr->num_successful = -1; tr->x_cost = 0.0; tr->initial_cost = 0.0;
-    }
-  }
+  lin_finish<MODE>(tr, red, cost);
 }
 template <int MODE>
 __global__ __launch_bounds__(LIN_THREADS) void k_lin(DevBatch B) {
@@ -1184,6 +1335,8 @@ __global__ __launch_bounds__(LIN_THREADS) void k_lin2(DevBatch B) {
 // LDS of k_lin: the fixed part, then whatever is left of the budget holds the prior's J0^T J0 for the assembly (priors of up
 // to lin_prh_n dims; the reference's are 6 + 9 + 6 x frames <= 75; larger ones are added in HBM by a third pass)
 constexpr size_t LIN_LDS_BUDGET = 158 * 1024;
+// (the terms in the order of lin_body's carve: Hv, gv, xp, xs, [imuJ | imur] and its tenants, prr + prdx + prg, red, pacc, plds;
+// invmap and imuact + tick + padding as ints; lin_smem adds prH, which sits between pacc and plds)
 inline size_t lin_smem_base(int maxP, int maxL) {
   return (size_t)(HV_DOUBLES + NV + 84 + 99 + lin_stage_doubles(maxL) + 3 * MAXPN + 18 + 14 * (maxP | 1) + 10 * PRE_LDS) * sizeof(double) + (size_t)(NC + 16) * sizeof(int);
 }

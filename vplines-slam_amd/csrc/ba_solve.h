@@ -748,7 +748,6 @@ __device__ __forceinline__ void cost_body(const DevBatch& B, const int w) {
     ln_load(lr, lob, lor);
     ln_eval(lr, lob, lor);
   }
-  (void)nP; (void)nL;
   __syncthreads();
   if (tid < 150) {
     const int f = tid / 15, a = tid - 15 * f;
@@ -804,8 +803,6 @@ __device__ __forceinline__ void cost_body(const DevBatch& B, const int w) {
     for (int i = tid; i < 6 * nL; i += T) B.lw[(size_t)w * B.maxL * 6 + i] = B.lw_c[(size_t)w * B.maxL * 6 + i];
   }
 }
-// two workgroups per CU (4 waves per SIMD, <= 128 VGPRs): the kernel is a latency chain per lane, occupancy is what helps
-// (0.327 -> 0.283 ms per step against one workgroup per CU at 136 VGPRs)
 #ifndef VPL_COST_WAVES
 #define VPL_COST_WAVES 4          // A/B switch, as VPL_BACK_WAVES
 #endif
