@@ -1,4 +1,4 @@
-"""The pivoted Cholesky rule of csrc/ba_marg.h restated in plain NumPy, the crafted matrices it is tried on and the checks a
+"""The pivoted Cholesky rule of csrc/ba_psd.h restated in plain NumPy, the crafted matrices it is tried on and the checks a
 factor has to meet -- shared by tests/test_psd_factor_reference.py (CPU) and tests/test_gpu_psd_factor.py.
 
 The rule (header comment of psd_pivoted_cholesky and of its one-wave form): P A P^T = L L^T with diagonal pivoting; the pivot

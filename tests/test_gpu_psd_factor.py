@@ -1,11 +1,18 @@
-"""The pivoted Cholesky factor that turns k_marg's kept block into the next prior (csrc/ba_marg.h), every hand-written form of
+"""The pivoted Cholesky factor that turns k_marg's kept block into the next prior (csrc/ba_psd.h), every hand-written form of
 it -- psd_pivoted_cholesky_wave<16>, _wave<48> (on 256 and on 512 threads), _wave4<19, 4> and the work-group version -- on
 crafted matrices through vpl_ba_debug_psd_factor (k_psd_factor: k_marg's geometry and k_marg's own write-out, one work-group
 per case, one launch per form), and the same checks on the kept blocks of real windows through k_marg itself.
 
 The reference is the rule restated in long double (tests/psd_factor_ref.py; tests/test_psd_factor_reference.py shows that it
-stays inside the bars on its own).  Every bar is derived (psd_factor_ref.check_factor); none is taken from the device."""
+stays inside the bars on its own).  Every bar is derived (psd_factor_ref.check_factor); none is taken from the device.
+
+Last: batches whose windows keep different sizes.  Every work-group of k_marg lays its LDS out for its own kept size and the
+dispatch is sized for the largest layout of any size up to the batch's (csrc/ba_marg_layout.h, marg_lds_doubles): a window
+gives in such a batch what it gives alone."""
 import ctypes as C
+import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -96,7 +103,7 @@ def _same_bits(world, ka, kb):
 
 
 def test_forms_give_the_same_bits(world):
-    """the claim of the comments in csrc/ba_marg.h: the one-wave forms, on either thread count, and the work-group version do
+    """the claim of the comments in csrc/ba_psd.h: the one-wave forms, on either thread count, and the work-group version do
     the same arithmetic per entry"""
     n = [_same_bits(world, "wave48@256", "wave48@512"), _same_bits(world, "wave16@256", "wave48@256"),
          _same_bits(world, "workgroup@256", "workgroup@512"), _same_bits(world, "wave48@256", "workgroup@256"),
@@ -133,14 +140,18 @@ def test_other_pairings_are_refused_without_a_launch(world):
 KMARG_ABS, KMARG_REL = 1e-8, 0.0     # kMargEps, kMargNoiseRel
 
 
-def _kept_block(ctx, w):
+def _kept_block_raw(ctx, w):
     A = np.zeros(80 * 80)
     b = np.zeros(80)
     dp = C.POINTER(C.c_double)
     n = ctx.lib.vpl_ba_debug_marg_Ab(ctx.h, w, A.ctypes.data_as(dp), b.ctypes.data_as(dp))
     assert n > 0
-    A = A[: n * n].reshape(n, n)
-    return 0.5 * (A + A.T), b[:n].copy()       # as marg_body symmetrises the copy it factors
+    return A[: n * n].reshape(n, n).copy(), b[:n].copy()
+
+
+def _kept_block(ctx, w):
+    A, b = _kept_block_raw(ctx, w)
+    return 0.5 * (A + A.T), b       # as marg_body symmetrises the copy it factors
 
 
 def _check_pivoted_factor(A, b, J0, r0, tag):
@@ -278,3 +289,129 @@ def test_k_marg_on_windows_without_points(monkeypatch, big, cap):
         assert pl[0].n == nf and pl[0].J().tobytes() == Jf.tobytes() and pl[0].r().tobytes() == rf.tobytes(), (cap, k)
         lived.close()
     _report("no points, capacity %s" % cap, rows)
+
+
+# ---- batches of mixed kept size ---------------------------------------------------------------------------------------------
+# MARGIN_OLD without a prior keeps 15 + 6 (k - 1) dims, k = the length of the tracks that start in frame 0
+MIXED_P, MIXED_L = 40, 12
+
+
+def _mixed_ctx(nw=2):
+    return v.Context(device=0, max_windows=nw, max_points=MIXED_P, max_point_obs=MIXED_P * 11, max_lines=MIXED_L,
+                     max_line_obs=MIXED_L * 11)
+
+
+def _mixed_windows(ctx, track_lens, opt):
+    wins = []
+    for k, tl in enumerate(track_lens):
+        cfg = v.workload.config(MIXED_P, MIXED_L)
+        cfg.track_len = tl
+        wins.append(v.workload.generate(v.workload.seed_for(3, 8300 + 16 * tl + k), cfg, 0.2 * k))
+    v.workload.set_preintegrations(wins, ctx.preintegrate(*v.workload.imu_batch_arrays(wins), opt))
+    return wins
+
+
+def _marg_result(ctx, pri, m, nn, i, win):
+    """everything vpl_ba_marginalize hands back for window i (win) of the call just made, its kept block, and the part of the
+    linearisation that the marginalisation pass of k_lin writes and k_marg reads (lin_H, lin_g out of
+    vpl_ba_debug_linearization: the camera block and the rows of the landmarks that start in frame 0; the pass leaves the rows
+    of every other landmark as they were), as arrays"""
+    A, b = _kept_block_raw(ctx, i)
+    nb = pri[i].n_blocks
+    x0 = np.array([list(pri[i].x0[k]) for k in range(nb)])
+    lin = ctx.debug_linearization(i)
+    nP = lin["n_points"]
+    rows = list(range(171)) + [171 + p for p in range(nP) if win.point_start[p] == 0]
+    for dl, l in enumerate(lin["line_index"]):
+        if win.line_start[l] == 0:
+            rows += [171 + nP + 4 * dl + a for a in range(4)]
+    lin = {"H": lin["H"][np.ix_(rows, rows)], "g": lin["g"][rows]}
+    return {"J0": pri[i].J(), "r0": pri[i].r(), "x0": x0, "m": np.array([int(m[i])]), "n": np.array([int(nn[i])]),
+            "mg_A": A, "mg_b": b, "lin_H": lin["H"], "lin_g": lin["g"]}
+
+
+def _differences(a, b):
+    """outputs that are not bit for bit equal -> {name: (entries that differ, of, largest difference)}"""
+    out = {}
+    for k in a:
+        if a[k].shape != b[k].shape:
+            out[k] = ("shape", a[k].shape, b[k].shape)
+        elif a[k].tobytes() != b[k].tobytes():
+            x, y = a[k].astype(np.float64).ravel(), b[k].astype(np.float64).ravel()
+            out[k] = (int((x.view(np.uint64) != y.view(np.uint64)).sum()), x.size, float(np.nanmax(np.abs(x - y))))
+    return out
+
+
+def _mixed_batch(ctx, track_lens, want_n, tag):
+    """the batch, the reference checks on each of its windows, then each window in a batch of its own on the same context;
+    -> per window, the outputs that differ from the window alone ({} if none): _differences"""
+    opt = v.default_options()
+    wins = _mixed_windows(ctx, track_lens, opt)
+    pri, m, nn = ctx.marginalize(wins, opt, capi.MARGIN_OLD)
+    assert [int(x) for x in nn] == list(want_n) and [pri[i].n for i in range(len(wins))] == list(want_n), (tag, list(nn))   # input condition
+    _report("mixed kept sizes %s" % (tag,), _check_all(ctx, pri, len(wins), tag))
+    together = [_marg_result(ctx, pri, m, nn, i, wins[i]) for i in range(len(wins))]
+    diff = []
+    for i, w in enumerate(wins):
+        p1, m1, n1 = ctx.marginalize([w], opt, capi.MARGIN_OLD)
+        _check_all(ctx, p1, 1, (tag, "alone", i), want_n[i])
+        alone = _marg_result(ctx, p1, m1, n1, 0, w)
+        diff.append(_differences(alone, together[i]))
+    return diff
+
+
+MIXED_SMALL = {"39,33": ((5, 4), (39, 33)), "33,39": ((4, 5), (33, 39))}
+
+
+@pytest.mark.parametrize("order", list(MIXED_SMALL))
+def test_k_marg_small_on_a_batch_of_mixed_kept_size(monkeypatch, order):
+    """k_marg<256>: the window that keeps 33 dims addresses 77 168 B of LDS, the one that keeps 39 only 67 536 B.
+    (The equality with the window alone also needs k_lin's line phase to lay a window's lanes out by the window's own
+    longest line track, not the batch's: DESIGN.md section 6.)"""
+    _set_big(monkeypatch, 0)
+    ctx = _mixed_ctx()
+    diff = _mixed_batch(ctx, *MIXED_SMALL[order], tag=("small", order))
+    ctx.close()
+    assert diff == [{}, {}], diff
+
+
+def test_k_marg_small_on_mixed_kept_sizes_leaves_the_guard_pads_intact():
+    """the same batches with 0xA5 behind every device array (VPL_DEBUG_GUARDS=1): closing the context reports no overrun"""
+    here = os.path.dirname(os.path.abspath(__file__))
+    script = r"""
+import sys
+sys.path.insert(0, %r)
+sys.path.insert(0, %r)
+import test_gpu_psd_factor as t
+ctx = t._mixed_ctx()
+diffs = [t._mixed_batch(ctx, *t.MIXED_SMALL[order], tag=("guards", order)) for order in t.MIXED_SMALL]
+ctx.close()
+print("guards ok")
+assert diffs == [[{}, {}]] * len(diffs), diffs
+""" % (os.path.dirname(here), here)
+    env = dict(os.environ, VPL_DEBUG_GUARDS="1")
+    env.pop("VPL_BA_MARG_BIG", None)
+    r = subprocess.run([sys.executable, "-c", script], capture_output=True, text=True, timeout=600, env=env, cwd=os.path.dirname(here))
+    assert "guards ok" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+
+
+MIXED_BIG = {"69,57": ((10, 8), (69, 57)), "39,33": ((5, 4), (39, 33))}
+
+
+@pytest.mark.parametrize("sizes", list(MIXED_BIG))
+def test_k_marg_big_on_a_batch_of_mixed_kept_size(monkeypatch, capsys, sizes):
+    """k_marg<512> (by the kept size, or VPL_BA_MARG_BIG=1 for the sizes the 256-thread form would take): at 57 dims a window
+    addresses 146 416 B, at 69 dims 137 520 B.  Equality with the window alone is asserted for n <= 48 and printed for both
+    (also in a run without -s; profiles/r15/README.md keeps the lines of the runs made for it), the linearisation's for both:
+    windows with the column-slice factorisation do not repeat their bits from run to run."""
+    _set_big(monkeypatch, 1)
+    ctx = _mixed_ctx()
+    diff = _mixed_batch(ctx, *MIXED_BIG[sizes], tag=("big", sizes))
+    ctx.close()
+    with capsys.disabled():      # (the line is part of the suite's output also when it runs without -s)
+        print("\nkept sizes %s on 512 threads: outputs that differ from the window alone (entries, of, largest): %s" % (sizes, diff))
+    # the linearisation is k_lin's, the same for every kept size: a window's sums do not depend on the batch
+    assert all("lin_H" not in d and "lin_g" not in d for d in diff), diff
+    if max(MIXED_BIG[sizes][1]) <= 48:
+        assert diff == [{}, {}], diff

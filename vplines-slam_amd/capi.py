@@ -423,7 +423,7 @@ class Context:
         return int(n.value), int(b.value)
 
     def debug_psd_factor(self, form, threads, cases):
-        """vpl_ba_debug_psd_factor: one form of the pivoted Cholesky factorisation of csrc/ba_marg.h (PSD_WAVE16, PSD_WAVE48,
+        """vpl_ba_debug_psd_factor: one form of the pivoted Cholesky factorisation of csrc/ba_psd.h (PSD_WAVE16, PSD_WAVE48,
         PSD_WAVE4, PSD_WORKGROUP) on `threads` threads over cases = [(A (n x n), b (n), abs_tol, rel_tol), ...], one launch.
         -> list of (rank, perm (n), J0 (n x n), r0 (n)); J0 and r0 hold NaN where the kernel wrote nothing.  Returns the
         VPL_E_* code instead when the call is refused."""

@@ -8,6 +8,7 @@
 //   full index k in [0,171 + maxP + 4 maxL): cam | inverse depths | line orth (4 each)
 #pragma once
 #include <stdint.h>
+#include "ba_limits.h"
 
 namespace vpl {
 
@@ -28,7 +29,6 @@ constexpr int SK_WSTRIDE = 64;         // ints per wave in sk_wave: chunk count,
 // non-zeros of the packed cam Hessian on the three-kernel path: 72 x 73 / 2 + 11 x 99 + 10 x 189 + 60 x 9
 constexpr int NZ_N = 2628 + 1089 + 1890 + 540;
 constexpr int SACC_N = 74 * 75 / 2;     // packed lower triangle of the compact Schur product: 72 vis dims, rhs row, Cauchy row
-constexpr int MAXKEEP = 80;            // new prior dim after MARGIN_OLD: <= 10*6 + 9 + 6 = 75
 
 __host__ __device__ inline int vis2cam(int v) { return v < 66 ? 15 * (v / 6) + (v % 6) : 165 + (v - 66); }
 __host__ __device__ inline int tri(int r, int c) { return r * (r + 1) / 2 + c; }  // r >= c
@@ -103,8 +103,9 @@ struct DevBatch {
   double *ln_obs;                                // [W][maxLO][8]
   int *nLO, *lo_ln;                              // [W] line observation count ; [W][maxLO] observation -> line
   // lane layout of the line phase of k_lin: every wave holds whole tracks, k-major.  Slot pass * 512 + wave * 64 + k * llNLW + i
-  // = observation k of the i-th line of that wave (index into ln_obs) or -1; lines sorted by start frame.  llK = longest
-  // line track of the batch, llNLW = 64 / llK lines per wave, ll_np[w] passes of 8 waves.
+  // = observation k of the i-th line of that wave (index into ln_obs) or -1; lines sorted by start frame.  Per window: K = its
+  // longest line track, NLW = 64 / K lines per wave, ll_np[w] = passes of 8 waves.  llK / llNLW: the gate
+  // lane / llNLW < llK in front of k_lin's table load, open for every lane (64, 1) since the layout is per window.
   int *ll_tab, *ll_np;                           // [W][llSlots][2] (observation, line | k << 16 | start << 20) ; [W]
   int llNLW, llK, llSlots;
   int *ln_removed;                               // [W][maxL] 1 = erased by removeLineOutlier (k_gauge)

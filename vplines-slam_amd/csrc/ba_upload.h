@@ -213,11 +213,10 @@ static int batch_strides(vpl_ctx* c, size_t W, const vpl_window* win, const vpl_
   }
   maxTrack = std::min(maxTrack, (int)NF);
   B.WS = 6 * maxTrack + 6;
-  int maxLineTrack = 1;
-  for (size_t w = 0; w < W; ++w)
-    for (int l = 0; l < win[w].n_lines; ++l) maxLineTrack = std::max(maxLineTrack, std::min(win[w].line_nobs[l], (int)NF));
-  B.llK = maxLineTrack;
-  B.llNLW = 64 / maxLineTrack;
+  // the line phase's lane layout is each window's own (build_layout); k_lin's gate `lane / llNLW < llK` in front of its table
+  // load stays open for every lane, the table alone says which lanes have an observation (-1: none)
+  B.llK = 64;
+  B.llNLW = 1;
   B.wfill = (minTrack != maxTrack || opt->remove_line_outliers) ? 1 : 0;
   return VPL_OK;
 }
@@ -346,11 +345,16 @@ static int build_layout(vpl_ctx* c, UploadArena& A, size_t w, const vpl_window& 
                         &A.sk_wave[w * 8 * SK_WSTRIDE], SCHUR_THREADS / 64, v.point_nobs, &A.ln_nobs[w * B.maxL],
                         B.WS + 2 > 48 ? SCHUR_NARROW_FRAMES : 0, wide_w, total_w) < 0)
     return fail(c, VPL_E_CAPACITY, "K-step table of the landmark elimination too small");
-  // lane layout of the line phase: llNLW whole tracks per wave, k-major; tracks in the caller's order (tracks that start in the
-  // same frame side by side would pile their LDS adds onto the same addresses)
-  const int NLW = B.llNLW, perPass = 8 * NLW;
-  A.ll_np[w] = (nl + perPass - 1) / perPass;
-  if (A.ll_np[w] * 512 > B.llSlots) return fail(c, VPL_E_CAPACITY, "line layout table too small");
+  // lane layout of the line phase: NLW whole tracks per wave, k-major; tracks in the caller's order (tracks that start in the
+  // same frame side by side would pile their LDS adds onto the same addresses).  NLW = 64 / (the longest line track of THIS
+  // window): the lanes a window's factors sit in, and with them the order of its sums, are the window's own and not the batch's
+  // -- a window gives in any batch what it gives alone.  The device goes by the table: slots without an observation hold -1.
+  int KL = 1;
+  for (int l = 0; l < v.n_lines; ++l) KL = std::max(KL, std::min(v.line_nobs[l], (int)NF));
+  const int NLW = 64 / KL, perPass = 8 * NLW;
+  const int np = (nl + perPass - 1) / perPass;
+  if (np * 512 > B.llSlots) return fail(c, VPL_E_CAPACITY, "line layout table too small");
+  A.ll_np[w] = np;
   for (int dl = 0; dl < nl; ++dl) {
     const int pass = dl / perPass, wave = (dl % perPass) / NLW, i = dl % NLW;
     const int no = std::min(A.ln_nobs[w * B.maxL + dl], (int)NF);
@@ -434,16 +438,17 @@ static int keep_blocks(vpl_ctx* c, UploadArena& A, size_t w, const vpl_window& v
 }
 
 // 9. the k_marg variant: kept blocks of up to 48 dims (the one-wave factorisations) whose workspace fits 79 KB take 256
-// threads, two work-groups per CU
+// threads, two work-groups per CU.  The workspace is the largest layout of any kept size up to the batch's (marg_lds_doubles):
+// every work-group lays out for its own n, which the device may have shrunk
 static int choose_marg(vpl_ctx* c, const Span<int>& mg_n, size_t W) {
   const DevBatch& B = c->B;
   int nmax = 0;
   for (size_t w = 0; w < W; ++w) nmax = std::max(nmax, mg_n[w]);
   c->marg_nmax = nmax;
   c->marg_small = nmax <= 48 && B.maxP <= 256 && B.maxL <= 256 &&
-                  (size_t)marg_layout(nmax, true).total * sizeof(double) <= MARG_LDS_SMALL && std::getenv("VPL_BA_MARG_BIG") == nullptr;
-  c->marg_smem = (size_t)marg_layout(nmax, c->marg_small).total * sizeof(double);
-  if (c->marg_smem > 159 * 1024) return fail(c, VPL_E_CAPACITY, "marginalisation workspace exceeds LDS");
+                  (size_t)marg_lds_doubles(nmax, true) * sizeof(double) <= MARG_LDS_SMALL && std::getenv("VPL_BA_MARG_BIG") == nullptr;
+  c->marg_smem = (size_t)marg_lds_doubles(nmax, c->marg_small) * sizeof(double);
+  if (c->marg_smem > MARG_LDS_MAX) return fail(c, VPL_E_CAPACITY, "marginalisation workspace exceeds LDS");
   return VPL_OK;
 }
 

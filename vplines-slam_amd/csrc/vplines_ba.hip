@@ -200,7 +200,7 @@ static int ctx_init(vpl_ctx* c, int device, int max_windows, int max_points, int
       {(const void*)k_solve, solve_max}, {(const void*)k_schur<3>, schur_max}, {(const void*)k_schur<5>, schur_max},
       {(const void*)k_schur_mixed, schur_max}, {(const void*)k_chol, CHOL_SMEM}, {(const void*)k_back, back_max},
       {(const void*)k_step<3, false>, step_max}, {(const void*)k_step<3, true>, step_max}, {(const void*)k_step<5, false>, step_max},
-      {(const void*)k_prep, PREP_SMEM}, {(const void*)k_marg<MARG_THREADS>, 159 * 1024}, {(const void*)k_marg<256>, MARG_LDS_SMALL},
+      {(const void*)k_prep, PREP_SMEM}, {(const void*)k_marg<MARG_THREADS>, MARG_LDS_MAX}, {(const void*)k_marg<256>, MARG_LDS_SMALL},
       {(const void*)k_prior_eigen, prior_eig_layout(MAXKEEP).bytes}, {(const void*)k_init_align, init_lds_bytes(INIT_NMAX)}};
   for (const auto& k : lds)
     if (hipFuncSetAttribute(k.first, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.second) != hipSuccess) return VPL_E_HIP;
@@ -1195,7 +1195,7 @@ int vpl_ba_debug_step(vpl_ctx* c, int w, double* scale, double* diag, double* gr
   return rs ? rs : NC + nP + 4 * nL;
 }
 
-// Debug/test access to the pivoted Cholesky factorisations of ba_marg.h on caller-supplied matrices (k_psd_factor): n_cases
+// Debug/test access to the pivoted Cholesky factorisations of ba_psd.h on caller-supplied matrices (k_psd_factor): n_cases
 // work-groups in one launch.  form 0: psd_pivoted_cholesky_wave<16> (256 threads, n <= 16); 1: _wave<48> (256 or 512, n <= 48);
 // 2: _wave4<19, 4> (512, n <= 76: on fewer than eight waves it would wait out its poll limit); 3: the work-group version (256 or
 // 512, n <= 80).  Any other pairing: VPL_E_INVALID, nothing is launched.  A, J0: [case][80 * 80] holding n x n row-major; b, r0,
