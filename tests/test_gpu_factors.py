@@ -145,3 +145,31 @@ def test_prior_factor_parity(gpu_ctx):
     rg, jg = gpu_ctx.prior_factor(pr, params)
     rc, jc = o.prior_factor(pr, params)
     assert close(rg, rc) and close(jg, jc)
+
+
+def test_imu_factor_information_form(gpu_ctx):
+    """vpl_imu_factor's whitened output in information form -- J^T J, J^T r, r^T r / 2 formed from it in long double, which do not
+    depend on the square root of cov^-1 the kernel whitened with -- against the long-double factor (imu_ref.py), on the factors of
+    m1 (displaced biases) and m2 (unequal intervals), in imu_ref's units.  The inputs are shared exactly: bar 8 x max(what the
+    float64 restatement of the device's path reaches on the same inputs, 1), imu_ref.YARDSTICK fH / fg / fcost."""
+    import imu_ref as ir
+    import step_ref as sr
+    for case in ("m1", "m2"):
+        w, opt, pose, sb, ref = ir.reference(case)
+        js = sorted(ref.factors)
+        pre = (v.Preintegration * len(js))()
+        params = np.zeros((len(js), 32))
+        for k, j in enumerate(js):
+            C.memmove(C.byref(pre[k]), C.byref(w.preint[j]), C.sizeof(pre[k]))
+            params[k] = np.concatenate([pose[j - 1], sb[j - 1], pose[j], sb[j]])
+        rg, jg = gpu_ctx.imu_factor(params, pre, g_norm=opt.g_norm)
+        assert np.all(jg.reshape(len(js), -1)[:, [6 + 7 * r for r in range(15)] + [246 + 7 * r for r in range(15)]] == 0.0)
+        worst = [0.0, 0.0, 0.0]
+        for k, j in enumerate(js):
+            f = ref.factors[j]
+            H, g, c = ir.from_whitened(rg[k], ir.jac480_to_30(jg[k]))
+            worst = [max(worst[0], sr.rho(H, f.H, f.unit_H)), max(worst[1], sr.rho(g, f.g, f.unit_g)),
+                     max(worst[2], float(abs(c - f.c)) / f.unit_c)]
+        print("imu_factor %s rho_H %.3g rho_g %.3g rho_cost %.3g (bars %.3g %.3g %.3g)"
+              % (case, worst[0], worst[1], worst[2], ir.bar("fH", case), ir.bar("fg", case), ir.bar("fcost", case)))
+        assert worst[0] <= ir.bar("fH", case) and worst[1] <= ir.bar("fg", case) and worst[2] <= ir.bar("fcost", case)

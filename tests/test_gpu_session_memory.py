@@ -216,3 +216,30 @@ def test_a_context_whose_session_was_closed_has_the_record_of_one_that_never_had
     assert out[0] == out[1]
     for ctx in (fresh, used):
         ctx.close()
+
+
+def test_a_context_closed_before_its_session_takes_the_session_with_it(monkeypatch):
+    """vpl_odo_destroy reads the context the session borrows, so the session has to go first whichever of the two the caller
+    closes -- or the garbage collector finalises -- first: Context.close() destroys a session that is still open (as
+    FrontendContext.close() does with its tracker session), after which the session's own close() has nothing left to do.  A
+    context that makes its own session likewise, and a new session on a context whose first one was closed is registered again."""
+    monkeypatch.setenv("VPL_DEBUG_GUARDS", "1")
+    ctx = _small_ctx(N_SEQ)
+    before = ctx.debug_allocs()
+    ses = make_session(ctx)
+    ses.close()
+    assert ctx._odo is None and ctx.debug_allocs() == before
+    ses = make_session(ctx)
+    ses.enable_keyframe_rule()
+    assert ctx._odo is ses and ctx.debug_allocs()[0] > before[0]
+    ctx.close()
+    assert not ses.h and not ctx.h and ctx._odo is None
+    ses.close()
+    del ses, ctx
+    own = v.Session(None, n_seq=1, opt=v.default_options(), max_point_tracks=MAX_PT, max_line_tracks=MAX_LT, device=0, max_windows=1,
+                    max_points=48, max_point_obs=48 * NF, max_lines=12, max_line_obs=12 * NF)      # (_small_ctx's capacities)
+    ctx = own.ctx
+    ctx.close()                                   # the borrowed side first
+    assert not own.h
+    own.close()
+    assert own.ctx is None

@@ -496,6 +496,8 @@ class Context:
         return out
 
     def close(self):
+        if self.h and getattr(self, "_odo", None) is not None:
+            self._odo._destroy()                   # the session goes before the context it borrows (vpl_odo_destroy reads the context)
         if self.h:
             bad = self.debug_guards() if os.environ.get("VPL_DEBUG_GUARDS") == "1" else 0
             msg = self.lib.vpl_last_error(self.h).decode() if bad else ""
@@ -852,14 +854,20 @@ class Session:
         if rc != 0:
             msg = self.lib.vpl_last_error(ctx.h)
             raise RuntimeError("vpl_odo_create failed (%d): %s" % (rc, msg.decode() if msg else ""))
+        ctx._odo = self        # Context.close() destroys a session that is still open first, whoever is closed or collected first
 
-    def close(self):
+    def _destroy(self):
         if self.h:
             self.lib.vpl_odo_destroy(self.h)
             self.h = C.c_void_p()
+            if getattr(self.ctx, "_odo", None) is self:
+                self.ctx._odo = None
+
+    def close(self):
+        self._destroy()
         if self.own_ctx and self.ctx is not None:
-            self.ctx.close()
-            self.ctx = None
+            ctx, self.ctx = self.ctx, None
+            ctx.close()
 
     def __del__(self):
         try:
