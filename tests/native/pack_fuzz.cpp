@@ -11,7 +11,7 @@
 #include "ba_pack.h"
 
 using namespace vpl;
-constexpr int SCHUR_THREADS = 256, SCHUR_NARROW_FRAMES = 6;   // csrc/ba_step.h:26, :178 (device header: not includable here)
+constexpr int SCHUR_THREADS = 256, SCHUR_NARROW_FRAMES = 6;   // csrc/ba_step.h:33, :184 (device header: not includable here)
 
 int main(int argc, char** argv) {
   const int trials = argc > 1 ? atoi(argv[1]) : 300;

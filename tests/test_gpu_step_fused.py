@@ -10,7 +10,7 @@ import pytest
 
 import oracle_api as o
 import vplines_slam_amd as v
-from test_gpu_solve import _relayout_points, make_windows
+from test_gpu_solve import POS_TOL, ROT_TOL, _relayout_points, make_windows, pose_err
 
 pytestmark = pytest.mark.gpu
 
@@ -84,6 +84,40 @@ def test_narrow_rows_same_bits(monkeypatch, small_windows):
     _assert_same_bits(out[0][0], out[1][0])
     _assert_same_bits(out[0][1], out[1][1])
     assert all(p.shape[0] > 0 for p in out[1][1]["J"])
+
+
+def test_capacity_beyond_the_compact_system_same_bits(monkeypatch, small_windows):
+    """The same windows on a context of 60 points and 214 lines: 4 maxP + 28 maxL = 6 232 doubles of landmark constants are
+    more than the 5 952 of the compact system that takes their place in k_schur's LDS (ba_step_layout.h: region r1), so every
+    region behind it starts where kP | kL end, not where Cacc ends.  The two forms give the same bits, and the result is the
+    oracle's within the bars of test_window_solve_parity_no_prior.  (Not compared with the small context: k_lin's tables depend
+    on the capacity.)  Lines, not points, carry the capacity over that side: k_lin keeps 14 doubles per point of capacity in
+    LDS (lin_smem_base), so vpl_ctx_create refuses 1000 points beside 80 lines, and with 80 lines every capacity it accepts
+    (at most 508 points) stays below the compact system; 214 lines leave k_lin room for a prior of 47 dims."""
+    ws, opt = small_windows
+    caps = dict(max_windows=4, max_points=60, max_point_obs=360, max_lines=214, max_line_obs=120)
+    assert 4 * 60 + 28 * 214 > 74 * 80 + 32
+    out, solved = [], None
+    for fused in ("0", "1"):
+        ctx = _context(monkeypatch, fused, **caps)
+        out.append(_solve_twice(ctx, ws, opt))
+        if fused == "1":
+            solved = _solve(ctx, ws, opt)
+        ctx.close()
+    _assert_same_bits(out[0][0], out[1][0])
+    _assert_same_bits(out[0][1], out[1][1])
+    wg, _, rep_g = solved
+    _assert_same_bits(out[1][0], _bits(*solved))
+    for i, w in enumerate(ws):
+        wc = w.copy()
+        _, rep_c = o.solve_window(wc, opt)
+        assert rep_g[i].iterations == rep_c.iterations and rep_g[i].num_successful_steps == rep_c.num_successful_steps, i
+        assert abs(rep_g[i].initial_cost - rep_c.initial_cost) <= 1e-9 * rep_c.initial_cost
+        assert abs(rep_g[i].final_cost - rep_c.final_cost) <= 5e-5 * max(1.0, rep_c.final_cost)
+        dp, dr = pose_err(wg[i], wc)
+        assert dp <= POS_TOL and dr <= ROT_TOL, (i, dp, dr)
+        assert np.abs(wg[i].speed_bias - wc.speed_bias).max() < 1e-4
+        assert np.abs(wg[i].inv_depth - wc.inv_depth).max() < 1e-5
 
 
 @pytest.fixture(scope="module")

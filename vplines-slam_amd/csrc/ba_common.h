@@ -8,8 +8,23 @@ namespace vpl {
 
 #ifdef VPL_STAMPS
 #define VPL_STAMP(B, w, i) do { if (threadIdx.x == 0) (B).dbg[(size_t)(w) * 64 + (i)] = (long long)__builtin_readcyclecounter(); } while (0)
+// Interval counters, the counterpart of VPL_STAMP for the time spent INSIDE a loop: VPL_IVAL(acc) declares an accumulator,
+// VPL_IVAL_START(t) takes a start time, VPL_IVAL_ADD(acc, t) adds the cycles since t, VPL_IVAL_LAP(acc, t) adds them and
+// restarts t, VPL_IVAL_STORE(cond, dst, values ...) has the threads for which cond holds store the values to dst[0 ..]
+// (dst: a pointer into B.dbg or nullptr).  Statements, each ends with its own semicolon at the place of use.
+#define VPL_IVAL(acc) long long acc = 0
+#define VPL_IVAL_START(t) long long t = __builtin_readcyclecounter()
+#define VPL_IVAL_ADD(acc, t) acc += __builtin_readcyclecounter() - (t)
+#define VPL_IVAL_LAP(acc, t) do { const long long now_ = __builtin_readcyclecounter(); acc += now_ - (t); t = now_; } while (0)
+#define VPL_IVAL_STORE(cond, dst, ...) do { long long* dst_ = (dst); if (dst_ && (cond)) { const long long v_[] = {__VA_ARGS__}; \
+  for (int i_ = 0; i_ < (int)(sizeof(v_) / sizeof(v_[0])); ++i_) dst_[i_] = v_[i_]; } } while (0)
 #else
 #define VPL_STAMP(B, w, i) do {} while (0)
+#define VPL_IVAL(acc) do {} while (0)
+#define VPL_IVAL_START(t) do {} while (0)
+#define VPL_IVAL_ADD(acc, t) do {} while (0)
+#define VPL_IVAL_LAP(acc, t) do {} while (0)
+#define VPL_IVAL_STORE(cond, dst, ...) do {} while (0)
 #endif
 
 // one workgroup reports that it did the work of kind k (0 k_lin, 1 k_solve new step, 2 k_solve re-used step, 3 k_cost)

@@ -2,14 +2,8 @@
 // Plain C++: tests/native/marg_layout_check.cpp includes it without HIP and checks, for every kept size and both forms, that the
 // regions tile [0, total), that every tenant stays inside the region it borrows and that the dispatch covers every window.
 #pragma once
-#include <stddef.h>
+#include "ba_layout.h"
 #include "ba_limits.h"
-
-#ifdef __HIPCC__
-#define VPL_LAYOUT_HD __host__ __device__
-#else
-#define VPL_LAYOUT_HD
-#endif
 
 namespace vpl {
 
@@ -45,11 +39,9 @@ VPL_LAYOUT_HD inline int marg_factor_scratch(int n, int ld, bool small) {
                                                         : 0;
 }
 
-// One text for two readers: P = int on the host (offsets in doubles from the start of the dynamic LDS: MargLayout, what the
-// size of the dispatch and the CPU check read) and P = double* on the device (marg_body's pointers).  On the device the carve
-// is then a chain of pointer increments, as it was when marg_body wrote it by hand, and the constant parts of an offset end up
-// in the immediate field of the LDS instruction; taken as base + integer offset k_marg<512> ran 1.6 % slower at n = 75.
-template <class P> struct MargSpanT { P at; int len; };
+// One text for two readers (ba_layout.h): P = int on the host (MargLayout, what the size of the dispatch and the CPU check read)
+// and P = double* on the device (marg_body's pointers).
+template <class P> using MargSpanT = LdsSpanT<P>;
 
 template <class P> struct MargLayoutT {
   typedef MargSpanT<P> MargSpan;
@@ -81,25 +73,23 @@ template <class P> struct MargLayoutT {
 typedef MargSpanT<int> MargSpan;
 typedef MargLayoutT<int> MargLayout;
 
-template <class P> VPL_LAYOUT_HD inline void marg_put(MargSpanT<P>& s, P& o, int len) { s.at = o; s.len = len; o = o + len; }
-
 // the carve for `mtrows` staged rows and nd = md + n dense dims from `base` on; returns its end
 template <class P> VPL_LAYOUT_HD inline P marg_carve(MargLayoutT<P>& L, P base, int n, int mtrows, int md) {
   const int nn = n < 2 ? 2 : n;
   L.nd = md + n;
   P o = base;
-  marg_put(L.G, o, L.EB);
-  marg_put(L.Ad, o, L.nd * L.ldd);
-  marg_put(L.tile, o, mtrows * MARG_ROW);
-  marg_put(L.E15, o, MARG_E15_DOUBLES);
-  marg_put(L.bv, o, L.nd);
-  marg_put(L.tmp, o, L.nd * 16 < MARG_TMP_MIN ? MARG_TMP_MIN : L.nd * 16);
-  marg_put(L.lam, o, nn + 16);
-  marg_put(L.red, o, MARG_RED_DOUBLES);
-  marg_put(L.perm, o, ((n < 16 ? 16 : n) + 1) / 2);
-  marg_put(L.dmap, o, (L.nd + 1) / 2);
-  marg_put(L.lst, o, L.loff);
-  marg_put(L.spare, o, (nn + L.nd + 16) / 2 + 4 - L.perm.len - L.dmap.len);
+  lds_put(L.G, o, L.EB);
+  lds_put(L.Ad, o, L.nd * L.ldd);
+  lds_put(L.tile, o, mtrows * MARG_ROW);
+  lds_put(L.E15, o, MARG_E15_DOUBLES);
+  lds_put(L.bv, o, L.nd);
+  lds_put(L.tmp, o, L.nd * 16 < MARG_TMP_MIN ? MARG_TMP_MIN : L.nd * 16);
+  lds_put(L.lam, o, nn + 16);
+  lds_put(L.red, o, MARG_RED_DOUBLES);
+  lds_put(L.perm, o, ((n < 16 ? 16 : n) + 1) / 2);
+  lds_put(L.dmap, o, (L.nd + 1) / 2);
+  lds_put(L.lst, o, L.loff);
+  lds_put(L.spare, o, (nn + L.nd + 16) / 2 + 4 - L.perm.len - L.dmap.len);
   return o;
 }
 

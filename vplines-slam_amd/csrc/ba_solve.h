@@ -12,15 +12,14 @@
 //    FunctionToleranceReached, IsStepSuccessful, HandleSuccessfulStep, HandleUnsuccessfulStep}).
 #pragma once
 #include "ba_common.h"
+#include "ba_step_layout.h"
 #include "ba_trust.h"
 
 namespace vpl {
 
 constexpr int SOLVE_THREADS = 512;
 constexpr int NA = NC + 1;                   // reduced system augmented with the rhs as last row
-constexpr int NT16 = 11;                     // 16x16 tiles per dimension (176 >= 172)
-constexpr int NTILES = NT16 * (NT16 + 1) / 2;  // lower-triangular tile count (66)
-constexpr int NAP = NTILES * 256;            // tile-major lower storage of the reduced system (16896 doubles)
+// (NT16 = 11 tiles per dimension, NAP doubles of tile-major lower storage: ba_step_layout.h)
 constexpr int TK = 16;                       // rows of the landmark tile staged per pass
 constexpr int TW = NV + 1;                   // tile width: 72 vis dims + rhs column
 constexpr int NB3 = 25;                      // 3-wide output blocks over the 73(+2 pad) tile columns
@@ -67,17 +66,14 @@ __device__ __forceinline__ bool tile_cholesky(double* S, double* Linv, double* i
     }
     Ct[tsw(kk, m)] = c.x; Ct[tsw(kk + 4, m)] = c.y; Ct[tsw(kk + 8, m)] = c.z; Ct[tsw(kk + 12, m)] = c.w;
   };
-#ifdef VPL_STAMPS
-  long long ta = 0, tb = 0, tc = 0, td = 0, t0 = __builtin_readcyclecounter();
-#endif
+  VPL_IVAL(ta); VPL_IVAL(tb); VPL_IVAL(tc); VPL_IVAL(td);
+  VPL_IVAL_START(t0);
   for (int K = 0; K < nt; ++K) {
     // C(I,K) -= sum_{J<K} L(I,J) L(K,J)^T is applied in parts: the terms J < K-1 by the idle waves while wave 0 factored
     // the previous diagonal tile (look-ahead); the term J = K-1 of the diagonal tile by wave 0 at the end of the previous
     // solve phase, of the tiles below it by the idle waves while wave 0 factors this diagonal tile.  Two barriers per
     // tile column.  The order of the terms, and therefore every bit of the result, is the one of a single pass.
-#ifdef VPL_STAMPS
-    { const long long t1 = __builtin_readcyclecounter(); ta += t1 - t0; t0 = t1; }
-#endif
+    VPL_IVAL_LAP(ta, t0);
     if (wv == 0) {
       // Diagonal tile in registers: lane (r4, cc) holds rows r4, r4+4, r4+8, r4+12 of column cc of the (symmetric)
       // tile.  Per column step the pivot comes by v_readlane, the pivot column of the lane's rows by ds_swizzle inside
@@ -93,13 +89,9 @@ __device__ __forceinline__ bool tile_cholesky(double* S, double* Linv, double* i
       double m[4];
 #pragma unroll
       for (int v = 0; v < 4; ++v) m[v] = (r4 + 4 * v == cc) ? 1.0 : 0.0;
-#ifdef VPL_STAMPS
-      const long long td0 = __builtin_readcyclecounter();
-#endif
+      VPL_IVAL_START(td0);
       diag_tile_factor(d, m, r4, cc, ncol, pivc, bad);
-#ifdef VPL_STAMPS
-      td += __builtin_readcyclecounter() - td0;
-#endif
+      VPL_IVAL_ADD(td, td0);
       if (bad) {
         if (lane == 0) flag[0] = 1;
       } else {
@@ -133,9 +125,7 @@ __device__ __forceinline__ bool tile_cholesky(double* S, double* Linv, double* i
         for (int I = K + 1 + (wv - 1); I < nt; I += nwv - 1) rank_update(K + 1, I, 0, K);
     }
     __syncthreads();
-#ifdef VPL_STAMPS
-    { const long long t1 = __builtin_readcyclecounter(); tb += t1 - t0; t0 = t1; }
-#endif
+    VPL_IVAL_LAP(tb, t0);
     if (flag[0]) break;
     // tiles below the diagonal tile (the rhs row is in the last tile row): X = A(I,K) L(K,K)^-T = A(I,K) Linv^T on the
     // matrix cores, X[m][n] = sum_k A[m][k] Linv[n][k]
@@ -159,13 +149,9 @@ __device__ __forceinline__ bool tile_cholesky(double* S, double* Linv, double* i
       }
     }
     __syncthreads();
-#ifdef VPL_STAMPS
-    { const long long t1 = __builtin_readcyclecounter(); tc += t1 - t0; t0 = t1; }
-#endif
+    VPL_IVAL_LAP(tc, t0);
   }
-#ifdef VPL_STAMPS
-  if (stamps && wv == 0 && lane == 0) { stamps[0] = ta; stamps[1] = tb; stamps[2] = tc; stamps[3] = td; }
-#endif
+  VPL_IVAL_STORE(wv == 0 && lane == 0, stamps, ta, tb, tc, td);
   __syncthreads();
   return flag[0] == 0;
 }
@@ -210,10 +196,8 @@ __device__ __forceinline__ void tile_back_substitute(const double* S, const doub
   }
 }
 
-// Compact "vis" system used by the Schur accumulation: 72 vis dims + rhs column (72) + Cauchy
-// column (73), padded to 80 = 5 tiles of 16.  15 lower tiles live in MFMA accumulators.
-constexpr int CW = 80;             // staged row width (doubles)
-constexpr int CROWS = 64;          // landmark rows per staged chunk
+// Compact "vis" system used by the Schur accumulation (CW = 80 columns, staged CROWS = 64 rows at a time: ba_step_layout.h).
+// 15 lower tiles live in MFMA accumulators.
 constexpr int NCT = 15;            // lower tiles of the 5x5 compact tile grid
 
 // (returns whether the window took this path)
@@ -224,17 +208,10 @@ __device__ __forceinline__ bool solve_body(const DevBatch& B, const int w, doubl
   if (tr->status != 0) return false;
   if (B.path[w] == 0) return false;     // the window takes the three-kernel path (ba_step.h)
   count_active(B, tr->reuse ? 2 : 1);
-  double* S = sm;                 // NAP tile-major lower (row NC = rhs); first used as 2 staging buffers
-  double* sc = S + NAP;           // 176 jacobi scale of cam dims
-  double* dg = sc + 176;          // 176 dogleg diagonal of cam dims
-  double* uc = dg + 176;          // 176 work vector (u for the Cauchy point, later S_c y_c)
-  double* yv = uc + 176;          // 176 solution of the reduced system / z
-  double* isd = yv + 176;         // 176 1/L_jj
-  double* Linv = isd + 176;       // 256  inverse of the current diagonal tile's factor (swizzled tile)
-  double* red = Linv + 256;       // 24
-  int* flag = (int*)(red + 24);   // 4
-  int* pSt = flag + 4;            // maxP  start frame of every point track (column map of the compact W rows)
-  int* lSt = pSt + B.maxP;        // maxL  same for the lines
+  // regions and tenants: SolveLayoutT (ba_step_layout.h); S is first used as 2 staging buffers
+  const SolveLayoutT<double*> L = solve_layout_at(sm, B.maxP, B.maxL, B.nfull);
+  double *S = L.S.at, *sc = L.sc.at, *dg = L.dg.at, *uc = L.uc.at, *yv = L.yv.at, *isd = L.isd.at, *Linv = L.Linv.at, *red = L.red.at;
+  int *flag = (int*)L.flag.at, *pSt = (int*)L.pSt.at, *lSt = (int*)L.lSt.at;
 
   const int nP = B.nP[w], nL = B.nL[w];
   const int WS = B.WS;
@@ -254,16 +231,16 @@ __device__ __forceinline__ bool solve_body(const DevBatch& B, const int w, doubl
 
   // The Gauss-Newton step and the dogleg step also live in LDS (the reduced system's space is free when they are made): read
   // back from HBM right after being stored, each cost the store's completion plus a load round trip (~3 k cycles apiece)
-  double* lgn = S + 4 * B.maxL;    // nfull  Gauss-Newton step (scaled space), copy of ggn
-  double* gdelta = lgn + B.nfull;  // nfull  step * jacobi scale
+  double* lgn = L.lgn.at;          // nfull  Gauss-Newton step (scaled space), copy of ggn
+  double* gdelta = L.gdelta.at;    // nfull  step * jacobi scale
   const bool reuse0 = tr->reuse != 0;
   VPL_STAMP(B, w, 0);
   if (!reuse0) {
     // ---- jacobi scaling (iteration 0 only), diagonal_, gradient_ --------------------------
     // The landmark constants it leaves in LDS take the space of the staging buffers (free until the first chunk is staged):
     // the first factorisation attempt reads them there.  A retry with a larger mu reloads from HBM.
-    double* kP = S;                          // nP x 4: s, d, g, H_pp
-    double* kL = S + 4 * B.maxP;             // nL x 28: s(4), d(4), g(4), H_ll(16)
+    double* kP = L.kP.at;                    // nP x 4: s, d, g, H_pp
+    double* kL = L.kL.at;                    // nL x 28: s(4), d(4), g(4), H_ll(16)
     double a1 = 0.0, q = 0.0;
     scale_and_gradient<T, true>(B, w, tr->iter == 0, kP, kL, uc, sc, dg, a1, q);
     a1 = block_sum(a1, red);
@@ -287,15 +264,15 @@ __device__ __forceinline__ bool solve_body(const DevBatch& B, const int w, doubl
       if (has1) tri_decode(wv + 8, ta1, tb1);
       const int nchP = (nP + CROWS - 1) / CROWS, nchL = (4 * nL + CROWS - 1) / CROWS;
       const int nch = nchP + nchL;
-      double* buf0 = S;
-      double* buf1 = S + CROWS * CW;
+      double* buf0 = L.buf0.at;
+      double* buf1 = L.buf1.at;
       // Per-landmark constants of the row transform, in LDS behind the two staging buffers: row scale and e-value of the
       // points, Cholesky factor / scale / e-vector of the lines.
-      double* pS = S + 2 * CROWS * CW;        // nP   s / sqrt(A)
-      double* pE = pS + B.maxP;               // nP   e = u / (s / sqrt(A))
-      double* lC = pE + B.maxP;               // nL x 10
-      double* lS = lC + 10 * B.maxL;          // nL x 4   jacobi scale / diagonal of C: the row solve multiplies, never divides
-      double* lE = lS + 4 * B.maxL;           // nL x 4   e = C^T (u ./ s),  u = s g~ / d  =>  u/s = g~/d
+      double* pS = L.pS.at;                   // nP   s / sqrt(A)
+      double* pE = L.pE.at;                   // nP   e = u / (s / sqrt(A))
+      double* lC = L.lC.at;                   // nL x 10
+      double* lS = L.lS.at;                   // nL x 4   jacobi scale / diagonal of C: the row solve multiplies, never divides
+      double* lE = L.lE.at;                   // nL x 4   e = C^T (u ./ s),  u = s g~ / d  =>  u/s = g~/d
       // per-landmark regularised blocks: points A = s^2 H + mu d^2 -> row scale s/sqrt(A); lines A_l = S H S + mu D^2 =
       // C C^T -> C to lch (the back substitution reads it) and, pre-divided, to LDS.  ONE pass per landmark kind, every
       // HBM operand requested before the arithmetic: as two passes with the row scale / factor handed over through HBM the
@@ -402,20 +379,14 @@ __device__ __forceinline__ bool solve_body(const DevBatch& B, const int w, doubl
           }
         }
       };
-#ifdef VPL_STAMPS
-      long long st_stage = 0, st_mfma = 0, st_bar = 0;
-#endif
+      VPL_IVAL(st_stage); VPL_IVAL(st_mfma); VPL_IVAL(st_bar);
       if (nch > 0) stage(0, buf0);
       __syncthreads();
       for (int ch = 0; ch < nch; ++ch) {
         double* cur = (ch & 1) ? buf1 : buf0;
-#ifdef VPL_STAMPS
-        long long t1 = __builtin_readcyclecounter();
-#endif
+        VPL_IVAL_START(t1);
         if (ch + 1 < nch) stage(ch + 1, (ch & 1) ? buf0 : buf1);
-#ifdef VPL_STAMPS
-        { const long long tt = __builtin_readcyclecounter(); st_stage += tt - t1; t1 = tt; }
-#endif
+        VPL_IVAL_LAP(st_stage, t1);
         const int m = lane & 15, kk = lane >> 4;
         // operands of step ks + 2 are read while the matrix cores work on step ks: with the reads issued right in front of
         // their MFMA a step took ~280 cycles (LDS latency) for 64 cycles of matrix-core time
@@ -439,14 +410,10 @@ __device__ __forceinline__ bool solve_body(const DevBatch& B, const int w, doubl
           acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc0, 0, 0, 0);
           if (has1) acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1v, b1v, acc1, 0, 0, 0);
         }
-#ifdef VPL_STAMPS
-        { const long long tt = __builtin_readcyclecounter(); st_mfma += tt - t1; t1 = tt; }
-#endif
+        VPL_IVAL_LAP(st_mfma, t1);
         __syncthreads();
-#ifdef VPL_STAMPS
-        { const long long tt = __builtin_readcyclecounter(); st_bar += tt - t1; t1 = tt; }
-        if (tid == 0 && ch + 1 == nch) { long long* dg_ = B.dbg + (size_t)w * 64; dg_[52] = st_stage; dg_[53] = st_mfma; dg_[54] = st_bar; }
-#endif
+        VPL_IVAL_LAP(st_bar, t1);
+        VPL_IVAL_STORE(tid == 0 && ch + 1 == nch, B.dbg + (size_t)w * 64 + 52, st_stage, st_mfma, st_bar);
       }
       VPL_STAMP(B, w, 2);
       // ---- reduced system: S = Hcc - X^T X (tile-major), rhs row = gc - X^T z; Cauchy denominator ----
@@ -545,7 +512,7 @@ __device__ __forceinline__ bool solve_body(const DevBatch& B, const int w, doubl
     //      system's space is free by now)
     back_substitute_points<T, 2, true>(B, w, mu, uc, pSt, lgn, a2, a3);
     VPL_STAMP(B, w, 9);
-    back_substitute_lines<T, 3, true>(B, w, uc, lSt, S, lgn, a2, a3);
+    back_substitute_lines<T, 3, true>(B, w, uc, lSt, L.lrhs.at, lgn, a2, a3);
     VPL_STAMP(B, w, 10);
     a2 = block_sum(a2, red);
     a3 = block_sum(a3, red);
@@ -576,9 +543,7 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(DevBatch B) {
   }
 }
 
-constexpr size_t SOLVE_SMEM = (size_t)(NAP + 5 * 176 + 256 + 24) * sizeof(double) + 4 * sizeof(int);   // + (maxP + maxL) ints, see solve_smem
-inline size_t solve_smem(int maxP, int maxL) { return SOLVE_SMEM + (size_t)(maxP + maxL) * sizeof(int); }
-static_assert(2 * CROWS * CW <= NAP, "the two staging buffers alias the reduced-system storage");
+inline size_t solve_smem(int maxP, int maxL) { return solve_lds_bytes(maxP, maxL); }
 
 // ---------------------------------------------------------------------------------------------------
 constexpr int COST_THREADS = 512;

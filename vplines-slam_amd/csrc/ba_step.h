@@ -1,6 +1,8 @@
 // The trust-region step of a window as three bodies of one launch shape (256 threads, two work-groups per CU, no scratch):
 // k_step runs them one after the other in ONE launch per step (the default); k_schur / k_chol / k_back run the same bodies
 // as three launches for the per-kernel attribution of the timing mode and for A/B runs (VPL_BA_STEP_FUSED=0).
+// Each body is its early-outs, one carve of the LDS by ba_step_layout.h (the layout the host sized the dispatch with: regions,
+// tenants, the slack) and the list of its phases; the barriers between the phases stand in the body, each with what it hands over.
 //
 //   k_schur  (~76 KB LDS at 200 points + 80 lines)  Jacobi scaling, dogleg diagonal / gradient, Cauchy point,
 //            regularised landmark blocks, and the landmark elimination: the rows of X = C^-1 S [W | g | e] go from HBM
@@ -22,7 +24,9 @@
 // from the reference tree) for the configuration at vins_estimator/src/estimator.cpp:1207-1215.
 #pragma once
 #include "ba_common.h"
+#include "ba_pack.h"
 #include "ba_solve.h"
+#include "ba_step_layout.h"
 
 namespace vpl {
 
@@ -52,8 +56,7 @@ __device__ __forceinline__ int compact2vis(int c, int s, int WS) {
 // ---------------------------------------------------------------------------------------------------------------------
 // NTC: 16-column tiles of the compact row (WS + 2 <= 16 NTC).  NTC = 3 covers tracks of up to 6 frames (the benchmark
 // shape): 6 lower tiles = 48 accumulator registers per lane; NTC = 5 covers every track length (15 tiles).
-constexpr int CSQ_LD = 80;                   // row stride of the compact system in k_schur's LDS
-constexpr int CSQ_N = 74 * CSQ_LD + 32;      // (+ slack: adds of exact zeros for frame slots past the window land behind a row's end)
+// (CSQ_LD = 80, the row stride of the compact system in LDS, and its size CSQ_N: ba_step_layout.h)
 // A WIDE chunk of k_schur_mixed (entries that hold a track of more than SCHUR_NARROW_FRAMES frames), out of line: its
 // register allocation is its own, the narrow product loop of the caller keeps its zero scratch.
 struct SchurWide {
@@ -179,55 +182,23 @@ __device__ __noinline__ void schur_wide_chunk(const SchurWide& A, const int k0, 
 // batch sent every entry through k_schur<5>: 120 accumulator + 120 prefetch registers (spills), 86 KB of LDS (one work-group
 // per CU), 5 x the time.
 constexpr int SCHUR_NARROW_FRAMES = 6;
-template <int NTC, bool MIXED = false>
-__device__ __forceinline__ void schur_body(const DevBatch& B, const int w, double* sm) {
-  static_assert(!MIXED || NTC == 3, "the narrow view is three column tiles");
-  constexpr int NLT = NTC * (NTC + 1) / 2;
-  const int tid = threadIdx.x, T = SCHUR_THREADS;
-  const int lane = tid & 63, wv = tid >> 6;
-  TrState* tr = &B.tr[w];
-  if (tr->status != 0 || tr->reuse != 0 || B.path[w] != 0) return;
-  count_active(B, 1);
-  const int nP = B.nP[w], nL = B.nL[w];
-  const int WS = B.WS;
-  // the view the table-driven product works in: logical row width WSv, memory column of logical column c >= WSv - 6 is c + coff
-  const int WSv = MIXED ? 6 * SCHUR_NARROW_FRAMES + 6 : WS;
-  const int coff = WS - WSv;
-  const int r1 = max(4 * B.maxP + 28 * B.maxL, CSQ_N);
-  double* kP = sm;                          // nP x 4: s, d, g, H_pp            (scaling -> landmark constants)
-  double* kL = sm + 4 * B.maxP;             // nL x 28: s(4), d(4), g(4), H_ll(16)
-  double* Cacc = sm;                        // CSQ_N: the compact system as a 74 x 80 row-major square (lower part used), after the constants are made
-  double* pS = sm + r1;                     // nP   s / sqrt(A)
-  double* pE = pS + B.maxP;                 // nP   e = u / (s / sqrt(A))
-  double* lC = pE + B.maxP;                 // nL x 10  Cholesky factor of the line block, off-diagonals pre-divided
-  double* lS = lC + 10 * B.maxL;            // nL x 4   jacobi scale / diagonal of C
-  double* lE = lS + 4 * B.maxL;             // nL x 4   e = C^T (u ./ s)
-  double* lG = lE + 4 * B.maxL;             // nL x 4   g column of X: C^-1 S g_l
-  double* pG = lG + 4 * B.maxL;             // nP       g column of X: (s / sqrt(A)) g_p
-  double* uc = pG + B.maxP;                 // 176  unscaled-space vector of gradient_ / diagonal_ (cam dims)
-  double* red = uc + 176;                   // 24
-  int* tick = (int*)(red + 24);             // 2
-  int* flag = tick + 2;                     // 2
-  int4* etab = (int4*)(((uintptr_t)(flag + 2) + 15) & ~(uintptr_t)15);   // maxKS entries of the K-step table
-  int* ftab = (int*)(etab + B.maxKS);       // NLT x 4 x 64 flush targets, see below
 
+// ---- the phases of schur_body, in its order; every thread of the work-group calls each ----
+
+// the window's K-step table to LDS; the ticket and the failure flag start at zero
+__device__ __forceinline__ void schur_copy_table(const DevBatch& B, const int w, int4* etab, int* tick, int* flag) {
+  const int tid = threadIdx.x, T = SCHUR_THREADS;
   {
     const int4* ktab = (const int4*)B.sk_tab + (size_t)w * B.maxKS;
     for (int k = tid; k < B.maxKS; k += T) etab[k] = ktab[k];
   }
-  const double* Hcc = B.Hcc + (size_t)w * NCP;
-  double* lch = B.lchol + (size_t)w * B.maxL * 10;
   if (tid == 0) { flag[0] = 0; tick[0] = 0; }
-  const double mu = tr->mu;
-  const bool first = (tr->iter == 0);
-  VPL_STAMP(B, w, 0);
-  // ---- jacobi scaling (iteration 0 only), diagonal_, gradient_ ----
-  double a1 = 0.0, q = 0.0;
-  scale_and_gradient<T, false>(B, w, first, kP, kL, uc, nullptr, nullptr, a1, q);
-  __syncthreads();   // uc, kP, kL complete
-  // camera part of the Cauchy denominator u^T Hcc u over the entries the factors can fill (B.nz_tab: 6147 of the 14706 of the
-  // packed triangle; everything else is a structural zero on this path), 12 loads in flight per thread
-  double qq = 0.0;
+}
+
+// camera part of the Cauchy denominator u^T Hcc u over the entries the factors can fill (B.nz_tab: 6147 of the 14706 of the
+// packed triangle; everything else is a structural zero on this path), 12 loads in flight per thread; added to qq
+__device__ __forceinline__ void schur_cauchy_camera(const DevBatch& B, const double* Hcc, const double* uc, double& qq) {
+  const int tid = threadIdx.x, T = SCHUR_THREADS;
   {
     constexpr int NB = (NZ_N + SCHUR_THREADS - 1) / SCHUR_THREADS;     // 25 at 256 threads
     constexpr int HALF = (NB + 1) / 2;
@@ -250,8 +221,14 @@ __device__ __forceinline__ void schur_body(const DevBatch& B, const int w, doubl
         }
     }
   }
-  VPL_STAMP(B, w, 1);
-  // ---- regularised landmark blocks: points A = s^2 H + mu d^2 -> row scale s / sqrt(A); lines A_l = S H S + mu D^2 = C C^T ----
+}
+
+// regularised landmark blocks: points A = s^2 H + mu d^2 -> row scale s / sqrt(A); lines A_l = S H S + mu D^2 = C C^T (to lch
+// for k_back).  Reads kP / kL; writes the constants of the row transform and raises flag[0] for a block that is not positive.
+__device__ __forceinline__ void schur_landmark_constants(const int nP, const int nL, const double mu, const double* kP, const double* kL,
+                                                         double* lch, double* pS, double* pE, double* pG, double* lC, double* lS,
+                                                         double* lE, double* lG, int* flag) {
+  const int tid = threadIdx.x, T = SCHUR_THREADS;
   for (int p = tid; p < nP; p += T) {
     const double s = kP[4 * p], d = kP[4 * p + 1], g = kP[4 * p + 2], h = kP[4 * p + 3];
     const double Al = s * s * h + mu * d * d;
@@ -281,7 +258,12 @@ __device__ __forceinline__ void schur_body(const DevBatch& B, const int w, doubl
       }
     }
   }
-  __syncthreads();   // constants complete; kP / kL are dead: their space becomes the compact system
+}
+
+// the compact system starts at zero; the flush targets of view width WSv
+template <int NLT>
+__device__ __forceinline__ void schur_zero_and_targets(const int WSv, double* Cacc, int* ftab) {
+  const int tid = threadIdx.x, T = SCHUR_THREADS;
   for (int i = tid; i < CSQ_N; i += T) Cacc[i] = 0.0;
   // Flush targets of the accumulator entries (tile t, register v, lane): entry (ca, cb) of the compact product of start
   // frame s goes to row va = map(ca), column vb = map(cb) of the 74 x 80 square, where a pose column maps to 6 s + c and an
@@ -300,11 +282,20 @@ __device__ __forceinline__ void schur_body(const DevBatch& B, const int w, doubl
     }
     ftab[i] = code;
   }
-  __syncthreads();
-  VPL_STAMP(B, w, 2);
-  // ---- X^T X on the matrix cores, operands straight from HBM ---------------------------------------------------------
-  // v_mfma_f64_16x16x4: the lane (kk, m) supplies A[k = kk][m] and B[kk][m] of the K-step and holds C[kk + 4 v][m].  With
-  // x[t] = X[row kk of the K-step][16 t + m] the lower tiles of the compact product are C(ta, tb) += x[ta] (x) x[tb].
+}
+
+// X^T X on the matrix cores, operands straight from HBM, every wave on its own span of rows; a wave adds its tiles to Cacc
+// when it holds the ticket.  No work-group barrier inside.
+// v_mfma_f64_16x16x4: the lane (kk, m) supplies A[k = kk][m] and B[kk][m] of the K-step and holds C[kk + 4 v][m].  With
+// x[t] = X[row kk of the K-step][16 t + m] the lower tiles of the compact product are C(ta, tb) += x[ta] (x) x[tb].
+// The view the table-driven product works in: logical row width WSv, memory column of logical column c >= WSv - 6 is c + coff.
+template <int NTC, bool MIXED>
+__device__ __forceinline__ void schur_product(const DevBatch& B, const int w, const int WS, const int WSv, const int coff, const int4* etab,
+                                              const int* ftab, double* Cacc, int* tick, const double* lC, const double* lS,
+                                              const double* lE, const double* lG, const double* pS, const double* pE, const double* pG) {
+  constexpr int NLT = NTC * (NTC + 1) / 2;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wv = tid >> 6;
   {
     const int m = lane & 15, kk = lane >> 4;
     // the wave's row of the span / ticket table: one int per lane, read with v_readlane
@@ -400,13 +391,9 @@ __device__ __forceinline__ void schur_body(const DevBatch& B, const int w, doubl
         }
       }
     };
-#ifdef VPL_STAMPS
-    long long st_flush = 0, st_wait = 0, st_xf = 0, st_mf = 0, st_ld = 0;
-#endif
+    VPL_IVAL(st_flush); VPL_IVAL(st_wait); VPL_IVAL(st_xf); VPL_IVAL(st_mf); VPL_IVAL(st_ld);
     auto flush = [&](int g, int seq) {
-#ifdef VPL_STAMPS
-      const long long tf0 = __builtin_readcyclecounter();
-#endif
+      VPL_IVAL_START(tf0);
       const int s6 = 6 * (g & 15);
       // targets first (one batch of LDS reads), then the ticket, then 4 NLT hardware adds (ds_add_f64: no read-back round
       // trip).  Only the holder of the ticket adds, one add per address: the order of the terms of every sum is the ticket order.
@@ -414,9 +401,7 @@ __device__ __forceinline__ void schur_body(const DevBatch& B, const int w, doubl
 #pragma unroll
       for (int i = 0; i < NLT * 4; ++i) code[i] = ftab[i * 64 + lane];
       lds_ticket_wait(&tick[0], seq);
-#ifdef VPL_STAMPS
-      st_wait += __builtin_readcyclecounter() - tf0;
-#endif
+      VPL_IVAL_ADD(st_wait, tf0);
 #pragma unroll
       for (int t = 0; t < NLT; ++t) {
         const double vals[4] = {acc[t].x, acc[t].y, acc[t].z, acc[t].w};
@@ -428,9 +413,7 @@ __device__ __forceinline__ void schur_body(const DevBatch& B, const int w, doubl
         acc[t] = v4d{0, 0, 0, 0};
       }
       lds_ticket_pass(&tick[0], seq, lane);
-#ifdef VPL_STAMPS
-      st_flush += __builtin_readcyclecounter() - tf0;
-#endif
+      VPL_IVAL_ADD(st_flush, tf0);
     };
     int nent = 0;
 #pragma unroll 1
@@ -454,20 +437,12 @@ __device__ __forceinline__ void schur_body(const DevBatch& B, const int w, doubl
       const int gcur = fetch(k0).x;
       auto step = [&](int k, double (&rw)[NTC][4]) {
         const int4 e = fetch(k);
-#ifdef VPL_STAMPS
-        const long long ts0 = __builtin_readcyclecounter();
-#endif
+        VPL_IVAL_START(ts);
         double x[NTC][4];
         transform(e, rw, x);
-#ifdef VPL_STAMPS
-        const long long ts1 = __builtin_readcyclecounter();
-        st_xf += ts1 - ts0;
-#endif
+        VPL_IVAL_LAP(st_xf, ts);
         load_raw(fetch(min(k + NPF, k1 - 1)), rw);      // (past the end: a harmless re-load of the last entry)
-#ifdef VPL_STAMPS
-        const long long ts2 = __builtin_readcyclecounter();
-        st_ld += ts2 - ts1;
-#endif
+        VPL_IVAL_LAP(st_ld, ts);
         const bool isl = (e.x & 32) != 0;
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
@@ -479,9 +454,7 @@ __device__ __forceinline__ void schur_body(const DevBatch& B, const int w, doubl
               for (int tb = 0; tb <= ta; ++tb, ++t) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(x[ta][a], x[tb][a], acc[t], 0, 0, 0);
           }
         }
-#ifdef VPL_STAMPS
-        st_mf += __builtin_readcyclecounter() - ts2;
-#endif
+        VPL_IVAL_ADD(st_mf, ts);
       };
 #pragma unroll 1
       for (int kb = k0; kb < k1; kb += NPF) {
@@ -491,15 +464,14 @@ __device__ __forceinline__ void schur_body(const DevBatch& B, const int w, doubl
       }
       flush(gcur, seq);
     }
-#ifdef VPL_STAMPS
-    if (lane == 0 && wv < 2) {
-      long long* dg_ = B.dbg + (size_t)w * 64 + 30 + 6 * wv;
-      dg_[0] = st_xf; dg_[1] = st_ld; dg_[2] = st_mf; dg_[3] = st_flush; dg_[4] = st_wait; dg_[5] = nent;
-    }
-#endif
+    VPL_IVAL_STORE(lane == 0 && wv < 2, B.dbg + (size_t)w * 64 + 30 + 6 * wv, st_xf, st_ld, st_mf, st_flush, st_wait, nent);
   }
-  __syncthreads();
-  VPL_STAMP(B, w, 3);
+}
+
+// the compact system to B.sacc for k_chol; the Cauchy point's alpha; a failed landmark block sends the window to k_solve
+__device__ __forceinline__ void schur_write_out(const DevBatch& B, const int w, TrState* tr, const double* Cacc, const double* uc, double* red,
+                                                const int* flag, double a1, double q, double qq) {
+  const int tid = threadIdx.x, T = SCHUR_THREADS;
   // Cauchy cross term (W^T u)_b u_c,b from the e-row of the compact system; alpha = |g~|^2 / (u^T H u)
   for (int b = tid; b < NV; b += T) qq += 2.0 * Cacc[(NV + 1) * CSQ_LD + b] * uc[vis2cam(b)];
   double* sacc = B.sacc + (size_t)w * SACC_N;
@@ -516,6 +488,49 @@ __device__ __forceinline__ void schur_body(const DevBatch& B, const int w, doubl
     tr->alpha = a1 / (q + qq);   // DoglegStrategy::ComputeCauchyPoint
     if (flag[0]) B.path[w] = 2;  // a landmark block is not positive definite: the retry loop lives in k_solve
   }
+}
+
+template <int NTC, bool MIXED = false>
+__device__ __forceinline__ void schur_body(const DevBatch& B, const int w, double* sm) {
+  static_assert(!MIXED || NTC == 3, "the narrow view is three column tiles");
+  constexpr int T = SCHUR_THREADS;
+  TrState* tr = &B.tr[w];
+  if (tr->status != 0 || tr->reuse != 0 || B.path[w] != 0) return;
+  count_active(B, 1);
+  const int nP = B.nP[w], nL = B.nL[w];
+  const int WS = B.WS;
+  // the view the table-driven product works in: logical row width WSv, memory column of logical column c >= WSv - 6 is c + coff
+  const int WSv = MIXED ? 6 * SCHUR_NARROW_FRAMES + 6 : WS;
+  const int coff = WS - WSv;
+  // regions and tenants: SchurLayoutT (ba_step_layout.h).  kP / kL and Cacc share the first region.
+  const SchurLayoutT<double*> L = schur_layout_at(sm, B.maxP, B.maxL, B.maxKS, NTC);
+  double *kP = L.kP.at, *kL = L.kL.at, *Cacc = L.Cacc.at, *pS = L.pS.at, *pE = L.pE.at, *lC = L.lC.at, *lS = L.lS.at, *lE = L.lE.at;
+  double *lG = L.lG.at, *pG = L.pG.at, *uc = L.uc.at, *red = L.red.at;
+  int *tick = (int*)L.tick.at, *flag = (int*)L.flag.at, *ftab = (int*)L.ftab.at;
+  int4* etab = (int4*)L.etab.at;
+
+  schur_copy_table(B, w, etab, tick, flag);
+  const double* Hcc = B.Hcc + (size_t)w * NCP;
+  double* lch = B.lchol + (size_t)w * B.maxL * 10;
+  const double mu = tr->mu;
+  const bool first = (tr->iter == 0);
+  VPL_STAMP(B, w, 0);
+  // ---- jacobi scaling (iteration 0 only), diagonal_, gradient_ ----
+  double a1 = 0.0, q = 0.0;
+  scale_and_gradient<T, false>(B, w, first, kP, kL, uc, nullptr, nullptr, a1, q);
+  __syncthreads();   // uc, kP, kL complete
+  double qq = 0.0;
+  schur_cauchy_camera(B, Hcc, uc, qq);
+  VPL_STAMP(B, w, 1);
+  schur_landmark_constants(nP, nL, mu, kP, kL, lch, pS, pE, pG, lC, lS, lE, lG, flag);
+  __syncthreads();   // constants complete; kP / kL are dead: their space becomes the compact system
+  schur_zero_and_targets<NTC * (NTC + 1) / 2>(WSv, Cacc, ftab);
+  __syncthreads();   // Cacc is zero, ftab and etab complete, tick and flag set
+  VPL_STAMP(B, w, 2);
+  schur_product<NTC, MIXED>(B, w, WS, WSv, coff, etab, ftab, Cacc, tick, lC, lS, lE, lG, pS, pE, pG);
+  __syncthreads();   // every wave has added its tiles: Cacc complete
+  VPL_STAMP(B, w, 3);
+  schur_write_out(B, w, tr, Cacc, uc, red, flag, a1, q, qq);
   VPL_STAMP(B, w, 4);
 }
 
@@ -530,11 +545,7 @@ __global__ __launch_bounds__(SCHUR_THREADS, 2) void k_schur_mixed(DevBatch B) {
   empty_next_order(B);
   schur_body<3, true>(B, ordered_window(B), sm);
 }
-inline size_t schur_smem(int maxP, int maxL, int ntc = 5) {
-  const int r1 = std::max(4 * maxP + 28 * maxL, (int)CSQ_N);
-  const int maxKS = maxP / 4 + maxL + NF + 2;
-  return (size_t)(r1 + 3 * maxP + 22 * maxL + 176 + 24) * sizeof(double) + (size_t)(8 + 4 * maxKS + ntc * (ntc + 1) / 2 * 256) * sizeof(int);
-}
+inline size_t schur_smem(int maxP, int maxL, int ntc = 5) { return schur_lds_bytes(maxP, maxL, max_schur_ksteps(maxP, maxL), ntc); }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // k_chol
@@ -549,14 +560,9 @@ inline size_t schur_smem(int maxP, int maxL, int ntc = 5) {
 //   chain A: slot a 0..8 | slot b 9..17 | speed/bias 0 18..26 | poses 0..5 27..62 | rhs 63
 //   chain B: slot a 0..8 | slot b 9..17 | poses 5..10 18..53 | rhs 54
 // tools/proto_chain.py is the NumPy statement of the same scheme (fronts, fill, back-substitution).
-constexpr int DN = 90;                       // dense dims (rhs row = DN)
-constexpr int DNT = 6;                       // 16x16 tiles per dimension of the dense system (96 >= 91)
-constexpr int DNAP = DNT * (DNT + 1) / 2 * 256;   // tile-major lower storage (5376 doubles)
-// The chains' X rows are stored in DENSE coordinates, five tile columns per chain: chain A tile columns 0, 1, 2, 4, 5 (dense
-// 0..47, 64..95), chain B 1..5 (dense 16..95).  Columns a chain never writes stay zero.
-constexpr int XLD = 80;                      // row stride of the X rows: five tile columns
+// (DN = 90 dense dims in DNT = 6 tiles per dimension; the chains' X rows, XROWS_A and XROWS_B of stride XLD, in dense
+// coordinates: ba_step_layout.h)
 constexpr int CHOL_MIN_WAVES = 2;
-constexpr int XROWS_A = 36, XROWS_B = 48;    // 4 x 9 rows ; 5 x 9 rows padded to a multiple of 4
 // position in a chain's X row of dense tile column J (J = 3 is not in chain A's rows, J = 0 not in chain B's)
 __device__ __forceinline__ constexpr int xcol(int ch, int J) { return ch == 0 ? 16 * (J > 3 ? J - 1 : J) : 16 * (J - 1); }
 // row I of tile t of the tile-major lower storage (t = I (I + 1) / 2 + J)
@@ -599,55 +605,26 @@ __device__ __forceinline__ int chain_dense(int ch, int lane) {
   return cam2dense(chain_col(ch, 0, lane));
 }
 
-__device__ __forceinline__ void chol_body(const DevBatch& B, const int w, double* sm) {
-  const int tid = threadIdx.x, T = CHOL_THREADS;
-  // Two work-groups share a CU, and the serial work of this kernel sits in "wave 0" and "wave 1" (the chains, the diagonal
-  // tiles): with the same roles in both, the two chains of the two windows would share one SIMD while the SIMDs of the
-  // partner waves idle.  Work-groups b and b + 256 are the ones that normally meet on a CU (round-robin over 8 XCDs x 32
-  // CUs): every second group of 256 rotates its roles by two waves.
-  const int lane = tid & 63, wv = ((tid >> 6) + ((blockIdx.x >> 8) & 1) * 2) & 3;
-  TrState* tr = &B.tr[w];
-  if (tr->status != 0 || tr->reuse != 0 || B.path[w] != 0) return;
-  count_active(B, 1);
-  constexpr int REG = (XROWS_A + XROWS_B) * XLD > DNAP ? (XROWS_A + XROWS_B) * XLD : DNAP;
-  double* XA = sm;                       // chain A's X rows (36 x XLD); chain B's behind them (48 x XLD)
-  double* XBm = sm + XROWS_A * XLD;
-  double* S = sm;                        // the dense system, tile-major lower, once the partner waves hold it in registers
-  double* scv = sm + REG;                // 176 jacobi scale of the cam dims
-  double* dgv = scv + 176;               // 176 dogleg diagonal
-  double* ycam = dgv + 176;              // 176 solution, cam-indexed (scaled space)
-  double* yv = ycam + 176;               // 96  dense solution
-  double* isd = yv + 96;                 // 96  1 / L_jj of the dense factor
-  double* Linv = isd + 96;               // 256 inverse of the current diagonal tile's factor
-  double* red = Linv + 256;              // 24
-  int* flag = (int*)(red + 24);          // [0] failure, [1], [2] blocks finished by chain A / B
-  double* rsL = (double*)(flag + 8);     // 2 x 5 x 9: 1 / L_kk of the chains' pivot blocks (for the back-substitution)
+// ---- the phases of chol_body, in its order.  wv is the wave's ROLE (0, 1: the chains; 2, 3: their partners), see chol_body.
+// One register array, two tenants, handed from phase to phase by reference: the chain waves keep X of every block for the
+// back-substitution (Xs(b, k) = U[9 b + k]), the partner waves their tiles of the dense system (11 or 10 tiles x 4 = U[0..43]).
+#define Xs(b, k) U[9 * (b) + (k)]
 
-  const size_t fb = (size_t)w * B.nfull;
-  const double* gscale = B.scale + fb;
-  const double* gdiag = B.diag + fb;
-  const double* ggrad = B.grad + fb;
-  double* ggn = B.gn + fb;
-  const double* Hcc = B.Hcc + (size_t)w * NCP;
-  const double* gc = B.gc + (size_t)w * NC;
-  const double* sacc = B.sacc + (size_t)w * SACC_N;
-  const double mu = tr->mu;
+// scale, diagonal and a zero solution to LDS; the flags; X (both chains' rows, XA | XBm) starts at zero
+__device__ __forceinline__ void chol_init(const double* gscale, const double* gdiag, double* scv, double* dgv, double* ycam, int* flag, double* X) {
+  const int tid = threadIdx.x, T = CHOL_THREADS;
   for (int c = tid; c < 176; c += T) { scv[c] = c < NC ? gscale[c] : 0.0; dgv[c] = c < NC ? gdiag[c] : 1.0; ycam[c] = 0.0; }
   if (tid < 4) flag[tid] = 0;
   // the columns of the X rows no chain lane writes, and rows 45..47 of chain B (K padding)
-  for (int i = tid; i < (XROWS_A + XROWS_B) * XLD; i += T) sm[i] = 0.0;
-  __syncthreads();
-  VPL_STAMP(B, w, 8);
+  for (int i = tid; i < (XROWS_A + XROWS_B) * XLD; i += T) X[i] = 0.0;
+}
 
-  // ================= phase 1: the two chains (waves 0, 1); the dense system assembled and the chains' X^T X taken off it
-  // on the matrix cores (waves 2, 3) =================================================================================
-  // One register array, two tenants: the chain waves keep X of every block for the back-substitution (Xs(b, k) = U[9 b + k]),
-  // the partner waves their tiles of the dense system (11 or 10 tiles x 4 = U[0..43]).
-  double U[45];
-#pragma unroll
-  for (int i = 0; i < 45; ++i) U[i] = 0.0;
-#define Xs(b, k) U[9 * (b) + (k)]
-  if (wv < 2) {
+// waves 0, 1: chain ch eliminates its speed/bias blocks; X of block b to U for the way back, to XA / XBm for the partner waves,
+// who are told through flag[1 + ch]; 1 / L_kk to rsL
+__device__ __forceinline__ void chol_chain_forward(const int wv, const int lane, const double* Hcc, const double* gc, const double* scv,
+                                                   const double* dgv, const double mu, double* XA, double* XBm, double* rsL, int* flag,
+                                                   double (&U)[45]) {
+  {
     const int ch = wv, nblk = ch == 0 ? 4 : 5;
     double* Xout = ch == 0 ? XA : XBm;
     const int xd = chain_dense(ch, lane);                 // the lane's X entries go to dense column xd (none: -1)
@@ -726,7 +703,14 @@ __device__ __forceinline__ void chol_body(const DevBatch& B, const int w, double
       }
     }
     if (bad && lane == 0) flag[0] = 1;
-  } else {
+  }
+}
+
+// waves 2, 3: the dense system assembled in U and the chains' X^T X taken off it on the matrix cores, as their rows arrive
+__device__ __forceinline__ void chol_partner_assemble(const int wv, const int lane, const double* Hcc, const double* gc, const double* sacc,
+                                                      const double* scv, const double* dgv, const double mu, const double* XA,
+                                                      const double* XBm, int* flag, double (&U)[45]) {
+  {
     // partner waves: the dense system in registers, tile t = (I, J) of the tile-major lower storage -- wave 2 the even
     // tiles, wave 3 the odd ones.  Each chain's product is summed from zero on the matrix cores, K-step by K-step as its X
     // rows are finished, and then subtracted: (H~ - P_A) - P_B.  The K-steps, the products and the roundings of every
@@ -808,10 +792,10 @@ __device__ __forceinline__ void chol_body(const DevBatch& B, const int w, double
       U[4 * i] = h.x; U[4 * i + 1] = h.y; U[4 * i + 2] = h.z; U[4 * i + 3] = h.w;
     }
   }
-  __syncthreads();   // the X rows are dead: their space becomes the dense system
-  VPL_STAMP(B, w, 9);
+}
 
-  // ================= phase 2: the dense system from the partner waves' registers into LDS ===========================
+// the dense system from the partner waves' registers into LDS
+__device__ __forceinline__ void chol_spill(const int wv, const int lane, double* S, const double (&U)[45]) {
   if (wv >= 2) {
     const int p = __builtin_amdgcn_readfirstlane(wv - 2);
     const int m = lane & 15, kk = lane >> 4;
@@ -827,23 +811,10 @@ __device__ __forceinline__ void chol_body(const DevBatch& B, const int w, double
       }
     }
   }
-  __syncthreads();
-  VPL_STAMP(B, w, 10);
+}
 
-  // ================= phase 3: left-looking tile Cholesky of the dense system (tile_cholesky of ba_solve.h, 6 tile columns,
-  // 4 waves); the rhs row rides along ==================================================================================
-  if (!tile_cholesky(S, Linv, isd, flag, DNT, DN, CHOL_THREADS / 64, lane, wv, nullptr)) {
-    // LINEAR_SOLVER_FAILURE: the retry with a larger mu is k_solve's loop
-    if (tid == 0) B.path[w] = 2;
-    return;
-  }
-  VPL_STAMP(B, w, 11);
-  // ================= phase 4: back substitution L^T y = z of the dense part =============================================
-  tile_back_substitute(S, isd, yv, DNT, DN, tid, T, lane, wv);
-  for (int d = tid; d < DN; d += T) ycam[dense2cam(d)] = yv[d];
-  __syncthreads();
-  VPL_STAMP(B, w, 12);
-  // ================= phase 5: the chains backwards ===================================================================
+// waves 0, 1: the chains backwards, from the dense solution in ycam; every block's nine entries of the solution to ycam
+__device__ __forceinline__ void chol_chain_backward(const int wv, const int lane, double* ycam, const double* rsL, const double (&U)[45]) {
   if (wv < 2) {
     const int ch = wv, nblk = ch == 0 ? 4 : 5;
 #pragma unroll
@@ -876,8 +847,12 @@ __device__ __forceinline__ void chol_body(const DevBatch& B, const int w, double
       }
     }
   }
-  __syncthreads();
-  // ================= outputs: S_c y_c for the landmark back-substitution, the Gauss-Newton step of the cam dims ==========
+}
+
+// outputs: S_c y_c for the landmark back-substitution, the Gauss-Newton step of the cam dims and its share of the dogleg sums
+__device__ __forceinline__ void chol_outputs(const DevBatch& B, const int w, const double* ycam, const double* scv, const double* dgv,
+                                             const double* ggrad, double* ggn, double* red) {
+  const int tid = threadIdx.x, T = CHOL_THREADS;
   double a2 = 0.0, a3 = 0.0;
   double* ycs = B.ycs + (size_t)w * 176;
   for (int c = tid; c < 176; c += T) {
@@ -895,14 +870,70 @@ __device__ __forceinline__ void chol_body(const DevBatch& B, const int w, double
   a2 = block_sum(a2, red);
   a3 = block_sum(a3, red);
   if (tid == 0) { B.sx[(size_t)w * 8] = a2; B.sx[(size_t)w * 8 + 1] = a3; }
-  VPL_STAMP(B, w, 13);
 }
 #undef Xs
+
+__device__ __forceinline__ void chol_body(const DevBatch& B, const int w, double* sm) {
+  const int tid = threadIdx.x, T = CHOL_THREADS;
+  // Two work-groups share a CU, and the serial work of this kernel sits in "wave 0" and "wave 1" (the chains, the diagonal
+  // tiles): with the same roles in both, the two chains of the two windows would share one SIMD while the SIMDs of the
+  // partner waves idle.  Work-groups b and b + 256 are the ones that normally meet on a CU (round-robin over 8 XCDs x 32
+  // CUs): every second group of 256 rotates its roles by two waves.
+  const int lane = tid & 63, wv = ((tid >> 6) + ((blockIdx.x >> 8) & 1) * 2) & 3;
+  TrState* tr = &B.tr[w];
+  if (tr->status != 0 || tr->reuse != 0 || B.path[w] != 0) return;
+  count_active(B, 1);
+  // regions and tenants: CholLayoutT (ba_step_layout.h).  The chains' X rows XA | XBm and the dense system S share the first region.
+  const CholLayoutT<double*> L = chol_layout_at(sm);
+  double *XA = L.XA.at, *XBm = L.XBm.at, *S = L.S.at, *scv = L.scv.at, *dgv = L.dgv.at, *ycam = L.ycam.at, *yv = L.yv.at, *isd = L.isd.at;
+  double *Linv = L.Linv.at, *red = L.red.at, *rsL = L.rsL.at;
+  int* flag = (int*)L.flag.at;
+
+  const size_t fb = (size_t)w * B.nfull;
+  const double* gscale = B.scale + fb;
+  const double* gdiag = B.diag + fb;
+  const double* ggrad = B.grad + fb;
+  double* ggn = B.gn + fb;
+  const double* Hcc = B.Hcc + (size_t)w * NCP;
+  const double* gc = B.gc + (size_t)w * NC;
+  const double* sacc = B.sacc + (size_t)w * SACC_N;
+  const double mu = tr->mu;
+  chol_init(gscale, gdiag, scv, dgv, ycam, flag, XA);
+  __syncthreads();   // scv, dgv complete; X and the flags are zero
+  VPL_STAMP(B, w, 8);
+  // the two chains (waves 0, 1); the dense system assembled and the chains' X^T X taken off it (waves 2, 3)
+  double U[45];
+#pragma unroll
+  for (int i = 0; i < 45; ++i) U[i] = 0.0;
+  if (wv < 2) chol_chain_forward(wv, lane, Hcc, gc, scv, dgv, mu, XA, XBm, rsL, flag, U);
+  else chol_partner_assemble(wv, lane, Hcc, gc, sacc, scv, dgv, mu, XA, XBm, flag, U);
+  __syncthreads();   // the X rows are dead: their space becomes the dense system
+  VPL_STAMP(B, w, 9);
+  chol_spill(wv, lane, S, U);
+  __syncthreads();   // S complete
+  VPL_STAMP(B, w, 10);
+  // left-looking tile Cholesky of the dense system (tile_cholesky of ba_solve.h, 6 tile columns, 4 waves); the rhs row rides along
+  if (!tile_cholesky(S, Linv, isd, flag, DNT, DN, CHOL_THREADS / 64, lane, wv, nullptr)) {
+    // LINEAR_SOLVER_FAILURE: the retry with a larger mu is k_solve's loop
+    if (tid == 0) B.path[w] = 2;
+    return;
+  }
+  VPL_STAMP(B, w, 11);
+  // back substitution L^T y = z of the dense part
+  tile_back_substitute(S, isd, yv, DNT, DN, tid, T, lane, wv);
+  for (int d = tid; d < DN; d += T) ycam[dense2cam(d)] = yv[d];
+  __syncthreads();   // the dense solution is in ycam
+  VPL_STAMP(B, w, 12);
+  chol_chain_backward(wv, lane, ycam, rsL, U);
+  __syncthreads();   // ycam complete
+  chol_outputs(B, w, ycam, scv, dgv, ggrad, ggn, red);
+  VPL_STAMP(B, w, 13);
+}
 __global__ __launch_bounds__(CHOL_THREADS, CHOL_MIN_WAVES) void k_chol(DevBatch B) {
   extern __shared__ double sm[];
   chol_body(B, ordered_window(B), sm);
 }
-constexpr size_t CHOL_SMEM = (size_t)(((XROWS_A + XROWS_B) * XLD > DNAP ? (XROWS_A + XROWS_B) * XLD : DNAP) + 3 * 176 + 2 * 96 + 256 + 24 + 96) * sizeof(double) + (8 + 128) * sizeof(int);
+inline size_t chol_smem() { return chol_lds_bytes(); }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // k_back : landmark back-substitution y_l = A_l^-1 S_l (g_l - W_l S_c y_c), then DoglegStrategy::ComputeTraditionalDoglegStep,
@@ -911,6 +942,16 @@ constexpr size_t CHOL_SMEM = (size_t)(((XROWS_A + XROWS_B) * XLD > DNAP ? (XROWS
 // ---------------------------------------------------------------------------------------------------------------------
 // FUSED (k_step): k_solve runs AFTER this body and is the flag's last reader -- a window of the general path leaves without
 // touching B.path, k_solve takes a one-iteration flag down itself.
+// the phase of back_body that reads: track start frames, S_c y_c in vis order (W's column order), the cam part of the Gauss-Newton step
+__device__ __forceinline__ void back_load(const DevBatch& B, const int w, const int nP, const int nL, const double* ggn, int* pSt, int* lSt,
+                                          double* uc, double* lgn) {
+  const int tid = threadIdx.x, T = BACK_THREADS;
+  for (int p = tid; p < nP; p += T) pSt[p] = B.pt_start[(size_t)w * B.maxP + p];
+  for (int l = tid; l < nL; l += T) lSt[l] = B.ln_start[(size_t)w * B.maxL + l];
+  for (int c = tid; c < 176; c += T) uc[c] = c < NV ? B.ycs[(size_t)w * 176 + vis2cam(c)] : 0.0;   // vis order: W's column order
+  for (int c = tid; c < NC; c += T) lgn[c] = ggn[c];
+}
+
 template <bool FUSED = false>
 __device__ __forceinline__ void back_body(const DevBatch& B, const int w, double* sm) {
   const int tid = threadIdx.x, T = BACK_THREADS;
@@ -924,24 +965,18 @@ __device__ __forceinline__ void back_body(const DevBatch& B, const int w, double
     return;
   }
   const int nP = B.nP[w], nL = B.nL[w];
-  double* uc = sm;                       // 176 S_c y_c
-  double* lrhs = uc + 176;               // 4 maxL
-  double* lgn = lrhs + 4 * B.maxL;       // nfull Gauss-Newton step (scaled space)
-  double* gdelta = lgn + B.nfull;        // nfull
-  double* red = gdelta + B.nfull;        // 24
-  int* pSt = (int*)(red + 24);
-  int* lSt = pSt + B.maxP;
+  // regions: BackLayoutT (ba_step_layout.h); no region changes its tenant
+  const BackLayoutT<double*> L = back_layout_at(sm, B.maxP, B.maxL, B.nfull);
+  double *uc = L.uc.at, *lrhs = L.lrhs.at, *lgn = L.lgn.at, *gdelta = L.gdelta.at, *red = L.red.at;
+  int *pSt = (int*)L.pSt.at, *lSt = (int*)L.lSt.at;
   double* ggn = B.gn + (size_t)w * B.nfull;
   const bool reuse0 = tr->reuse != 0;
   count_active(B, reuse0 ? 2 : 1);
   VPL_STAMP(B, w, 5);
   if (!reuse0) {
     const double mu = tr->mu;
-    for (int p = tid; p < nP; p += T) pSt[p] = B.pt_start[(size_t)w * B.maxP + p];
-    for (int l = tid; l < nL; l += T) lSt[l] = B.ln_start[(size_t)w * B.maxL + l];
-    for (int c = tid; c < 176; c += T) uc[c] = c < NV ? B.ycs[(size_t)w * 176 + vis2cam(c)] : 0.0;   // vis order: W's column order
-    for (int c = tid; c < NC; c += T) lgn[c] = ggn[c];
-    __syncthreads();
+    back_load(B, w, nP, nL, ggn, pSt, lSt, uc, lgn);
+    __syncthreads();   // pSt, lSt, uc and the cam part of lgn complete
     double a2 = 0.0, a3 = 0.0;
     back_substitute_points<T, 4, false>(B, w, mu, uc, pSt, lgn, a2, a3);
     back_substitute_lines<T, 5, false>(B, w, uc, lSt, lrhs, lgn, a2, a3);
@@ -952,7 +987,7 @@ __device__ __forceinline__ void back_body(const DevBatch& B, const int w, double
       tr->a3 = a3 + B.sx[(size_t)w * 8 + 1];
       tr->reuse = 1;   // DoglegStrategy::ComputeStep sets reuse_ = true
     }
-    __syncthreads();
+    __syncthreads();   // lgn complete, tr written
   }
   VPL_STAMP(B, w, 6);
   dogleg_step_and_candidate<T>(B, w, reuse0, lgn, gdelta, red);
@@ -964,10 +999,7 @@ __global__ __launch_bounds__(BACK_THREADS, VPL_BACK_WAVES) void k_back(DevBatch 
   extern __shared__ double sm[];
   back_body(B, ordered_window(B), sm);
 }
-inline size_t back_smem(int maxP, int maxL) {
-  const int nfull = NC + maxP + 4 * maxL;
-  return (size_t)(176 + 4 * maxL + 2 * nfull + 24) * sizeof(double) + (size_t)(maxP + maxL) * sizeof(int);
-}
+inline size_t back_smem(int maxP, int maxL) { return back_lds_bytes(maxP, maxL); }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // k_step : the three bodies above, one after the other, for the window of this work-group -- one launch per step.
@@ -976,7 +1008,7 @@ inline size_t back_smem(int maxP, int maxL) {
 // barriers here.  A body hands over through HBM exactly as between launches (B.path, sacc, ycs, sx, the scale / diag / grad
 // vectors, tr: written by a few lanes, read by all): __syncthreads() is a release / acquire pair at work-group scope, which
 // completes the stores of every wave before any wave of the work-group goes on to load.  One LDS block, the largest of the
-// three layouts; every body initialises what it reads of it.  The general path follows this kernel (k_step -> k_solve ->
+// three layouts of ba_step_layout.h (step_lds_bytes); every body carves it for itself and initialises what it reads of it.  The general path follows this kernel (k_step -> k_solve ->
 // k_cost), see back_body<true>.
 static_assert(SCHUR_THREADS == CHOL_THREADS && CHOL_THREADS == BACK_THREADS, "k_step runs the three bodies with one work-group shape");
 template <int NTC, bool MIXED>
@@ -990,8 +1022,6 @@ __global__ __launch_bounds__(SCHUR_THREADS, 2) void k_step(DevBatch B) {
   __syncthreads();
   back_body<true>(B, w, sm);
 }
-inline size_t step_smem(int maxP, int maxL, int ntc = 5) {
-  return std::max(std::max(schur_smem(maxP, maxL, ntc), (size_t)CHOL_SMEM), back_smem(maxP, maxL));
-}
+inline size_t step_smem(int maxP, int maxL, int ntc = 5) { return step_lds_bytes(maxP, maxL, max_schur_ksteps(maxP, maxL), ntc); }
 
 }  // namespace vpl

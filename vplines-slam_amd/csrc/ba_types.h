@@ -12,9 +12,7 @@
 
 namespace vpl {
 
-constexpr int NF = 11;                 // WINDOW_SIZE + 1 frames
-constexpr int NC = 171;                // cam dims
-constexpr int NV = 72;                 // vis dims
+// (NF = 11 frames, NC = 171 cam dims, NV = 72 vis dims: ba_limits.h)
 // column of vis dim c (0..71) in the compact W row of a track that starts in frame s; -1: structurally zero
 __host__ __device__ inline int wcol(int c, int s, int WS) {
   if (c >= 66) return WS - 72 + c;

@@ -115,10 +115,7 @@ static int ctx_init(vpl_ctx* c, int device, int max_windows, int max_points, int
   c->maxPO = max_point_obs > 0 ? max_point_obs : 1;
   c->maxL = max_lines > 0 ? max_lines : 1;
   c->maxLO = max_line_obs > 0 ? max_line_obs : 1;
-  // k_solve keeps 2 doubles per point and 18 per line in the LDS space behind its two staging buffers
-  if (2 * c->maxP + 18 * c->maxL > NAP - 2 * CROWS * CW) return VPL_E_CAPACITY;
-  // ... and 4 doubles per point and 28 per line in the staging buffers' space between the scaling and the first chunk
-  if (4 * c->maxP + 28 * c->maxL > 2 * CROWS * CW) return VPL_E_CAPACITY;
+  if (!solve_layout_fits(c->maxP, c->maxL)) return VPL_E_CAPACITY;
   if (solve_smem(c->maxP, c->maxL) > 159 * 1024) return VPL_E_CAPACITY;
   DevBatch& B = c->B;
   std::memset(&B, 0, sizeof(B));
@@ -198,7 +195,7 @@ static int ctx_init(vpl_ctx* c, int device, int max_windows, int max_points, int
   const std::pair<const void*, size_t> lds[] = {
       {(const void*)k_lin2, lin_max}, {(const void*)k_lin<1>, lin_max}, {(const void*)k_lin<2>, lin_max},
       {(const void*)k_solve, solve_max}, {(const void*)k_schur<3>, schur_max}, {(const void*)k_schur<5>, schur_max},
-      {(const void*)k_schur_mixed, schur_max}, {(const void*)k_chol, CHOL_SMEM}, {(const void*)k_back, back_max},
+      {(const void*)k_schur_mixed, schur_max}, {(const void*)k_chol, chol_smem()}, {(const void*)k_back, back_max},
       {(const void*)k_step<3, false>, step_max}, {(const void*)k_step<3, true>, step_max}, {(const void*)k_step<5, false>, step_max},
       {(const void*)k_prep, PREP_SMEM}, {(const void*)k_marg<MARG_THREADS>, MARG_LDS_MAX}, {(const void*)k_marg<256>, MARG_LDS_SMALL},
       {(const void*)k_prior_eigen, prior_eig_layout(MAXKEEP).bytes}, {(const void*)k_init_align, init_lds_bytes(INIT_NMAX)}};
@@ -726,7 +723,7 @@ static void launch_solve(vpl_ctx* c, int w0, int nw, hipStream_t s, int restore)
     } else {
       { KTimer t(c, "k_schur"); hipLaunchKernelGGL(kschur, grid, dim3(SCHUR_THREADS), schur_smem(B.maxP, B.maxL, ntc), s, B); }
       ++B.launch;
-      { KTimer t(c, "k_chol"); hipLaunchKernelGGL(k_chol, grid, dim3(CHOL_THREADS), CHOL_SMEM, s, B); }
+      { KTimer t(c, "k_chol"); hipLaunchKernelGGL(k_chol, grid, dim3(CHOL_THREADS), chol_smem(), s, B); }
       ++B.launch;
       { KTimer t(c, "k_solve"); hipLaunchKernelGGL(k_solve, grid, dim3(SOLVE_THREADS), solve_smem(B.maxP, B.maxL), s, B); }
       ++B.launch;
