@@ -183,9 +183,9 @@ int vpl_preintegrate_batch(vpl_ctx* ctx, int n, const int* offset, const int* ns
 /* ---- visual-inertial alignment  (replaces Estimator::visualInitialAlign, estimator.cpp:512-588, with VisualIMUAlignment =
  *      solveGyroscopeBias + LinearAlignment + RefineGravity, initial/initial_aligment.cpp:3-207, and Utility::g2R,
  *      utility.cpp:3-13) for n sequences in one call ------------------------------------------------------------------------ *
- * The vision-only structure before it (relativePose, GlobalSFM::construct, the PnP of the non-key frames) stays with the
- * caller, who hands in what it produced: ImageFrame::R and ImageFrame::T of every image frame, and the raw IMU samples between
- * them.  On the device, per sequence:
+ * The vision-only structure before it is vpl_init_structure_batch below (GlobalSFM::construct, the PnP of the non-key frames;
+ * relativePose stays with the caller), whose result has the form taken here: ImageFrame::R and ImageFrame::T of every image
+ * frame; with them the raw IMU samples between the frames.  On the device, per sequence:
  *   1. the F - 1 image intervals are pre-integrated under (lin_ba, lin_bg), the arithmetic of vpl_preintegrate_batch;
  *   2. solveGyroscopeBias: delta_bg from the 3 x 3 normal equations, summed in frame order; Bgs[i] += delta_bg for the 11 frames;
  *   3. the image intervals are integrated again under (0, Bgs[0]), the ten window intervals -- window interval i spans the image
@@ -243,6 +243,80 @@ int vpl_init_align_batch(vpl_ctx* ctx, int n, const vpl_init_input* in, const vp
  * intervals 1 .. 10; offset in samples; acc0_row: the sample row whose measurement starts the job (always offset - 1),
  * -1 = the input's acc0 / gyr0.  jobs needs room for F + 9 rows.  Refusals as above. */
 int vpl_init_debug_jobs(int n_frames, const int* n_samples, const int* key, int* jobs);
+
+/* ---- vision-only initial structure  (replaces GlobalSFM::construct, initial/initial_sfm.cpp:117-312, and the PnP of every
+ *      non-key image frame, estimator.cpp:432-501, inside Estimator::initialStructure) for n sequences in one call ----------- *
+ * What stays with the caller is the five-point RANSAC before it (relativePose / solveRelativeRT: cv::findFundamentalMat and
+ * cv::recoverPose), whose result -- l, relative_R, relative_T -- is an input here.  R and T of the result have the form
+ * vpl_init_input.R / .T take.  Per sequence, on the device:
+ *   1. the chain of construct (k_sfm_construct, one work-group per sequence): frames l and 10 from the relative pose; forward,
+ *      l+1 .. 9: PnP from the neighbour's pose, triangulation against frame 10; l against l+1 .. 9; backward, l-1 .. 0: PnP,
+ *      triangulation against l; what is left from its first and last observation.  Which track is triangulated when and from
+ *      which frames, and which tracks a PnP sees, depends on where observations exist only: the host builds that schedule as
+ *      integer tables (vpl_sfm_debug_plan) and the device works from them;
+ *   2. the full BA in the same launch: 11 cameras, the rotation of l and the translations of l and frame 10 constant, every
+ *      triangulated point a 3 x 3 block eliminated into the reduced camera system (57 free dims, tile Cholesky in LDS);
+ *   3. the PnP of the non-key image frames (k_sfm_frames, one work-group per frame) from the pose of the key frame
+ *      estimator.cpp:440-453 picks, then R / T of every image frame (k_sfm_finish).
+ * One Levenberg-Marquardt routine serves all three: ceres' trust-region minimiser with its defaults (Jacobi scaling, initial
+ * radius 1e4, min_relative_decrease 1e-3, tolerances 1e-6 / 1e-10 / 1e-8, 50 iterations) on ReprojectionError3D with analytic
+ * Jacobians and QuaternionParameterization.  Deviations: cv::solvePnP(ITERATIVE, useExtrinsicGuess) is that routine with the
+ * points constant (points and observations rounded to float as cv::Point3f / cv::Point2f do) -- the same minimiser where the
+ * problem is well posed, not the same iterates; max_solver_time_in_seconds = 0.2 has no counterpart, only the iteration cap
+ * ends a solve that does not converge.  FP64 throughout; every sum in a fixed order.
+ * A sequence's result has the same bits wherever it sits in the batch and whatever else the batch holds. */
+#define VPL_SFM_MAX_TRACKS 1024        /* point tracks per sequence */
+#define VPL_SFM_MAX_FRAME_POINTS 1024  /* (id, x, y) entries of one non-key image frame */
+#define VPL_SFM_FAIL_KEY_PNP 1         /* a key frame's PnP saw fewer than 10 points              (initial_sfm.cpp:45-50) */
+#define VPL_SFM_FAIL_FRAME_PNP 2       /* a non-key frame's PnP saw fewer than 6                  (estimator.cpp:481) */
+#define VPL_SFM_FAIL_BA 4              /* the BA ended neither in CONVERGENCE nor with final_cost < 5e-3 (initial_sfm.cpp:281) */
+#define VPL_SFM_FAIL_NUMERIC 8         /* a factorisation failed or a value was not finite */
+typedef struct vpl_sfm_input {
+  int n_frames;               /* F = all_image_frame.size(), 11 <= F <= VPL_INIT_MAX_FRAMES */
+  int key[VPL_NFRAMES];       /* image-frame index of window frame i, as in vpl_init_input */
+  int l;                      /* 0 .. 9: the window frame relativePose chose */
+  double relative_R[9], relative_T[3]; /* row-major; what relativePose returned */
+  double ric[9];              /* RIC[0], row-major */
+  int n_tracks;               /* f_manager.feature in list order, <= VPL_SFM_MAX_TRACKS */
+  const int* track_id;        /* [n_tracks] feature_id */
+  const int* track_start;     /* [n_tracks] start_frame (a window frame) */
+  const int* track_nobs;      /* [n_tracks] 1 .. 11 observations in consecutive window frames, start + nobs <= 11 */
+  const double* track_obs;    /* [sum nobs][2] (x, y) of feature_per_frame, track after track */
+  const int* frame_npts;      /* [F] entries of image frame f's point list; read for non-key frames only */
+  const int* frame_id;        /* [sum over the non-key frames, in frame order] feature id */
+  const double* frame_xy;     /* [the same][2] */
+} vpl_sfm_input;
+typedef struct vpl_sfm_result {
+  int ok;                     /* 1: construct returned true, every non-key frame's PnP ran, every result is finite */
+  int fail;                   /* VPL_SFM_FAIL_* mask, 0 when ok */
+  int n_tracked;              /* entries of sfm_tracked_points */
+  int iterations, successful_steps, termination; /* of the BA, as vpl_solve_report counts them */
+  int pnp_iterations[VPL_NFRAMES];           /* iterations of the key frame's PnP inside the chain, -1: none */
+  int frame_iterations[VPL_INIT_MAX_FRAMES]; /* iterations of the non-key image frame's PnP, -1: none */
+  double initial_cost, final_cost;           /* of the BA */
+  double chain_q[VPL_NFRAMES][4], chain_t[VPL_NFRAMES][3]; /* c_rotation (w, x, y, z) / c_translation after the chain */
+  double ba_q[VPL_NFRAMES][4], ba_t[VPL_NFRAMES][3];       /* ... after the BA */
+  double Q[VPL_NFRAMES][4], T[VPL_NFRAMES][3];             /* q (w, x, y, z) and T as construct returns them */
+  double frame_R[VPL_INIT_MAX_FRAMES][9], frame_T[VPL_INIT_MAX_FRAMES][3]; /* ImageFrame::R / T: vpl_init_input.R / .T */
+} vpl_sfm_result;
+/* in [n], out [n].  points_chain / points_ba: NULL or [n][VPL_SFM_MAX_TRACKS][3], every track's position after the chain / after
+ * the BA (a track that never gets one: zero).  tracked_id / tracked_xyz: NULL or [n][VPL_SFM_MAX_TRACKS] / [..][3],
+ * sfm_tracked_points in track order, n_tracked entries.  A sequence that fails (ok = 0) has everything behind the failing stage
+ * zeroed -- the chain (a starved key-frame PnP zeroes the chain's own output too), the BA, Q / T and the tracked points, the
+ * frames; the other sequences of the batch are untouched by it.  Host in, host out: one host-to-device copy, the kernels, one
+ * copy back and one synchronisation.  Refused before anything is launched -- VPL_E_INVALID: null arrays, F < 11, key not as
+ * described, l outside 0 .. 9, a track with nobs < 1 or running past frame 10, a negative count; VPL_E_CAPACITY:
+ * F > VPL_INIT_MAX_FRAMES, n_tracks > VPL_SFM_MAX_TRACKS, a frame list longer than VPL_SFM_MAX_FRAME_POINTS, n > max_windows. */
+int vpl_init_structure_batch(vpl_ctx* ctx, int n, const vpl_sfm_input* in, vpl_sfm_result* out, double* points_chain,
+                             double* points_ba, int* tracked_id, double* tracked_xyz);
+/* Host only, no device call: the schedule of construct for one sequence as vpl_init_structure_batch builds it.  step [n_tracks]:
+ * 1 frame l against frame 10, 2 frames l+1 .. 9 against 10, 3 l against l+1 .. 9, 4 frames l-1 .. 0 against l, 5 first against
+ * last observation, -1 the track never gets a position; fa / fb [n_tracks]: the two window frames in the order
+ * triangulateTwoFrames takes them (-1 with step -1); count [11]: the points the PnP of window frame i sees, -1 for l and frame 10
+ * and for a frame the chain does not reach; *first_fail: the first frame, in the order of the chain, whose count is below 10
+ * (the chain ends there and every later track keeps step -1), or -1.  Refusals as above. */
+int vpl_sfm_debug_plan(int l, int n_tracks, const int* track_start, const int* track_nobs, int* step, int* fa, int* fb, int* count,
+                       int* first_fail);
 
 /* ---- single-factor batch evaluators ------------------------------------- *
  * Each replaces one CostFunction::Evaluate (signature

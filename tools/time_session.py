@@ -12,7 +12,10 @@ MARGIN_OLD flags in both so that the two do the same work; medians over keyframe
 --mode init-align: vpl_init_align_batch (the visual-inertial alignment, once per start of a sequence) for 1 and for --batch
 sequences of 14 and of 40 image frames, pre-integrations read back; median, min and max of 7 calls after one warm-up call.
 --mode init: vpl_odo_init (the session takes its first window from the alignment: observations up, alignment, triangulation, scale)
-for sessions of 1 and of --batch sequences of 14 image frames; the same statistics."""
+for sessions of 1 and of --batch sequences of 14 image frames; the same statistics.
+--mode init-structure: vpl_init_structure_batch (GlobalSFM::construct and the PnP of the non-key frames, once per start) on the
+inputs of tests/sfm_inputs.py -- one 11-frame sequence, the 40 / 11 / 14-frame batch of the tests, one and eight 40-frame sequences
+of 150 tracks; median, min and max of 30 calls after three warm-up calls, then the kernels' device events from a call of its own."""
 import argparse
 import os
 import sys
@@ -110,6 +113,30 @@ def run_init_align(n, F):
     return ts[1:]
 
 
+def run_init_structure(tag, kws, reps=30):
+    """one line: wall time per vpl_init_structure_batch call over the sequences sfm_inputs.sequence(**kw) builds, and its kernels"""
+    import time
+    import sfm_inputs as si
+    qs = [v.SfmInput(**si.sequence(**kw)[0]) for kw in kws]
+    ctx = v.Context(device=0, max_windows=len(qs), max_points=8, max_point_obs=64, max_lines=8, max_line_obs=64)
+    for _ in range(3):
+        res = ctx.init_structure(qs)[0]
+    assert all(r.ok for r in res)
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        ctx.init_structure(qs)
+        ts.append(time.perf_counter() - t0)
+    ts = np.array(ts) * 1e3
+    ctx.enable_kernel_timing(True)
+    ctx.init_structure(qs)
+    kt = {k: round(x[0], 3) for k, x in ctx.kernel_times().items() if k.startswith("k_sfm")}
+    ctx.close()
+    print("init_structure %s: tracks %s, observations %s, BA iterations %s: median %.3f ms (min %.3f, max %.3f) per call; kernels ms %s"
+          % (tag, [len(q.track_start) for q in qs], [int(q.track_nobs.sum()) for q in qs], [r.iterations for r in res], np.median(ts), ts.min(),
+             ts.max(), kt))
+
+
 def run_init(n):
     """seconds per vpl_odo_init call of a session of n sequences, each the 14-frame input with its observations"""
     import init_align_inputs as A
@@ -133,13 +160,21 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--batch-keyframes", type=int, default=12)
-    ap.add_argument("--mode", choices=("plain", "imu", "halves", "rule", "init-align", "init"), default="plain")
+    ap.add_argument("--mode", choices=("plain", "imu", "halves", "rule", "init-align", "init", "init-structure"), default="plain")
     ap.add_argument("--repeat", type=int, default=1, help="imu / halves: run the sequence this many times, the two modes alternating")
     a = ap.parse_args()
     if a.mode == "init":
         for n in (1, a.batch):
             ts = np.array(run_init(n)) * 1e3
             print("odo_init F=14 n_seq=%d: median %.3f ms (min %.3f, max %.3f) per call" % (n, np.median(ts), ts.min(), ts.max()))
+        sys.exit(0)
+    if a.mode == "init-structure":
+        import sfm_inputs as si
+        big = dict(F=40, key=si.KEY40, l=3, noisy=True, n_tracks=150)
+        run_init_structure("1 x F=11", [dict(F=11, key=si.KEY11, l=4, noisy=True)])
+        run_init_structure("F=40, 11, 14", [dict(F=40, key=si.KEY40, l=3, noisy=True), dict(F=11, key=si.KEY11, l=4, noisy=True), dict(F=14, key=si.KEY14, l=4)])
+        run_init_structure("1 x F=40, 150 tracks", [big])
+        run_init_structure("8 x F=40, 150 tracks", [dict(big, track_seed=k) for k in range(8)])
         sys.exit(0)
     if a.mode == "init-align":
         for F in (14, 40):

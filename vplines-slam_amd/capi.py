@@ -127,6 +127,84 @@ def init_debug_jobs(n_samples, key):
     return jobs if rc == 0 else rc
 
 
+SFM_MAX_TRACKS = 1024
+SFM_MAX_FRAME_POINTS = 1024
+SFM_FAIL_KEY_PNP, SFM_FAIL_FRAME_PNP, SFM_FAIL_BA, SFM_FAIL_NUMERIC = 1, 2, 4, 8
+
+
+class CSfmInput(C.Structure):   # vpl_sfm_input
+    _fields_ = [("n_frames", C.c_int), ("key", C.c_int * NF), ("l", C.c_int), ("relative_R", C.c_double * 9),
+                ("relative_T", C.c_double * 3), ("ric", C.c_double * 9), ("n_tracks", C.c_int), ("track_id", _ip),
+                ("track_start", _ip), ("track_nobs", _ip), ("track_obs", _dp), ("frame_npts", _ip), ("frame_id", _ip),
+                ("frame_xy", _dp)]
+
+
+class SfmResult(C.Structure):   # vpl_sfm_result
+    _fields_ = [("ok", C.c_int), ("fail", C.c_int), ("n_tracked", C.c_int), ("iterations", C.c_int), ("successful_steps", C.c_int),
+                ("termination", C.c_int), ("pnp_iterations", C.c_int * NF), ("frame_iterations", C.c_int * INIT_MAX_FRAMES),
+                ("initial_cost", C.c_double), ("final_cost", C.c_double),
+                ("chain_q", (C.c_double * 4) * NF), ("chain_t", (C.c_double * 3) * NF),
+                ("ba_q", (C.c_double * 4) * NF), ("ba_t", (C.c_double * 3) * NF),
+                ("Q", (C.c_double * 4) * NF), ("T", (C.c_double * 3) * NF),
+                ("frame_R", (C.c_double * 9) * INIT_MAX_FRAMES), ("frame_T", (C.c_double * 3) * INIT_MAX_FRAMES)]
+
+    def arrays(self):
+        """the array members as numpy copies"""
+        return {f: np.array(getattr(self, f)) for f in ("pnp_iterations", "frame_iterations", "chain_q", "chain_t", "ba_q", "ba_t", "Q", "T",
+                                                        "frame_R", "frame_T")}
+
+
+class SfmInput:
+    """numpy-backed owner of one vpl_sfm_input: what the feature manager, the image frames and relativePose hand to the initial
+    structure.  key [11]; l; relative_R [3,3], relative_T [3]; ric [3,3]; track_id / track_start / track_nobs [N], track_obs [sum,2]
+    (track after track); frame_pts {non-key image frame: (ids [k], xy [k,2])}, a missing frame has an empty list."""
+
+    def __init__(self, n_frames, key, l, relative_R, relative_T, ric, track_id, track_start, track_nobs, track_obs, frame_pts=None):
+        self.n_frames, self.l = int(n_frames), int(l)
+        self.key = _arr(key, np.int32).copy()
+        self.relative_R = _arr(relative_R, np.float64).reshape(9).copy()
+        self.relative_T = _arr(relative_T, np.float64).reshape(3).copy()
+        self.ric = _arr(ric, np.float64).reshape(9).copy()
+        self.track_id, self.track_start, self.track_nobs = (_arr(a, np.int32).copy() for a in (track_id, track_start, track_nobs))
+        self.track_obs = _arr(track_obs, np.float64).reshape(-1, 2).copy()
+        frame_pts = frame_pts or {}
+        self.frame_npts = np.zeros(max(self.n_frames, 1), dtype=np.int32)
+        ids, xy = [np.zeros(0, dtype=np.int32)], [np.zeros((0, 2))]
+        for f in sorted(frame_pts):
+            i, x = frame_pts[f]
+            self.frame_npts[f] = len(i)
+            ids.append(_arr(i, np.int32))
+            xy.append(_arr(x, np.float64).reshape(-1, 2))
+        self.frame_id, self.frame_xy = np.concatenate(ids).astype(np.int32), np.concatenate(xy).astype(np.float64)
+
+    def to_c(self, ci=None):
+        ci = ci if ci is not None else CSfmInput()
+        ci.n_frames, ci.l, ci.n_tracks = self.n_frames, self.l, len(self.track_start)
+        for i in range(NF):
+            ci.key[i] = int(self.key[i])
+        for k in range(9):
+            ci.relative_R[k], ci.ric[k] = self.relative_R[k], self.ric[k]
+        for k in range(3):
+            ci.relative_T[k] = self.relative_T[k]
+        ci.track_id, ci.track_start, ci.track_nobs = (a.ctypes.data_as(_ip) for a in (self.track_id, self.track_start, self.track_nobs))
+        ci.track_obs, ci.frame_xy = _p(self.track_obs), _p(self.frame_xy)
+        ci.frame_npts, ci.frame_id = self.frame_npts.ctypes.data_as(_ip), self.frame_id.ctypes.data_as(_ip)
+        return ci
+
+
+def sfm_debug_plan(l, track_start, track_nobs):
+    """vpl_sfm_debug_plan (host only): the schedule of GlobalSFM::construct -> dict step / fa / fb [N], count [11], first_fail; the
+    VPL_E_* code instead when the tables are refused"""
+    lib = load_hip_library()
+    start, nobs = _arr(track_start, np.int32), _arr(track_nobs, np.int32)
+    n = len(start)
+    step, fa, fb = (np.zeros(max(n, 1), dtype=np.int32) for _ in range(3))
+    count, first = np.zeros(NF, dtype=np.int32), C.c_int(0)
+    rc = lib.vpl_sfm_debug_plan(int(l), n, start.ctypes.data_as(_ip), nobs.ctypes.data_as(_ip), step.ctypes.data_as(_ip),
+                                fa.ctypes.data_as(_ip), fb.ctypes.data_as(_ip), count.ctypes.data_as(_ip), C.byref(first))
+    return dict(step=step[:n], fa=fa[:n], fb=fb[:n], count=count, first_fail=first.value) if rc == 0 else rc
+
+
 class CWindow(C.Structure):
     _fields_ = [("pose", (C.c_double * 7) * NF), ("speed_bias", (C.c_double * 9) * NF), ("ex_pose", C.c_double * 7),
                 ("n_points", C.c_int), ("point_start", _ip), ("point_nobs", _ip), ("point_obs", _dp),
@@ -322,6 +400,8 @@ def load_hip_library():
     lib.vpl_init_align_batch.argtypes = [vp, C.c_int, C.POINTER(CInitInput), C.POINTER(BaOptions), C.POINTER(InitResult),
                                          C.POINTER(Preintegration), C.POINTER(Preintegration)]
     lib.vpl_init_debug_jobs.argtypes = [C.c_int, _ip, _ip, _ip]
+    lib.vpl_init_structure_batch.argtypes = [vp, C.c_int, C.POINTER(CSfmInput), C.POINTER(SfmResult), _dp, _dp, _ip, _dp]
+    lib.vpl_sfm_debug_plan.argtypes = [C.c_int, C.c_int, _ip, _ip, _ip, _ip, _ip, _ip, _ip]
     for name in ("vpl_projection_factor_evaluate", "vpl_line_factor_evaluate", "vpl_vp_factor_evaluate"):
         getattr(lib, name).argtypes = [vp, C.c_int, _dp, _dp, C.c_double, _dp, _dp]
     lib.vpl_imu_factor_evaluate.argtypes = [vp, C.c_int, _dp, C.POINTER(Preintegration), C.c_double, _dp, _dp]
@@ -648,6 +728,28 @@ class Context:
             return rc
         self._check(rc, "vpl_init_align_batch")
         return res, wpre, ipre
+
+    def init_structure(self, inputs, check=True):
+        """vpl_init_structure_batch over a list of SfmInput: GlobalSFM::construct and the PnP of the non-key image frames of every
+        sequence in one call.  -> (results [n] of SfmResult, points_chain [n, SFM_MAX_TRACKS, 3], points_ba [the same], tracked: per
+        sequence (ids [k], xyz [k, 3]) = sfm_tracked_points).  check=False: a refusal comes back as its VPL_E_* code instead of an
+        exception."""
+        self._settle()
+        n = len(inputs)
+        ci = (CSfmInput * n)()
+        for i, q in enumerate(inputs):
+            if isinstance(q, CSfmInput):
+                C.memmove(C.byref(ci[i]), C.byref(q), C.sizeof(CSfmInput))   # as the caller filled it (tests of the refusals)
+            else:
+                q.to_c(ci[i])
+        res = (SfmResult * n)()
+        pc, pb, txyz = (np.zeros((n, SFM_MAX_TRACKS, 3)) for _ in range(3))
+        tid = np.zeros((n, SFM_MAX_TRACKS), dtype=np.int32)
+        rc = self.lib.vpl_init_structure_batch(self.h, n, ci, res, _p(pc), _p(pb), tid.ctypes.data_as(_ip), _p(txyz))
+        if rc != 0 and not check:
+            return rc
+        self._check(rc, "vpl_init_structure_batch")
+        return res, pc, pb, [(tid[i, :res[i].n_tracked].copy(), txyz[i, :res[i].n_tracked].copy()) for i in range(n)]
 
     # ---- window solve ---------------------------------------------------------------
     def upload(self, windows, opt, chained=False):

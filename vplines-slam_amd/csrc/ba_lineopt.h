@@ -73,6 +73,45 @@ __global__ __launch_bounds__(128) void k_triangulate(DevBatch B) {
   }
 }
 
+// The right singular vector of the smallest singular value of the m x 4 matrix A (row-major, destroyed): one-sided Jacobi on
+// the columns, V (4 x 4, row-major) collects the rotations.  Returns the column of V that holds it (ties resolved to the first
+// column, as the oracle's sort).  Shared by k_triangulate_points and the triangulation of the initial structure (init_sfm.h).
+__device__ __forceinline__ int dlt_null_column(double* A, int m, double* V) {
+  for (int i = 0; i < 16; ++i) V[i] = (i % 5 == 0) ? 1.0 : 0.0;
+  for (int sweep = 0; sweep < 60; ++sweep) {
+    bool rotated = false;
+    for (int pp = 0; pp < 3; ++pp)
+      for (int q = pp + 1; q < 4; ++q) {
+        double al = 0, be = 0, ga = 0;
+        for (int r = 0; r < m; ++r) { al += A[r * 4 + pp] * A[r * 4 + pp]; be += A[r * 4 + q] * A[r * 4 + q]; ga += A[r * 4 + pp] * A[r * 4 + q]; }
+        if (ga == 0.0 || fabs(ga) <= 1e-15 * sqrt(al * be)) continue;
+        rotated = true;
+        const double zeta = (be - al) / (2.0 * ga);
+        const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+        const double c = 1.0 / sqrt(1.0 + t * t), sn = c * t;
+        for (int r = 0; r < m; ++r) {
+          const double a = A[r * 4 + pp], b = A[r * 4 + q];
+          A[r * 4 + pp] = c * a - sn * b;
+          A[r * 4 + q] = sn * a + c * b;
+        }
+        for (int r = 0; r < 4; ++r) {
+          const double a = V[r * 4 + pp], b = V[r * 4 + q];
+          V[r * 4 + pp] = c * a - sn * b;
+          V[r * 4 + q] = sn * a + c * b;
+        }
+      }
+    if (!rotated) break;
+  }
+  int cmin = 0;
+  double smin = 0;
+  for (int c = 0; c < 4; ++c) {
+    double s2 = 0;
+    for (int r = 0; r < m; ++r) s2 += A[r * 4 + c] * A[r * 4 + c];
+    if (c == 0 || s2 < smin) { smin = s2; cmin = c; }
+  }
+  return cmin;
+}
+
 // FeatureManager::triangulate (feature_manager.cpp:565-621), one lane per track whose inverse depth is negative (the
 // reference's estimated_depth = -1): DLT rows of every observation in the start camera frame, one-sided Jacobi SVD of
 // the 2m x 4 matrix (kept in per-lane scratch: this runs once per new track, not in the solve loop).
@@ -113,38 +152,7 @@ __global__ __launch_bounds__(128) void k_triangulate_points(DevBatch B, double i
       }
     }
     double V[16];
-    for (int i = 0; i < 16; ++i) V[i] = (i % 5 == 0) ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 60; ++sweep) {
-      bool rotated = false;
-      for (int pp = 0; pp < 3; ++pp)
-        for (int q = pp + 1; q < 4; ++q) {
-          double al = 0, be = 0, ga = 0;
-          for (int r = 0; r < m; ++r) { al += A[r * 4 + pp] * A[r * 4 + pp]; be += A[r * 4 + q] * A[r * 4 + q]; ga += A[r * 4 + pp] * A[r * 4 + q]; }
-          if (ga == 0.0 || fabs(ga) <= 1e-15 * sqrt(al * be)) continue;
-          rotated = true;
-          const double zeta = (be - al) / (2.0 * ga);
-          const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-          const double c = 1.0 / sqrt(1.0 + t * t), sn = c * t;
-          for (int r = 0; r < m; ++r) {
-            const double a = A[r * 4 + pp], b = A[r * 4 + q];
-            A[r * 4 + pp] = c * a - sn * b;
-            A[r * 4 + q] = sn * a + c * b;
-          }
-          for (int r = 0; r < 4; ++r) {
-            const double a = V[r * 4 + pp], b = V[r * 4 + q];
-            V[r * 4 + pp] = c * a - sn * b;
-            V[r * 4 + q] = sn * a + c * b;
-          }
-        }
-      if (!rotated) break;
-    }
-    int cmin = 0;
-    double smin = 0;
-    for (int c = 0; c < 4; ++c) {
-      double s2 = 0;
-      for (int r = 0; r < m; ++r) s2 += A[r * 4 + c] * A[r * 4 + c];
-      if (c == 0 || s2 < smin) { smin = s2; cmin = c; }   // (ties resolved to the first column, as the oracle's sort)
-    }
+    const int cmin = dlt_null_column(A, m, V);
     double depth = V[2 * 4 + cmin] / V[3 * 4 + cmin];
     if (depth < 0.1) depth = init_depth;
     B.invd[pi] = 1.0 / depth;

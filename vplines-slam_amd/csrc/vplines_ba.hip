@@ -39,6 +39,7 @@ using namespace vpl;
 #include "ba_ctx.h"
 #include "ba_upload.h"
 #include "init_align_host.h"
+#include "init_sfm_host.h"
 
 template <typename Launch>
 static int eval_generic(vpl_ctx* c, int n, const double* params, int psz, const double* consts, int csz, int nres,
