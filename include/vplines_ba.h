@@ -184,7 +184,7 @@ int vpl_preintegrate_batch(vpl_ctx* ctx, int n, const int* offset, const int* ns
  *      solveGyroscopeBias + LinearAlignment + RefineGravity, initial/initial_aligment.cpp:3-207, and Utility::g2R,
  *      utility.cpp:3-13) for n sequences in one call ------------------------------------------------------------------------ *
  * The vision-only structure before it is vpl_init_structure_batch below (GlobalSFM::construct, the PnP of the non-key frames;
- * relativePose stays with the caller), whose result has the form taken here: ImageFrame::R and ImageFrame::T of every image
+ * relativePose is vpl_init_relative_pose_batch behind it), whose result has the form taken here: ImageFrame::R and ImageFrame::T of every image
  * frame; with them the raw IMU samples between the frames.  On the device, per sequence:
  *   1. the F - 1 image intervals are pre-integrated under (lin_ba, lin_bg), the arithmetic of vpl_preintegrate_batch;
  *   2. solveGyroscopeBias: delta_bg from the 3 x 3 normal equations, summed in frame order; Bgs[i] += delta_bg for the 11 frames;
@@ -246,9 +246,10 @@ int vpl_init_debug_jobs(int n_frames, const int* n_samples, const int* key, int*
 
 /* ---- vision-only initial structure  (replaces GlobalSFM::construct, initial/initial_sfm.cpp:117-312, and the PnP of every
  *      non-key image frame, estimator.cpp:432-501, inside Estimator::initialStructure) for n sequences in one call ----------- *
- * What stays with the caller is the five-point RANSAC before it (relativePose / solveRelativeRT: cv::findFundamentalMat and
- * cv::recoverPose), whose result -- l, relative_R, relative_T -- is an input here.  R and T of the result have the form
- * vpl_init_input.R / .T take.  Per sequence, on the device:
+ * The relative pose before it (relativePose / solveRelativeRT) is vpl_init_relative_pose_batch below, whose result -- l,
+ * relative_R, relative_T -- is an input here; vpl_init_visual_batch runs the two in a row.  What stays with the caller is
+ * OpenCV's own random sequence (the device draws its samples from a stream of its own), CalibrationExRotation and the wiring
+ * into vpl_odo_init.  R and T of the result have the form vpl_init_input.R / .T take.  Per sequence, on the device:
  *   1. the chain of construct (k_sfm_construct, one work-group per sequence): frames l and 10 from the relative pose; forward,
  *      l+1 .. 9: PnP from the neighbour's pose, triangulation against frame 10; l against l+1 .. 9; backward, l-1 .. 0: PnP,
  *      triangulation against l; what is left from its first and last observation.  Which track is triangulated when and from
@@ -317,6 +318,86 @@ int vpl_init_structure_batch(vpl_ctx* ctx, int n, const vpl_sfm_input* in, vpl_s
  * (the chain ends there and every later track keeps step -1), or -1.  Refusals as above. */
 int vpl_sfm_debug_plan(int l, int n_tracks, const int* track_start, const int* track_nobs, int* step, int* fa, int* fb, int* count,
                        int* first_fail);
+
+/* ---- relative pose  (replaces Estimator::relativePose, estimator.cpp:590-622, and MotionEstimator::solveRelativeRT,
+ *      initial/solve_5pts.cpp:193-228 -- cv::findFundamentalMat(FM_RANSAC, 0.3 / 460, 0.99) and cv::recoverPose) for n
+ *      sequences in one call: the stage in front of vpl_init_structure_batch, whose l / relative_R / relative_T it fills ------- *
+ * Per sequence and per candidate window frame i = 0 .. 9 (k_relpose_ransac, one work-group per pair, all of them side by side):
+ *   1. getCorresponding(i, 10) in track-list order; corres.size() > 20 and average_parallax * 460 > 30, or the frame is not tried;
+ *   2. the RANSAC of findFundamentalMat: 7-point minimal samples, every real root of det(lambda F1 + (1 - lambda) F2) = 0 in
+ *      ascending lambda a hypothesis, the error of FMEstimatorCallback::computeError against (0.3 / 460)^2, a hypothesis wins with
+ *      good > max(best, 6), confidence 0.99, at most 1000 iterations, the adaptive stop.  256 iterations run at a time, one
+ *      lane each; the sequential rule is replayed over their counts in (iteration, root) order, so the result is that of the
+ *      sequential loop over the same sample stream;
+ *   3. recoverPose (solve_5pts.cpp:30-181): SVD of the winning F, R1 / R2 / +-t, the four cheirality masks ANDed with the RANSAC
+ *      mask, the >= cascade; Rotation = R^T, Translation = -R^T t; success with good > 12.
+ * k_relpose_finish picks l, the smallest i that succeeded.  Every candidate is evaluated and reported, also those behind l.
+ * What replaces OpenCV's random sequence is a counter-based integer stream of `seed`, the candidate, the iteration and the
+ * draw (csrc/init_relpose_plan.h; vpl_relpose_debug_plan hands it out): the same rules on another sample stream -- the same
+ * answer wherever the problem is well posed, not the same iterates.  Deviations: F is not scaled to F33 = 1 (it is handed out
+ * with unit Frobenius norm; nothing downstream depends on its scale); where OpenCV would assert on an empty model the
+ * candidate gets VPL_RELPOSE_NO_MODEL; findFundamentalMat's collinearity test of a sample (checkSubset) is not made, a
+ * degenerate sample is one more hypothesis that does not win.  FP64 throughout, every sum in a fixed order, no atomics: a
+ * sequence's result has the same bits wherever it sits in the batch and whatever else the batch holds. */
+#define VPL_RELPOSE_MAX_ITERS 1000
+#define VPL_RELPOSE_FEW_CORRES 0       /* corres.size() <= 20: not tried                          (estimator.cpp:598) */
+#define VPL_RELPOSE_LOW_PARALLAX 1     /* average_parallax * 460 <= 30: not tried                  (estimator.cpp:613) */
+#define VPL_RELPOSE_NO_MODEL 2         /* no hypothesis had more than 6 inliers */
+#define VPL_RELPOSE_FEW_GOOD 3         /* recoverPose's count <= 12                                (solve_5pts.cpp:222) */
+#define VPL_RELPOSE_SUCCESS 4
+#define VPL_RELPOSE_FAIL_NONE 1        /* no candidate frame succeeded: relativePose returns false */
+#define VPL_RELPOSE_FAIL_NUMERIC 8     /* a NaN / inf among the correspondences of a candidate */
+typedef struct vpl_relpose_input {
+  int n_tracks;               /* the track table exactly as vpl_sfm_input has it */
+  const int* track_start;     /* [n_tracks] */
+  const int* track_nobs;      /* [n_tracks] */
+  const double* track_obs;    /* [sum nobs][2] */
+  unsigned long long seed;    /* of the sample stream */
+} vpl_relpose_input;
+typedef struct vpl_relpose_candidate {
+  int n_corres;               /* corres.size() */
+  int status;                 /* VPL_RELPOSE_* */
+  int iterations;             /* niters when the loop ended (0: not tried) */
+  int best_iteration, best_root; /* of the winning hypothesis, -1: none */
+  int inliers;                /* its inlier count */
+  int good;                   /* recoverPose's count */
+  int numeric;                /* 1: a correspondence was not finite */
+  int pose_choice;            /* which of recoverPose's four poses won the vote: 0 (R1, t), 1 (R2, t), 2 (R1, -t), 3 (R2, -t) */
+  int pad_;
+  double average_parallax;
+  double F[9];                /* the winning F, row-major, x_10^T F x_i = 0, unit Frobenius norm */
+  double R[9], T[3];          /* Rotation / Translation of solveRelativeRT for this candidate, row-major */
+} vpl_relpose_candidate;
+typedef struct vpl_relpose_result {
+  int ok;                     /* 1: relativePose returns true */
+  int fail;                   /* VPL_RELPOSE_FAIL_* mask, 0 when ok */
+  int l;                      /* the smallest i with VPL_RELPOSE_SUCCESS; -1 when ok = 0 */
+  int pad_;
+  double relative_R[9], relative_T[3]; /* candidate l's R / T, in the form vpl_sfm_input takes; zero when ok = 0 */
+  vpl_relpose_candidate cand[VPL_WINDOW_SIZE];
+} vpl_relpose_result;
+/* in [n], out [n].  mask_ransac / mask_pose: NULL or [n][10][VPL_SFM_MAX_TRACKS] bytes, the inlier mask of the winning
+ * hypothesis and the mask recoverPose leaves, in correspondence order (zero behind n_corres and for a candidate without a
+ * model).  hyp_count: NULL or [n][10][1000][3], the inlier count of every hypothesis the sequential loop evaluates, -1 for a
+ * root that does not exist and for every iteration the loop does not reach.  Host in, host out: one host-to-device copy, the
+ * kernels, one copy back and one synchronisation.  Refused before anything is allocated -- VPL_E_INVALID: null arrays, a
+ * track with nobs < 1 or running past frame 10, a negative count; VPL_E_CAPACITY: n_tracks > VPL_SFM_MAX_TRACKS,
+ * n > max_windows.  A non-finite observation is not refused: the sequence comes back with ok = 0 and
+ * VPL_RELPOSE_FAIL_NUMERIC, the other sequences of the batch are untouched by it. */
+int vpl_init_relative_pose_batch(vpl_ctx* ctx, int n, const vpl_relpose_input* in, vpl_relpose_result* out,
+                                 unsigned char* mask_ransac, unsigned char* mask_pose, int* hyp_count);
+/* Host only, no device call: the sample stream and the stopping table of candidate frame i over n_corres correspondences as the
+ * kernel uses them.  samples [1000][7]: the indices of every iteration's minimal sample, in the order drawn; niters_after
+ * [n_corres + 1]: RANSACUpdateNumIters(0.99, (n_corres - good) / n_corres, 7, 1000) for good = 0 .. n_corres.
+ * VPL_E_INVALID: i outside 0 .. 9, n_corres < 7, a null array; VPL_E_CAPACITY: n_corres > VPL_SFM_MAX_TRACKS. */
+int vpl_relpose_debug_plan(unsigned long long seed, int i, int n_corres, int* samples, int* niters_after);
+/* vpl_init_relative_pose_batch, then vpl_init_structure_batch over the sequences whose relative pose succeeded, with l /
+ * relative_R / relative_T taken from it (those members of `in` are not read); the same host-side composition a caller would
+ * write.  seeds [n].  rel [n]: the relative pose's results.  A sequence whose relative pose fails has its vpl_sfm_result zeroed
+ * but for fail = VPL_SFM_FAIL_RELATIVE_POSE, and zeros in the optional arrays.  Refusals: those of the two calls. */
+#define VPL_SFM_FAIL_RELATIVE_POSE 16  /* vpl_init_visual_batch: relativePose returned false */
+int vpl_init_visual_batch(vpl_ctx* ctx, int n, const vpl_sfm_input* in, const unsigned long long* seeds, vpl_relpose_result* rel,
+                          vpl_sfm_result* out, double* points_chain, double* points_ba, int* tracked_id, double* tracked_xyz);
 
 /* ---- single-factor batch evaluators ------------------------------------- *
  * Each replaces one CostFunction::Evaluate (signature

@@ -15,7 +15,10 @@ sequences of 14 and of 40 image frames, pre-integrations read back; median, min 
 for sessions of 1 and of --batch sequences of 14 image frames; the same statistics.
 --mode init-structure: vpl_init_structure_batch (GlobalSFM::construct and the PnP of the non-key frames, once per start) on the
 inputs of tests/sfm_inputs.py -- one 11-frame sequence, the 40 / 11 / 14-frame batch of the tests, one and eight 40-frame sequences
-of 150 tracks; median, min and max of 30 calls after three warm-up calls, then the kernels' device events from a call of its own."""
+of 150 tracks; median, min and max of 30 calls after three warm-up calls, then the kernels' device events from a call of its own.
+--mode init-relpose: vpl_init_relative_pose_batch (Estimator::relativePose, once per start) on scenes of tests/relpose_inputs.py --
+1 and --batch sequences of 100 tracks with 20 % outliers and of 1024 tracks with 30 %; the C call alone, without the optional
+arrays: median, min and max of 30 calls after three warm-up calls, then the kernels' device events from a call of its own."""
 import argparse
 import os
 import sys
@@ -137,6 +140,36 @@ def run_init_structure(tag, kws, reps=30):
              ts.max(), kt))
 
 
+def run_init_relpose(name, n, reps=30):
+    """one line: wall time per vpl_init_relative_pose_batch call over n copies of a scene (seeds 0 .. n - 1), and its kernels"""
+    import ctypes as C
+    import time
+    import relpose_inputs as ri
+    Sc, _ = ri.scene(name)
+    qs = [v.RelPoseInput(seed=k, **Sc) for k in range(n)]
+    ci = (v.capi.CRelPoseInput * n)()
+    for k, q in enumerate(qs):
+        q.to_c(ci[k])
+    res = (v.capi.RelPoseResult * n)()
+    ctx = v.Context(device=0, max_windows=n, max_points=8, max_point_obs=64, max_lines=8, max_line_obs=64)
+    call = lambda: ctx.lib.vpl_init_relative_pose_batch(ctx.h, n, ci, res, None, None, None)
+    for _ in range(3):
+        assert call() == 0
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        call()
+        ts.append(time.perf_counter() - t0)
+    ts = np.array(ts) * 1e3
+    ctx.enable_kernel_timing(True)
+    assert call() == 0
+    kt = {k: round(x[0], 3) for k, x in ctx.kernel_times().items() if k.startswith("k_relpose")}
+    its = [res[0].cand[i].iterations for i in range(10)]
+    print("init_relative_pose %s, n_seq=%d: ok %d of %d, iterations of sequence 0 %s: median %.3f ms (min %.3f, max %.3f) per call; kernels ms %s"
+          % (name, n, sum(r.ok for r in res), n, its, np.median(ts), ts.min(), ts.max(), kt))
+    ctx.close()
+
+
 def run_init(n):
     """seconds per vpl_odo_init call of a session of n sequences, each the 14-frame input with its observations"""
     import init_align_inputs as A
@@ -160,13 +193,18 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--batch-keyframes", type=int, default=12)
-    ap.add_argument("--mode", choices=("plain", "imu", "halves", "rule", "init-align", "init", "init-structure"), default="plain")
+    ap.add_argument("--mode", choices=("plain", "imu", "halves", "rule", "init-align", "init", "init-structure", "init-relpose"), default="plain")
     ap.add_argument("--repeat", type=int, default=1, help="imu / halves: run the sequence this many times, the two modes alternating")
     a = ap.parse_args()
     if a.mode == "init":
         for n in (1, a.batch):
             ts = np.array(run_init(n)) * 1e3
             print("odo_init F=14 n_seq=%d: median %.3f ms (min %.3f, max %.3f) per call" % (n, np.median(ts), ts.min(), ts.max()))
+        sys.exit(0)
+    if a.mode == "init-relpose":
+        for name in ("100 tracks, 20 % outliers", "1024 tracks"):
+            for n in (1, a.batch):
+                run_init_relpose(name, n)
         sys.exit(0)
     if a.mode == "init-structure":
         import sfm_inputs as si

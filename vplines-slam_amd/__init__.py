@@ -10,7 +10,7 @@ from .capi import (  # noqa: F401
     BaOptions, Preintegration, Prior, Window, SolveReport, Context, SlideTracks, default_options, load_hip_library,
     Session, Frame, ImuFrame, OdoResult, OdoImuOut, OdoDecision, OdoKeyframeRule, FailureLimits,
     default_keyframe_rule, default_failure_limits, failure_detection, InitInput, InitResult,
-    SfmInput, SfmResult, sfm_debug_plan,
+    SfmInput, SfmResult, sfm_debug_plan, RelPoseInput, RelPoseResult, relpose_debug_plan,
     MARGIN_OLD, MARGIN_SECOND_NEW, MARGIN_NONE, PRIOR_PIVOTED_CHOLESKY, PRIOR_EIGEN,
 )
 from . import workload  # noqa: F401

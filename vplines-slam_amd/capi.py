@@ -205,6 +205,59 @@ def sfm_debug_plan(l, track_start, track_nobs):
     return dict(step=step[:n], fa=fa[:n], fb=fb[:n], count=count, first_fail=first.value) if rc == 0 else rc
 
 
+RELPOSE_MAX_ITERS = 1000
+RELPOSE_FEW_CORRES, RELPOSE_LOW_PARALLAX, RELPOSE_NO_MODEL, RELPOSE_FEW_GOOD, RELPOSE_SUCCESS = 0, 1, 2, 3, 4
+RELPOSE_FAIL_NONE, RELPOSE_FAIL_NUMERIC = 1, 8
+SFM_FAIL_RELATIVE_POSE = 16
+
+
+class CRelPoseInput(C.Structure):   # vpl_relpose_input
+    _fields_ = [("n_tracks", C.c_int), ("track_start", _ip), ("track_nobs", _ip), ("track_obs", _dp), ("seed", C.c_ulonglong)]
+
+
+class RelPoseCandidate(C.Structure):   # vpl_relpose_candidate
+    _fields_ = [("n_corres", C.c_int), ("status", C.c_int), ("iterations", C.c_int), ("best_iteration", C.c_int), ("best_root", C.c_int),
+                ("inliers", C.c_int), ("good", C.c_int), ("numeric", C.c_int), ("pose_choice", C.c_int), ("pad_", C.c_int), ("average_parallax", C.c_double),
+                ("F", C.c_double * 9), ("R", C.c_double * 9), ("T", C.c_double * 3)]
+
+
+class RelPoseResult(C.Structure):   # vpl_relpose_result
+    _fields_ = [("ok", C.c_int), ("fail", C.c_int), ("l", C.c_int), ("pad_", C.c_int), ("relative_R", C.c_double * 9),
+                ("relative_T", C.c_double * 3), ("cand", RelPoseCandidate * (NF - 1))]
+
+
+class RelPoseInput:
+    """numpy-backed owner of one vpl_relpose_input: the track table as SfmInput has it -- track_start / track_nobs [N], track_obs
+    [sum,2] (track after track) -- and the seed of the sample stream."""
+
+    def __init__(self, track_start, track_nobs, track_obs, seed=0):
+        self.track_start, self.track_nobs = (_arr(a, np.int32).copy() for a in (track_start, track_nobs))
+        self.track_obs = _arr(track_obs, np.float64).reshape(-1, 2).copy()
+        self.seed = int(seed)
+
+    @classmethod
+    def of(cls, sfm_input, seed=0):
+        """from the arrays of an SfmInput"""
+        return cls(sfm_input.track_start, sfm_input.track_nobs, sfm_input.track_obs, seed)
+
+    def to_c(self, ci=None):
+        ci = ci if ci is not None else CRelPoseInput()
+        ci.n_tracks, ci.seed = len(self.track_start), self.seed
+        ci.track_start, ci.track_nobs = (a.ctypes.data_as(_ip) for a in (self.track_start, self.track_nobs))
+        ci.track_obs = _p(self.track_obs)
+        return ci
+
+
+def relpose_debug_plan(seed, i, N):
+    """vpl_relpose_debug_plan (host only): the sample stream and the stopping table of candidate frame i over N correspondences ->
+    dict samples [1000, 7], niters_after [N + 1]; the VPL_E_* code instead when the arguments are refused"""
+    lib = load_hip_library()
+    samples = np.zeros((RELPOSE_MAX_ITERS, 7), dtype=np.int32)
+    table = np.zeros(max(int(N), 0) + 1, dtype=np.int32)
+    rc = lib.vpl_relpose_debug_plan(int(seed), int(i), int(N), samples.ctypes.data_as(_ip), table.ctypes.data_as(_ip))
+    return dict(samples=samples, niters_after=table) if rc == 0 else rc
+
+
 class CWindow(C.Structure):
     _fields_ = [("pose", (C.c_double * 7) * NF), ("speed_bias", (C.c_double * 9) * NF), ("ex_pose", C.c_double * 7),
                 ("n_points", C.c_int), ("point_start", _ip), ("point_nobs", _ip), ("point_obs", _dp),
@@ -402,6 +455,11 @@ def load_hip_library():
     lib.vpl_init_debug_jobs.argtypes = [C.c_int, _ip, _ip, _ip]
     lib.vpl_init_structure_batch.argtypes = [vp, C.c_int, C.POINTER(CSfmInput), C.POINTER(SfmResult), _dp, _dp, _ip, _dp]
     lib.vpl_sfm_debug_plan.argtypes = [C.c_int, C.c_int, _ip, _ip, _ip, _ip, _ip, _ip, _ip]
+    _bp = C.POINTER(C.c_ubyte)
+    lib.vpl_init_relative_pose_batch.argtypes = [vp, C.c_int, C.POINTER(CRelPoseInput), C.POINTER(RelPoseResult), _bp, _bp, _ip]
+    lib.vpl_relpose_debug_plan.argtypes = [C.c_ulonglong, C.c_int, C.c_int, _ip, _ip]
+    lib.vpl_init_visual_batch.argtypes = [vp, C.c_int, C.POINTER(CSfmInput), C.POINTER(C.c_ulonglong), C.POINTER(RelPoseResult),
+                                          C.POINTER(SfmResult), _dp, _dp, _ip, _dp]
     for name in ("vpl_projection_factor_evaluate", "vpl_line_factor_evaluate", "vpl_vp_factor_evaluate"):
         getattr(lib, name).argtypes = [vp, C.c_int, _dp, _dp, C.c_double, _dp, _dp]
     lib.vpl_imu_factor_evaluate.argtypes = [vp, C.c_int, _dp, C.POINTER(Preintegration), C.c_double, _dp, _dp]
@@ -750,6 +808,63 @@ class Context:
             return rc
         self._check(rc, "vpl_init_structure_batch")
         return res, pc, pb, [(tid[i, :res[i].n_tracked].copy(), txyz[i, :res[i].n_tracked].copy()) for i in range(n)]
+
+    def init_relative_pose(self, inputs, check=True, want_masks=True, want_hyp=True):
+        """vpl_init_relative_pose_batch over a list of RelPoseInput: Estimator::relativePose -- the RANSAC of findFundamentalMat and
+        recoverPose for every candidate frame 0 .. 9 of every sequence, and the choice of l -- in one call.  -> (results [n] of
+        RelPoseResult, mask_ransac [n, 10, SFM_MAX_TRACKS] uint8, mask_pose [the same], hyp_count [n, 10, 1000, 3] int32); the
+        optional arrays None when not wanted.  check=False: a refusal comes back as its VPL_E_* code instead of an exception."""
+        self._settle()
+        n = len(inputs)
+        ci = (CRelPoseInput * n)()
+        for i, q in enumerate(inputs):
+            if isinstance(q, CRelPoseInput):
+                C.memmove(C.byref(ci[i]), C.byref(q), C.sizeof(CRelPoseInput))   # as the caller filled it (tests of the refusals)
+            else:
+                q.to_c(ci[i])
+        res = (RelPoseResult * n)()
+        m0 = np.zeros((n, NF - 1, SFM_MAX_TRACKS), dtype=np.uint8) if want_masks else None
+        m1 = np.zeros((n, NF - 1, SFM_MAX_TRACKS), dtype=np.uint8) if want_masks else None
+        hyp = np.zeros((n, NF - 1, RELPOSE_MAX_ITERS, 3), dtype=np.int32) if want_hyp else None
+        _bp = C.POINTER(C.c_ubyte)
+        rc = self.lib.vpl_init_relative_pose_batch(self.h, n, ci, res, m0.ctypes.data_as(_bp) if want_masks else None,
+                                                   m1.ctypes.data_as(_bp) if want_masks else None,
+                                                   hyp.ctypes.data_as(_ip) if want_hyp else None)
+        if rc != 0 and not check:
+            return rc
+        self._check(rc, "vpl_init_relative_pose_batch")
+        return res, m0, m1, hyp
+
+    def init_visual(self, inputs, seeds=None, check=True):
+        """The vision-only start in one go: init_relative_pose over the track tables of a list of SfmInput (their l / relative_R /
+        relative_T are not read), those three copied into the sequences whose relative pose succeeded, init_structure over these.
+        seeds: one per sequence, default 0.  -> (relative-pose results [n] of RelPoseResult, structure: a list [n] with
+        (SfmResult, points_chain [SFM_MAX_TRACKS, 3], points_ba, (ids, xyz)) per sequence, None where the relative pose failed).
+        vpl_init_visual_batch is the same composition in C."""
+        seeds = [0] * len(inputs) if seeds is None else list(seeds)
+        rel = self.init_relative_pose([RelPoseInput.of(q, s) for q, s in zip(inputs, seeds)], check=check, want_masks=False, want_hyp=False)
+        if isinstance(rel, int):
+            return rel
+        rel = rel[0]
+        go = [i for i in range(len(inputs)) if rel[i].ok]
+        filled = []
+        for i in go:
+            ci = inputs[i].to_c()                     # (points into the arrays of inputs[i])
+            ci.l = rel[i].l
+            for k in range(9):
+                ci.relative_R[k] = rel[i].relative_R[k]
+            for k in range(3):
+                ci.relative_T[k] = rel[i].relative_T[k]
+            filled.append(ci)
+        out = [None] * len(inputs)
+        if go:
+            st = self.init_structure(filled, check=check)
+            if isinstance(st, int):
+                return st
+            res, pc, pb, tr = st
+            for k, i in enumerate(go):
+                out[i] = (res[k], pc[k], pb[k], tr[k])
+        return rel, out
 
     # ---- window solve ---------------------------------------------------------------
     def upload(self, windows, opt, chained=False):
