@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "ba_types.h"
+#include "ba_asm_pattern.h"
 #include "vpl_math.h"
 
 namespace vpl {
@@ -90,12 +91,7 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
 // hardware LDS f64 add (ds_add_f64)
 __device__ __forceinline__ void lds_add(double* p, double v) { unsafeAtomicAdd(p, v); }
 
-// cam index -> vis index or -1
-__host__ __device__ __forceinline__ int cam2vis(int c) {
-  if (c >= 165) return 66 + (c - 165);
-  int o = c % 15;
-  return o < 6 ? 6 * (c / 15) + o : -1;
-}
+// (cam2vis, cam index -> vis index or -1: ba_asm_pattern.h)
 
 // decode a packed lower-triangular index into (r, c), r >= c
 __device__ __forceinline__ void tri_decode(int idx, int& r, int& c) {

@@ -35,6 +35,10 @@ struct vpl_ctx {
   std::vector<vpl_prior> h_pass_priors;
   bool any_second_new = false;
   int maxPriorN = 0;                             // largest prior of the uploaded batch (k_prep stages J0 in LDS)
+  // a window of the uploaded batch takes the general path (B.path == 1, VPL_BA_GENERAL=1 included): k_lin may store to entries
+  // of Hcc outside the fast path's pattern, which every other window expects to hold the zeros Hcc was allocated with -- the
+  // next upload zero-fills Hcc
+  bool hcc_general = false;
   bool prior_resident = false;                   // the last solve / marginalisation of the uploaded batch left its priors in mg_* (vpl_ba_upload_chained)
   int prior_resident_nW = 0;
   // signature of the track layout (start frames, lengths, selected lines) of the last upload: when the next batch has the same

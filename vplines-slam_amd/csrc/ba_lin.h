@@ -262,31 +262,9 @@ __global__ __launch_bounds__(PREP_THREADS) void k_prep(DevBatch B, int nstage, i
 }
 
 // ---------------------------------------------------------------------------------------
-// The vis Hessian in LDS: lower block triangle of 12 x 12 blocks of 6 x 6 (frames 0..10, extrinsic), every block stored
-// full -- 78 blocks = 2808 doubles instead of the 72 x 72 square.  Entry (r, c), r >= c in vis indices:
-constexpr int HV_DOUBLES = 78 * 36;
+// The vis Hessian in LDS (HV_DOUBLES, hvi) and the static description of a packed cam-Hessian entry for the assembly pass
+// (lin_asm_entry): ba_asm_pattern.h
 constexpr int LIN_PART = 78 * 36 + 72 + 8;      // B.lin_part per window: visual Hessian | gradient | cost of the point factors (k_lin2)
-__host__ __device__ __forceinline__ int hvi(int r, int c) {
-  const int br = r / 6, bc = c / 6;
-  return 36 * (br * (br + 1) / 2 + bc) + 6 * (r - 6 * br) + (c - 6 * bc);
-}
-
-// Static description of packed cam-Hessian entry (r, c), r >= c, for the assembly pass of k_lin (the same for every
-// window; built once per context):  x = (index into the LDS vis Hessian + 1) | (index into the LDS IMU blocks + 1) << 16,
-// 0 meaning "no such source";  y = r | c << 8.  IMU blocks: 11 diagonal 15x15 lower triangles (120 each), then 10
-// sub-diagonal full blocks (225 each).
-inline void lin_asm_entry(int r, int c, int* out) {
-  int hv = 0, im = 0;
-  const int vr = cam2vis(r), vc = cam2vis(c);
-  if (vr >= 0 && vc >= 0) hv = hvi(vr, vc) + 1;
-  if (r < 165) {
-    const int fr = r / 15, ar = r - 15 * fr, fc = c / 15, bc = c - 15 * fc;
-    if (fc == fr) im = 120 * fr + ar * (ar + 1) / 2 + bc + 1;
-    else if (fc == fr - 1) im = 11 * 120 + 225 * (fr - 1) + 15 * ar + bc + 1;
-  }
-  out[0] = hv | im << 16;
-  out[1] = r | c << 8;
-}
 
 
 // ---------------------------------------------------------------------------------------
@@ -342,8 +320,8 @@ struct PriorRegs {
   int pmap = -1;
   double j0[LIN_PJ], hv[LIN_PJ], r0 = 0.0, g0 = 0.0;
 };
-// the static table entries of a thread's packed entries of Hcc (e = u T + tid): lin_asm_request -> lin_assemble
-constexpr int LIN_ASM_PER_THREAD = (NCP + LIN_THREADS - 1) / LIN_THREADS;
+// the static table entries of a thread's pattern entries of Hcc (the u T + tid -th of B.asm_tab): lin_asm_request -> lin_assemble
+constexpr int LIN_ASM_PER_THREAD = (NZ_N + LIN_THREADS - 1) / LIN_THREADS;
 
 // ---- the phases of lin_body, in the order it calls them ---------------------------------------------------------------
 // stage: zeroing, states and pre-integrations to LDS; the prior's requests
@@ -594,14 +572,14 @@ __device__ __forceinline__ void lin_imu_raw(const DevBatch& B, const int w, cons
     }
   }
 }
-// the static table entries of this thread's packed entries (e = u T + tid): one batch of loads, requested before the
-// whitening
+// the static table entries of this thread's pattern entries (the u T + tid -th: consecutive lanes, increasing addresses of
+// Hcc): one batch of loads, requested before the whitening
 __device__ __forceinline__ void lin_asm_request(const DevBatch& B, int2 (&asmd)[LIN_ASM_PER_THREAD]) {
   const int tid = threadIdx.x, T = LIN_THREADS;
 #pragma unroll
   for (int u = 0; u < LIN_ASM_PER_THREAD; ++u) {
-    const int e = u * T + tid;
-    asmd[u] = ((const int2*)B.asm_tab)[e < NCP ? e : 0];
+    const int i = u * T + tid;
+    asmd[u] = ((const int2*)B.asm_tab)[i < NZ_N ? i : 0];
   }
 }
 // Whitening J <- S J (S upper triangular 15 x 15, [J | r] 15 x 31) and the factor's J^T J on the FP64 matrix cores: one
@@ -731,7 +709,25 @@ __device__ __forceinline__ void lin_handover_in(const DevBatch& B, const int w, 
 }
 
 // ---- assemble the packed cam Hessian and gradient in HBM -----------------------------------
-// Hv, gv, imuH, imuJ | imur, prH, prg, invmap, asmd -> Hcc in one pass, the third pass for n > PRH_N, gc
+// one entry of Hcc from its table entry d (lin_asm_entry): visual block + IMU block + prior (J0^T J0 staged in LDS by the
+// prior phase), summed in registers in that order, stored once
+__device__ __forceinline__ void lin_asm_store(const int2 d, const double* Hv, const double* imuH, const double* prH, const int* invmap,
+                                                 const bool prior_lds, const bool ex_free, double* Hout) {
+  const int hv = d.x & 0xffff, im = d.x >> 16, r = d.y & 255, c = (d.y >> 8) & 255, e = d.y >> 16;
+  // branch-free: every source is read (clamped index) and selected, so that the LDS reads of many entries overlap
+  const double vh = Hv[hv ? hv - 1 : 0], vi = imuH[im ? im - 1 : 0];
+  const int ir = prior_lds ? invmap[r] : -1, ic = prior_lds ? invmap[c] : -1;
+  const bool hp = ir >= 0 && ic >= 0;
+  const int hi_ = ic > ir ? ic : ir, lo_ = ic > ir ? ir : ic;
+  const double vp = prH[hp ? hi_ * (hi_ + 1) / 2 + lo_ : 0];
+  double v = hv ? vh : 0.0;
+  v += im ? vi : 0.0;
+  v += hp ? vp : 0.0;
+  if (!ex_free && r >= 165) v = 0.0;
+  Hout[e] = v;
+}
+// Hv, gv, imuH, imuJ | imur, prH, prg, invmap, asmd -> Hcc in one pass over the pattern entries (a second over the complement
+// for a window of the general path), the third pass for n > PRH_N, gc
 __device__ __forceinline__ void lin_assemble(const DevBatch& B, const int w, const double* Hv, const double* gv, double* imuJ, const double* imur,
                                                 const double* prg, const double* prH, const int PRH_N, const int* invmap,
                                                 const int* imuact, const int n, const bool ex_free,
@@ -743,29 +739,36 @@ __device__ __forceinline__ void lin_assemble(const DevBatch& B, const int w, con
   // Every entry is stored ONCE, with its three sources summed in registers: adding to what an earlier pass had stored
   // is a global read-modify-write, i.e. a full round trip (~3 k cycles with all CUs in this phase) behind every store.
   // (1) the 3570 entries the IMU factors touch (11 diagonal 15x15 blocks, 10 sub-diagonal ones), each summing its one or
-  // two J^T J terms, go to LDS; (2) rows to waves, columns to lanes: visual block + IMU block + prior (J0^T J0 staged in LDS
-  // by the prior phase), coalesced stores, no index decoding beyond c / 15.  Priors larger than PRH_N (none in the
-  // reference's windows) take a third pass that adds their entries in HBM.
+  // two J^T J terms, go to LDS; (2) pass A, every window: the NZ_N entries the factors of a fast-path window can fill
+  // (ba_asm_pattern.h), in increasing packed index over the lanes -- coalesced stores with gaps only where a run of the
+  // pattern ends.  The NZ_C entries of the complement have no source on that path: they hold the zeros Hcc was allocated
+  // with (the upload fills them again behind a batch that had a window of the general path) and are neither computed nor
+  // stored.  (3) pass B, windows of the general path (path == 1, uniform over the work-group; 2 is set and cleared inside a
+  // step): the complement, where such a window's prior has terms.  Priors larger than PRH_N (none in the reference's
+  // windows) take a further pass that adds their entries in HBM, behind both.
   VPL_STAMP(B, w, 26);
   const bool prior_lds = n > 0 && n <= PRH_N;
   {
-    // flat over the packed triangle: fully coalesced stores; the table entries were requested before the IMU blocks
+    // the table entries were requested before the IMU blocks
 #pragma unroll
     for (int u = 0; u < LIN_ASM_PER_THREAD; ++u) {
-      const int e = u * T + tid;
-      if (e >= NCP) continue;
-      const int hv = asmd[u].x & 0xffff, im = asmd[u].x >> 16, r = asmd[u].y & 255, c = asmd[u].y >> 8;
-      // branch-free: every source is read (clamped index) and selected, so that the LDS reads of many entries overlap
-      const double vh = Hv[hv ? hv - 1 : 0], vi = imuH[im ? im - 1 : 0];
-      const int ir = prior_lds ? invmap[r] : -1, ic = prior_lds ? invmap[c] : -1;
-      const bool hp = ir >= 0 && ic >= 0;
-      const int hi_ = ic > ir ? ic : ir, lo_ = ic > ir ? ir : ic;
-      const double vp = prH[hp ? hi_ * (hi_ + 1) / 2 + lo_ : 0];
-      double v = hv ? vh : 0.0;
-      v += im ? vi : 0.0;
-      v += hp ? vp : 0.0;
-      if (!ex_free && r >= 165) v = 0.0;
-      Hout[e] = v;
+      if (u * T + tid >= NZ_N) continue;
+      lin_asm_store(asmd[u], Hv, imuH, prH, invmap, prior_lds, ex_free, Hout);
+    }
+  }
+  if (B.path[w] == 1) {
+    // (rare: the table entries are loaded here, four per thread at a time, with nothing to hide them under)
+    const int2* const ctab = (const int2*)B.asm_tab + NZ_N;
+    for (int base = 0; base < NZ_C; base += 4 * T) {
+      int2 d[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int i = base + u * T + tid;
+        d[u] = ctab[i < NZ_C ? i : 0];
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (base + u * T + tid < NZ_C) lin_asm_store(d[u], Hv, imuH, prH, invmap, prior_lds, ex_free, Hout);
     }
   }
   VPL_STAMP(B, w, 27);

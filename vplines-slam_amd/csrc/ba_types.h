@@ -123,8 +123,10 @@ struct DevBatch {
   int *pr_map;                                   // [W][171] prior-local column -> cam index
 
   // ---- linearisation (one buffer set; written by k_lin at the current x) ----
+  // Hcc: k_lin stores the NZ_N entries of the pattern below for every window and the others only for a window of the general
+  // path (path == 1); everywhere else those hold the zeros of the allocation (vpl_ctx::hcc_general)
   double *Hcc, *gc;                              // [W][NCP] [W][NC]
-  int *asm_tab;                                  // [NCP][2] static: sources of every packed cam-Hessian entry, see lin_asm_entry()
+  int *asm_tab;                                  // [NCP][2] static: sources of the packed cam-Hessian entries, see lin_asm_entry(): the NZ_N of the pattern, then the complement's
   double *Hpp, *gp, *Wp;                         // [W][maxP] [W][maxP] [W][maxP][WS]
   double *Hll, *gl, *Wl;                         // [W][maxL][16] [W][maxL][4] [W][maxL][4][WS]
   // W rows are stored compact: the 6 x 6 blocks of the frames start .. start + maxTrack - 1 of the track, then the 6

@@ -569,6 +569,11 @@ static int upload_body(vpl_ctx* c, int nW, const vpl_window* win, const vpl_ba_o
   // with a tenth of the point tracks long, 3.2 ms with every track long, against 1.5 - 1.65 ms of k_schur<5> either way
   if (!same_layout) c->schur_mostly_wide = schur_total_w > 0 && 20 * schur_wide_w > 7 * schur_total_w;
   if (c->force_general) std::fill(A.path.begin(), A.path.end(), 1);
+  // k_lin writes the entries of Hcc outside the fast path's pattern only for windows of the general path; a batch that had
+  // one may have left values there, in slots whose next windows count on zeros (ba_ctx.h).  On the stream, in front of the
+  // scatter and so of the first linearisation of the new batch.
+  if (c->hcc_general) HIPCHK(c, hipMemsetAsync(B.Hcc, 0, (size_t)c->maxW * NCP * sizeof(double), c->stream));
+  c->hcc_general = std::any_of(A.path.begin(), A.path.end(), [](int p) { return p != 0; });
   if (SG.overflow) return fail(c, VPL_E_CAPACITY, "internal: staging arena bound too small");
   stage_upload(SG, A, B, W, same_layout, dev_prior, odo);
   if (chained && (rc = hand_over_priors(c, ctab, prev_prS))) return rc;

@@ -168,23 +168,13 @@ static int ctx_init(vpl_ctx* c, int device, int max_windows, int max_points, int
   if (e != hipSuccess) return VPL_E_HIP;
   if (lin_smem_base(c->maxP, c->maxL) > LIN_LDS_BUDGET) return VPL_E_CAPACITY;
   B.prhN = lin_prh_n(c->maxP, c->maxL);
-  {   // static table of the assembly pass of k_lin
-    std::vector<int> tab(2 * NCP);
-    for (int r = 0, e2 = 0; r < NC; ++r)
-      for (int cc = 0; cc <= r; ++cc, ++e2) lin_asm_entry(r, cc, &tab[2 * e2]);
+  {   // non-zero pattern of the packed cam Hessian of a fast-path window, and the static tables of the assembly passes of
+      // k_lin over the pattern and over its complement: one predicate for the three (ba_asm_pattern.h)
+    std::vector<int> nz, tab;
+    asm_build_tables(nz, tab);
+    if ((int)nz.size() != NZ_N || (int)tab.size() != 2 * NCP) return VPL_E_HIP;
     if (hipMemcpy(B.asm_tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return VPL_E_HIP;
-  }
-  {   // non-zero pattern of the packed cam Hessian of a fast-path window (ba_types.h)
-    std::vector<int> nz;
-    for (int r = 0; r < NC; ++r)
-      for (int cc = 0; cc <= r; ++cc) {
-        const bool vis = cam2vis(r) >= 0 && cam2vis(cc) >= 0;
-        const int fr = r < 165 ? r / 15 : -1, fc = cc < 165 ? cc / 15 : -1;
-        const bool band = fr >= 0 && fc >= 0 && (fr == fc || fr == fc + 1);
-        const bool sb0 = cc >= 6 && cc < 15 && cam2vis(r) >= 0;
-        if (vis || band || sb0) nz.push_back(tri(r, cc) | r << 14 | cc << 22);
-      }
-    if ((int)nz.size() != NZ_N || hipMemcpy(B.nz_tab, nz.data(), nz.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return VPL_E_HIP;
+    if (hipMemcpy(B.nz_tab, nz.data(), nz.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return VPL_E_HIP;
   }
   // the attribute is per kernel, not per context: never lower what a larger context of this process has asked for
   static size_t lin_max = 0, solve_max = 0, schur_max = 0, back_max = 0, step_max = 0;
