@@ -399,6 +399,92 @@ int vpl_relpose_debug_plan(unsigned long long seed, int i, int n_corres, int* sa
 int vpl_init_visual_batch(vpl_ctx* ctx, int n, const vpl_sfm_input* in, const unsigned long long* seeds, vpl_relpose_result* rel,
                           vpl_sfm_result* out, double* points_chain, double* points_ba, int* tracked_id, double* tracked_xyz);
 
+/* ---- feature selector  (replaces FeatureSelector::select, feature_selector.cpp:71-198, with HorizonGenerator::imu,
+ *      utility/selector/horizon_generator.cpp:24-68; use_feature_selector: 1, called at estimator_node.cpp:335-349) for n
+ *      sequences in one call: expected-information greedy selection of the new features of an image -------------------------- *
+ * Per sequence:
+ *   1. the horizon: states k and k + 1 as given, k + 2 .. k + 4 by constant-a, constant-w propagation over n_imu steps of
+ *      delta_imu, gravity (0, 0, -9.80665) -- or the caller's own five poses (which also covers the reference's ground-truth mode);
+ *   2. Omega_kkH (calcInfoFromRobotMotion, addOmegaPrior), 45 x 45 over five states of position, velocity, accelerometer bias;
+ *   3. every feature's depth guess: the depth of its nearest cloud point in (x, y), the lowest index on an exact tie, 1.0 when
+ *      the cloud is empty (initKDTree / findNNDepth; the cloud -- x, y, depth in camera k + 1 -- is the caller's here);
+ *   4. every feature's Delta (calcInfoFromFeatures): projection into frames k + 2 .. k + 4 by PinholeCamera::spaceToPlane with
+ *      the radtan distortion and no sign test on the depth, inFOV with std::round, q_IC applied twice in Bh as the reference
+ *      writes it; a feature no future frame sees has no matrix: as a new feature it is never a candidate (n_invisible), as a
+ *      used feature it adds nothing;
+ *   5. kappa greedy rounds (selectInformativeFeatures): Omega = Omega_kkH + sum of the used features' Delta (no prob on them);
+ *      per round and candidate ub = sum log diag(Omega + OmegaS + p Delta) and f = logdet of the same by Cholesky; candidates
+ *      with equal ub collapse to the one with the highest id (the reference's std::map; the other is eligible again once that one
+ *      is taken); the largest f wins if it is > -1.0 (strictly), ties go to the larger ub; OmegaS += p Delta.  Lazy evaluation is
+ *      not reproduced: since ub >= f it selects what evaluating everything selects.
+ * The matrices are not factored at 45 x 45 per candidate: Delta, the used sum and OmegaS live in the 12 position dimensions of
+ * states 1 .. 4; with those ordered last the 33 x 33 block and its coupling are fixed for the call, are factored once per
+ * sequence, and every evaluation is logdet A + a 12 x 12 Cholesky of the Schur complement (csrc/sel_kernels.h).
+ * Deviations: a candidate whose Cholesky meets a pivot that is not finite or not > 0 is not eligible in that round and is counted
+ * in n_ineligible (Eigen's LLT goes on with an unfinished factor; the reference logs "logdet returned nan!" where it notices);
+ * a round that selects nothing ends the loop (no later round could select anything either).  Only the PINHOLE camera model is
+ * described by vpl_sel_params.  Three launches per call whatever kappa is; FP64, every sum in a fixed order: a sequence's result
+ * has the same bits wherever it sits in the batch. */
+#define VPL_SEL_MAX_FEATURES 1024      /* longest list of new features, of used features and of cloud points */
+typedef struct vpl_sel_params {
+  double acc_var, acc_bias_var;      /* the reference passes ACC_N, ACC_W */
+  int max_features, init_thresh;     /* of the id book (vpl_sel_debug_book): kappa = max(0, max_features - |subset|) */
+  int width, height;                 /* PINHOLE camera with radtan distortion */
+  double fx, fy, cx, cy, k1, k2, p1, p2;
+  double q_ic[4];                    /* w, x, y, z */
+  double t_ic[3];
+} vpl_sel_params;
+typedef struct vpl_sel_input {
+  double P0[3], Q0[4], V0[3], Ba0[3];   /* state k (slot 10 of the window); quaternions w, x, y, z */
+  double P1[3], Q1[4], V1[3], Ba1[3];   /* state k + 1, the IMU-propagated new frame (Ba1 is carried, the reference does not read it) */
+  double acc[3], gyr[3];                /* the last accelerometer sample and the unbiased gyroscope sample */
+  double delta_imu;                     /* > 0 */
+  int n_imu;                            /* >= 1 */
+  int kappa;                            /* >= 0: the number of greedy rounds */
+  const double* horizon;                /* NULL, or [5][7] = position, quaternion of states k .. k + 4 (then step 1 is skipped) */
+  int n_new;
+  const int* new_id;                    /* [n_new], distinct */
+  const double *new_x, *new_y, *new_prob;   /* [n_new]: normalised image coordinates and the tracking probability */
+  int n_used;
+  const double *used_x, *used_y;        /* [n_used] */
+  int n_cloud;
+  const double* cloud;                  /* [n_cloud][3] = x, y (normalised, camera k + 1), depth */
+} vpl_sel_input;
+typedef struct vpl_sel_result {
+  int n_selected;                       /* <= min(kappa, n_new) */
+  int n_invisible;                      /* new features no future frame sees */
+  int n_ineligible;                     /* evaluations (candidate, round) that met a bad pivot */
+  int n_candidates;                     /* n_new - n_invisible */
+} vpl_sel_result;
+/* in [n], out [n]; selected_id / round_f [n][VPL_SEL_MAX_FEATURES]: the ids in selection order and the f each was selected with,
+ * n_selected entries, zero behind.  Host in, host out: one host-to-device copy, three kernels, one copy back and one
+ * synchronisation.  Refused before anything is written -- VPL_E_INVALID: null arrays, n_imu < 1, delta_imu not > 0 (the
+ * reference produces 0 on its first image through a static, and its result is infinite), a negative count, width or height < 1, an id twice in new_id;
+ * VPL_E_CAPACITY: a list longer than VPL_SEL_MAX_FEATURES, n > max_windows. */
+int vpl_select_features_batch(vpl_ctx* ctx, int n, const vpl_sel_params* params, const vpl_sel_input* in, vpl_sel_result* out,
+                              int* selected_id, double* round_f);
+/* One sequence, one round's values after a forced prefix of selections: prefix_id [n_prefix] are taken first, in that order
+ * (an id that is not a candidate is passed over).  f / ub [n_new]: the round's values of every new feature, NaN for one that is
+ * not a candidate (invisible, in the prefix) and f = NaN for one that is not eligible.  omega45x45 [45 * 45]: Omega_kkH, row-major,
+ * natural order.  delta12 [(n_new + n_used)][78]: every feature's Delta over the 12 position dimensions of states 1 .. 4 (rows and
+ * columns 9 i .. 9 i + 2, i = 1 .. 4), packed lower triangle row after row; zeros for an invisible feature.  Any output may be
+ * NULL.  kappa is not read.  Refusals as above. */
+int vpl_select_debug_values(vpl_ctx* ctx, const vpl_sel_params* params, const vpl_sel_input* in, const int* prefix_id, int n_prefix,
+                            double* f, double* ub, double* omega45x45, double* delta12);
+/* kernel launches and bytes copied each way by the last vpl_select_features_batch / vpl_select_debug_values of the context */
+int vpl_select_stats(vpl_ctx* ctx, long long* launches, long long* h2d_bytes, long long* d2h_bytes);
+/* Host only, no device call: the id book of select() (lastFeatureId_, trackedFeatures_, firstImage_, init_thresh, kappa) replayed
+ * over a script of n_images images (csrc/sel_book.h).  Image s: its feature ids n_ids[s] of ids (one image after the other),
+ * initialized[s] (solver_flag == NON_LINEAR), and n_offer[s] of offer standing in for the greedy selection: the first kappa
+ * offered ids that are new in this image are "selected".  Out, per image: n_new[s], kappa[s], n_selected[s] and
+ * selected[s * max_ids ..], n_out[s] and out_ids[s * max_ids ..] (ascending: what is handed to the back end), n_tracked[s] and
+ * last_id[s] after the image; tracked [max_tracked]: the tracked list after the last image, in its order (it only grows).
+ * VPL_E_INVALID: null arrays, negative counts; VPL_E_CAPACITY: an image with more than max_ids distinct ids, a tracked list longer
+ * than max_tracked. */
+int vpl_sel_debug_book(int max_features, int init_thresh, int n_images, const int* n_ids, const int* ids, const unsigned char* initialized,
+                       const int* n_offer, const int* offer, int max_ids, int* n_new, int* kappa, int* n_selected, int* selected,
+                       int* n_out, int* out_ids, int* n_tracked, int* last_id, int max_tracked, int* tracked);
+
 /* ---- single-factor batch evaluators ------------------------------------- *
  * Each replaces one CostFunction::Evaluate (signature
  *   bool Evaluate(double const* const* parameters, double* residuals, double** jacobians) const )
@@ -783,6 +869,46 @@ int vpl_odo_get_tracks(vpl_odo* odo, int seq, int* n_points, int* point_id, int*
  * (VPL_ODO_D2H_PAD_BYTES of alignment padding). */
 #define VPL_ODO_D2H_PAD_BYTES 0
 int vpl_odo_stats(vpl_odo* odo, long long* h2d_payload_bytes, long long* h2d_table_bytes, long long* d2h_bytes);
+
+/* ---- the feature selector of a session ----------------------------------- *
+ * FeatureSelector::select (see "feature selector" above) for the next image of every sequence of a session, with what the
+ * reference reads from the estimator taken from the session instead of the caller:
+ *   - state k is slot 10 of the store as it stands (vpl_odo_get_states);
+ *   - the cloud of initKDTree is gathered on the device (k_sel_cloud) from the resident point tracks with nobs >= 2,
+ *     start < WINDOW_SIZE - 2, start <= 0.75 * WINDOW_SIZE that have taken part in a vpl_odo_solve (solve_flag == 1; a track whose
+ *     depth came out <= 0 is erased by the advance that follows the solve): first observation / inv_depth, through the store's
+ *     extrinsic and the pose of its start frame into the world, through state k + 1 and q_ic / t_ic of the params into the camera,
+ *     normalised; depth = 1 / inv_depth.  A window that has not been solved since vpl_odo_set_window / vpl_odo_init has an empty
+ *     cloud: every depth guess is 1.0;
+ *   - the id book (lastFeatureId_, trackedFeatures_, firstImage_) is kept per sequence by the session, from its creation on;
+ *     `initialized` is true once the sequence holds a window.  For a sequence without one only the book runs (the first image
+ *     passes whole, then init_thresh applies) and no state is read.
+ * To be called where an image may enter: not between vpl_odo_solve and vpl_odo_advance (VPL_E_INVALID).  The session's windows,
+ * tracks, traffic counters (vpl_odo_stats) and launches are not touched; a session that never calls it is what it was.
+ * One upload, four launches (k_sel_cloud, then the three of vpl_select_features_batch) and one read-back for the sequences that
+ * hold a window; vpl_select_stats counts them.  Refusals, before any book moves: those of vpl_select_features_batch, an image of
+ * more than VPL_SEL_MAX_FEATURES features or a cloud of more than VPL_SEL_MAX_FEATURES tracks (VPL_E_CAPACITY). */
+typedef struct vpl_odo_sel_frame {
+  double P1[3], Q1[4], V1[3], Ba1[3];   /* state k + 1: setNextStateFromImuPropagation (quaternion w, x, y, z) */
+  double acc[3], gyr[3];                /* the last accelerometer sample, the unbiased gyroscope sample */
+  double delta_imu;                     /* > 0 */
+  int n_imu;                            /* >= 1 */
+  const double* horizon;                /* NULL or [5][7], as in vpl_sel_input */
+  int n_features;                       /* the image: every feature the front end reports */
+  const int* id;                        /* [n_features]; an id given twice counts once (its first entry) */
+  const double *x, *y, *prob;           /* [n_features] */
+} vpl_odo_sel_frame;
+typedef struct vpl_odo_sel_result {
+  vpl_sel_result sel;                   /* zeros for a sequence without a window */
+  int initialized;
+  int n_new, n_used, kappa, n_cloud;    /* what the book and the filter handed to the selection */
+  int n_out;                            /* ids in out_ids: what goes to the back end */
+} vpl_odo_sel_result;
+/* frames [n_seq], out [n_seq]; selected_id / round_f [n_seq][VPL_SEL_MAX_FEATURES] as in vpl_select_features_batch; out_ids
+ * [n_seq][VPL_SEL_MAX_FEATURES]: the image handed to vpl_odo_advance* / vpl_odo_keyframe* -- the tracked ids that are present and
+ * the selected ones, ascending. */
+int vpl_odo_select(vpl_odo* odo, const vpl_sel_params* params, const vpl_odo_sel_frame* frames, vpl_odo_sel_result* out,
+                   int* selected_id, double* round_f, int* out_ids);
 /* wall clock of the stages of the last keyframe in ms: triangulations | onlyLineOpt | solve | slide + new frame */
 int vpl_odo_debug_ms(vpl_odo* odo, double* ms4);
 

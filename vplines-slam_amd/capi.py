@@ -258,6 +258,140 @@ def relpose_debug_plan(seed, i, N):
     return dict(samples=samples, niters_after=table) if rc == 0 else rc
 
 
+SEL_MAX_FEATURES = 1024   # VPL_SEL_MAX_FEATURES
+
+
+class SelectParams(C.Structure):   # vpl_sel_params
+    """acc_var / acc_bias_var (the reference passes ACC_N, ACC_W), the id book's max_features / init_thresh, the PINHOLE camera with
+    its radtan distortion, the extrinsic q_ic (w, x, y, z) / t_ic"""
+    _fields_ = [("acc_var", C.c_double), ("acc_bias_var", C.c_double), ("max_features", C.c_int), ("init_thresh", C.c_int),
+                ("width", C.c_int), ("height", C.c_int), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("k1", C.c_double), ("k2", C.c_double), ("p1", C.c_double), ("p2", C.c_double), ("q_ic", C.c_double * 4), ("t_ic", C.c_double * 3)]
+
+    @classmethod
+    def of(cls, p):
+        """from anything with the members by name (q_ic / t_ic as sequences)"""
+        o = cls()
+        for f, t in cls._fields_:
+            v = getattr(p, f)
+            if f in ("q_ic", "t_ic"):
+                for k, x in enumerate(v):
+                    getattr(o, f)[k] = float(x)
+            else:
+                setattr(o, f, int(v) if t is C.c_int else float(v))
+        return o
+
+
+class CSelectInput(C.Structure):   # vpl_sel_input
+    _fields_ = [("P0", C.c_double * 3), ("Q0", C.c_double * 4), ("V0", C.c_double * 3), ("Ba0", C.c_double * 3),
+                ("P1", C.c_double * 3), ("Q1", C.c_double * 4), ("V1", C.c_double * 3), ("Ba1", C.c_double * 3),
+                ("acc", C.c_double * 3), ("gyr", C.c_double * 3), ("delta_imu", C.c_double), ("n_imu", C.c_int), ("kappa", C.c_int),
+                ("horizon", _dp), ("n_new", C.c_int), ("new_id", _ip), ("new_x", _dp), ("new_y", _dp), ("new_prob", _dp),
+                ("n_used", C.c_int), ("used_x", _dp), ("used_y", _dp), ("n_cloud", C.c_int), ("cloud", _dp)]
+
+
+class SelectResult(C.Structure):   # vpl_sel_result
+    _fields_ = [("n_selected", C.c_int), ("n_invisible", C.c_int), ("n_ineligible", C.c_int), ("n_candidates", C.c_int)]
+
+
+class CSelectFrame(C.Structure):   # vpl_odo_sel_frame
+    _fields_ = [("P1", C.c_double * 3), ("Q1", C.c_double * 4), ("V1", C.c_double * 3), ("Ba1", C.c_double * 3), ("acc", C.c_double * 3),
+                ("gyr", C.c_double * 3), ("delta_imu", C.c_double), ("n_imu", C.c_int), ("horizon", _dp), ("n_features", C.c_int), ("id", _ip),
+                ("x", _dp), ("y", _dp), ("prob", _dp)]
+
+
+class OdoSelectResult(C.Structure):   # vpl_odo_sel_result
+    _fields_ = [("sel", SelectResult), ("initialized", C.c_int), ("n_new", C.c_int), ("n_used", C.c_int), ("kappa", C.c_int),
+                ("n_cloud", C.c_int), ("n_out", C.c_int)]
+
+
+class SelectFrame:
+    """numpy-backed owner of one vpl_odo_sel_frame: state k + 1 (P1, Q1 (w, x, y, z), V1, Ba1), acc, unbiased gyr, n_imu, delta_imu,
+    horizon (None or [5, 7]) and the image -- id, x, y, prob of every feature the front end reports"""
+    _VEC = ("P1", "Q1", "V1", "Ba1", "acc", "gyr")
+
+    def __init__(self, P1, Q1, V1, Ba1, acc, gyr, n_imu, delta_imu, id, x, y, prob, horizon=None):
+        for k, a in zip(self._VEC, (P1, Q1, V1, Ba1, acc, gyr)):
+            setattr(self, k, _arr(a, np.float64).copy())
+        self.n_imu, self.delta_imu = int(n_imu), float(delta_imu)
+        self.id = _arr(id, np.int32).copy()
+        self.x, self.y, self.prob = (_arr(a, np.float64).copy() for a in (x, y, prob))
+        self.horizon = None if horizon is None else _arr(horizon, np.float64).reshape(5, 7).copy()
+
+    def to_c(self, cf):
+        for k in self._VEC:
+            for j, v in enumerate(getattr(self, k)):
+                getattr(cf, k)[j] = v
+        cf.delta_imu, cf.n_imu, cf.n_features = self.delta_imu, self.n_imu, len(self.id)
+        cf.horizon = _p(self.horizon) if self.horizon is not None else None
+        cf.id = self.id.ctypes.data_as(_ip)
+        cf.x, cf.y, cf.prob = _p(self.x), _p(self.y), _p(self.prob)
+        return cf
+
+
+class SelectInput:
+    """numpy-backed owner of one vpl_sel_input: states k and k + 1 (P, Q (w, x, y, z), V, Ba), acc, unbiased gyr, n_imu, delta_imu,
+    horizon (None or [5, 7]), the new features (id, x, y, prob), the used features (x, y), the cloud [m, 3] = x, y, depth, kappa"""
+    _VEC = ("P0", "Q0", "V0", "Ba0", "P1", "Q1", "V1", "Ba1", "acc", "gyr")
+
+    def __init__(self, P0, Q0, V0, Ba0, P1, Q1, V1, Ba1, acc, gyr, n_imu, delta_imu, new_id, new_x, new_y, new_prob, used_x=(), used_y=(),
+                 cloud=(), kappa=0, horizon=None):
+        for k, a in zip(self._VEC, (P0, Q0, V0, Ba0, P1, Q1, V1, Ba1, acc, gyr)):
+            setattr(self, k, _arr(a, np.float64).copy())
+        self.n_imu, self.delta_imu, self.kappa = int(n_imu), float(delta_imu), int(kappa)
+        self.new_id = _arr(new_id, np.int32).copy()
+        self.new_x, self.new_y, self.new_prob, self.used_x, self.used_y = (_arr(a, np.float64).copy() for a in (new_x, new_y, new_prob, used_x, used_y))
+        self.cloud = _arr(cloud, np.float64).reshape(-1, 3).copy()
+        self.horizon = None if horizon is None else _arr(horizon, np.float64).reshape(5, 7).copy()
+
+    @classmethod
+    def of(cls, s, **over):
+        """from anything with the members by name"""
+        kw = {k: getattr(s, k) for k in cls._VEC + ("n_imu", "delta_imu", "new_id", "new_x", "new_y", "new_prob", "used_x", "used_y", "cloud", "kappa", "horizon")}
+        kw.update(over)
+        return cls(**kw)
+
+    def to_c(self, ci=None):
+        ci = ci if ci is not None else CSelectInput()
+        for k in self._VEC:
+            for j, x in enumerate(getattr(self, k)):
+                getattr(ci, k)[j] = x
+        ci.delta_imu, ci.n_imu, ci.kappa = self.delta_imu, self.n_imu, self.kappa
+        ci.horizon = _p(self.horizon) if self.horizon is not None else None
+        ci.n_new, ci.n_used, ci.n_cloud = len(self.new_id), len(self.used_x), len(self.cloud)
+        ci.new_id = self.new_id.ctypes.data_as(_ip)
+        for k in ("new_x", "new_y", "new_prob", "used_x", "used_y", "cloud"):
+            setattr(ci, k, _p(getattr(self, k)))
+        return ci
+
+
+def select_debug_book(max_features, init_thresh, images, initialized, offers):
+    """vpl_sel_debug_book (host only): the id book of FeatureSelector::select replayed over a script.  images: a list of id lists;
+    initialized: a flag per image; offers: per image the ids that stand in for the greedy selection (the first kappa of them that
+    are new are selected).  -> dict n_new, kappa, last_id, n_tracked [n], selected / out (lists of id arrays), tracked (the
+    tracked list after the last image); the VPL_E_* code instead when the call is refused"""
+    lib = load_hip_library()
+    n = len(images)
+    ip = lambda a: a.ctypes.data_as(_ip)
+    n_ids = np.array([len(a) for a in images], dtype=np.int32)
+    n_off = np.array([len(a) for a in offers], dtype=np.int32)
+    cat = lambda ls: np.concatenate([np.asarray(a, dtype=np.int32).reshape(-1) for a in ls] + [np.zeros(1, np.int32)])
+    ids, off = cat(images), cat(offers)
+    init = np.array([1 if f else 0 for f in initialized], dtype=np.uint8)
+    max_ids = max([1] + [len(a) for a in images])
+    max_tracked = int(n_ids.sum()) + 1
+    n_new, kappa, n_sel, n_out, n_tr, last = (np.zeros(n + 1, dtype=np.int32) for _ in range(6))
+    sel, out = np.zeros((n + 1, max_ids), dtype=np.int32), np.zeros((n + 1, max_ids), dtype=np.int32)
+    tracked = np.zeros(max_tracked, dtype=np.int32)
+    rc = lib.vpl_sel_debug_book(int(max_features), int(init_thresh), n, ip(n_ids), ip(ids), init.ctypes.data_as(C.POINTER(C.c_ubyte)), ip(n_off),
+                                ip(off), max_ids, ip(n_new), ip(kappa), ip(n_sel), ip(sel), ip(n_out), ip(out), ip(n_tr), ip(last), max_tracked,
+                                ip(tracked))
+    if rc != 0:
+        return rc
+    return dict(n_new=n_new[:n], kappa=kappa[:n], last_id=last[:n], n_tracked=n_tr[:n], selected=[sel[i, :n_sel[i]].copy() for i in range(n)],
+                out=[out[i, :n_out[i]].copy() for i in range(n)], tracked=tracked[:n_tr[n - 1]].copy() if n else tracked[:0])
+
+
 class CWindow(C.Structure):
     _fields_ = [("pose", (C.c_double * 7) * NF), ("speed_bias", (C.c_double * 9) * NF), ("ex_pose", C.c_double * 7),
                 ("n_points", C.c_int), ("point_start", _ip), ("point_nobs", _ip), ("point_obs", _dp),
@@ -460,6 +594,10 @@ def load_hip_library():
     lib.vpl_relpose_debug_plan.argtypes = [C.c_ulonglong, C.c_int, C.c_int, _ip, _ip]
     lib.vpl_init_visual_batch.argtypes = [vp, C.c_int, C.POINTER(CSfmInput), C.POINTER(C.c_ulonglong), C.POINTER(RelPoseResult),
                                           C.POINTER(SfmResult), _dp, _dp, _ip, _dp]
+    lib.vpl_select_features_batch.argtypes = [vp, C.c_int, C.POINTER(SelectParams), C.POINTER(CSelectInput), C.POINTER(SelectResult), _ip, _dp]
+    lib.vpl_select_debug_values.argtypes = [vp, C.POINTER(SelectParams), C.POINTER(CSelectInput), _ip, C.c_int, _dp, _dp, _dp, _dp]
+    lib.vpl_select_stats.argtypes = [vp] + [C.POINTER(C.c_longlong)] * 3
+    lib.vpl_sel_debug_book.argtypes = [C.c_int, C.c_int, C.c_int, _ip, _ip, _bp, _ip, _ip, C.c_int] + [_ip] * 8 + [C.c_int, _ip]
     for name in ("vpl_projection_factor_evaluate", "vpl_line_factor_evaluate", "vpl_vp_factor_evaluate"):
         getattr(lib, name).argtypes = [vp, C.c_int, _dp, _dp, C.c_double, _dp, _dp]
     lib.vpl_imu_factor_evaluate.argtypes = [vp, C.c_int, _dp, C.POINTER(Preintegration), C.c_double, _dp, _dp]
@@ -508,6 +646,7 @@ def load_hip_library():
     _llp = C.POINTER(C.c_longlong)
     lib.vpl_odo_stats.argtypes = [vp, _llp, _llp, _llp]
     lib.vpl_odo_debug_ms.argtypes = [vp, _dp]
+    lib.vpl_odo_select.argtypes = [vp, C.POINTER(SelectParams), C.POINTER(CSelectFrame), C.POINTER(OdoSelectResult), _ip, _dp, _ip]
     lib.vpl_odo_debug_tracks.argtypes = [C.c_int, C.c_int, _ip, _ip, _ip, C.POINTER(C.c_ubyte), _ip, _ip, _ip, _ip, _ip, _ip]
     lib.vpl_odo_default_keyframe_rule.argtypes = [C.POINTER(OdoKeyframeRule)]
     lib.vpl_odo_default_keyframe_rule.restype = None
@@ -834,6 +973,59 @@ class Context:
             return rc
         self._check(rc, "vpl_init_relative_pose_batch")
         return res, m0, m1, hyp
+
+    @staticmethod
+    def _select_c(params, inputs):
+        par = params if isinstance(params, SelectParams) else SelectParams.of(params)
+        ci = (CSelectInput * len(inputs))()
+        keep = []
+        for i, q in enumerate(inputs):
+            if isinstance(q, CSelectInput):
+                C.memmove(C.byref(ci[i]), C.byref(q), C.sizeof(CSelectInput))   # as the caller filled it (tests of the refusals)
+            else:
+                q = q if isinstance(q, SelectInput) else SelectInput.of(q)
+                keep.append(q)
+                q.to_c(ci[i])
+        return par, ci, keep
+
+    def select_features(self, params, inputs, check=True):
+        """vpl_select_features_batch over a list of SelectInput (or of objects with its members): FeatureSelector::select's horizon,
+        motion information, per-feature information and greedy selection for every sequence in one call.  -> list [n] of dict
+        ids (in selection order), f (of every selection), n_invisible, n_ineligible, n_candidates.  check=False: a refusal comes
+        back as its VPL_E_* code instead of an exception."""
+        self._settle()
+        n = len(inputs)
+        par, ci, keep = self._select_c(params, inputs)
+        res = (SelectResult * max(n, 1))()
+        ids = np.zeros((max(n, 1), SEL_MAX_FEATURES), dtype=np.int32)
+        f = np.zeros((max(n, 1), SEL_MAX_FEATURES))
+        rc = self.lib.vpl_select_features_batch(self.h, n, C.byref(par), ci, res, ids.ctypes.data_as(_ip), _p(f))
+        if rc != 0 and not check:
+            return rc
+        self._check(rc, "vpl_select_features_batch")
+        return [dict(ids=ids[i, :res[i].n_selected].copy(), f=f[i, :res[i].n_selected].copy(), n_invisible=res[i].n_invisible,
+                     n_ineligible=res[i].n_ineligible, n_candidates=res[i].n_candidates) for i in range(n)]
+
+    def select_debug_values(self, params, inp, prefix=(), check=True):
+        """vpl_select_debug_values: one round's f and ub of every new feature of one sequence after the ids of `prefix` have been
+        taken (NaN for what is not a candidate), Omega_kkH [45, 45] and the Delta12 [n_new + n_used, 78] of every feature"""
+        self._settle()
+        par, ci, keep = self._select_c(params, [inp])
+        n_new, nf = ci[0].n_new, ci[0].n_new + ci[0].n_used
+        pre = _arr(list(prefix), np.int32)
+        f, ub = np.zeros(max(n_new, 1)), np.zeros(max(n_new, 1))
+        om, d12 = np.zeros((45, 45)), np.zeros((max(nf, 1), 78))
+        rc = self.lib.vpl_select_debug_values(self.h, C.byref(par), ci, pre.ctypes.data_as(_ip), len(pre), _p(f), _p(ub), _p(om), _p(d12))
+        if rc != 0 and not check:
+            return rc
+        self._check(rc, "vpl_select_debug_values")
+        return dict(f=f[:n_new], ub=ub[:n_new], omega=om, delta12=d12[:nf])
+
+    def select_stats(self):
+        """vpl_select_stats: (kernel launches, bytes up, bytes down) of the last selector call"""
+        a, b, d = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+        self._check(self.lib.vpl_select_stats(self.h, C.byref(a), C.byref(b), C.byref(d)), "vpl_select_stats")
+        return int(a.value), int(b.value), int(d.value)
 
     def init_visual(self, inputs, seeds=None, check=True):
         """The vision-only start in one go: init_relative_pose over the track tables of a list of SfmInput (their l / relative_R /
@@ -1319,6 +1511,30 @@ class Session:
         a, b = n[0], n[1]
         return dict(point_id=pi[:a], point_start=ps[:a], point_nobs=pn[:a], inv_depth=invd[:a], line_id=li[:b],
                     line_start=ls[:b], line_nobs=ln[:b], line_triangulated=lt[:b], line_plk=plk[:b])
+
+    def select(self, params, frames, check=True):
+        """vpl_odo_select: FeatureSelector::select for the next image of every sequence (one SelectFrame each) -- state k, the
+        cloud and the id book are the session's.  Not between solve and advance.  -> list [n_seq] of dict ids (selection order),
+        f, out (the ids to hand to advance / keyframe, ascending), initialized, n_new, n_used, kappa, n_cloud, n_invisible,
+        n_ineligible, n_candidates.  check=False: a refusal comes back as its VPL_E_* code."""
+        n = self.n_seq
+        assert len(frames) == n
+        par = params if isinstance(params, SelectParams) else SelectParams.of(params)
+        cf = (CSelectFrame * n)()
+        for i, f in enumerate(frames):
+            f.to_c(cf[i])
+        res = (OdoSelectResult * n)()
+        ids, out = np.zeros((n, SEL_MAX_FEATURES), dtype=np.int32), np.zeros((n, SEL_MAX_FEATURES), dtype=np.int32)
+        fs = np.zeros((n, SEL_MAX_FEATURES))
+        self.ctx._settle()
+        rc = self.lib.vpl_odo_select(self.h, C.byref(par), cf, res, ids.ctypes.data_as(_ip), _p(fs), out.ctypes.data_as(_ip))
+        if rc != 0 and not check:
+            return rc
+        self.ctx._check(rc, "vpl_odo_select")
+        return [dict(ids=ids[i, :res[i].sel.n_selected].copy(), f=fs[i, :res[i].sel.n_selected].copy(), out=out[i, :res[i].n_out].copy(),
+                     initialized=bool(res[i].initialized), n_new=res[i].n_new, n_used=res[i].n_used, kappa=res[i].kappa,
+                     n_cloud=res[i].n_cloud, n_invisible=res[i].sel.n_invisible, n_ineligible=res[i].sel.n_ineligible,
+                     n_candidates=res[i].sel.n_candidates) for i in range(n)]
 
     def stats(self):
         """(h2d_payload_bytes, h2d_table_bytes, d2h_bytes) of the last keyframe"""

@@ -19,6 +19,7 @@ struct vpl_ctx {
   std::vector<DevAlloc> allocs;      // host_common.h: the context's own arrays (owner null), then those of the session that borrows it
   bool guards = false;
   std::string err;
+  long long sel_stats[3] = {0, 0, 0};   // vpl_select_stats: launches, bytes up, bytes down of the last selector call
   // ---- capacities
   int maxW = 0, maxP = 0, maxPO = 0, maxL = 0, maxLO = 0;
   // ---- the uploaded batch's host tables

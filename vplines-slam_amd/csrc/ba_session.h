@@ -19,6 +19,7 @@ struct OdoSeq {
   bool dec_set = false;
   double last_pose[7] = {};        // Estimator::last_P (failureDetection): pose[9] of vpl_odo_set_window, then pose[10] of every solve
   int failure = 0;                 // VPL_FAIL_* of the last solve, default limits
+  SelBook sel_book;                // vpl_odo_select: the selector's id book, from the session's creation on
 };
 
 // What vpl_odo_solve's last copy left in h_out behind the results, for vpl_odo_advance to read: offsets in ints of the three
@@ -524,6 +525,7 @@ int vpl_odo_solve(vpl_odo* o, const int* flags, vpl_odo_result* out) {
     if (o->lstart[w].empty()) std::memset(&r.line_report, 0, sizeof(r.line_report));
     r.line_report.n_lines_removed = lrem1[w];
     r.n_points_solved = c->h_nP[w];
+    for (int i : o->psrc[w]) q.P.t[i].solved = 1;   // setDepth: solve_flag (vpl_odo_select's cloud)
     r.n_lines_solved = c->h_nL[w];
     r.n_point_tracks = (int)q.P.t.size();
     r.n_line_tracks = (int)q.L.t.size();
@@ -1065,6 +1067,107 @@ int vpl_odo_get_tracks(vpl_odo* o, int seq, int* n_points, int* point_id, int* p
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (inv_depth && nP) HIPCHK(c, hipMemcpy(inv_depth, S.invd + (size_t)seq * S.maxPT, nP * 8, hipMemcpyDeviceToHost));
   if (line_plk && nL) HIPCHK(c, hipMemcpy(line_plk, S.plk + (size_t)seq * S.maxLT * 6, nL * 6 * 8, hipMemcpyDeviceToHost));
+  return VPL_OK;
+}
+
+// FeatureSelector::select for the next image of every sequence: the book on the host, state k and the cloud from the store
+int vpl_odo_select(vpl_odo* o, const vpl_sel_params* par, const vpl_odo_sel_frame* frames, vpl_odo_sel_result* out, int* selected_id,
+                   double* round_f, int* out_ids) {
+  if (!o || !par || !frames || !out || !selected_id || !round_f || !out_ids) return VPL_E_INVALID;
+  vpl_ctx* c = o->c;
+  const int nS = o->nS;
+  if (o->solved) return fail(c, VPL_E_INVALID, "odo_select: the window has been solved and not advanced (vpl_odo_advance)");
+  for (int w = 0; w < nS; ++w) {
+    const vpl_odo_sel_frame& f = frames[w];
+    if (f.n_features < 0 || (f.n_features && (!f.id || !f.x || !f.y || !f.prob))) return fail(c, VPL_E_INVALID, "odo_select: null array or negative count");
+    if (f.n_features > VPL_SEL_MAX_FEATURES) return fail(c, VPL_E_CAPACITY, "odo_select: an image of more than VPL_SEL_MAX_FEATURES features");
+  }
+  // the books move on copies: a refusal below leaves every sequence as it was
+  struct Job {
+    SelBook book;
+    SelImage im;
+    std::vector<int> new_id;
+    std::vector<double> nx, ny, np, ux, uy;
+    int entry = -1, n_cloud = 0;
+  };
+  std::vector<Job> jobs(nS);
+  std::vector<vpl_sel_input> in;
+  SelGather gs;
+  std::vector<std::vector<int>> lists;
+  for (int w = 0; w < nS; ++w) {
+    const vpl_odo_sel_frame& f = frames[w];
+    Job& j = jobs[w];
+    j.book = o->seq[w].sel_book;
+    j.book.max_features = par->max_features;
+    j.book.init_thresh = par->init_thresh;
+    sel_book_split(j.book, f.id, f.n_features, j.im);
+    if (!o->seq[w].set) continue;
+    std::unordered_map<int, int> at;          // id -> its first entry in the image
+    for (int i = f.n_features - 1; i >= 0; --i) at[f.id[i]] = i;
+    for (int fid : j.im.image_new) { const int i = at[fid]; j.new_id.push_back(fid); j.nx.push_back(f.x[i]); j.ny.push_back(f.y[i]); j.np.push_back(f.prob[i]); }
+    for (int fid : j.im.subset) { const int i = at[fid]; j.ux.push_back(f.x[i]); j.uy.push_back(f.y[i]); }
+    lists.emplace_back();
+    odo_cloud_list(o->seq[w].P, lists.back());
+    if ((int)lists.back().size() > VPL_SEL_MAX_FEATURES) return fail(c, VPL_E_CAPACITY, "odo_select: a cloud of more than VPL_SEL_MAX_FEATURES tracks");
+    j.n_cloud = (int)lists.back().size();
+    j.entry = (int)in.size();
+    vpl_sel_input q{};
+    std::memcpy(q.P1, f.P1, 24); std::memcpy(q.Q1, f.Q1, 32); std::memcpy(q.V1, f.V1, 24); std::memcpy(q.Ba1, f.Ba1, 24);
+    std::memcpy(q.acc, f.acc, 24); std::memcpy(q.gyr, f.gyr, 24);
+    q.Q0[0] = 1.0;                            // (state k is written by k_sel_cloud)
+    q.delta_imu = f.delta_imu; q.n_imu = f.n_imu; q.kappa = j.im.kappa; q.horizon = f.horizon;
+    q.n_new = (int)j.new_id.size(); q.n_used = (int)j.ux.size(); q.n_cloud = j.n_cloud;
+    in.push_back(q);
+  }
+  const int n = (int)in.size();
+  for (int w = 0; w < nS; ++w) {              // (the vectors no longer move)
+    Job& j = jobs[w];
+    if (j.entry < 0) continue;
+    vpl_sel_input& q = in[j.entry];
+    q.new_id = j.new_id.data(); q.new_x = j.nx.data(); q.new_y = j.ny.data(); q.new_prob = j.np.data();
+    q.used_x = j.ux.data(); q.used_y = j.uy.data();
+  }
+  std::vector<vpl_sel_result> res(std::max(n, 1));
+  std::vector<int> ids((size_t)std::max(n, 1) * VPL_SEL_MAX_FEATURES, 0);
+  std::vector<double> fs((size_t)std::max(n, 1) * VPL_SEL_MAX_FEATURES, 0.0);
+  if (n) {
+    const OdoStore& S = o->st[o->cur];
+    gs.G = DevSelGather{S.pobs, S.invd, S.pose, S.sb, S.ex, S.maxPT, nullptr};
+    gs.tab.assign(3 * (size_t)n, 0);
+    for (int w = 0; w < nS; ++w) {
+      const Job& j = jobs[w];
+      if (j.entry < 0) continue;
+      const std::vector<int>& l = lists[j.entry];
+      gs.tab[3 * j.entry] = w; gs.tab[3 * j.entry + 1] = (int)gs.tab.size(); gs.tab[3 * j.entry + 2] = (int)l.size();
+      gs.tab.insert(gs.tab.end(), l.begin(), l.end());
+    }
+    const int rc = sel_run(c, n, par, in.data(), res.data(), ids.data(), fs.data(), nullptr, &gs);
+    if (rc) return rc;
+  }
+  for (int w = 0; w < nS; ++w) {
+    Job& j = jobs[w];
+    vpl_odo_sel_result& r = out[w];
+    std::memset(&r, 0, sizeof r);
+    int* sid = selected_id + (size_t)w * VPL_SEL_MAX_FEATURES;
+    double* sf = round_f + (size_t)w * VPL_SEL_MAX_FEATURES;
+    std::fill(sid, sid + VPL_SEL_MAX_FEATURES, 0);
+    std::fill(sf, sf + VPL_SEL_MAX_FEATURES, 0.0);
+    const bool init = j.entry >= 0;
+    if (init) {
+      r.sel = res[j.entry];
+      std::memcpy(sid, &ids[(size_t)j.entry * VPL_SEL_MAX_FEATURES], VPL_SEL_MAX_FEATURES * 4);
+      std::memcpy(sf, &fs[(size_t)j.entry * VPL_SEL_MAX_FEATURES], VPL_SEL_MAX_FEATURES * 8);
+    }
+    std::vector<int> image;
+    sel_book_finish(j.book, j.im, init, sid, r.sel.n_selected, image);
+    r.initialized = init ? 1 : 0;
+    r.n_new = (int)j.im.image_new.size(); r.n_used = (int)j.im.subset.size(); r.kappa = j.im.kappa; r.n_cloud = j.n_cloud;
+    r.n_out = (int)image.size();
+    int* oi = out_ids + (size_t)w * VPL_SEL_MAX_FEATURES;
+    std::fill(oi, oi + VPL_SEL_MAX_FEATURES, 0);
+    std::copy(image.begin(), image.end(), oi);
+    o->seq[w].sel_book = j.book;
+  }
   return VPL_OK;
 }
 

@@ -17,6 +17,8 @@ constexpr int ODO_NF = 11;   // VPL_NFRAMES
 
 struct OdoTrack {
   int id, start, nobs, tri;
+  int solved = 0;   // point tracks: has taken part in a vpl_odo_solve (FeaturePerId::solve_flag == 1; a depth that came out
+                    // <= 0 erases the track at the next advance, removeFailures).  Read by vpl_odo_select's cloud filter only
 };
 
 struct OdoBook {   // one kind of tracks (points or lines) of one sequence
@@ -77,7 +79,7 @@ inline int odo_erase_slide(OdoBook& b, const unsigned char* erase, bool second_n
     ++entered;
     if (n == 0) continue;
     mv.push_back(OdoMove{(int)i, d, (!second_new && t.start == 0) ? 1 : 0});
-    nt.push_back(OdoTrack{t.id, s, n, t.tri});
+    nt.push_back(OdoTrack{t.id, s, n, t.tri, t.solved});
   }
   b.t.swap(nt);
   b.reindex();
@@ -125,6 +127,16 @@ inline int odo_parallax_list(const OdoBook& b, int* list, int* last_track_num) {
   }
   *last_track_num = last;
   return n;
+}
+
+// The point tracks FeatureSelector::initKDTree takes into its cloud (feature_selector.cpp:561-566): used_num >= 2,
+// start_frame < WINDOW_SIZE - 2, start_frame <= 0.75 * WINDOW_SIZE, solve_flag == 1.  list: track | start << 20, in the book's order
+inline void odo_cloud_list(const OdoBook& b, std::vector<int>& list) {
+  constexpr int WS = ODO_NF - 1;
+  for (size_t i = 0; i < b.t.size(); ++i) {
+    const OdoTrack& t = b.t[i];
+    if (t.nobs >= 2 && t.start < WS - 2 && 4 * t.start <= 3 * WS && t.solved) list.push_back((int)i | t.start << 20);
+  }
 }
 
 }  // namespace vpl
