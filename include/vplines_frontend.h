@@ -222,6 +222,64 @@ int vpl_line_track_ids(int n_new, const float* ends_new, int n_prev, const int* 
                        int* tcnt_out, int* vertical_new, int* n_vertical_new);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Point front-end, detection.  Drop-in boundary:
+ *   cvmodified::goodFeaturesToTrack(image, corners, scores, maxCorners, 0.01, minDistance, mask)
+ *        feature_tracker/src/cvmodified/cvmodified.cpp:38-216, blockSize 3, gradientSize 3, no Harris
+ * as FeatureTracker::detect_features calls it, for a batch of frames: the cornerMinEigenVal plane, its maximum under the mask,
+ * THRESH_TOZERO at 0.01 max, the 3 x 3 local-maximum test inside the mask, the descending sort (equal scores: the higher
+ * linear pixel index first, greaterThanPtr :16-21) and the greedy min-distance selection until max_corners are kept.
+ * vpl_pt_reserve (once per context) fixes the capacity of a frame's candidate list (<= 16384), the row length
+ * max_corners of the detector's outputs (<= 2048) and the row length max_points of a tracked point list (<= 1024).  A frame
+ * with more candidates than the list holds is refused -- VPL_E_CAPACITY for the call, the frame and its count in
+ * vpl_fe_last_error, no output written -- never cut short.
+ *   images      [n][H][W], or NULL: the n frames that lie in the context's image slots (after vpl_edlines_upload / vpl_pre_run)
+ *   masks       [n][H][W] 8-bit planes, non-zero = allowed (NULL: no frame has one); use_mask [n] (NULL: every frame uses its plane)
+ *   max_corners [n] in 1 .. the reserved max_corners;  min_distance [n] >= 0 (below 1: no suppression)
+ *   corners     [n][max_corners][2] integer pixel positions (x, y) as float, in the order kept;  scores [n][max_corners] the
+ *               min-eigenvalue of each;  counts [n].  Rows past counts[i] are left as they were.
+ * Two host-to-device copies (frames, parameters; a third for the masks), one copy back, one synchronisation.  The float
+ * arithmetic OpenCV leaves to its build (Sobel scale and tap order, the box sum) is stated in csrc/pt_kernels.h.
+ * vpl_pt_debug_detect: test access to frame `img` of the last call (any pointer may be NULL): the plane [H*W], the number
+ * of candidates found.
+ * ------------------------------------------------------------------------------------------------------------ */
+int vpl_pt_reserve(vpl_fe_ctx* ctx, int max_candidates, int max_corners, int max_points);
+int vpl_pt_detect_batch(vpl_fe_ctx* ctx, int n_images, const uint8_t* images, const uint8_t* masks, const int* use_mask,
+                        const int* max_corners, const double* min_distance, float* corners, float* scores, int* counts);
+int vpl_pt_debug_detect(vpl_fe_ctx* ctx, int img, float* eig, int* n_candidates);
+
+/* cv::calcOpticalFlowPyrLK(prev, next, pts, next_pts, status, err, Size(21, 21), 3) with OpenCV's defaults (30 iterations or a
+ * step of 0.01, minEigThreshold 1e-4, no initial flow) as FeatureTracker::readImage calls it (feature_tracker.cpp:139), for a
+ * batch of image pairs.  The images are those in the context's slots (vpl_edlines_upload, or the result of vpl_pre_run); a
+ * pair names two of them.  Pyramid levels are halved until four stand or the next would be no larger than the window; the
+ * window I, dIx, dIy in 16-bit fixed point from W_BITS = 14 weights; the level-0 min-eigenvalue test and the out-of-image
+ * tests clear status.  err is not produced.  The float sums over the window run row by row: each row left to right, the 21
+ * row sums top to bottom (csrc/pt_kernels.h); OpenCV's own order depends on its SIMD build.
+ *   prev_image, next_image [n];  prev_pts [n][max_points][2];  counts [n] (0 is allowed)
+ *   next_pts [n][max_points][2], status [n][max_points]: the first counts[i] entries of a row are written
+ * Frames must be larger than 21 x 21; n_pairs <= max_images.  One copy each way, one synchronisation. */
+int vpl_pt_flow_batch(vpl_fe_ctx* ctx, int n_pairs, const int* prev_image, const int* next_image, const float* prev_pts,
+                      const int* counts, float* next_pts, uint8_t* status);
+
+/* FeatureTracker::rejectWithF (feature_tracker/src/feature_tracker.cpp:226-261) for a batch of point lists: both lists are
+ * lifted through the camera model (PinholeCamera::liftProjective with k1, k2, p1, p2: the recursive distortion removal, 8
+ * steps), re-projected to focal_length x / z + COL / 2, focal_length y / z + ROW / 2 (COL, ROW: the context's frame size) and
+ * rounded to float; cv::findFundamentalMat(FM_RANSAC, f_threshold, 0.99) decides.  The estimator is the one of
+ * vpl_init_relative_pose_batch (vplines_ba.h: the 7-point solver, the symmetric epipolar error, RANSACUpdateNumIters, the
+ * integer sample stream of vpl_relpose_debug_plan with candidate 0 and the caller's seed), its deviations included.
+ *   cur_pts, forw_pts [n][max_points][2] pixel positions;  counts [n];  seeds [n]
+ *   status [n][max_points]: 1 = kept; the first counts[i] entries of a row are written.  A list of fewer than 8 points passes
+ *   unchanged (all 1).  A list for which no sample yields a model -- where the reference reads a mask OpenCV did not write --
+ *   loses every point (all 0).
+ * One copy each way, one synchronisation. */
+typedef struct vpl_pt_camera {
+  double fx, fy, cx, cy;
+  double k1, k2, p1, p2;
+} vpl_pt_camera;
+int vpl_pt_reject_f_batch(vpl_fe_ctx* ctx, int n_lists, const float* cur_pts, const float* forw_pts, const int* counts,
+                          const vpl_pt_camera* cam, double focal_length, double f_threshold, const unsigned long long* seeds,
+                          uint8_t* status);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Tracker session: LineFeatureTracker::readImage (line_feature_tracker.cpp:57-286) and the wire format of
  * line_feature_tracker_node.cpp:77-153 for n_seq independent cameras or sequences, one call per image.  What survives
  * from frame to frame -- the prepared image of the last frame taken over, its kept lines, ids, t_cnt, allfeature_cnt
@@ -294,6 +352,55 @@ int vpl_trk_get_frame(vpl_trk* trk, int seq, uint8_t* img, vpl_line* lines, int*
 int vpl_trk_debug_ids(vpl_fe_ctx* ctx, int n_new, const float* ends_new, int n_prev, const int* id_prev, const int* tcnt_prev,
                       int n_tcnt_prev, const int* prev_to_new, int max_h_lines, int max_v_lines, int* allfeature_cnt, int* keep,
                       int* id_out, int* tcnt_out, int* vertical_new, int* n_vertical_new);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Point tracker session: FeatureTracker::readImage (feature_tracker/src/feature_tracker.cpp:107-224) and updateID (:263-273)
+ * for n_seq independent cameras, one call per image; the counterpart of vpl_trk_*.  What survives from image to image lives
+ * in HBM: the prepared previous image, cur_pts, ids, track_cnt, forw_scores, the previous undistorted points by id, prev_time
+ * and the per-sequence id counter.  vpl_ptrk_frame copies the raw frames, times, publish flags and seeds down (one copy),
+ * the results and rows back (one copy) and synchronises once.  Per sequence, in the reference's order: CLAHE; LK from cur_pts
+ * (vpl_pt_flow_batch's kernels); the inBorder test (cvRound, border 1); compaction; track_cnt++.  When publish[i] is set:
+ * rejectWithF with seed[i]; setMask; detection of max_cnt - kept corners under that mask; addPoints (id -1, track_cnt 1).
+ * Then undistortedPoints (un-points, velocity against the previous image's points by id, score / max score) and updateID in
+ * list order.  Rows are written for published frames, for the points with track_cnt > 1, in list order:
+ *   row_id [n_seq][max_points];  rows [n_seq][max_points][7] = x, y (undistorted: float widened, what vpl_odo_frame.pt_xy1
+ *   takes with a 1 behind them), u, v, vx, vy, prob
+ * Kept as the reference has it, or stated where it leaves something open:
+ *   - setMask orders by falling track_cnt with std::sort, which is not stable; here equal counts keep their list order;
+ *   - the filled circle is OpenCV's integer midpoint walk (csrc/pt_plan.h), restated from its description, not pinned by a run;
+ *   - prob of EVERY row is forw_un_scores[0] (feature_tracker_node.cpp:154 indexes with the camera); the per-point values are
+ *     in vpl_ptrk_get_frame;
+ *   - vx, vy: float difference of the two un-points, divided by dt in double, stored as cv::Point2f;
+ *   - the id counter is per sequence (the reference's static n_id serves NUM_OF_CAM = 1); no stereo branch;
+ *   - the node's first-image skip, first-publication skip and FREQ rule stay with the caller, who passes publish.
+ * The session borrows the context: image slots [0, n_seq) for the new frames, [n_seq, 2 n_seq) for the previous ones, so
+ * max_images >= 2 n_seq; vpl_pt_reserve with max_points and max_corners >= max_cnt; no undistortion maps.  One point session
+ * per context (a second is VPL_E_INVALID).  VPL_E_CAPACITY when a published frame yields more corner candidates than
+ * max_candidates: a refused call leaves every sequence as it was.  vpl_ptrk_reset: the sequence starts again with its next
+ * image and keeps its id counter.  vpl_ptrk_set_mask: the fisheye mask [H][W] setMask starts from (NULL: all 255).
+ * vpl_ptrk_get_frame: test access to the state (any pointer may be NULL; arrays of max_points entries).
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct vpl_ptrk vpl_ptrk;
+typedef struct vpl_ptrk_options {
+  int max_cnt, min_dist;            /* 150, 30 */
+  double f_threshold, focal_length; /* 1.0, 460 */
+  int equalize;                     /* 1 */
+  double clip_limit;                /* 3.0 */
+  int tiles_x, tiles_y;             /* 8, 8 */
+  double fx, fy, cx, cy, k1, k2, p1, p2;
+} vpl_ptrk_options;
+typedef struct vpl_ptrk_result {    /* counts after each stage */
+  int tracked, after_border, after_f, after_mask, detected, published;
+} vpl_ptrk_result;
+void vpl_ptrk_default_options(vpl_ptrk_options* opt);
+int vpl_ptrk_create(vpl_ptrk** out, vpl_fe_ctx* ctx, int n_seq, const vpl_ptrk_options* opt);
+void vpl_ptrk_destroy(vpl_ptrk* trk);
+int vpl_ptrk_set_mask(vpl_ptrk* trk, const uint8_t* fisheye_mask);
+int vpl_ptrk_reset(vpl_ptrk* trk, int seq);
+int vpl_ptrk_frame(vpl_ptrk* trk, const uint8_t* raw, const double* time, const int* publish, const unsigned long long* seed,
+                   vpl_ptrk_result* res, int* row_id, double* rows);
+int vpl_ptrk_get_frame(vpl_ptrk* trk, int seq, int* n, float* pts, int* ids, int* track_cnt, float* scores, float* un_pts,
+                       float* un_scores, int* next_id);
 
 #ifdef __cplusplus
 }

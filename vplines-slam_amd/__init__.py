@@ -18,3 +18,4 @@ from . import workload  # noqa: F401
 from . import shard  # noqa: F401
 from . import frontend  # noqa: F401
 from .frontend import TrackerSession, TrackerOptions, TrackerResult, default_tracker_options  # noqa: F401
+from .frontend import PointCamera, PointTrackerSession, PointTrackerOptions, PointTrackerResult, default_point_tracker_options  # noqa: F401

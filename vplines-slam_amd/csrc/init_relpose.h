@@ -17,10 +17,10 @@
 #include "ba_common.h"
 #include "ba_lineopt.h"
 #include "init_relpose_plan.h"
+#include "relpose_f7.h"
 
 namespace vpl {
 
-constexpr int REL_THREADS = 256;
 constexpr int REL_NCAND = VPL_WINDOW_SIZE;
 constexpr int REL_TRACKS_PER_LANE = VPL_SFM_MAX_TRACKS / REL_THREADS;
 static_assert(REL_TRACKS_PER_LANE * REL_THREADS == VPL_SFM_MAX_TRACKS, "every lane gathers the same number of tracks");
@@ -51,137 +51,11 @@ struct DevRelArgs {
 struct RelLds {
   double pt[4 * VPL_SFM_MAX_TRACKS];   // x_i, y_i, x_10, y_10 per correspondence, rounded to float
   double red[24];
-  double F[9];                         // the winning hypothesis
   double R1[9], R2[9], t[3];           // decomposeEssentialMat
-  int cnt[3 * REL_THREADS];            // the round's inlier counts, (iteration, root)
+  RelRansacLds R;                      // the loop's state, the winning hypothesis in R.F
   int scan[REL_THREADS + 1];
-  int st[8];                           // niters, best, best_it, best_root, n_eval, winning lane of the round, -, -
   unsigned char m0[VPL_SFM_MAX_TRACKS], m1[VPL_SFM_MAX_TRACKS];
 };
-enum { RS_NITERS = 0, RS_BEST = 1, RS_BEST_IT = 2, RS_BEST_ROOT = 3, RS_NEVAL = 4, RS_WIN_LANE = 5 };
-
-// FMEstimatorCallback::computeError (modules/calib3d/src/fundam.cpp) for one correspondence against the squared threshold
-__device__ __forceinline__ bool rel_inlier(const double (&F)[9], double x1, double y1, double x2, double y2) {
-  double a = F[0] * x1 + F[1] * y1 + F[2];
-  double b = F[3] * x1 + F[4] * y1 + F[5];
-  double c = F[6] * x1 + F[7] * y1 + F[8];
-  const double s2 = 1.0 / (a * a + b * b);
-  const double d2 = x2 * a + y2 * b + c;
-  a = F[0] * x2 + F[3] * y2 + F[6];
-  b = F[1] * x2 + F[4] * y2 + F[7];
-  c = F[2] * x2 + F[5] * y2 + F[8];
-  const double s1 = 1.0 / (a * a + b * b);
-  const double d1 = x1 * a + y1 * b + c;
-  return fmax(d1 * d1 * s1, d2 * d2 * s2) <= REL_THRESHOLD * REL_THRESHOLD;
-}
-
-__device__ __forceinline__ double rel_det3(const double* a, const double* b, const double* c) {
-  return a[0] * (b[1] * c[2] - b[2] * c[1]) - a[1] * (b[0] * c[2] - b[2] * c[0]) + a[2] * (b[0] * c[1] - b[1] * c[0]);
-}
-
-// The real roots of c3 x^3 + c2 x^2 + c1 x + c0 in ascending order -> their number.  A vanishing leading coefficient leaves
-// the quadratic (or the linear equation); three real roots come from the trigonometric form, one from Cardano's; of a
-// repeated root (discriminant exactly zero) only the simple partner is a root here.
-__device__ __forceinline__ int rel_cubic(double c3, double c2, double c1, double c0, double (&x)[3]) {
-  x[0] = x[1] = x[2] = 0.0;
-  if (c3 == 0.0) {
-    if (c2 == 0.0) {
-      if (c1 == 0.0) return 0;
-      x[0] = -c0 / c1;
-      return 1;
-    }
-    const double disc = c1 * c1 - 4.0 * c2 * c0;
-    if (disc < 0.0) return 0;
-    if (disc == 0.0) { x[0] = -c1 / (2.0 * c2); return 1; }
-    const double q = -(c1 + (c1 >= 0.0 ? 1.0 : -1.0) * sqrt(disc)) / 2.0;
-    const double r0 = q / c2, r1 = c0 / q;
-    x[0] = fmin(r0, r1); x[1] = fmax(r0, r1);
-    return 2;
-  }
-  const double a = c2 / c3, b = c1 / c3, c = c0 / c3;
-  const double Q = (a * a - 3.0 * b) / 9.0, R = (2.0 * a * a * a - 9.0 * a * b + 27.0 * c) / 54.0;
-  const double Q3 = Q * Q * Q, d = Q3 - R * R;
-  if (d > 0.0) {
-    const double two_pi = 6.283185307179586476925286766559;
-    const double theta = acos(fmin(1.0, fmax(-1.0, R / sqrt(Q3)))), m = -2.0 * sqrt(Q), sh = a / 3.0;
-    double r0 = m * cos(theta / 3.0) - sh, r1 = m * cos((theta + two_pi) / 3.0) - sh, r2 = m * cos((theta - two_pi) / 3.0) - sh;
-    double t;
-    if (r1 < r0) { t = r0; r0 = r1; r1 = t; }
-    if (r2 < r1) { t = r1; r1 = r2; r2 = t; }
-    if (r1 < r0) { t = r0; r0 = r1; r1 = t; }
-    x[0] = r0; x[1] = r1; x[2] = r2;
-    return 3;
-  }
-  double e = cbrt(sqrt(-d) + fabs(R));
-  if (R > 0.0) e = -e;
-  x[0] = (e + (e != 0.0 ? Q / e : 0.0)) - a / 3.0;
-  return 1;
-}
-
-// The hypotheses of one minimal sample: F[r] for the nroots real roots, in ascending lambda.
-__device__ __forceinline__ int rel_seven_point(const double* pt, const int (&idx)[RELPOSE_SAMPLE], double (&F)[3][9]) {
-  double a[7][9];
-#pragma unroll
-  for (int k = 0; k < 7; ++k) {
-    const double* p = pt + 4 * idx[k];
-    const double x1 = p[0], y1 = p[1], x2 = p[2], y2 = p[3];
-    a[k][0] = x2 * x1; a[k][1] = x2 * y1; a[k][2] = x2;
-    a[k][3] = y2 * x1; a[k][4] = y2 * y1; a[k][5] = y2;
-    a[k][6] = x1; a[k][7] = y1; a[k][8] = 1.0;
-  }
-  // Householder on the rows: reflection k maps row k onto e_k and is kept in its place (entries k .. 8)
-  double beta[7];
-#pragma unroll
-  for (int k = 0; k < 7; ++k) {
-    double s = 0.0;
-#pragma unroll
-    for (int r = k; r < 9; ++r) s += a[k][r] * a[k][r];
-    const double nx = sqrt(s);
-    a[k][k] -= a[k][k] >= 0.0 ? -nx : nx;
-    double vv = 0.0;
-#pragma unroll
-    for (int r = k; r < 9; ++r) vv += a[k][r] * a[k][r];
-    beta[k] = vv > 0.0 ? 2.0 / vv : 0.0;
-#pragma unroll
-    for (int j = k + 1; j < 7; ++j) {
-      double d = 0.0;
-#pragma unroll
-      for (int r = k; r < 9; ++r) d += a[k][r] * a[j][r];
-      d *= beta[k];
-#pragma unroll
-      for (int r = k; r < 9; ++r) a[j][r] -= d * a[k][r];
-    }
-  }
-  // the null space: Q e7, Q e8 with Q = H0 H1 .. H6
-  double f1[9], f2[9];
-#pragma unroll
-  for (int r = 0; r < 9; ++r) { f1[r] = r == 7 ? 1.0 : 0.0; f2[r] = r == 8 ? 1.0 : 0.0; }
-#pragma unroll
-  for (int k = 6; k >= 0; --k) {
-    double d1 = 0.0, d2 = 0.0;
-#pragma unroll
-    for (int r = k; r < 9; ++r) { d1 += a[k][r] * f1[r]; d2 += a[k][r] * f2[r]; }
-    d1 *= beta[k]; d2 *= beta[k];
-#pragma unroll
-    for (int r = k; r < 9; ++r) { f1[r] -= d1 * a[k][r]; f2[r] -= d2 * a[k][r]; }
-  }
-  // det(F2 + lambda G), G = F1 - F2, by rows
-  double g[9];
-#pragma unroll
-  for (int r = 0; r < 9; ++r) g[r] = f1[r] - f2[r];
-  const double* h = f2;
-  const double c0 = rel_det3(h, h + 3, h + 6);
-  const double c1 = rel_det3(g, h + 3, h + 6) + rel_det3(h, g + 3, h + 6) + rel_det3(h, h + 3, g + 6);
-  const double c2 = rel_det3(g, g + 3, h + 6) + rel_det3(g, h + 3, g + 6) + rel_det3(h, g + 3, g + 6);
-  const double c3 = rel_det3(g, g + 3, g + 6);
-  double x[3];
-  const int nroots = rel_cubic(c3, c2, c1, c0, x);
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int k = 0; k < 9; ++k) F[r][k] = r < nroots ? x[r] * f1[k] + (1.0 - x[r]) * f2[k] : 0.0;
-  return nroots;
-}
 
 // cv::decomposeEssentialMat (solve_5pts.cpp:5-28) by one-sided Jacobi on the columns of F: F V = B with orthogonal columns,
 // the columns ordered by falling norm, u1 / u2 the first two normalised, u3 = u1 x u2 (det U = +1 by construction), V's sign
@@ -313,74 +187,12 @@ __global__ __launch_bounds__(REL_THREADS) void k_relpose_ransac(DevRelArgs A) {
   }
   if (!run) return;
   const int* niters_after = itab + q.nit[cand];
-  // ---- the RANSAC, 256 iterations at a time
+  // ---- the RANSAC, 256 iterations at a time (relpose_f7.h)
+  rel_ransac_run(L.pt, N, q.seed, cand, niters_after, REL_THRESHOLD * REL_THRESHOLD, L.R, A.hyp ? A.hyp + slot * RELPOSE_MAX_ITERS * 3 : nullptr);
+  const int best_it = L.R.st[RS_BEST_IT];
   if (tid == 0) {
-    L.st[RS_NITERS] = RELPOSE_MAX_ITERS; L.st[RS_BEST] = 0; L.st[RS_BEST_IT] = -1; L.st[RS_BEST_ROOT] = -1; L.st[RS_NEVAL] = 0;
-  }
-  __syncthreads();
-  for (int base = 0; base < RELPOSE_MAX_ITERS; base += REL_THREADS) {
-    const int niters = L.st[RS_NITERS];
-    if (base >= niters) break;
-    const int it = base + tid;
-    double F[3][9];
-    int cnt[3] = {-1, -1, -1};
-    if (it < niters) {
-      int idx[RELPOSE_SAMPLE] = {-1, -1, -1, -1, -1, -1, -1};
-      relpose_sample(q.seed, cand, it, N, idx);
-      const int nroots = rel_seven_point(L.pt, idx, F);
-#pragma unroll
-      for (int r = 0; r < 3; ++r) cnt[r] = r < nroots ? 0 : -1;
-      for (int p = 0; p < N; ++p) {
-        const double x1 = L.pt[4 * p], y1 = L.pt[4 * p + 1], x2 = L.pt[4 * p + 2], y2 = L.pt[4 * p + 3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-          if (r < nroots) cnt[r] += rel_inlier(F[r], x1, y1, x2, y2) ? 1 : 0;
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 3; ++r) L.cnt[3 * tid + r] = cnt[r];
-    __syncthreads();
-    if (tid == 0) {   // the sequential rule over the round (modules/calib3d/src/ptsetreg.cpp, RANSACPointSetRegistrator::run)
-      int nit = niters, best = L.st[RS_BEST], win = -1;
-      for (int k = 0; k < REL_THREADS; ++k) {
-        if (base + k >= nit) break;
-        L.st[RS_NEVAL] = base + k + 1;
-        for (int r = 0; r < 3; ++r) {
-          const int good = L.cnt[3 * k + r];
-          if (good > (best > RELPOSE_SAMPLE - 1 ? best : RELPOSE_SAMPLE - 1)) {
-            best = good;
-            L.st[RS_BEST_IT] = base + k; L.st[RS_BEST_ROOT] = r;
-            win = k;
-            nit = niters_after[good];
-          }
-        }
-      }
-      L.st[RS_NITERS] = nit; L.st[RS_BEST] = best; L.st[RS_WIN_LANE] = win;
-    }
-    __syncthreads();
-    if (tid == L.st[RS_WIN_LANE]) {
-      const int root = L.st[RS_BEST_ROOT];
-      double n2 = 0.0;
-#pragma unroll
-      for (int k = 0; k < 9; ++k) {
-        const double f = root == 0 ? F[0][k] : (root == 1 ? F[1][k] : F[2][k]);
-        n2 += f * f;
-      }
-      const double n = sqrt(n2);
-#pragma unroll
-      for (int k = 0; k < 9; ++k) L.F[k] = (root == 0 ? F[0][k] : (root == 1 ? F[1][k] : F[2][k])) / n;
-    }
-    if (A.hyp && it < L.st[RS_NEVAL]) {
-      int* h = A.hyp + (slot * RELPOSE_MAX_ITERS + it) * 3;
-#pragma unroll
-      for (int r = 0; r < 3; ++r) h[r] = cnt[r];
-    }
-    __syncthreads();
-  }
-  const int best_it = L.st[RS_BEST_IT];
-  if (tid == 0) {
-    o.iterations = L.st[RS_NITERS];
-    o.best_iteration = best_it; o.best_root = L.st[RS_BEST_ROOT];
+    o.iterations = L.R.st[RS_NITERS];
+    o.best_iteration = best_it; o.best_root = L.R.st[RS_BEST_ROOT];
   }
   if (best_it < 0) {
     if (tid == 0) o.status = VPL_RELPOSE_NO_MODEL;
@@ -389,15 +201,15 @@ __global__ __launch_bounds__(REL_THREADS) void k_relpose_ransac(DevRelArgs A) {
   // ---- the winner's mask (findInliers), then recoverPose
   double Fw[9];
 #pragma unroll
-  for (int k = 0; k < 9; ++k) Fw[k] = L.F[k];
+  for (int k = 0; k < 9; ++k) Fw[k] = L.R.F[k];
   double inl = 0.0;
   for (int p = tid; p < N; p += REL_THREADS) {
-    const bool m = rel_inlier(Fw, L.pt[4 * p], L.pt[4 * p + 1], L.pt[4 * p + 2], L.pt[4 * p + 3]);
+    const bool m = rel_inlier(Fw, L.pt[4 * p], L.pt[4 * p + 1], L.pt[4 * p + 2], L.pt[4 * p + 3], REL_THRESHOLD * REL_THRESHOLD);
     L.m0[p] = m ? 1 : 0;
     inl += m ? 1.0 : 0.0;
   }
   inl = block_sum(inl, L.red);
-  if (tid == 0) rel_decompose(L.F, L.R1, L.R2, L.t);
+  if (tid == 0) rel_decompose(L.R.F, L.R1, L.R2, L.t);
   __syncthreads();
   double g[4] = {0.0, 0.0, 0.0, 0.0};
   for (int p = tid; p < N; p += REL_THREADS) {
@@ -429,7 +241,7 @@ __global__ __launch_bounds__(REL_THREADS) void k_relpose_ransac(DevRelArgs A) {
     const double sg = pick < 2 ? 1.0 : -1.0;
     const V3 t{sg * L.t[0], sg * L.t[1], sg * L.t[2]};
     M3 Rm;
-    for (int k = 0; k < 9; ++k) { Rm.m[k] = R[k]; o.F[k] = L.F[k]; }
+    for (int k = 0; k < 9; ++k) { Rm.m[k] = R[k]; o.F[k] = L.R.F[k]; }
     const M3 Rt = transpose(Rm);          // Rotation = R^T, Translation = -R^T t (solve_5pts.cpp:220-221)
     const V3 T = -mul(Rt, t);
     for (int k = 0; k < 9; ++k) o.R[k] = Rt.m[k];

@@ -1,5 +1,5 @@
 // HIP kernels of the KLT line matcher (line front-end), batch of frame pairs of one size.
-//   k_lm_level0 / k_lm_down : padded image pyramid (pyrDown [1 4 6 4 1]^2 / 256, BORDER_REFLECT_101 border of 13 px)
+//   k_lm_level0 / k_lm_down : padded image pyramid (pyrDown [1 4 6 4 1]^2 / 256, BORDER_REFLECT_101 border as wide as the window)
 //   k_lm_scharr             : Scharr 3/10/3 derivative planes, zero border (klt.cpp:42-122, :613)
 //   k_lm_anchors            : LineMatching::Anchors (line_matching.cpp:532-602), one lane per reference line
 //   k_lm_klt                : pyramidal LK with per-iteration gain/bias (lk_tracker_invoker_2d.cpp:28-479), ONE LANE PER
@@ -25,8 +25,12 @@ constexpr int LM_MAXCOUNT = 30;
 constexpr int LM_KLT_SMEM = LM_NPX * 64 * 2;       // J windows of the 64 lanes of a wave
 constexpr int LM_KLT_GRID = 256 * 7;              // persistent waves: 7 per CU fit the LDS
 
-struct LmBatch {
+// The padded pyramids of a batch of frames and their Scharr planes: what k_lm_level0 / k_lm_down / k_lm_scharr build.  The
+// border is as wide as the tracking window that reads it: LM_WIN for the line matcher's 13 x 13 KLT, 21 for the point
+// tracker's calcOpticalFlowPyrLK (pt_kernels.h), which keeps a second LmPyr over the same frames.
+struct LmPyr {
   int N, W, H;                 // images (shared with the EDLines batch)
+  int border;                  // pixels of BORDER_REFLECT_101 padding around every level; smaller than every level's sides
   int nLevels;                 // levels built (buildOpticalFlowPyramid's return value + 1)
   int lw[LM_LEVELS], lh[LM_LEVELS], ls[LM_LEVELS];   // level width / height / padded stride
   size_t loff[LM_LEVELS];      // offset of the level inside one image's pyramid block (pixels)
@@ -34,6 +38,29 @@ struct LmBatch {
   const uint8_t* img;          // [N][H][W]
   uint8_t* pyr;                // [N][pyrSize]
   int16_t* der;                // [N][pyrSize][2]
+};
+
+// buildOpticalFlowPyramid's level rule for a win x win window: halve until max_levels levels stand or the next one would be no
+// larger than the window.  Fills the level table of P (border = win) and returns the padded pixels of one image.
+inline size_t lm_pyr_layout(LmPyr& P, int W, int H, int win, int max_levels) {
+  P.W = W; P.H = H; P.border = win;
+  int w = W, h = H, l = 0;
+  size_t off = 0;
+  for (;;) {
+    P.lw[l] = w; P.lh[l] = h; P.ls[l] = w + 2 * win; P.loff[l] = off;
+    off += (size_t)(w + 2 * win) * (h + 2 * win);
+    off = (off + 63) & ~(size_t)63;
+    if (l == max_levels - 1) break;
+    const int nw = (w + 1) / 2, nh = (h + 1) / 2;
+    if (nw <= win || nh <= win) break;
+    w = nw; h = nh; ++l;
+  }
+  P.nLevels = l + 1;
+  P.pyrSize = off;
+  return off;
+}
+
+struct LmBatch : LmPyr {
   // pairs
   int nPairs, maxLines, maxK;
   const int *refImg, *curImg;  // [P]
@@ -56,27 +83,31 @@ struct LmBatch {
 
 __device__ __forceinline__ int lm_r101(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
 
+// The three pyramid kernels take the border width as a template argument (the line matcher's LM_WIN, the point tracker's 21):
+// one arithmetic, the address computations folded per width.
 // level 0: copy with a reflect-101 border
-__global__ __launch_bounds__(256) void k_lm_level0(LmBatch B) {
+template <int BORDER>
+__global__ __launch_bounds__(256) void k_lm_level0(LmPyr B) {
   const int n = blockIdx.y;
-  const int S = B.ls[0], HP = B.lh[0] + 2 * LM_WIN;
+  const int S = B.ls[0], HP = B.lh[0] + 2 * BORDER;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= S * HP) return;
   const int py = i / S, px = i - py * S;
-  const int x = lm_r101(px - LM_WIN, B.W), y = lm_r101(py - LM_WIN, B.H);
+  const int x = lm_r101(px - BORDER, B.W), y = lm_r101(py - BORDER, B.H);
   B.pyr[(size_t)n * B.pyrSize + B.loff[0] + i] = B.img[((size_t)n * B.H + y) * B.W + x];
 }
 
 // level l from the padded level l-1 (reads reach 2 px into the border, which already holds the reflected pixels)
-__global__ __launch_bounds__(256) void k_lm_down(LmBatch B, int l) {
+template <int BORDER>
+__global__ __launch_bounds__(256) void k_lm_down(LmPyr B, int l) {
   const int n = blockIdx.y;
-  const int S = B.ls[l], HP = B.lh[l] + 2 * LM_WIN;
+  const int S = B.ls[l], HP = B.lh[l] + 2 * BORDER;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= S * HP) return;
   const int py = i / S, px = i - py * S;
-  const int x = lm_r101(px - LM_WIN, B.lw[l]), y = lm_r101(py - LM_WIN, B.lh[l]);
+  const int x = lm_r101(px - BORDER, B.lw[l]), y = lm_r101(py - BORDER, B.lh[l]);
   const int SP = B.ls[l - 1];
-  const uint8_t* src = B.pyr + (size_t)n * B.pyrSize + B.loff[l - 1] + (size_t)(2 * y - 2 + LM_WIN) * SP + (2 * x - 2 + LM_WIN);
+  const uint8_t* src = B.pyr + (size_t)n * B.pyrSize + B.loff[l - 1] + (size_t)(2 * y - 2 + BORDER) * SP + (2 * x - 2 + BORDER);
   int s = 0;
 #pragma unroll
   for (int j = 0; j < 5; ++j) {
@@ -88,14 +119,15 @@ __global__ __launch_bounds__(256) void k_lm_down(LmBatch B, int l) {
 }
 
 // Scharr planes of every level (blockIdx.z = level); zero outside the image
-__global__ __launch_bounds__(256) void k_lm_scharr(LmBatch B) {
+template <int BORDER>
+__global__ __launch_bounds__(256) void k_lm_scharr(LmPyr B) {
   const int n = blockIdx.y, l = blockIdx.z;
   if (l >= B.nLevels) return;
-  const int S = B.ls[l], HP = B.lh[l] + 2 * LM_WIN;
+  const int S = B.ls[l], HP = B.lh[l] + 2 * BORDER;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= S * HP) return;
   const int py = i / S, px = i - py * S;
-  const int x = px - LM_WIN, y = py - LM_WIN;
+  const int x = px - BORDER, y = py - BORDER;
   short dx = 0, dy = 0;
   if (x >= 0 && x < B.lw[l] && y >= 0 && y < B.lh[l]) {
     const uint8_t* c = B.pyr + (size_t)n * B.pyrSize + B.loff[l] + i;
@@ -167,21 +199,24 @@ __device__ __forceinline__ LmWeights lm_weights(float a, float b) {
   return w;
 }
 
-// 14 consecutive bytes of one window row from an arbitrarily aligned address: five aligned dword loads + v_alignbyte
-// (a byte gather per pixel costs one cache-line lookup per lane per byte; this is 5 lookups per 14 pixels)
-__device__ __forceinline__ void lm_load_row(const uint8_t* p, int (&v)[LM_WIN + 1]) {
+// NB consecutive bytes from an arbitrarily aligned address: ceil(NB / 4) + 1 aligned dword loads + v_alignbyte
+// (a byte gather per pixel costs one cache-line lookup per lane per byte; for the 14 bytes of a 13-pixel window row this is 5
+// lookups).  Reads up to 3 bytes past the last one asked for: every pyramid block is followed by the allocation's pad.
+template <int NB>
+__device__ __forceinline__ void lm_load_bytes(const uint8_t* p, int (&v)[NB]) {
+  constexpr int NW = (NB + 3) / 4;
   const uintptr_t a = (uintptr_t)p;
   const unsigned* q = (const unsigned*)(a & ~(uintptr_t)3);
   const unsigned sh = (unsigned)(a & 3);
-  const unsigned d0 = q[0], d1 = q[1], d2 = q[2], d3 = q[3], d4 = q[4];
-  unsigned w[4];
-  w[0] = __builtin_amdgcn_alignbyte(d1, d0, sh);
-  w[1] = __builtin_amdgcn_alignbyte(d2, d1, sh);
-  w[2] = __builtin_amdgcn_alignbyte(d3, d2, sh);
-  w[3] = __builtin_amdgcn_alignbyte(d4, d3, sh);
+  unsigned d[NW + 1], w[NW];
 #pragma unroll
-  for (int x = 0; x <= LM_WIN; ++x) v[x] = (int)((w[x >> 2] >> ((x & 3) * 8)) & 255u);
+  for (int k = 0; k <= NW; ++k) d[k] = q[k];
+#pragma unroll
+  for (int k = 0; k < NW; ++k) w[k] = __builtin_amdgcn_alignbyte(d[k + 1], d[k], sh);
+#pragma unroll
+  for (int x = 0; x < NB; ++x) v[x] = (int)((w[x >> 2] >> ((x & 3) * 8)) & 255u);
 }
+__device__ __forceinline__ void lm_load_row(const uint8_t* p, int (&v)[LM_WIN + 1]) { lm_load_bytes<LM_WIN + 1>(p, v); }
 
 // bilinear J window (scaled x32) into the lane's LDS column; returns sum and sum of squares (exact integers).
 // Row r contributes to window row r-1 as its lower neighbour and to row r as its upper one: one load per row.

@@ -14,11 +14,13 @@
 #include "ed_kernels.h"
 #include "lm_kernels.h"
 #include "pre_kernels.h"
+#include "pt_kernels.h"
 #include "vp_kernels.h"
 
 using namespace vpl;
 
 struct vpl_trk;
+struct vpl_ptrk;
 
 struct vpl_fe_ctx {
   int device = 0;
@@ -49,12 +51,27 @@ struct vpl_fe_ctx {
   int *d_vpNHyp = nullptr, *d_vpNAll = nullptr, *d_vpFirst = nullptr;
   uint32_t* d_vpSeed = nullptr;
   int vpN = 0;
+  // point detector (vpl_pt_reserve)
+  PtBatch P;
+  bool ptReserved = false;
+  uint8_t* d_ptMask = nullptr;        // [maxN][H][W], made by the first call that passes a mask
+  unsigned char* d_ptIn = nullptr;    // one call's parameters: minDist [n] doubles, useMask [n], maxCorners [n]
+  int* d_ptOut = nullptr;             // one call's results: count [n], found [n], corners [n][maxC][2], scores [n][maxC]
+  int ptN = 0;                        // frames of the last vpl_pt_detect_batch (vpl_pt_debug_detect)
+  int ptMaxPoints = 0;                // row length of the tracked point lists
+  unsigned char* d_rejIn = nullptr;   // vpl_pt_reject_f_batch: the one upload (pt_reject_upload_bytes)
+  uint8_t* d_rejStatus = nullptr;     // [maxN][ptMaxPoints]
+  LmPyr ptPyr;                        // vpl_pt_flow_batch: the pyramids with a border of 21 (frames of at least 22 x 22)
+  bool ptFlowReserved = false;
+  unsigned char* d_flowIn = nullptr;  // one call's upload: prevImg [n], nextImg [n], counts [n], prev [n][ptMaxPoints][2]
+  unsigned char* d_flowOut = nullptr; // one call's results: next [n][ptMaxPoints][2] floats, status [n][ptMaxPoints]
   std::vector<DevAlloc> allocs;      // host_common.h: the context's own arrays (owner null, the lazy ones included) and the tracker session's
   bool guards = false;
   std::string err;
   bool timing = false;                                    // vpl_fe_enable_kernel_timing
   std::vector<std::pair<const char*, double>> ktimes;     // (kernel, ms) of the launches since timing was enabled
   vpl_trk* trk = nullptr;                                 // the tracker session this context lends itself to (trk_session.h)
+  vpl_ptrk* ptrk = nullptr;                               // the point tracker session (pt_session.h)
 };
 
 // times one kernel launch with hipEvents on the context's stream when timing is on (bench.py: k_ed_grad GB/s)
@@ -78,6 +95,17 @@ struct FeTimer {
     }
   }
 };
+
+// the pyramid and Scharr launches for the P.N frames of P.img (the matcher's pyramid, and the point tracker's with its wider border)
+template <int BORDER>
+static void lm_pyr_launch(vpl_fe_ctx* c, const LmPyr& P, const char* name_pyr, const char* name_scharr) {
+  hipStream_t s = c->stream;   // (P.border == BORDER: lm_pyr_layout was called with it)
+  auto blocks = [&](int l) { return (unsigned)(((size_t)P.ls[l] * (P.lh[l] + 2 * P.border) + 255) / 256); };
+  { FeTimer t(c, name_pyr);
+    hipLaunchKernelGGL(k_lm_level0<BORDER>, dim3(blocks(0), P.N), dim3(256), 0, s, P);
+    for (int l = 1; l < P.nLevels; ++l) hipLaunchKernelGGL(k_lm_down<BORDER>, dim3(blocks(l), P.N), dim3(256), 0, s, P, l); }
+  { FeTimer t(c, name_scharr); hipLaunchKernelGGL(k_lm_scharr<BORDER>, dim3(blocks(0), P.N, P.nLevels), dim3(256), 0, s, P); }
+}
 
 extern "C" {
 
@@ -190,6 +218,7 @@ int vpl_fe_create(vpl_fe_ctx** out, int device, int max_images, int width, int h
 void vpl_fe_destroy(vpl_fe_ctx* c) {
   if (!c) return;
   if (c->trk) vpl_trk_destroy(c->trk);   // a session that is still open goes first (its arrays are the context's)
+  if (c->ptrk) vpl_ptrk_destroy(c->ptrk);
   // (teardown: a failure has nobody to be reported to)
   (void)hipSetDevice(c->device);
   (void)hipDeviceSynchronize();
@@ -577,21 +606,9 @@ int vpl_match_reserve(vpl_fe_ctx* c, int max_pairs, int max_kps) {
   HIPCHK(c, hipSetDevice(c->device));
   LmBatch& M = c->M;
   std::memset(&M, 0, sizeof(M));
-  M.W = c->W; M.H = c->H; M.img = c->B.img;
+  M.img = c->B.img;
   // buildOpticalFlowPyramid: halve until maxLevel or until the next level would not exceed the window
-  int w = c->W, h = c->H, l = 0;
-  size_t off = 0;
-  for (;;) {
-    M.lw[l] = w; M.lh[l] = h; M.ls[l] = w + 2 * LM_WIN; M.loff[l] = off;
-    off += (size_t)(w + 2 * LM_WIN) * (h + 2 * LM_WIN);
-    off = (off + 63) & ~(size_t)63;
-    if (l == LM_LEVELS - 1) break;
-    const int nw = (w + 1) / 2, nh = (h + 1) / 2;
-    if (nw <= LM_WIN || nh <= LM_WIN) break;
-    w = nw; h = nh; ++l;
-  }
-  M.nLevels = l + 1;
-  M.pyrSize = off;
+  lm_pyr_layout(M, c->W, c->H, LM_WIN, LM_LEVELS);
   M.maxLines = c->maxLines; M.maxK = max_kps;
   c->maxPairs = max_pairs;
   const size_t N = c->maxN, P = max_pairs, ML = c->maxLines, MK = max_kps;
@@ -680,11 +697,7 @@ static int lm_launch(vpl_fe_ctx* c, const vpl_match_param* p, int n_images, int 
   double eps = std::min(std::max(0.001, 0.), 10.);   // TermCriteria(COUNT|EPS, 30, 0.001) through KLT::KLT, klt.cpp:28-33
   M.epsilon = eps * eps;
   hipStream_t s = c->stream;
-  auto blocks = [&](int l) { return (unsigned)(((size_t)M.ls[l] * (M.lh[l] + 2 * LM_WIN) + 255) / 256); };
-  { FeTimer t(c, "k_lm_pyramid");
-    hipLaunchKernelGGL(k_lm_level0, dim3(blocks(0), n_images), dim3(256), 0, s, M);
-    for (int l = 1; l < M.nLevels; ++l) hipLaunchKernelGGL(k_lm_down, dim3(blocks(l), n_images), dim3(256), 0, s, M, l); }
-  { FeTimer t(c, "k_lm_scharr"); hipLaunchKernelGGL(k_lm_scharr, dim3(blocks(0), n_images, M.nLevels), dim3(256), 0, s, M); }
+  lm_pyr_launch<LM_WIN>(c, M, "k_lm_pyramid", "k_lm_scharr");
   { FeTimer t(c, "k_lm_anchors"); hipLaunchKernelGGL(k_lm_anchors, dim3(n_pairs), dim3(256), (size_t)M.maxLines * sizeof(int), s, M);
     hipLaunchKernelGGL(k_lm_plan, dim3(1), dim3(64), 0, s, M); }
   { FeTimer t(c, "k_lm_klt"); hipLaunchKernelGGL(k_lm_klt, dim3(LM_KLT_GRID), dim3(64), LM_KLT_SMEM, s, M); }
@@ -850,6 +863,252 @@ int vpl_vp_debug(vpl_fe_ctx* c, int frame, double* grid, int* pairs, int* best_i
   return VPL_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Point front-end: cvmodified::goodFeaturesToTrack (pt_kernels.h)
+// ---------------------------------------------------------------------------------------------------------------
+int vpl_pt_reserve(vpl_fe_ctx* c, int max_candidates, int max_corners, int max_points) {
+  if (!c) return VPL_E_INVALID;
+  if (c->ptReserved) return fail(c, VPL_E_INVALID, "vpl_pt_reserve called twice");
+  if (!pt_capacities_ok(max_candidates, max_corners, max_points))
+    return fail(c, VPL_E_CAPACITY, "vpl_pt_reserve: max_candidates above " + std::to_string(PT_MAX_CANDIDATES) + ", max_corners above " +
+                                       std::to_string(PT_MAX_CORNERS) + " or max_points above " + std::to_string(PT_MAX_POINTS) + " (or below 1)");
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t mark = c->allocs.size();
+  PtBatch& P = c->P;
+  std::memset(&P, 0, sizeof(P));
+  P.W = c->W; P.H = c->H; P.img = c->B.img;
+  P.capCand = max_candidates; P.capCorners = max_corners;
+  const size_t N = c->maxN, PX = (size_t)c->W * c->H;
+  hipError_t e = hipSuccess;
+#define AL(ptr, n) if (e == hipSuccess) e = dalloc(c, &ptr, (size_t)(n))
+  AL(P.eig, N * PX); AL(P.maxKey, N); AL(P.nCand, N); AL(P.keys, N * max_candidates);
+  AL(c->d_ptIn, N * 16); AL(c->d_ptOut, N * (2 + 3 * (size_t)max_corners));
+  AL(c->d_rejIn, pt_reject_upload_bytes((int)N, max_points)); AL(c->d_rejStatus, N * max_points);
+  // the point tracker's pyramid: the matcher's kernels with a border of 21 (frames no larger than the window cannot be tracked)
+  std::memset(&c->ptPyr, 0, sizeof(c->ptPyr));
+  if (c->W > PT_WIN && c->H > PT_WIN) {
+    LmPyr& Q = c->ptPyr;
+    lm_pyr_layout(Q, c->W, c->H, PT_WIN, LM_LEVELS);
+    Q.img = c->B.img;
+    AL(Q.pyr, N * Q.pyrSize); AL(Q.der, N * Q.pyrSize * 2);
+    AL(c->d_flowIn, N * (12 + (size_t)max_points * 8)); AL(c->d_flowOut, N * (size_t)max_points * 9);
+    c->ptFlowReserved = e == hipSuccess;
+  }
+#undef AL
+  c->ptMaxPoints = max_points;
+  // (per call, not remembered per process: the attribute belongs to the device the context is on)
+  const size_t smem = pt_select_lds_bytes(max_candidates, max_corners);
+  if (e == hipSuccess && smem > 48 * 1024)
+    e = hipFuncSetAttribute((const void*)k_pt_select, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+  if (e != hipSuccess) {   // nothing of a failed reservation stays
+    std::vector<void*> mine;
+    for (size_t k = mark; k < c->allocs.size(); ++k) mine.push_back(c->allocs[k].p);
+    for (void* q : mine) dfree(c, q);
+    std::memset(&c->P, 0, sizeof(c->P));
+    std::memset(&c->ptPyr, 0, sizeof(c->ptPyr));
+    c->d_ptIn = nullptr; c->d_ptOut = nullptr; c->d_rejIn = nullptr; c->d_rejStatus = nullptr; c->d_flowIn = nullptr; c->d_flowOut = nullptr;
+    c->ptFlowReserved = false; c->ptMaxPoints = 0;
+    return fail(c, VPL_E_HIP, std::string("vpl_pt_reserve: ") + hipGetErrorString(e));
+  }
+  c->ptReserved = true;
+  return VPL_OK;
+}
+
+static PtCamera pt_camera(const vpl_pt_camera& k) {   // PinholeCamera's constructor (:292-295)
+  PtCamera c;
+  c.inv_K11 = 1.0 / k.fx; c.inv_K13 = -k.cx / k.fx; c.inv_K22 = 1.0 / k.fy; c.inv_K23 = -k.cy / k.fy;
+  c.k1 = k.k1; c.k2 = k.k2; c.p1 = k.p1; c.p2 = k.p2;
+  return c;
+}
+
+// the detector's launches on image slots [0, n); parameters and masks lie in HBM, P's pointers are set
+static int pt_detect_launch(vpl_fe_ctx* c, int n) {
+  hipStream_t s = c->stream;
+  PtBatch& P = c->P;
+  P.N = n;
+  const size_t PX = (size_t)c->W * c->H;
+  HIPCHK(c, hipMemsetAsync(P.maxKey, 0, (size_t)n * 4, s));
+  HIPCHK(c, hipMemsetAsync(P.nCand, 0, (size_t)n * 4, s));
+  { FeTimer t(c, "k_pt_mineig");
+    hipLaunchKernelGGL(k_pt_mineig, dim3((c->W + PT_TW - 1) / PT_TW, (c->H + PT_TH - 1) / PT_TH, n), dim3(PT_TW * PT_TH), 0, s, P); }
+  { FeTimer t(c, "k_pt_localmax"); hipLaunchKernelGGL(k_pt_localmax, dim3((unsigned)((PX + 255) / 256), n), dim3(256), 0, s, P); }
+  { FeTimer t(c, "k_pt_select");
+    hipLaunchKernelGGL(k_pt_select, dim3(n), dim3(PT_SELECT_THREADS), pt_select_lds_bytes(P.capCand, P.capCorners), s, P); }
+  HIPCHK(c, hipGetLastError());
+  return VPL_OK;
+}
+
+int vpl_pt_detect_batch(vpl_fe_ctx* c, int n, const uint8_t* images, const uint8_t* masks, const int* use_mask, const int* max_corners,
+                        const double* min_distance, float* corners, float* scores, int* counts) {
+  if (!c || n < 1 || !max_corners || !min_distance || !corners || !scores || !counts) return VPL_E_INVALID;
+  if (!c->ptReserved) return fail(c, VPL_E_INVALID, "vpl_pt_reserve has not been called");
+  if (n > c->maxN) return fail(c, VPL_E_CAPACITY, "more images than max_images");
+  if (!images && n > c->n) return fail(c, VPL_E_INVALID, "no images passed and fewer than n_images in the context");
+  PtBatch& P = c->P;
+  const int MC = P.capCorners;
+  bool any_mask = false;
+  for (int i = 0; i < n; ++i) {
+    if (max_corners[i] < 1 || !(min_distance[i] >= 0.0) || !std::isfinite(min_distance[i]))
+      return fail(c, VPL_E_INVALID, "image " + std::to_string(i) + ": max_corners below 1 or a bad min_distance");
+    if (max_corners[i] > MC) return fail(c, VPL_E_CAPACITY, "image " + std::to_string(i) + ": max_corners above the reserved " + std::to_string(MC));
+    any_mask = any_mask || (masks && (!use_mask || use_mask[i]));
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  const size_t PX = (size_t)c->W * c->H;
+  if (any_mask && !c->d_ptMask) HIPCHK(c, dalloc(c, &c->d_ptMask, (size_t)c->maxN * PX));
+  if (images) { const int rc = vpl_edlines_upload(c, n, images); if (rc) return rc; }
+  if (any_mask) HIPCHK(c, hipMemcpyAsync(c->d_ptMask, masks, (size_t)n * PX, hipMemcpyHostToDevice, s));
+  std::vector<unsigned char> in((size_t)n * 16);
+  {
+    double* md = (double*)in.data();
+    int* um = (int*)(in.data() + (size_t)n * 8);
+    int* mc = um + n;
+    for (int i = 0; i < n; ++i) { md[i] = min_distance[i]; um[i] = (masks && (!use_mask || use_mask[i])) ? 1 : 0; mc[i] = max_corners[i]; }
+  }
+  HIPCHK(c, hipMemcpyAsync(c->d_ptIn, in.data(), in.size(), hipMemcpyHostToDevice, s));
+  P.mask = c->d_ptMask;
+  P.minDist = (const double*)c->d_ptIn;
+  P.useMask = (const int*)(c->d_ptIn + (size_t)n * 8);
+  P.maxCorners = P.useMask + n;
+  P.count = c->d_ptOut;
+  P.found = c->d_ptOut + n;
+  P.corners = (float*)(c->d_ptOut + 2 * (size_t)n);
+  P.scores = P.corners + (size_t)n * MC * 2;
+  { const int rc = pt_detect_launch(c, n); if (rc) return rc; }
+  std::vector<int> out((size_t)n * (2 + 3 * (size_t)MC));
+  HIPCHK(c, hipMemcpyAsync(out.data(), c->d_ptOut, out.size() * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  c->ptN = n;
+  for (int i = 0; i < n; ++i)
+    if (out[i] < 0)
+      return fail(c, VPL_E_CAPACITY, "image " + std::to_string(i) + ": " + std::to_string(out[n + i]) + " corner candidates, max_candidates is " +
+                                         std::to_string(P.capCand));
+  const float* oc = (const float*)(out.data() + 2 * (size_t)n);
+  const float* os = oc + (size_t)n * MC * 2;
+  for (int i = 0; i < n; ++i) {
+    counts[i] = out[i];
+    std::memcpy(corners + (size_t)i * MC * 2, oc + (size_t)i * MC * 2, (size_t)out[i] * 8);
+    std::memcpy(scores + (size_t)i * MC, os + (size_t)i * MC, (size_t)out[i] * 4);
+  }
+  return VPL_OK;
+}
+
+int vpl_pt_debug_detect(vpl_fe_ctx* c, int img, float* eig, int* n_candidates) {
+  if (!c || !c->ptReserved || img < 0 || img >= c->ptN) return VPL_E_INVALID;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const size_t PX = (size_t)c->W * c->H;
+  if (eig) HIPCHK(c, hipMemcpy(eig, c->P.eig + img * PX, PX * 4, hipMemcpyDeviceToHost));
+  if (n_candidates) HIPCHK(c, hipMemcpy(n_candidates, c->P.nCand + img, 4, hipMemcpyDeviceToHost));
+  return VPL_OK;
+}
+
+int vpl_pt_reject_f_batch(vpl_fe_ctx* c, int n, const float* cur_pts, const float* forw_pts, const int* counts, const vpl_pt_camera* cam,
+                          double focal_length, double f_threshold, const unsigned long long* seeds, uint8_t* status) {
+  if (!c || n < 1 || !cur_pts || !forw_pts || !counts || !cam || !seeds || !status) return VPL_E_INVALID;
+  if (!c->ptReserved) return fail(c, VPL_E_INVALID, "vpl_pt_reserve has not been called");
+  if (n > c->maxN) return fail(c, VPL_E_CAPACITY, "more lists than max_images");
+  if (!(cam->fx != 0.0) || !(cam->fy != 0.0) || !(f_threshold > 0.0) || !std::isfinite(focal_length))
+    return fail(c, VPL_E_INVALID, "vpl_pt_reject_f_batch: fx or fy 0, or a threshold that is not positive");
+  const int MP = c->ptMaxPoints;
+  size_t ntab = 0;
+  for (int i = 0; i < n; ++i) {
+    if (counts[i] < 0) return fail(c, VPL_E_INVALID, "list " + std::to_string(i) + ": negative count");
+    if (counts[i] > MP) return fail(c, VPL_E_CAPACITY, "list " + std::to_string(i) + ": more points than the reserved max_points");
+    if (counts[i] >= 8) ntab += (size_t)counts[i] + 1;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  // the one upload: seeds | cur | forw | counts | table offsets | tables
+  const size_t oCur = (size_t)n * 8, oForw = oCur + (size_t)n * MP * 8, oCnt = oForw + (size_t)n * MP * 8, oOff = oCnt + (size_t)n * 4,
+               oTab = oOff + (size_t)n * 4, total = oTab + ntab * 4;
+  std::vector<unsigned char> in(total);
+  std::memcpy(in.data(), seeds, (size_t)n * 8);
+  std::memcpy(in.data() + oCur, cur_pts, (size_t)n * MP * 8);
+  std::memcpy(in.data() + oForw, forw_pts, (size_t)n * MP * 8);
+  std::memcpy(in.data() + oCnt, counts, (size_t)n * 4);
+  {
+    int* off = (int*)(in.data() + oOff);
+    int* tab = (int*)(in.data() + oTab);
+    int at = 0;
+    for (int i = 0; i < n; ++i) {
+      off[i] = at;
+      if (counts[i] >= 8) { relpose_niters_table(counts[i], tab + at); at += counts[i] + 1; }
+    }
+  }
+  HIPCHK(c, hipMemcpyAsync(c->d_rejIn, in.data(), total, hipMemcpyHostToDevice, s));
+  PtRejBatch R;
+  std::memset(&R, 0, sizeof(R));
+  R.seed = (const unsigned long long*)c->d_rejIn;
+  R.cur = (const float*)(c->d_rejIn + oCur); R.forw = (const float*)(c->d_rejIn + oForw);
+  R.cnt = (const int*)(c->d_rejIn + oCnt); R.nitOff = (const int*)(c->d_rejIn + oOff); R.itab = (const int*)(c->d_rejIn + oTab);
+  R.status = c->d_rejStatus; R.maxPts = MP;
+  R.cam = pt_camera(*cam);
+  R.focal = focal_length; R.halfCol = c->W / 2.0; R.halfRow = c->H / 2.0;
+  R.thr2 = f_threshold * f_threshold;
+  { FeTimer t(c, "k_pt_reject_f"); hipLaunchKernelGGL(k_pt_reject_f, dim3(n), dim3(REL_THREADS), 0, s, R); }
+  HIPCHK(c, hipGetLastError());
+  std::vector<uint8_t> out((size_t)n * MP);
+  HIPCHK(c, hipMemcpyAsync(out.data(), c->d_rejStatus, out.size(), hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  for (int i = 0; i < n; ++i) std::memcpy(status + (size_t)i * MP, out.data() + (size_t)i * MP, (size_t)counts[i]);
+  return VPL_OK;
+}
+
+int vpl_pt_flow_batch(vpl_fe_ctx* c, int n, const int* prev_image, const int* next_image, const float* prev_pts, const int* counts,
+                      float* next_pts, uint8_t* status) {
+  if (!c || n < 1 || !prev_image || !next_image || !prev_pts || !counts || !next_pts || !status) return VPL_E_INVALID;
+  if (!c->ptReserved) return fail(c, VPL_E_INVALID, "vpl_pt_reserve has not been called");
+  if (!c->ptFlowReserved) return fail(c, VPL_E_INVALID, "frames no larger than the 21 x 21 window cannot be tracked");
+  if (n > c->maxN) return fail(c, VPL_E_CAPACITY, "more pairs than max_images");
+  if (c->n < 1) return fail(c, VPL_E_INVALID, "no images in the context");
+  const int MP = c->ptMaxPoints;
+  int most = 0;
+  for (int i = 0; i < n; ++i) {
+    if (prev_image[i] < 0 || prev_image[i] >= c->n || next_image[i] < 0 || next_image[i] >= c->n)
+      return fail(c, VPL_E_INVALID, "pair names an image that is not in the context");
+    if (counts[i] < 0) return fail(c, VPL_E_INVALID, "pair " + std::to_string(i) + ": negative count");
+    if (counts[i] > MP) return fail(c, VPL_E_CAPACITY, "pair " + std::to_string(i) + ": more points than the reserved max_points");
+    most = std::max(most, counts[i]);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  const size_t oPts = (size_t)n * 12, total = oPts + (size_t)n * MP * 8;
+  std::vector<unsigned char> in(total);
+  std::memcpy(in.data(), prev_image, (size_t)n * 4);
+  std::memcpy(in.data() + (size_t)n * 4, next_image, (size_t)n * 4);
+  std::memcpy(in.data() + (size_t)n * 8, counts, (size_t)n * 4);
+  std::memcpy(in.data() + oPts, prev_pts, (size_t)n * MP * 8);
+  HIPCHK(c, hipMemcpyAsync(c->d_flowIn, in.data(), total, hipMemcpyHostToDevice, s));
+  c->ptPyr.N = c->n;
+  lm_pyr_launch<PT_WIN>(c, c->ptPyr, "k_lm_pyramid_b21", "k_lm_scharr_b21");
+  const size_t oSt = (size_t)n * MP * 8, outBytes = oSt + (size_t)n * MP;
+  if (most > 0) {
+    PtFlowBatch F;
+    std::memset(&F, 0, sizeof(F));
+    F.P = c->ptPyr;
+    F.nPairs = n; F.maxPts = MP;
+    F.prevImg = (const int*)c->d_flowIn; F.nextImg = F.prevImg + n; F.cnt = F.nextImg + n;
+    F.prev = (const float*)(c->d_flowIn + oPts);
+    F.next = (float*)c->d_flowOut; F.status = c->d_flowOut + oSt;
+    const double eps = std::min(std::max(0.01, 0.), 10.);   // TermCriteria(COUNT + EPS, 30, 0.01), squared as calcOpticalFlowPyrLK does
+    F.epsilon = eps * eps;
+    F.minEigThreshold = 1e-4f;
+    FeTimer t(c, "k_pt_flow");
+    hipLaunchKernelGGL(k_pt_flow, dim3((most + PT_PER_WAVE - 1) / PT_PER_WAVE, n), dim3(64), 0, s, F);
+  }
+  HIPCHK(c, hipGetLastError());
+  std::vector<unsigned char> out(outBytes);
+  if (most > 0) HIPCHK(c, hipMemcpyAsync(out.data(), c->d_flowOut, outBytes, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  for (int i = 0; i < n; ++i) {
+    std::memcpy(next_pts + (size_t)i * MP * 2, out.data() + (size_t)i * MP * 8, (size_t)counts[i] * 8);
+    std::memcpy(status + (size_t)i * MP, out.data() + oSt + (size_t)i * MP, (size_t)counts[i]);
+  }
+  return VPL_OK;
+}
+
 // LineFeatureTracker::readImage, the lists after the match (line_feature_tracker.cpp:109-229).  Plain host code, as in the
 // reference: a few hundred integers per frame.
 int vpl_line_track_ids(int n_new, const float* ends, int n_prev, const int* id_prev, const int* tcnt_prev, int n_tcnt_prev,
@@ -897,3 +1156,4 @@ int vpl_line_track_ids(int n_new, const float* ends, int n_prev, const int* id_p
 }  // extern "C"
 
 #include "trk_session.h"
+#include "pt_session.h"

@@ -45,6 +45,23 @@ class TrackerResult(C.Structure):
                 ("allfeature_cnt", C.c_int)]
 
 
+class PointCamera(C.Structure):
+    """vpl_pt_camera: PinholeCamera with radial-tangential distortion"""
+    _fields_ = [(k, C.c_double) for k in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2")]
+
+
+class PointTrackerOptions(C.Structure):
+    """vpl_ptrk_options"""
+    _fields_ = [("max_cnt", C.c_int), ("min_dist", C.c_int), ("f_threshold", C.c_double), ("focal_length", C.c_double),
+                ("equalize", C.c_int), ("clip_limit", C.c_double), ("tiles_x", C.c_int), ("tiles_y", C.c_int)] + \
+               [(k, C.c_double) for k in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2")]
+
+
+class PointTrackerResult(C.Structure):
+    """vpl_ptrk_result: counts after each stage"""
+    _fields_ = [(k, C.c_int) for k in ("tracked", "after_border", "after_f", "after_mask", "detected", "published")]
+
+
 # numpy view of vpl_line (56 bytes) for bulk packing / unpacking without per-line Python loops
 LINE_DTYPE = np.dtype({"names": ["line_endpoint", "line_equation", "center", "length"],
                        "formats": [("<f4", 4), ("<f8", 3), ("<f4", 2), "<f4"],
@@ -150,6 +167,22 @@ def _bind(lib):
     lib.vpl_trk_get_frame.argtypes = [vp, C.c_int, C.POINTER(C.c_uint8), C.POINTER(Line), ip, ip, ip, ip, ip]
     lib.vpl_trk_debug_ids.argtypes = [vp, C.c_int, fp, C.c_int, ip, ip, C.c_int, ip, C.c_int, C.c_int, ip, ip, ip, ip, ip, ip]
     lib.vpl_fe_debug_allocs.argtypes = [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    dp = C.POINTER(C.c_double)
+    lib.vpl_pt_reserve.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+    lib.vpl_ptrk_default_options.argtypes = [C.POINTER(PointTrackerOptions)]
+    lib.vpl_ptrk_default_options.restype = None
+    lib.vpl_ptrk_create.argtypes = [C.POINTER(vp), vp, C.c_int, C.POINTER(PointTrackerOptions)]
+    lib.vpl_ptrk_destroy.argtypes = [vp]
+    lib.vpl_ptrk_destroy.restype = None
+    lib.vpl_ptrk_set_mask.argtypes = [vp, C.POINTER(C.c_uint8)]
+    lib.vpl_ptrk_reset.argtypes = [vp, C.c_int]
+    lib.vpl_ptrk_frame.argtypes = [vp, C.POINTER(C.c_uint8), dp, ip, C.POINTER(C.c_ulonglong), C.POINTER(PointTrackerResult), ip, dp]
+    lib.vpl_ptrk_get_frame.argtypes = [vp, C.c_int, ip, fp, ip, ip, fp, fp, fp, ip]
+    lib.vpl_pt_flow_batch.argtypes = [vp, C.c_int, ip, ip, fp, ip, fp, C.POINTER(C.c_uint8)]
+    lib.vpl_pt_reject_f_batch.argtypes = [vp, C.c_int, fp, fp, ip, C.POINTER(PointCamera), C.c_double, C.c_double,
+                                          C.POINTER(C.c_ulonglong), C.POINTER(C.c_uint8)]
+    lib.vpl_pt_detect_batch.argtypes = [vp, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), ip, ip, dp, fp, fp, ip]
+    lib.vpl_pt_debug_detect.argtypes = [vp, C.c_int, fp, ip]
     _bound = True
 
 
@@ -180,6 +213,8 @@ class FrontendContext:
     def close(self):
         if self.h and getattr(self, "_trk", None) is not None:
             self._trk.close()                      # the session goes before the context it borrows
+        if self.h and getattr(self, "_ptrk", None) is not None:
+            self._ptrk.close()
         if self.h:
             bad = self.debug_guards() if os.environ.get("VPL_DEBUG_GUARDS") == "1" else 0
             msg = self.lib.vpl_fe_last_error(self.h).decode() if bad else ""
@@ -438,6 +473,98 @@ class FrontendContext:
                     "vpl_match_debug_level")
         return px, d
 
+    # ---- point front-end: goodFeaturesToTrack (cvmodified.cpp:38-216) ---------------------------------------
+    def pt_reserve(self, max_candidates=8192, max_corners=256, max_points=256):
+        self.pt_max_candidates, self.pt_max_corners, self.pt_max_points = max_candidates, max_corners, max_points
+        self._check(self.lib.vpl_pt_reserve(self.h, max_candidates, max_corners, max_points), "vpl_pt_reserve")
+
+    def _pack_points(self, lists):
+        n, MP = len(lists), self.pt_max_points
+        a = np.zeros((n, MP, 2), np.float32)
+        cnt = np.zeros(n, np.int32)
+        for i, l in enumerate(lists):
+            l = np.asarray(l, np.float32).reshape(-1, 2)
+            cnt[i] = len(l)
+            if len(l) <= MP:               # otherwise the library reports VPL_E_CAPACITY
+                a[i, :len(l)] = l
+        return a, cnt
+
+    def pt_flow(self, pairs, prev_pts):
+        """calcOpticalFlowPyrLK(21 x 21, 3 levels) on the frames in the context's slots (upload() / pre_run()): pairs a list of
+        (prev image, next image), prev_pts per pair a [k][2] array.  Returns per pair (next_pts [k][2] float32, status [k] uint8)."""
+        n = len(pairs)
+        pi = np.ascontiguousarray([p[0] for p in pairs], np.int32)
+        ni = np.ascontiguousarray([p[1] for p in pairs], np.int32)
+        prev, cnt = self._pack_points(prev_pts)
+        assert len(cnt) == n
+        nxt = np.zeros_like(prev)
+        status = np.zeros((n, self.pt_max_points), np.uint8)
+        ip, fp = C.POINTER(C.c_int), C.POINTER(C.c_float)
+        self._check(self.lib.vpl_pt_flow_batch(self.h, n, pi.ctypes.data_as(ip), ni.ctypes.data_as(ip), prev.ctypes.data_as(fp),
+                                               cnt.ctypes.data_as(ip), nxt.ctypes.data_as(fp), status.ctypes.data_as(C.POINTER(C.c_uint8))),
+                    "vpl_pt_flow_batch")
+        return [(nxt[i, :cnt[i]].copy(), status[i, :cnt[i]].copy()) for i in range(n)]
+
+    def pt_reject_f(self, cur_pts, forw_pts, camera, seeds, focal_length=460.0, f_threshold=1.0):
+        """rejectWithF for a batch: cur_pts / forw_pts lists of [k][2] arrays, camera a PointCamera, seeds one per list.
+        Returns per list the 0 / 1 status [k] (uint8)."""
+        cur, cnt = self._pack_points(cur_pts)
+        forw, cnt2 = self._pack_points(forw_pts)
+        assert np.array_equal(cnt, cnt2)
+        n = len(cnt)
+        seeds = np.ascontiguousarray(seeds, np.uint64)
+        assert seeds.shape == (n,)
+        status = np.zeros((n, self.pt_max_points), np.uint8)
+        ip, fp = C.POINTER(C.c_int), C.POINTER(C.c_float)
+        self._check(self.lib.vpl_pt_reject_f_batch(self.h, n, cur.ctypes.data_as(fp), forw.ctypes.data_as(fp), cnt.ctypes.data_as(ip),
+                                                   C.byref(camera), focal_length, f_threshold,
+                                                   seeds.ctypes.data_as(C.POINTER(C.c_ulonglong)), status.ctypes.data_as(C.POINTER(C.c_uint8))),
+                    "vpl_pt_reject_f_batch")
+        return [status[i, :cnt[i]].copy() for i in range(n)]
+
+    def pt_detect(self, images, max_corners, min_distance, masks=None):
+        """images [n][H][W] uint8 (None: the frames in the context's slots, n = len(max_corners)); max_corners, min_distance:
+        a number or one per image; masks: None, or a list with per image an [H][W] plane (non-zero = allowed) or None.
+        Returns per image (corners [k][2] float32, scores [k] float32)."""
+        u8 = C.POINTER(C.c_uint8)
+        if images is not None:
+            images = np.ascontiguousarray(images, np.uint8)
+            assert images.ndim == 3 and images.shape[1:] == (self.H, self.W)
+            n = images.shape[0]
+            self.n = n
+        else:
+            n = len(max_corners)
+        mc = np.ascontiguousarray(np.broadcast_to(np.asarray(max_corners, np.int32), (n,)))
+        md = np.ascontiguousarray(np.broadcast_to(np.asarray(min_distance, np.float64), (n,)))
+        mp, up = None, None
+        if masks is not None and any(m is not None for m in masks):
+            assert len(masks) == n
+            planes = np.zeros((n, self.H, self.W), np.uint8)
+            use = np.zeros(n, np.int32)
+            for i, m in enumerate(masks):
+                if m is not None:
+                    planes[i] = np.asarray(m, np.uint8)
+                    use[i] = 1
+            mp, up = planes.ctypes.data_as(u8), use.ctypes.data_as(C.POINTER(C.c_int))
+        MC = self.pt_max_corners
+        corners = np.zeros((n, MC, 2), np.float32)
+        scores = np.zeros((n, MC), np.float32)
+        counts = np.zeros(n, np.int32)
+        ip, fp = C.POINTER(C.c_int), C.POINTER(C.c_float)
+        self._check(self.lib.vpl_pt_detect_batch(self.h, n, images.ctypes.data_as(u8) if images is not None else None, mp, up,
+                                                 mc.ctypes.data_as(ip), md.ctypes.data_as(C.POINTER(C.c_double)),
+                                                 corners.ctypes.data_as(fp), scores.ctypes.data_as(fp), counts.ctypes.data_as(ip)),
+                    "vpl_pt_detect_batch")
+        return [(corners[i, :counts[i]].copy(), scores[i, :counts[i]].copy()) for i in range(n)]
+
+    def pt_debug_detect(self, img):
+        """test access: (cornerMinEigenVal plane [H][W] float32, candidates found) of frame `img` of the last pt_detect"""
+        eig = np.zeros((self.H, self.W), np.float32)
+        nc = C.c_int(0)
+        self._check(self.lib.vpl_pt_debug_detect(self.h, img, eig.ctypes.data_as(C.POINTER(C.c_float)), C.byref(nc)),
+                    "vpl_pt_debug_detect")
+        return eig, nc.value
+
 
 def default_tracker_options(max_h_lines=25, max_v_lines=25, fx=1.0, fy=1.0, cx=0.0, cy=0.0, equalize=True):
     """vpl_trk_default_options with the quota and K_ filled in"""
@@ -513,3 +640,91 @@ class TrackerSession:
                                              ids.ctypes.data_as(ip), tc.ctypes.data_as(ip), C.byref(n_tc), match.ctypes.data_as(ip),
                                              vpi.ctypes.data_as(ip)), "vpl_trk_get_frame")
         return dict(img=img, lines=rec, ids=ids, t_cnt=tc[:n_tc.value].copy(), match=match, vp_ids=vpi)
+
+
+def default_point_tracker_options(camera=None, **kw):
+    """vpl_ptrk_default_options (150 points, min_dist 30, F threshold 1, focal length 460, CLAHE 3.0 8 x 8) with the camera
+    (fx, fy, cx, cy, k1, k2, p1, p2) and any field given by name filled in"""
+    lib = load_hip_library()
+    _bind(lib)
+    o = PointTrackerOptions()
+    lib.vpl_ptrk_default_options(C.byref(o))
+    if camera is not None:
+        o.fx, o.fy, o.cx, o.cy, o.k1, o.k2, o.p1, o.p2 = camera
+    for k, val in kw.items():
+        setattr(o, k, val)
+    return o
+
+
+class PointTrackerSession:
+    """vpl_ptrk_*: FeatureTracker::readImage for n_seq cameras with the tracker's lists resident on the device.  Borrows a
+    FrontendContext made with max_images >= 2 * n_seq on which pt_reserve(max_corners, max_points >= max_cnt) was called."""
+
+    def __init__(self, fe, n_seq, options=None):
+        self.fe, self.lib, self.n_seq = fe, fe.lib, n_seq
+        self.opt = options or default_point_tracker_options()
+        self.h = C.c_void_p()
+        fe._check(self.lib.vpl_ptrk_create(C.byref(self.h), fe.h, n_seq, C.byref(self.opt)), "vpl_ptrk_create")
+        fe._ptrk = self
+        MP = fe.pt_max_points
+        self._res = (PointTrackerResult * n_seq)()
+        self._ids = np.zeros((n_seq, MP), np.int32)
+        self._rows = np.zeros((n_seq, MP, 7))
+
+    def close(self):
+        if self.h:
+            self.lib.vpl_ptrk_destroy(self.h)
+            self.h = C.c_void_p()
+            if getattr(self.fe, "_ptrk", None) is self:
+                self.fe._ptrk = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_mask(self, plane):
+        p = None if plane is None else np.ascontiguousarray(plane, np.uint8)
+        assert p is None or p.shape == (self.fe.H, self.fe.W)
+        self.fe._check(self.lib.vpl_ptrk_set_mask(self.h, None if p is None else p.ctypes.data_as(C.POINTER(C.c_uint8))), "vpl_ptrk_set_mask")
+
+    def reset(self, seq):
+        self.fe._check(self.lib.vpl_ptrk_reset(self.h, seq), "vpl_ptrk_reset")
+
+    def frame(self, raw, time, publish, seed):
+        """raw [n_seq][H][W] uint8, time / publish / seed [n_seq] -> per sequence a dict: the fields of vpl_ptrk_result, `ids`
+        [published] and `rows` [published][7] (x, y undistorted, u, v, vx, vy, prob): ids and rows[:, :2] with a 1 behind them are
+        what vpl_odo_frame takes as pt_id / pt_xy1"""
+        raw = np.ascontiguousarray(raw, np.uint8)
+        assert raw.shape == (self.n_seq, self.fe.H, self.fe.W)
+        tm = np.ascontiguousarray(time, np.float64)
+        pub = np.ascontiguousarray(publish, np.int32)
+        sd = np.ascontiguousarray(seed, np.uint64)
+        assert tm.shape == pub.shape == sd.shape == (self.n_seq,)
+        self.fe._check(self.lib.vpl_ptrk_frame(self.h, raw.ctypes.data_as(C.POINTER(C.c_uint8)), tm.ctypes.data_as(C.POINTER(C.c_double)),
+                                               pub.ctypes.data_as(C.POINTER(C.c_int)), sd.ctypes.data_as(C.POINTER(C.c_ulonglong)),
+                                               self._res, self._ids.ctypes.data_as(C.POINTER(C.c_int)),
+                                               self._rows.ctypes.data_as(C.POINTER(C.c_double))), "vpl_ptrk_frame")
+        out = []
+        for s in range(self.n_seq):
+            r = self._res[s]
+            d = {f: getattr(r, f) for f, _ in PointTrackerResult._fields_}
+            d["ids"] = self._ids[s, :r.published].copy()
+            d["rows"] = self._rows[s, :r.published].copy()
+            out.append(d)
+        return out
+
+    def get_frame(self, seq):
+        """test access: the tracker's lists after the last accepted call"""
+        MP = self.fe.pt_max_points
+        n, nid = C.c_int(0), C.c_int(0)
+        pts, un = np.zeros((MP, 2), np.float32), np.zeros((MP, 2), np.float32)
+        ids, cnt = np.zeros(MP, np.int32), np.zeros(MP, np.int32)
+        sc, usc = np.zeros(MP, np.float32), np.zeros(MP, np.float32)
+        ip, fp = C.POINTER(C.c_int), C.POINTER(C.c_float)
+        self.fe._check(self.lib.vpl_ptrk_get_frame(self.h, seq, C.byref(n), pts.ctypes.data_as(fp), ids.ctypes.data_as(ip),
+                                                   cnt.ctypes.data_as(ip), sc.ctypes.data_as(fp), un.ctypes.data_as(fp),
+                                                   usc.ctypes.data_as(fp), C.byref(nid)), "vpl_ptrk_get_frame")
+        m = n.value
+        return dict(n=m, pts=pts[:m], ids=ids[:m], track_cnt=cnt[:m], scores=sc[:m], un_pts=un[:m], un_scores=usc[:m], next_id=nid.value)
