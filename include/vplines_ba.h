@@ -973,6 +973,73 @@ int vpl_ba_debug_point_units(int n_points, const int* point_start, const int* po
                              int* lane_table, int* unit_table, int* rounds, int* rounds0);
 int vpl_ba_debug_point_chains(const int* unit_table, int rounds, int rounds0, int marg_pass);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Loop verification: KeyFrame::findConnection from the PnP on (pose_graph/src/keyframe.cpp:406-516) for a batch of
+ * (current keyframe, candidate) pairs, on the lists already reduced by the descriptor match (vpl_lc_match_batch of
+ * vplines_frontend.h and the reduceVector calls behind it).  In the reference's order:
+ *   1. count > min_loop_num, or nothing runs (stage VPL_LOOP_FEW_POINTS, has_loop 0, status all 0);
+ *   2. PnPRANSAC (:200-256): cv::solvePnPRansac(pts3d, old_norm, K = I, no distortion, useExtrinsicGuess = true, max_iters,
+ *      reproj_error, confidence) from the guess R_w_c^-1, -R_w_c^-1 T_w_c of the current camera (origin_vio_R qic,
+ *      origin_vio_T + origin_vio_R tic); status = its inliers; PnP_R_old = R_pnp^T qic^T, PnP_T_old = -R_pnp^T t_pnp - PnP_R_old tic;
+ *   3. the number of inliers > min_loop_num (else VPL_LOOP_FEW_INLIERS: pose and status stand, has_loop 0);
+ *   4. relative_t = PnP_R_old^T (origin_vio_T - PnP_T_old), relative_q = Quaterniond(PnP_R_old^T origin_vio_R),
+ *      relative_yaw = normalizeAngle(R2ypr(origin_vio_R).x - R2ypr(PnP_R_old).x) in degrees -> loop_info [8] = t, q (w x y z), yaw
+ *      (written whenever step 4 is reached; the reference stores it only when the loop is accepted);
+ *   5. has_loop = |relative_yaw| < max_yaw_deg and |relative_t| < max_t (else VPL_LOOP_REJECTED).
+ * The RANSAC is stated as vpl_init_relative_pose_batch states its own -- OpenCV is not available to compare against:
+ *   sample    five distinct indices (OpenCV's model_points for more than four points) from the integer stream of
+ *             vpl_relpose_debug_plan with candidate 0 and the item's seed (csrc/loop_plan.h; vpl_loop_debug_plan hands it out);
+ *   model     not OpenCV's minimal solver but the PnP of vpl_init_structure_batch (the Levenberg-Marquardt minimiser sfm_lm, the
+ *             points constant, six free dims) on the five points, started from the extrinsic guess; a solve that ends in FAILURE
+ *             yields no model;
+ *   error     the squared reprojection distance in the normalised plane, compared in double with reproj_error^2 (<=);
+ *   update    a model replaces the best only with strictly more inliers (and more than four); the iteration cap is then read
+ *             from RANSACUpdateNumIters(confidence, (N - good) / N, 5, max_iters) and never rises;
+ *   final     the same minimiser on all inliers of the best model, started from that model; status is the best model's mask;
+ *             a final solve that ends in FAILURE is VPL_LOOP_NUMERIC (has_loop 0, the pose is not written);
+ *   no model  when no sample yields one: VPL_LOOP_NO_MODEL, has_loop 0, status all 0.
+ * The result is that of the sequential loop over the stream.  No max_solver_time; rotations travel as quaternions (mat2q), not
+ * through cv::Rodrigues.  count <= VPL_LOOP_MAX_POINTS; n <= max_windows.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define VPL_LOOP_MAX_POINTS 1024
+#define VPL_LOOP_MAX_ITERS 1000       /* the largest max_iters accepted */
+#define VPL_LOOP_FEW_POINTS 0
+#define VPL_LOOP_NO_MODEL 1
+#define VPL_LOOP_NUMERIC 2
+#define VPL_LOOP_FEW_INLIERS 3
+#define VPL_LOOP_REJECTED 4
+#define VPL_LOOP_CLOSED 5
+typedef struct vpl_loop_options {
+  int min_loop_num;        /* MIN_LOOP_NUM = 25 */
+  int max_iters;           /* 100 */
+  double reproj_error;     /* 10.0 / 460.0 */
+  double confidence;       /* 0.99 */
+  double max_yaw_deg;      /* 30 */
+  double max_t;            /* 20 */
+} vpl_loop_options;
+void vpl_loop_default_options(vpl_loop_options* opt);
+typedef struct vpl_loop_input {
+  int count;
+  const float* pts3d;      /* [count][3] matched_3d, as cv::Point3f holds them */
+  const float* old_norm;   /* [count][2] matched_2d_old_norm, as cv::Point2f holds them */
+  double origin_vio_T[3], origin_vio_R[9], tic[3], qic[9];   /* matrices row-major */
+  unsigned long long seed;
+} vpl_loop_input;
+typedef struct vpl_loop_result {
+  int has_loop, stage;                 /* VPL_LOOP_* : where findConnection ended */
+  int ransac_iterations, best_inliers; /* iterations the loop ran | inliers of the best model = entries set in status */
+  int lm_iterations, lm_termination;   /* the final solve: ceres-style iteration count, vpl_solve_report's termination codes */
+  double PnP_T_old[3], PnP_R_old[9], loop_info[8];
+} vpl_loop_result;
+/* in [n], out [n]; status [n][VPL_LOOP_MAX_POINTS] bytes, the first count entries of a row are written.  One copy each way, one
+ * synchronisation.  VPL_E_INVALID: null pointers, a negative count, options out of range (max_iters outside 1 .. VPL_LOOP_MAX_ITERS,
+ * min_loop_num < 4, reproj_error or confidence not in (0, ..)); VPL_E_CAPACITY: count > VPL_LOOP_MAX_POINTS, n > max_windows. */
+int vpl_loop_verify_batch(vpl_ctx* ctx, int n, const vpl_loop_input* in, const vpl_loop_options* opt, vpl_loop_result* out,
+                          unsigned char* status);
+/* host only: samples [max_iters][5] of the stream for a list of n_points and niters_after [n_points + 1].
+ * VPL_E_INVALID: n_points < 5, max_iters outside 1 .. VPL_LOOP_MAX_ITERS, a null array; VPL_E_CAPACITY: n_points > VPL_LOOP_MAX_POINTS */
+int vpl_loop_debug_plan(unsigned long long seed, int n_points, double confidence, int max_iters, int* samples, int* niters_after);
+
 #ifdef __cplusplus
 }
 #endif

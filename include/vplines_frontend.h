@@ -45,6 +45,7 @@ typedef struct vpl_fe_ctx vpl_fe_ctx;   /* opaque: device buffers for a batch of
 
 void vpl_edline_default_param(vpl_edline_param* p);   /* {5, 1, 30, 5, 2, 35, 1.8} */
 
+/* width, height >= 7 (the smallest frame with a FAST candidate, vpl_lc_keyframe_batch); the line detector takes frames from 8 x 8 */
 int vpl_fe_create(vpl_fe_ctx** out, int device, int max_images, int width, int height, int max_lines_per_image);
 void vpl_fe_destroy(vpl_fe_ctx* ctx);
 int vpl_fe_set_stream(vpl_fe_ctx* ctx, void* hip_stream);   /* (work in flight on the stream used so far is completed first) */
@@ -401,6 +402,57 @@ int vpl_ptrk_frame(vpl_ptrk* trk, const uint8_t* raw, const double* time, const 
                    vpl_ptrk_result* res, int* row_id, double* rows);
 int vpl_ptrk_get_frame(vpl_ptrk* trk, int seq, int* n, float* pts, int* ids, int* track_cnt, float* scores, float* un_pts,
                        float* un_scores, int* next_id);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Loop-closure front-end: what a pose_graph KeyFrame computes from its image, and the descriptor search of a loop candidate,
+ * for a batch of frames / of pairs.  Stage calls, host in and host out; nothing depends on where an item sits in the batch and
+ * the same inputs give the same bits twice.
+ *   KeyFrame::KeyFrame (pose_graph/src/keyframe.cpp:14-41): computeWindowBRIEFPoint (:75-85) and computeBRIEFPoint (:87-113)
+ *        -> vpl_lc_keyframe_batch
+ *   KeyFrame::searchByBRIEFDes / searchInAera (:121-171), the first step of findConnection (:259-520)
+ *        -> vpl_lc_match_batch
+ * vpl_lc_reserve (once per context) fixes the row length max_keypoints of a frame's FAST list (1 .. 65535: an index travels in
+ * 16 bits of the search key) and max_window_points of a window point list (1 .. 1024).  The 15 EuRoC frames (752 x 480) under
+ * tests/golden hold 2572 .. 3330 FAST corners at threshold 20; 8192 is a comfortable row for such frames.  A frame with more corners
+ * than the row holds is refused -- VPL_E_CAPACITY for the call, the frame and its count in vpl_fe_last_error, no output written
+ * -- never cut short.
+ * vpl_lc_set_pattern: the BRIEF test pairs as integers (the reference reads them from its settings file brief_pattern.yml:
+ * x1, y1, x2, y2).  n_bits must be 256.  The library ships no pattern: vpl_lc_keyframe_batch before it is VPL_E_INVALID.
+ * A descriptor is four 64-bit words; bit i of the reference's bitset is bit i % 64 of word i / 64.
+ *
+ * vpl_lc_keyframe_batch:
+ *   images       [n][H][W], or NULL: the n frames in the context's image slots
+ *   window_pts   [n][max_window_points][2] the window's tracked points in pixels (point_2d_uv);  window_counts [n] (0 is allowed)
+ *   cam          the camera model of m_camera->liftProjective;  fast_threshold: 20 in the reference (0 .. 255)
+ *   keypoints      [n][max_keypoints][2] cv::FAST(image, keypoints, fast_threshold, true): pixel positions in raster order
+ *   keypoints_norm [n][max_keypoints][2] the lifted x / z, y / z rounded to float as cv::Point2f does
+ *   kp_counts [n];  brief [n][max_keypoints][4];  window_brief [n][max_window_points][4]
+ *   Rows past kp_counts[i] / window_counts[i] are left as they were.
+ * Two copies down (the frames when passed, the window lists), one copy back, one synchronisation.
+ * What OpenCV leaves to its version or build is stated in csrc/lc_kernels.h, from its description and not pinned by a run: the
+ * float arithmetic of GaussianBlur(9 x 9, sigma 2), and FAST's score and list order.
+ * vpl_lc_debug_frame: test access to frame `img` of the last call (any pointer may be NULL): the blurred plane [H*W] and the
+ * FAST score plane [H*W] (0 = no corner).
+ *
+ * vpl_lc_match_batch, per pair (n_pairs <= max_images):
+ *   window_brief [n][max_window_points][4], window_counts [n]: the current keyframe's window descriptors
+ *   old_brief [n][max_keypoints][4], old_keypoints, old_keypoints_norm [n][max_keypoints][2], old_counts [n]: the candidate's
+ *   matched_2d_old, matched_2d_old_norm [n][max_window_points][2]: the old point of least Hamming distance among those below 128
+ *   (the first index on a tie), taken when that distance is below 80, else (0, 0);  status [n][max_window_points] 1 / 0
+ *   best_dist, best_index [n][max_window_points] (may be NULL; tests): 128 / -1 when no distance was below 128
+ *   The first window_counts[i] entries of a row are written.  Counts of 0 are legal on either side.
+ * One copy each way, one synchronisation.
+ * ------------------------------------------------------------------------------------------------------------ */
+int vpl_lc_reserve(vpl_fe_ctx* ctx, int max_keypoints, int max_window_points);
+int vpl_lc_set_pattern(vpl_fe_ctx* ctx, int n_bits, const int* x1, const int* y1, const int* x2, const int* y2);
+int vpl_lc_keyframe_batch(vpl_fe_ctx* ctx, int n_images, const uint8_t* images, const float* window_pts, const int* window_counts,
+                          const vpl_pt_camera* cam, int fast_threshold, float* keypoints, float* keypoints_norm, int* kp_counts,
+                          unsigned long long* brief, unsigned long long* window_brief);
+int vpl_lc_debug_frame(vpl_fe_ctx* ctx, int img, uint8_t* blurred, uint8_t* score);
+int vpl_lc_match_batch(vpl_fe_ctx* ctx, int n_pairs, const unsigned long long* window_brief, const int* window_counts,
+                       const unsigned long long* old_brief, const float* old_keypoints, const float* old_keypoints_norm,
+                       const int* old_counts, float* matched_2d_old, float* matched_2d_old_norm, uint8_t* status, int* best_dist,
+                       int* best_index);
 
 #ifdef __cplusplus
 }

@@ -258,6 +258,66 @@ def relpose_debug_plan(seed, i, N):
     return dict(samples=samples, niters_after=table) if rc == 0 else rc
 
 
+LOOP_MAX_POINTS, LOOP_MAX_ITERS = 1024, 1000   # VPL_LOOP_MAX_POINTS, VPL_LOOP_MAX_ITERS
+LOOP_FEW_POINTS, LOOP_NO_MODEL, LOOP_NUMERIC, LOOP_FEW_INLIERS, LOOP_REJECTED, LOOP_CLOSED = 0, 1, 2, 3, 4, 5
+
+
+class LoopOptions(C.Structure):   # vpl_loop_options
+    _fields_ = [("min_loop_num", C.c_int), ("max_iters", C.c_int), ("reproj_error", C.c_double), ("confidence", C.c_double),
+                ("max_yaw_deg", C.c_double), ("max_t", C.c_double)]
+
+
+def default_loop_options():
+    o = LoopOptions()
+    load_hip_library().vpl_loop_default_options(C.byref(o))
+    return o
+
+
+class CLoopInput(C.Structure):   # vpl_loop_input
+    _fields_ = [("count", C.c_int), ("pts3d", C.POINTER(C.c_float)), ("old_norm", C.POINTER(C.c_float)), ("origin_vio_T", C.c_double * 3),
+                ("origin_vio_R", C.c_double * 9), ("tic", C.c_double * 3), ("qic", C.c_double * 9), ("seed", C.c_ulonglong)]
+
+
+class LoopResult(C.Structure):   # vpl_loop_result
+    _fields_ = [("has_loop", C.c_int), ("stage", C.c_int), ("ransac_iterations", C.c_int), ("best_inliers", C.c_int),
+                ("lm_iterations", C.c_int), ("lm_termination", C.c_int), ("PnP_T_old", C.c_double * 3), ("PnP_R_old", C.c_double * 9),
+                ("loop_info", C.c_double * 8)]
+
+
+class LoopInput:
+    """numpy-backed owner of one vpl_loop_input: the lists findConnection has reduced by the match status -- pts3d [k][3],
+    old_norm [k][2], kept as float32 -- the current keyframe's origin_vio_T / origin_vio_R, the extrinsics tic / qic (matrices
+    [3][3]) and the seed of the sample stream."""
+
+    def __init__(self, pts3d, old_norm, origin_vio_T, origin_vio_R, tic, qic, seed=0):
+        self.pts3d = _arr(pts3d, np.float32).reshape(-1, 3).copy()
+        self.old_norm = _arr(old_norm, np.float32).reshape(-1, 2).copy()
+        if len(self.pts3d) != len(self.old_norm):
+            raise ValueError("LoopInput: %d points, %d observations" % (len(self.pts3d), len(self.old_norm)))
+        self.origin_vio_T, self.tic = (_arr(a, np.float64).reshape(3).copy() for a in (origin_vio_T, tic))
+        self.origin_vio_R, self.qic = (_arr(a, np.float64).reshape(3, 3).copy() for a in (origin_vio_R, qic))
+        self.seed = int(seed)
+
+    def to_c(self, ci=None):
+        ci = ci if ci is not None else CLoopInput()
+        ci.count, ci.seed = len(self.pts3d), self.seed
+        fp = C.POINTER(C.c_float)
+        ci.pts3d, ci.old_norm = self.pts3d.ctypes.data_as(fp), self.old_norm.ctypes.data_as(fp)
+        ci.origin_vio_T[:], ci.tic[:] = self.origin_vio_T.tolist(), self.tic.tolist()
+        ci.origin_vio_R[:], ci.qic[:] = self.origin_vio_R.ravel().tolist(), self.qic.ravel().tolist()
+        return ci
+
+
+def loop_debug_plan(seed, N, confidence=0.99, max_iters=100):
+    """vpl_loop_debug_plan (host only): the five-point sample stream and the stopping table of a list of N points -> dict samples
+    [max_iters, 5], niters_after [N + 1]; the VPL_E_* code instead when the arguments are refused"""
+    lib = load_hip_library()
+    samples = np.zeros((max(int(max_iters), 1), 5), dtype=np.int32)
+    table = np.zeros(max(int(N), 0) + 1, dtype=np.int32)
+    rc = lib.vpl_loop_debug_plan(int(seed), int(N), float(confidence), int(max_iters), samples.ctypes.data_as(_ip), table.ctypes.data_as(_ip))
+    return dict(samples=samples, niters_after=table) if rc == 0 else rc
+
+
 SEL_MAX_FEATURES = 1024   # VPL_SEL_MAX_FEATURES
 
 
@@ -592,6 +652,10 @@ def load_hip_library():
     _bp = C.POINTER(C.c_ubyte)
     lib.vpl_init_relative_pose_batch.argtypes = [vp, C.c_int, C.POINTER(CRelPoseInput), C.POINTER(RelPoseResult), _bp, _bp, _ip]
     lib.vpl_relpose_debug_plan.argtypes = [C.c_ulonglong, C.c_int, C.c_int, _ip, _ip]
+    lib.vpl_loop_default_options.argtypes = [C.POINTER(LoopOptions)]
+    lib.vpl_loop_default_options.restype = None
+    lib.vpl_loop_verify_batch.argtypes = [vp, C.c_int, C.POINTER(CLoopInput), C.POINTER(LoopOptions), C.POINTER(LoopResult), _bp]
+    lib.vpl_loop_debug_plan.argtypes = [C.c_ulonglong, C.c_int, C.c_double, C.c_int, _ip, _ip]
     lib.vpl_init_visual_batch.argtypes = [vp, C.c_int, C.POINTER(CSfmInput), C.POINTER(C.c_ulonglong), C.POINTER(RelPoseResult),
                                           C.POINTER(SfmResult), _dp, _dp, _ip, _dp]
     lib.vpl_select_features_batch.argtypes = [vp, C.c_int, C.POINTER(SelectParams), C.POINTER(CSelectInput), C.POINTER(SelectResult), _ip, _dp]
@@ -973,6 +1037,27 @@ class Context:
             return rc
         self._check(rc, "vpl_init_relative_pose_batch")
         return res, m0, m1, hyp
+
+    def loop_verify(self, inputs, options=None, check=True):
+        """vpl_loop_verify_batch over a list of LoopInput: KeyFrame::findConnection from the PnP RANSAC on -- the inliers, PnP_T_old
+        / PnP_R_old, loop_info and has_loop of every item -- in one call.  -> (results [n] of LoopResult, status per item [count]
+        uint8).  check=False: a refusal comes back as its VPL_E_* code instead of an exception."""
+        self._settle()
+        n = len(inputs)
+        ci = (CLoopInput * n)()
+        for i, q in enumerate(inputs):
+            if isinstance(q, CLoopInput):
+                C.memmove(C.byref(ci[i]), C.byref(q), C.sizeof(CLoopInput))   # as the caller filled it (tests of the refusals)
+            else:
+                q.to_c(ci[i])
+        opt = options if options is not None else default_loop_options()
+        res = (LoopResult * n)()
+        st = np.zeros((n, LOOP_MAX_POINTS), dtype=np.uint8)
+        rc = self.lib.vpl_loop_verify_batch(self.h, n, ci, C.byref(opt), res, st.ctypes.data_as(C.POINTER(C.c_ubyte)))
+        if rc != 0 and not check:
+            return rc
+        self._check(rc, "vpl_loop_verify_batch")
+        return res, [st[i, :ci[i].count].copy() for i in range(n)]
 
     @staticmethod
     def _select_c(params, inputs):

@@ -41,6 +41,7 @@ using namespace vpl;
 #include "init_align_host.h"
 #include "init_sfm_host.h"
 #include "init_relpose_host.h"
+#include "loop_host.h"
 #include "sel_host.h"
 
 template <typename Launch>

@@ -15,6 +15,7 @@
 #include "lm_kernels.h"
 #include "pre_kernels.h"
 #include "pt_kernels.h"
+#include "lc_kernels.h"
 #include "vp_kernels.h"
 
 using namespace vpl;
@@ -65,6 +66,15 @@ struct vpl_fe_ctx {
   bool ptFlowReserved = false;
   unsigned char* d_flowIn = nullptr;  // one call's upload: prevImg [n], nextImg [n], counts [n], prev [n][ptMaxPoints][2]
   unsigned char* d_flowOut = nullptr; // one call's results: next [n][ptMaxPoints][2] floats, status [n][ptMaxPoints]
+  // loop-closure front-end (vpl_lc_reserve)
+  LcBatch L;
+  bool lcReserved = false, lcPattern = false;
+  int* d_lcPat = nullptr;             // [4][256] the BRIEF test pairs
+  unsigned char* d_lcIn = nullptr;    // vpl_lc_keyframe_batch: window points [n][capWin][2] floats, window counts [n]
+  unsigned char* d_lcOut = nullptr;   // its results (lc_out_layout)
+  unsigned char* d_lcmIn = nullptr;   // vpl_lc_match_batch: the one upload (lc_match_layout)
+  unsigned char* d_lcmOut = nullptr;  // its results
+  int lcN = 0;                        // frames of the last vpl_lc_keyframe_batch (vpl_lc_debug_frame)
   std::vector<DevAlloc> allocs;      // host_common.h: the context's own arrays (owner null, the lazy ones included) and the tracker session's
   bool guards = false;
   std::string err;
@@ -148,7 +158,8 @@ __global__ __launch_bounds__(256) void k_lm_take_lines(const vpl_line* sorted, c
 }
 
 int vpl_fe_create(vpl_fe_ctx** out, int device, int max_images, int width, int height, int max_lines_per_image) {
-  if (!out || max_images < 1 || width < 8 || height < 8 || max_lines_per_image < 1) return VPL_E_INVALID;
+  // (7 x 7: the smallest frame with a FAST candidate; the line detector itself takes frames from 8 x 8, ed_launch)
+  if (!out || max_images < 1 || width < 7 || height < 7 || max_lines_per_image < 1) return VPL_E_INVALID;
   int nd = 0;
   if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0 || device >= nd) return VPL_E_NODEVICE;
   if (hipSetDevice(device) != hipSuccess) return VPL_E_NODEVICE;
@@ -418,6 +429,7 @@ int vpl_fe_keep_blurred(vpl_fe_ctx* c, int enable) {
 // EDLineDetector::EDline(image, lines, smoothed) for image slots [0, n) (edline_detector.cpp:1176-1198 -> EdgeDrawing :81-710)
 static int ed_launch(vpl_fe_ctx* c, const vpl_edline_param* p, int smoothed, int n) {
   if (p->scanIntervals < 1 || p->minLineLen < 2) return fail(c, VPL_E_INVALID, "bad EDLine parameters");
+  if (c->W < 8 || c->H < 8) return fail(c, VPL_E_INVALID, "the line detector takes frames of at least 8 x 8");
   EdBatch& B = c->B;
   // member types of EDLineDetector: short gradienThreshold_, unsigned char anchorThreshold_ (edline_detector.h:113-117)
   B.gradTh = (int)(short)p->gradientThreshold;
@@ -1105,6 +1117,205 @@ int vpl_pt_flow_batch(vpl_fe_ctx* c, int n, const int* prev_image, const int* ne
   for (int i = 0; i < n; ++i) {
     std::memcpy(next_pts + (size_t)i * MP * 2, out.data() + (size_t)i * MP * 8, (size_t)counts[i] * 8);
     std::memcpy(status + (size_t)i * MP, out.data() + oSt + (size_t)i * MP, (size_t)counts[i]);
+  }
+  return VPL_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Loop-closure front-end (lc_kernels.h)
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+// one call's results of vpl_lc_keyframe_batch for n frames: brief | window brief | keypoints | keypoints_norm | count | found
+struct LcOutLayout { size_t brief, winBrief, kp, kpNorm, count, found, total; };
+LcOutLayout lc_out_layout(size_t n, size_t capKp, size_t capWin) {
+  LcOutLayout o;
+  o.brief = 0; o.winBrief = o.brief + n * capKp * 32; o.kp = o.winBrief + n * capWin * 32; o.kpNorm = o.kp + n * capKp * 8;
+  o.count = o.kpNorm + n * capKp * 8; o.found = o.count + n * 4; o.total = o.found + n * 4;
+  return o;
+}
+// the upload of vpl_lc_match_batch for n pairs: window brief | old brief | old keypoints | old keypoints_norm | counts; and its
+// results: matched_2d_old | matched_2d_old_norm | best_dist | best_index | status
+struct LcMatchLayout { size_t winBrief, oldBrief, oldKp, oldNorm, winCnt, oldCnt, inTotal, m2d, m2dNorm, dist, index, status, outTotal; };
+LcMatchLayout lc_match_layout(size_t n, size_t capKp, size_t capWin) {
+  LcMatchLayout o;
+  o.winBrief = 0; o.oldBrief = o.winBrief + n * capWin * 32; o.oldKp = o.oldBrief + n * capKp * 32; o.oldNorm = o.oldKp + n * capKp * 8;
+  o.winCnt = o.oldNorm + n * capKp * 8; o.oldCnt = o.winCnt + n * 4; o.inTotal = o.oldCnt + n * 4;
+  o.m2d = 0; o.m2dNorm = o.m2d + n * capWin * 8; o.dist = o.m2dNorm + n * capWin * 8; o.index = o.dist + n * capWin * 4;
+  o.status = o.index + n * capWin * 4; o.outTotal = o.status + n * capWin;
+  return o;
+}
+}  // namespace
+
+int vpl_lc_reserve(vpl_fe_ctx* c, int max_keypoints, int max_window_points) {
+  if (!c || max_keypoints < 1 || max_window_points < 1) return VPL_E_INVALID;
+  if (c->lcReserved) return fail(c, VPL_E_INVALID, "vpl_lc_reserve called twice");
+  if (max_keypoints > LC_MAX_KEYPOINTS || max_window_points > LC_MAX_WINDOW)
+    return fail(c, VPL_E_CAPACITY, "vpl_lc_reserve: at most 65535 keypoints and 1024 window points per frame");
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t mark = c->allocs.size();
+  LcBatch& L = c->L;
+  std::memset(&L, 0, sizeof(L));
+  L.W = c->W; L.H = c->H; L.img = c->B.img;
+  L.capKp = max_keypoints; L.capWin = max_window_points;
+  {   // the taps of the 9 x 9, sigma 2 blur (lc_kernels.h)
+    double g[2 * LC_BLUR_R + 1], sum = 0;
+    for (int i = 0; i <= 2 * LC_BLUR_R; ++i) { const double x = i - LC_BLUR_R; g[i] = std::exp(-(x * x) / (2.0 * 2.0 * 2.0)); sum += g[i]; }
+    for (int i = 0; i <= 2 * LC_BLUR_R; ++i) L.taps[i] = (float)(g[i] / sum);
+  }
+  const size_t N = c->maxN, PX = (size_t)c->W * c->H;
+  const LcOutLayout O = lc_out_layout(N, max_keypoints, max_window_points);
+  const LcMatchLayout M = lc_match_layout(N, max_keypoints, max_window_points);
+  hipError_t e = hipSuccess;
+#define AL(ptr, n) if (e == hipSuccess) e = dalloc(c, &ptr, (size_t)(n))
+  AL(L.blur, N * PX); AL(L.score, N * PX); AL(L.rowOff, N * c->H);
+  AL(c->d_lcPat, 4 * LC_BITS); AL(c->d_lcIn, N * ((size_t)max_window_points * 8 + 4)); AL(c->d_lcOut, O.total);
+  AL(c->d_lcmIn, M.inTotal); AL(c->d_lcmOut, M.outTotal);
+#undef AL
+  if (e != hipSuccess) {   // nothing of a failed reservation stays
+    std::vector<void*> mine;
+    for (size_t k = mark; k < c->allocs.size(); ++k) mine.push_back(c->allocs[k].p);
+    for (void* q : mine) dfree(c, q);
+    std::memset(&c->L, 0, sizeof(c->L));
+    c->d_lcPat = nullptr; c->d_lcIn = nullptr; c->d_lcOut = nullptr; c->d_lcmIn = nullptr; c->d_lcmOut = nullptr;
+    return fail(c, VPL_E_HIP, std::string("vpl_lc_reserve: ") + hipGetErrorString(e));
+  }
+  L.pat = c->d_lcPat;
+  c->lcReserved = true;
+  return VPL_OK;
+}
+
+int vpl_lc_set_pattern(vpl_fe_ctx* c, int n_bits, const int* x1, const int* y1, const int* x2, const int* y2) {
+  if (!c || !x1 || !y1 || !x2 || !y2) return VPL_E_INVALID;
+  if (!c->lcReserved) return fail(c, VPL_E_INVALID, "vpl_lc_reserve has not been called");
+  if (n_bits != LC_BITS) return fail(c, VPL_E_INVALID, "vpl_lc_set_pattern: n_bits must be 256");
+  HIPCHK(c, hipSetDevice(c->device));
+  std::vector<int> pat(4 * LC_BITS);
+  const int* src[4] = {x1, y1, x2, y2};
+  for (int k = 0; k < 4; ++k) std::memcpy(pat.data() + k * LC_BITS, src[k], LC_BITS * sizeof(int));
+  HIPCHK(c, hipMemcpyAsync(c->d_lcPat, pat.data(), pat.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));   // `pat` goes away
+  c->lcPattern = true;
+  return VPL_OK;
+}
+
+int vpl_lc_keyframe_batch(vpl_fe_ctx* c, int n, const uint8_t* images, const float* window_pts, const int* window_counts,
+                          const vpl_pt_camera* cam, int fast_threshold, float* keypoints, float* keypoints_norm, int* kp_counts,
+                          unsigned long long* brief, unsigned long long* window_brief) {
+  if (!c || n < 1 || !window_pts || !window_counts || !cam || !keypoints || !keypoints_norm || !kp_counts || !brief || !window_brief)
+    return VPL_E_INVALID;
+  if (!c->lcReserved) return fail(c, VPL_E_INVALID, "vpl_lc_reserve has not been called");
+  if (!c->lcPattern) return fail(c, VPL_E_INVALID, "vpl_lc_set_pattern has not been called");
+  if (n > c->maxN) return fail(c, VPL_E_CAPACITY, "more images than max_images");
+  if (!images && n > c->n) return fail(c, VPL_E_INVALID, "no images passed and fewer than n_images in the context");
+  if (fast_threshold < 0 || fast_threshold > 255 || !(cam->fx != 0.0) || !(cam->fy != 0.0))
+    return fail(c, VPL_E_INVALID, "vpl_lc_keyframe_batch: a threshold outside 0 .. 255, or fx or fy 0");
+  LcBatch& L = c->L;
+  const size_t KP = L.capKp, WP = L.capWin;
+  for (int i = 0; i < n; ++i) {
+    if (window_counts[i] < 0) return fail(c, VPL_E_INVALID, "frame " + std::to_string(i) + ": negative window count");
+    if ((size_t)window_counts[i] > WP)
+      return fail(c, VPL_E_CAPACITY, "frame " + std::to_string(i) + ": more window points than the reserved max_window_points");
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  if (images) { const int rc = vpl_edlines_upload(c, n, images); if (rc) return rc; }
+  const size_t oCnt = (size_t)n * WP * 8;
+  std::vector<unsigned char> in(oCnt + (size_t)n * 4);
+  std::memcpy(in.data(), window_pts, oCnt);
+  std::memcpy(in.data() + oCnt, window_counts, (size_t)n * 4);
+  HIPCHK(c, hipMemcpyAsync(c->d_lcIn, in.data(), in.size(), hipMemcpyHostToDevice, s));
+  const LcOutLayout O = lc_out_layout(n, KP, WP);
+  L.N = n; L.threshold = fast_threshold; L.cam = pt_camera(*cam);
+  L.winPts = (const float*)c->d_lcIn; L.winCnt = (const int*)(c->d_lcIn + oCnt);
+  L.brief = (unsigned long long*)(c->d_lcOut + O.brief); L.winBrief = (unsigned long long*)(c->d_lcOut + O.winBrief);
+  L.kp = (float*)(c->d_lcOut + O.kp); L.kpNorm = (float*)(c->d_lcOut + O.kpNorm);
+  L.count = (int*)(c->d_lcOut + O.count); L.found = (int*)(c->d_lcOut + O.found);
+  const dim3 tiles((c->W + LC_TW - 1) / LC_TW, (c->H + LC_TH - 1) / LC_TH, n);
+  { FeTimer t(c, "k_lc_blur"); hipLaunchKernelGGL(k_lc_blur, tiles, dim3(LC_TW * LC_TH), 0, s, L); }
+  { FeTimer t(c, "k_lc_fast"); hipLaunchKernelGGL(k_lc_fast, tiles, dim3(LC_TW * LC_TH), 0, s, L); }
+  { FeTimer t(c, "k_lc_compact");
+    hipLaunchKernelGGL(k_lc_rows, dim3(c->H, n), dim3(64), 0, s, L);
+    hipLaunchKernelGGL(k_lc_scan, dim3(n), dim3(256), 0, s, L);
+    hipLaunchKernelGGL(k_lc_scatter, dim3(c->H, n), dim3(64), 0, s, L); }
+  { FeTimer t(c, "k_lc_brief"); hipLaunchKernelGGL(k_lc_brief, dim3(LC_BRIEF_BLOCKS, n, 2), dim3(256), 0, s, L); }
+  HIPCHK(c, hipGetLastError());
+  std::vector<unsigned char> out(O.total);
+  HIPCHK(c, hipMemcpyAsync(out.data(), c->d_lcOut, O.total, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  c->lcN = n;
+  const int* cnt = (const int*)(out.data() + O.count);
+  const int* found = (const int*)(out.data() + O.found);
+  for (int i = 0; i < n; ++i)
+    if (cnt[i] < 0)
+      return fail(c, VPL_E_CAPACITY, "image " + std::to_string(i) + ": " + std::to_string(found[i]) + " FAST corners, max_keypoints is " +
+                                         std::to_string(L.capKp));
+  for (int i = 0; i < n; ++i) {
+    const size_t k = cnt[i], w = window_counts[i];
+    kp_counts[i] = cnt[i];
+    std::memcpy(keypoints + (size_t)i * KP * 2, out.data() + O.kp + (size_t)i * KP * 8, k * 8);
+    std::memcpy(keypoints_norm + (size_t)i * KP * 2, out.data() + O.kpNorm + (size_t)i * KP * 8, k * 8);
+    std::memcpy(brief + (size_t)i * KP * 4, out.data() + O.brief + (size_t)i * KP * 32, k * 32);
+    std::memcpy(window_brief + (size_t)i * WP * 4, out.data() + O.winBrief + (size_t)i * WP * 32, w * 32);
+  }
+  return VPL_OK;
+}
+
+int vpl_lc_debug_frame(vpl_fe_ctx* c, int img, uint8_t* blurred, uint8_t* score) {
+  if (!c || !c->lcReserved || img < 0 || img >= c->lcN) return VPL_E_INVALID;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const size_t PX = (size_t)c->W * c->H;
+  if (blurred) HIPCHK(c, hipMemcpy(blurred, c->L.blur + img * PX, PX, hipMemcpyDeviceToHost));
+  if (score) HIPCHK(c, hipMemcpy(score, c->L.score + img * PX, PX, hipMemcpyDeviceToHost));
+  return VPL_OK;
+}
+
+int vpl_lc_match_batch(vpl_fe_ctx* c, int n, const unsigned long long* window_brief, const int* window_counts,
+                       const unsigned long long* old_brief, const float* old_keypoints, const float* old_keypoints_norm,
+                       const int* old_counts, float* matched_2d_old, float* matched_2d_old_norm, uint8_t* status, int* best_dist,
+                       int* best_index) {
+  if (!c || n < 1 || !window_brief || !window_counts || !old_brief || !old_keypoints || !old_keypoints_norm || !old_counts ||
+      !matched_2d_old || !matched_2d_old_norm || !status)
+    return VPL_E_INVALID;
+  if (!c->lcReserved) return fail(c, VPL_E_INVALID, "vpl_lc_reserve has not been called");
+  if (n > c->maxN) return fail(c, VPL_E_CAPACITY, "more pairs than max_images");
+  const size_t KP = c->L.capKp, WP = c->L.capWin;
+  for (int i = 0; i < n; ++i) {
+    if (window_counts[i] < 0 || old_counts[i] < 0) return fail(c, VPL_E_INVALID, "pair " + std::to_string(i) + ": negative count");
+    if ((size_t)window_counts[i] > WP || (size_t)old_counts[i] > KP)
+      return fail(c, VPL_E_CAPACITY, "pair " + std::to_string(i) + ": more descriptors than the reserved row lengths");
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  const LcMatchLayout M = lc_match_layout(n, KP, WP);
+  std::vector<unsigned char> in(M.inTotal);
+  std::memcpy(in.data() + M.winBrief, window_brief, (size_t)n * WP * 32);
+  std::memcpy(in.data() + M.oldBrief, old_brief, (size_t)n * KP * 32);
+  std::memcpy(in.data() + M.oldKp, old_keypoints, (size_t)n * KP * 8);
+  std::memcpy(in.data() + M.oldNorm, old_keypoints_norm, (size_t)n * KP * 8);
+  std::memcpy(in.data() + M.winCnt, window_counts, (size_t)n * 4);
+  std::memcpy(in.data() + M.oldCnt, old_counts, (size_t)n * 4);
+  HIPCHK(c, hipMemcpyAsync(c->d_lcmIn, in.data(), M.inTotal, hipMemcpyHostToDevice, s));
+  LcMatchBatch B;
+  std::memset(&B, 0, sizeof(B));
+  B.nPairs = n; B.capKp = (int)KP; B.capWin = (int)WP;
+  B.winBrief = (const unsigned long long*)(c->d_lcmIn + M.winBrief); B.oldBrief = (const unsigned long long*)(c->d_lcmIn + M.oldBrief);
+  B.oldKp = (const float*)(c->d_lcmIn + M.oldKp); B.oldNorm = (const float*)(c->d_lcmIn + M.oldNorm);
+  B.winCnt = (const int*)(c->d_lcmIn + M.winCnt); B.oldCnt = (const int*)(c->d_lcmIn + M.oldCnt);
+  B.m2d = (float*)(c->d_lcmOut + M.m2d); B.m2dNorm = (float*)(c->d_lcmOut + M.m2dNorm);
+  B.bestDist = (int*)(c->d_lcmOut + M.dist); B.bestIndex = (int*)(c->d_lcmOut + M.index); B.status = c->d_lcmOut + M.status;
+  { FeTimer t(c, "k_lc_match"); hipLaunchKernelGGL(k_lc_match, dim3(n), dim3(256), 0, s, B); }
+  HIPCHK(c, hipGetLastError());
+  std::vector<unsigned char> out(M.outTotal);
+  HIPCHK(c, hipMemcpyAsync(out.data(), c->d_lcmOut, M.outTotal, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  for (int i = 0; i < n; ++i) {
+    const size_t w = window_counts[i], r = (size_t)i * WP;
+    std::memcpy(matched_2d_old + r * 2, out.data() + M.m2d + r * 8, w * 8);
+    std::memcpy(matched_2d_old_norm + r * 2, out.data() + M.m2dNorm + r * 8, w * 8);
+    std::memcpy(status + r, out.data() + M.status + r, w);
+    if (best_dist) std::memcpy(best_dist + r, out.data() + M.dist + r * 4, w * 4);
+    if (best_index) std::memcpy(best_index + r, out.data() + M.index + r * 4, w * 4);
   }
   return VPL_OK;
 }

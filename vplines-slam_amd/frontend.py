@@ -183,6 +183,12 @@ def _bind(lib):
                                           C.POINTER(C.c_ulonglong), C.POINTER(C.c_uint8)]
     lib.vpl_pt_detect_batch.argtypes = [vp, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), ip, ip, dp, fp, fp, ip]
     lib.vpl_pt_debug_detect.argtypes = [vp, C.c_int, fp, ip]
+    u8p, u64p = C.POINTER(C.c_uint8), C.POINTER(C.c_ulonglong)
+    lib.vpl_lc_reserve.argtypes = [vp, C.c_int, C.c_int]
+    lib.vpl_lc_set_pattern.argtypes = [vp, C.c_int, ip, ip, ip, ip]
+    lib.vpl_lc_keyframe_batch.argtypes = [vp, C.c_int, u8p, fp, ip, C.POINTER(PointCamera), C.c_int, fp, fp, ip, u64p, u64p]
+    lib.vpl_lc_debug_frame.argtypes = [vp, C.c_int, u8p, u8p]
+    lib.vpl_lc_match_batch.argtypes = [vp, C.c_int, u64p, ip, u64p, fp, fp, ip, fp, fp, u8p, ip, ip]
     _bound = True
 
 
@@ -564,6 +570,128 @@ class FrontendContext:
         self._check(self.lib.vpl_pt_debug_detect(self.h, img, eig.ctypes.data_as(C.POINTER(C.c_float)), C.byref(nc)),
                     "vpl_pt_debug_detect")
         return eig, nc.value
+
+    # ---- loop-closure front-end: KeyFrame's FAST / BRIEF and searchByBRIEFDes (pose_graph/src/keyframe.cpp) ----
+    def lc_reserve(self, max_keypoints=8192, max_window_points=256):
+        self.lc_max_keypoints, self.lc_max_window_points = max_keypoints, max_window_points
+        self._check(self.lib.vpl_lc_reserve(self.h, max_keypoints, max_window_points), "vpl_lc_reserve")
+
+    def lc_set_pattern(self, x1, y1, x2, y2):
+        """the BRIEF test pairs (brief_pattern.yml of the reference): four lists of 256 integers"""
+        p = [np.ascontiguousarray(a, np.int32) for a in (x1, y1, x2, y2)]
+        assert all(a.shape == p[0].shape and a.ndim == 1 for a in p)
+        ip = C.POINTER(C.c_int)
+        self._check(self.lib.vpl_lc_set_pattern(self.h, len(p[0]), *[a.ctypes.data_as(ip) for a in p]), "vpl_lc_set_pattern")
+
+    def lc_keyframe(self, images, window_pts, camera, fast_threshold=20, out=None):
+        """images [n][H][W] uint8 (None: the frames in the context's slots, n = len(window_pts)); window_pts per frame a [k][2]
+        array of pixel positions; camera a PointCamera.  Returns per frame a dict: keypoints [m][2], keypoints_norm [m][2] float32,
+        brief [m][4] uint64, window_brief [k][4] uint64.  out (tests): the raw output arrays to write into."""
+        u8 = C.POINTER(C.c_uint8)
+        if images is not None:
+            images = np.ascontiguousarray(images, np.uint8)
+            assert images.ndim == 3 and images.shape[1:] == (self.H, self.W)
+            assert len(window_pts) == images.shape[0]
+            self.n = images.shape[0]
+        n, KP, WP = len(window_pts), self.lc_max_keypoints, self.lc_max_window_points
+        win = np.zeros((n, WP, 2), np.float32)
+        wcnt = np.zeros(n, np.int32)
+        for i, l in enumerate(window_pts):
+            l = np.asarray(l, np.float32).reshape(-1, 2)
+            wcnt[i] = len(l)
+            if len(l) <= WP:               # otherwise the library reports VPL_E_CAPACITY
+                win[i, :len(l)] = l
+        if out is None:
+            out = (np.zeros((n, KP, 2), np.float32), np.zeros((n, KP, 2), np.float32), np.zeros(n, np.int32),
+                   np.zeros((n, KP, 4), np.uint64), np.zeros((n, WP, 4), np.uint64))
+        kp, kn, cnt, br, wbr = out
+        ip, fp, u64 = C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_ulonglong)
+        self._check(self.lib.vpl_lc_keyframe_batch(self.h, n, images.ctypes.data_as(u8) if images is not None else None,
+                                                   win.ctypes.data_as(fp), wcnt.ctypes.data_as(ip), C.byref(camera), fast_threshold,
+                                                   kp.ctypes.data_as(fp), kn.ctypes.data_as(fp), cnt.ctypes.data_as(ip),
+                                                   br.ctypes.data_as(u64), wbr.ctypes.data_as(u64)), "vpl_lc_keyframe_batch")
+        return [dict(keypoints=kp[i, :cnt[i]].copy(), keypoints_norm=kn[i, :cnt[i]].copy(), brief=br[i, :cnt[i]].copy(),
+                     window_brief=wbr[i, :wcnt[i]].copy()) for i in range(n)]
+
+    def lc_debug_frame(self, img):
+        """test access: (blurred plane, FAST score plane) [H][W] uint8 of frame `img` of the last lc_keyframe"""
+        b, s = np.zeros((self.H, self.W), np.uint8), np.zeros((self.H, self.W), np.uint8)
+        u8 = C.POINTER(C.c_uint8)
+        self._check(self.lib.vpl_lc_debug_frame(self.h, img, b.ctypes.data_as(u8), s.ctypes.data_as(u8)), "vpl_lc_debug_frame")
+        return b, s
+
+    def lc_match(self, window_brief, old_brief, old_keypoints, old_keypoints_norm):
+        """searchByBRIEFDes for a batch of pairs: per pair the window descriptors [k][4] and the candidate's descriptors [m][4],
+        keypoints [m][2] and keypoints_norm [m][2].  Returns per pair a dict: matched_2d_old, matched_2d_old_norm [k][2] float32,
+        status [k] uint8, best_dist, best_index [k] int32."""
+        n, KP, WP = len(window_brief), self.lc_max_keypoints, self.lc_max_window_points
+        assert len(old_brief) == len(old_keypoints) == len(old_keypoints_norm) == n
+        wb, ob = np.zeros((n, WP, 4), np.uint64), np.zeros((n, KP, 4), np.uint64)
+        okp, onr = np.zeros((n, KP, 2), np.float32), np.zeros((n, KP, 2), np.float32)
+        wcnt, ocnt = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        for i in range(n):
+            w, o = np.asarray(window_brief[i], np.uint64).reshape(-1, 4), np.asarray(old_brief[i], np.uint64).reshape(-1, 4)
+            k, q = np.asarray(old_keypoints[i], np.float32).reshape(-1, 2), np.asarray(old_keypoints_norm[i], np.float32).reshape(-1, 2)
+            assert len(o) == len(k) == len(q)
+            wcnt[i], ocnt[i] = len(w), len(o)
+            if len(w) <= WP and len(o) <= KP:   # otherwise the library reports VPL_E_CAPACITY
+                wb[i, :len(w)], ob[i, :len(o)], okp[i, :len(o)], onr[i, :len(o)] = w, o, k, q
+        m2d, m2n = np.zeros((n, WP, 2), np.float32), np.zeros((n, WP, 2), np.float32)
+        st, bd, bi = np.zeros((n, WP), np.uint8), np.zeros((n, WP), np.int32), np.zeros((n, WP), np.int32)
+        ip, fp, u64 = C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_ulonglong)
+        self._check(self.lib.vpl_lc_match_batch(self.h, n, wb.ctypes.data_as(u64), wcnt.ctypes.data_as(ip), ob.ctypes.data_as(u64),
+                                                okp.ctypes.data_as(fp), onr.ctypes.data_as(fp), ocnt.ctypes.data_as(ip),
+                                                m2d.ctypes.data_as(fp), m2n.ctypes.data_as(fp), st.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                bd.ctypes.data_as(ip), bi.ctypes.data_as(ip)), "vpl_lc_match_batch")
+        return [dict(matched_2d_old=m2d[i, :wcnt[i]].copy(), matched_2d_old_norm=m2n[i, :wcnt[i]].copy(), status=st[i, :wcnt[i]].copy(),
+                     best_dist=bd[i, :wcnt[i]].copy(), best_index=bi[i, :wcnt[i]].copy()) for i in range(n)]
+
+
+def reduce_vector(v, status):
+    """reduceVector (pose_graph/src/keyframe.cpp:3-11): the entries of v whose status is non-zero, in order"""
+    v, status = np.asarray(v), np.asarray(status)
+    if len(v) != len(status):
+        raise ValueError("reduce_vector: %d entries, %d status flags" % (len(v), len(status)))
+    return v[status != 0]
+
+
+def loop_matches(fe, cur, old):
+    """The descriptor step of KeyFrame::findConnection (keyframe.cpp:259-330) for one pair: searchByBRIEFDes of the current
+    keyframe's window descriptors against the candidate, then reduceVector of every window list by the match status.
+      cur: dict with window_brief [k][4], point_2d_uv [k][2], point_2d_norm [k][2], point_3d [k][3], point_id [k]
+      old: dict with brief [m][4], keypoints [m][2], keypoints_norm [m][2] (an entry of FrontendContext.lc_keyframe)
+    Returns a dict of the reduced lists: matched_2d_cur, matched_2d_cur_norm, matched_3d, matched_id, matched_2d_old,
+    matched_2d_old_norm, and `status`, the unreduced match status."""
+    k = len(cur["window_brief"])
+    for name in ("point_2d_uv", "point_2d_norm", "point_3d", "point_id"):
+        if len(cur[name]) != k:
+            raise ValueError("loop_matches: %s has %d entries, window_brief %d" % (name, len(cur[name]), k))
+    m = fe.lc_match([cur["window_brief"]], [old["brief"]], [old["keypoints"]], [old["keypoints_norm"]])[0]
+    st = m["status"]
+    return dict(matched_2d_cur=reduce_vector(cur["point_2d_uv"], st), matched_2d_cur_norm=reduce_vector(cur["point_2d_norm"], st),
+                matched_3d=reduce_vector(cur["point_3d"], st), matched_id=reduce_vector(cur["point_id"], st),
+                matched_2d_old=reduce_vector(m["matched_2d_old"], st), matched_2d_old_norm=reduce_vector(m["matched_2d_old_norm"], st),
+                status=st)
+
+
+MATCHED_LISTS = ("matched_2d_cur", "matched_2d_cur_norm", "matched_3d", "matched_id", "matched_2d_old", "matched_2d_old_norm")
+
+
+def find_connection(fe, ctx, cur, old, seed=0, options=None):
+    """KeyFrame::findConnection (keyframe.cpp:259-520) for one pair, as the reference chains it: loop_matches (the descriptor
+    search and its reduceVector calls) on the front-end context `fe`, then Context.loop_verify on `ctx` (the PnP RANSAC, the
+    MIN_LOOP_NUM gates, the relative pose and its acceptance) and, when the PnP ran, the reduceVector calls by its inliers.
+      cur: as for loop_matches, and origin_vio_T [3], origin_vio_R [3][3], tic [3], qic [3][3];  seed: of the sample stream
+    Returns a dict: has_loop, result (the LoopResult), the six matched lists as findConnection leaves them, match_status [k] and
+    pnp_status (None when fewer than min_loop_num + 1 matches were left and nothing ran)."""
+    from .capi import LoopInput, LOOP_FEW_POINTS
+    m = loop_matches(fe, cur, old)
+    q = LoopInput(m["matched_3d"], m["matched_2d_old_norm"], cur["origin_vio_T"], cur["origin_vio_R"], cur["tic"], cur["qic"], seed)
+    res, status = ctx.loop_verify([q], options)
+    ran = res[0].stage != LOOP_FEW_POINTS
+    out = {k: (reduce_vector(m[k], status[0]) if ran else m[k]) for k in MATCHED_LISTS}
+    out.update(has_loop=bool(res[0].has_loop), result=res[0], match_status=m["status"], pnp_status=status[0] if ran else None)
+    return out
 
 
 def default_tracker_options(max_h_lines=25, max_v_lines=25, fx=1.0, fy=1.0, cx=0.0, cy=0.0, equalize=True):
