@@ -1040,6 +1040,66 @@ int vpl_loop_verify_batch(vpl_ctx* ctx, int n, const vpl_loop_input* in, const v
  * VPL_E_INVALID: n_points < 5, max_iters outside 1 .. VPL_LOOP_MAX_ITERS, a null array; VPL_E_CAPACITY: n_points > VPL_LOOP_MAX_POINTS */
 int vpl_loop_debug_plan(unsigned long long seed, int n_points, double confidence, int max_iters, int* samples, int* niters_after);
 
+/* ---- pose-graph optimisation: PoseGraph::optimize4DoF (pose_graph.cpp:403-579, functors pose_graph.h:89-250) for a batch of
+ * independent graphs of one live sequence each.  Per graph the keyframes first_looped_index .. cur_index are the local nodes
+ * 0 .. n-1; a node's parameters are its yaw in degrees and t, pitch and roll of R2ypr(qmat(mat2q(vio_R))) stay fixed, node 0 is
+ * constant.  Edges: FourDOFError between i and i-j, j = 1..4 (no loss), measured on the incoming poses; FourDOFWeightError of
+ * loop_info (t, and yaw / loop_yaw_scale) under HuberLoss(huber_delta) between a node and loop_local[node] < node.  Minimiser:
+ * ceres' trust-region loop with the Levenberg-Marquardt strategy and Jacobi scaling (the rules of oracle/problem.cpp,
+ * SolveWith<LevenbergMarquardt>), the normal equations solved directly in f64 by a block-banded Cholesky of the sequential part
+ * and a capacitance system of the loop edges.  All max_iterations rounds are enqueued at once; nothing is read back
+ * between them.  Then yaw_drift / r_drift / t_drift as at :549-557 from node n-1, and the tail poses r_drift P + t_drift,
+ * r_drift R (:562-571).  A graph whose `sequence` values differ is not run (VPL_PG_UNSUPPORTED: a loaded map or a second session
+ * gives a floating chain).  n = 1 comes back with zero iterations.  Limits VPL_PG_MAX_NODES / VPL_PG_MAX_LOOPS per graph. */
+#define VPL_PG_MAX_NODES 4096
+#define VPL_PG_MAX_LOOPS 256
+#define VPL_PG_OK 0
+#define VPL_PG_UNSUPPORTED 1
+#define VPL_PG_NO_CONVERGENCE 0   /* termination, ceres' TerminationType as oracle/problem.h numbers it */
+#define VPL_PG_CONVERGENCE 1
+#define VPL_PG_FAILURE 2
+typedef struct vpl_pg_options {
+  int max_iterations;              /* options.max_num_iterations = 5 (pose_graph.cpp:437) */
+  int max_consecutive_invalid_steps; /* 5 */
+  double huber_delta;              /* HuberLoss(0.1); <= 0: no loss on the loop edges */
+  double loop_yaw_scale;           /* 10: the loop edge's yaw residual is divided by it */
+  double initial_radius, max_radius, min_radius;   /* 1e4, 1e16, 1e-32 */
+  double min_relative_decrease;    /* 1e-3 */
+  double function_tolerance, gradient_tolerance, parameter_tolerance; /* 1e-6, 1e-10, 1e-8 */
+  double min_lm_diagonal, max_lm_diagonal;         /* 1e-6, 1e32 */
+} vpl_pg_options;
+void vpl_pg_default_options(vpl_pg_options* opt);
+typedef struct vpl_pg_input {
+  int n, n_tail;
+  const double* vio_T;     /* [n][3] */
+  const double* vio_R;     /* [n][9] row-major */
+  const int* loop_local;   /* [n]: -1, or the local index of the old keyframe (< the node's own) */
+  const double* loop_info; /* [n][8] = t, q, yaw as vpl_loop_result writes it; t and yaw are read, rows without a loop are not */
+  const int* sequence;     /* NULL, or [n] */
+  const double* tail_T;    /* NULL when n_tail = 0, or [n_tail][3]: later keyframes, only drift-corrected */
+  const double* tail_R;    /* [n_tail][9] */
+} vpl_pg_input;
+typedef struct vpl_pg_result {
+  int status, termination;   /* VPL_PG_OK / VPL_PG_UNSUPPORTED | VPL_PG_* termination */
+  int iterations;            /* the number of the iteration the minimiser ended in */
+  int successful_steps, unsuccessful_steps;   /* as ceres counts them: iteration 0 is a successful one */
+  int reserved;
+  double initial_cost, final_cost;
+  double yaw_drift, r_drift[9], t_drift[3];
+  double* T;                 /* caller's [n][3], written */
+  double* R;                 /* caller's [n][9], written */
+  double* tail_T;            /* caller's [n_tail][3] / [n_tail][9], written; may be NULL when n_tail = 0 */
+  double* tail_R;
+} vpl_pg_result;
+/* in [n_graphs], out [n_graphs] with the four arrays of every out[] set by the caller.  One copy each way, one synchronisation.
+ * VPL_E_INVALID: null arrays, n < 1, loop_local >= own index, options out of range; VPL_E_CAPACITY: n > VPL_PG_MAX_NODES, more
+ * than VPL_PG_MAX_LOOPS loops, n_graphs > max_windows. */
+int vpl_pg_optimize_batch(vpl_ctx* ctx, int n_graphs, const vpl_pg_input* in, const vpl_pg_options* opt, vpl_pg_result* out);
+/* test access: the first linear solve of one graph.  g [4(n-1)] = J^T r in parameter units, step [4(n-1)] = the first trust-region
+ * step in parameter units (Jacobi scale applied), model_cost_change [1]; the order of the unknowns is (yaw, tx, ty, tz) of node 1,
+ * node 2, ...  Same refusals as the batch call; VPL_E_NUMERIC when the factorisation fails. */
+int vpl_pg_debug_step(vpl_ctx* ctx, const vpl_pg_input* in, const vpl_pg_options* opt, double* g, double* step, double* model_cost_change);
+
 #ifdef __cplusplus
 }
 #endif

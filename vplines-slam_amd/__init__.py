@@ -13,6 +13,7 @@ from .capi import (  # noqa: F401
     SfmInput, SfmResult, sfm_debug_plan, RelPoseInput, RelPoseResult, relpose_debug_plan,
     SelectParams, SelectInput, SelectResult, SelectFrame, OdoSelectResult, select_debug_book,
     LoopInput, LoopOptions, LoopResult, default_loop_options, loop_debug_plan,
+    PoseGraphInput, PoseGraphResult, PgOptions, default_pg_options,
     MARGIN_OLD, MARGIN_SECOND_NEW, MARGIN_NONE, PRIOR_PIVOTED_CHOLESKY, PRIOR_EIGEN,
 )
 from . import workload  # noqa: F401

@@ -318,6 +318,81 @@ def loop_debug_plan(seed, N, confidence=0.99, max_iters=100):
     return dict(samples=samples, niters_after=table) if rc == 0 else rc
 
 
+PG_MAX_NODES, PG_MAX_LOOPS = 4096, 256   # VPL_PG_MAX_NODES, VPL_PG_MAX_LOOPS
+PG_OK, PG_UNSUPPORTED = 0, 1
+PG_NO_CONVERGENCE, PG_CONVERGENCE, PG_FAILURE = 0, 1, 2
+
+
+class PgOptions(C.Structure):   # vpl_pg_options
+    _fields_ = [("max_iterations", C.c_int), ("max_consecutive_invalid_steps", C.c_int), ("huber_delta", C.c_double),
+                ("loop_yaw_scale", C.c_double), ("initial_radius", C.c_double), ("max_radius", C.c_double), ("min_radius", C.c_double),
+                ("min_relative_decrease", C.c_double), ("function_tolerance", C.c_double), ("gradient_tolerance", C.c_double),
+                ("parameter_tolerance", C.c_double), ("min_lm_diagonal", C.c_double), ("max_lm_diagonal", C.c_double)]
+
+
+def default_pg_options(**changes):
+    o = PgOptions()
+    load_hip_library().vpl_pg_default_options(C.byref(o))
+    for k, val in changes.items():
+        setattr(o, k, val)
+    return o
+
+
+class CPgInput(C.Structure):   # vpl_pg_input
+    _fields_ = [("n", C.c_int), ("n_tail", C.c_int), ("vio_T", _dp), ("vio_R", _dp), ("loop_local", _ip), ("loop_info", _dp),
+                ("sequence", _ip), ("tail_T", _dp), ("tail_R", _dp)]
+
+
+class CPgResult(C.Structure):   # vpl_pg_result
+    _fields_ = [("status", C.c_int), ("termination", C.c_int), ("iterations", C.c_int), ("successful_steps", C.c_int),
+                ("unsuccessful_steps", C.c_int), ("reserved", C.c_int), ("initial_cost", C.c_double), ("final_cost", C.c_double),
+                ("yaw_drift", C.c_double), ("r_drift", C.c_double * 9), ("t_drift", C.c_double * 3), ("T", _dp), ("R", _dp),
+                ("tail_T", _dp), ("tail_R", _dp)]
+
+
+class PoseGraphInput:
+    """numpy-backed owner of one vpl_pg_input: the keyframes first_looped_index .. cur_index as local nodes 0 .. n-1 -- vio_T [n][3],
+    vio_R [n][3][3], loop_local [n] (-1, or the local index of the old keyframe), loop_info [n][8] as LoopResult.loop_info -- and
+    optionally sequence [n] and the later keyframes tail_T / tail_R, which are only drift-corrected."""
+
+    def __init__(self, vio_T, vio_R, loop_local, loop_info, sequence=None, tail_T=None, tail_R=None):
+        self.vio_T = _arr(vio_T, np.float64).reshape(-1, 3).copy()
+        n = len(self.vio_T)
+        self.vio_R = _arr(vio_R, np.float64).reshape(n, 3, 3).copy()
+        self.loop_local = _arr(loop_local, np.int32).reshape(n).copy()
+        self.loop_info = _arr(loop_info, np.float64).reshape(n, 8).copy()
+        self.sequence = None if sequence is None else _arr(sequence, np.int32).reshape(n).copy()
+        self.tail_T = np.zeros((0, 3)) if tail_T is None else _arr(tail_T, np.float64).reshape(-1, 3).copy()
+        self.tail_R = np.zeros((0, 3, 3)) if tail_R is None else _arr(tail_R, np.float64).reshape(len(self.tail_T), 3, 3).copy()
+
+    def to_c(self, ci=None):
+        ci = ci if ci is not None else CPgInput()
+        ci.n, ci.n_tail = len(self.vio_T), len(self.tail_T)
+        ci.vio_T, ci.vio_R, ci.loop_info = (a.ctypes.data_as(_dp) for a in (self.vio_T, self.vio_R, self.loop_info))
+        ci.loop_local = self.loop_local.ctypes.data_as(_ip)
+        ci.sequence = self.sequence.ctypes.data_as(_ip) if self.sequence is not None else None
+        ci.tail_T = self.tail_T.ctypes.data_as(_dp) if len(self.tail_T) else None
+        ci.tail_R = self.tail_R.ctypes.data_as(_dp) if len(self.tail_T) else None
+        return ci
+
+
+class PoseGraphResult:
+    """one graph's vpl_pg_result with the arrays it points to: head (CPgResult), T [n][3], R [n][3][3], tail_T, tail_R"""
+
+    def __init__(self, head, T, R, tail_T, tail_R):
+        self.head, self.T, self.R, self.tail_T, self.tail_R = head, T, R, tail_T, tail_R
+
+    def __getattr__(self, name):
+        return getattr(self.head, name)
+
+    def data(self):
+        """every value the call wrote, as bytes (the pointers left out)"""
+        h = self.head
+        ints = np.array([h.status, h.termination, h.iterations, h.successful_steps, h.unsuccessful_steps], dtype=np.int32)
+        dbl = np.array([h.initial_cost, h.final_cost, h.yaw_drift] + list(h.r_drift) + list(h.t_drift))
+        return b"".join(a.tobytes() for a in (ints, dbl, self.T, self.R, self.tail_T, self.tail_R))
+
+
 SEL_MAX_FEATURES = 1024   # VPL_SEL_MAX_FEATURES
 
 
@@ -656,6 +731,10 @@ def load_hip_library():
     lib.vpl_loop_default_options.restype = None
     lib.vpl_loop_verify_batch.argtypes = [vp, C.c_int, C.POINTER(CLoopInput), C.POINTER(LoopOptions), C.POINTER(LoopResult), _bp]
     lib.vpl_loop_debug_plan.argtypes = [C.c_ulonglong, C.c_int, C.c_double, C.c_int, _ip, _ip]
+    lib.vpl_pg_default_options.argtypes = [C.POINTER(PgOptions)]
+    lib.vpl_pg_default_options.restype = None
+    lib.vpl_pg_optimize_batch.argtypes = [vp, C.c_int, C.POINTER(CPgInput), C.POINTER(PgOptions), C.POINTER(CPgResult)]
+    lib.vpl_pg_debug_step.argtypes = [vp, C.POINTER(CPgInput), C.POINTER(PgOptions), _dp, _dp, _dp]
     lib.vpl_init_visual_batch.argtypes = [vp, C.c_int, C.POINTER(CSfmInput), C.POINTER(C.c_ulonglong), C.POINTER(RelPoseResult),
                                           C.POINTER(SfmResult), _dp, _dp, _ip, _dp]
     lib.vpl_select_features_batch.argtypes = [vp, C.c_int, C.POINTER(SelectParams), C.POINTER(CSelectInput), C.POINTER(SelectResult), _ip, _dp]
@@ -1058,6 +1137,48 @@ class Context:
             return rc
         self._check(rc, "vpl_loop_verify_batch")
         return res, [st[i, :ci[i].count].copy() for i in range(n)]
+
+    @staticmethod
+    def _pg_c(inputs):
+        ci = (CPgInput * len(inputs))()
+        for i, q in enumerate(inputs):
+            if isinstance(q, CPgInput):
+                C.memmove(C.byref(ci[i]), C.byref(q), C.sizeof(CPgInput))   # as the caller filled it (tests of the refusals)
+            else:
+                q.to_c(ci[i])
+        return ci
+
+    def pose_graph_optimize(self, inputs, opt=None, check=True):
+        """vpl_pg_optimize_batch over a list of PoseGraphInput: PoseGraph::optimize4DoF per graph -- the corrected poses, the drift
+        and the drift-corrected tail -- in one call.  -> list of PoseGraphResult.  check=False: a refusal comes back as its
+        VPL_E_* code instead of an exception."""
+        self._settle()
+        n = len(inputs)
+        ci = self._pg_c(inputs)
+        opt = opt if opt is not None else default_pg_options()
+        res = (CPgResult * n)()
+        out = []
+        for i in range(n):
+            nn, nt = max(int(ci[i].n), 0), max(int(ci[i].n_tail), 0)
+            arrs = (np.zeros((nn, 3)), np.zeros((nn, 3, 3)), np.zeros((nt, 3)), np.zeros((nt, 3, 3)))
+            res[i].T, res[i].R, res[i].tail_T, res[i].tail_R = (a.ctypes.data_as(_dp) for a in arrs)
+            out.append(arrs)
+        rc = self.lib.vpl_pg_optimize_batch(self.h, n, ci, C.byref(opt), res)
+        if rc != 0 and not check:
+            return rc
+        self._check(rc, "vpl_pg_optimize_batch")
+        return [PoseGraphResult(res[i], *out[i]) for i in range(n)]
+
+    def pose_graph_debug_step(self, q, opt=None):
+        """vpl_pg_debug_step: the first linear solve of one graph -> dict g, step [4 (n - 1)], model_cost_change"""
+        self._settle()
+        ci = self._pg_c([q])
+        opt = opt if opt is not None else default_pg_options()
+        m = 4 * (int(ci[0].n) - 1)
+        g, step, mc = np.zeros(max(m, 1)), np.zeros(max(m, 1)), np.zeros(1)
+        rc = self.lib.vpl_pg_debug_step(self.h, ci, C.byref(opt), g.ctypes.data_as(_dp), step.ctypes.data_as(_dp), mc.ctypes.data_as(_dp))
+        self._check(rc, "vpl_pg_debug_step")
+        return dict(g=g[:m], step=step[:m], model_cost_change=float(mc[0]))
 
     @staticmethod
     def _select_c(params, inputs):

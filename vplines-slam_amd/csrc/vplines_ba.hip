@@ -42,6 +42,7 @@ using namespace vpl;
 #include "init_sfm_host.h"
 #include "init_relpose_host.h"
 #include "loop_host.h"
+#include "pg_host.h"
 #include "sel_host.h"
 
 template <typename Launch>
