@@ -8,6 +8,8 @@ the prior, the IMU factors 1..10, every point track's observation 0 against k >=
 (line factor, VP factor when its flag is set).  Residuals and Jacobians come from the oracle's factor evaluators in double
 and are promoted; everything after that (Huber scaling, J^T J, the scaling, the Cholesky solve, the dogleg step, the model
 cost change) is long double.  Columns are local coordinates: the evaluators' zero seventh pose column is dropped.
+Problem(w, opt, evaluators=vis_ref.Evaluators) takes the point, line and VP rows from vis_ref.py instead, in true long double
+(test_gpu_vis_factors.py); the IMU rows have their long-double form in imu_ref.py; the prior rows stay the oracle's.
 
 Index of a window with nP points and nL triangulated lines (n = 171 + nP + 4 nL): frame f pose 15 f + 0..5, speed/bias
 15 f + 6..14, extrinsic 165..170, inverse depth of point p 171 + p, line l 171 + nP + 4 l + 0..3.
@@ -85,8 +87,10 @@ def plk_from_pose(plk, Rcw, tcw):
 
 # ---- the problem of one window -----------------------------------------------------------------------------------------
 class Problem:
-    def __init__(self, w, opt):
-        self.w, self.opt = w, opt
+    def __init__(self, w, opt, evaluators=o):
+        """evaluators: what has projection_factor, line_factor and vp_factor(params, observations, sqrt_info) -> r, jac for the
+        point, line and VP rows: the oracle's (float64) by default; vis_ref.Evaluators gives long-double rows"""
+        self.w, self.opt, self.ev = w, opt, evaluators
         self.nP = len(w.point_start)
         nl_all = len(w.line_start)
         self.lines = np.nonzero(np.asarray(w.line_triangulated[:nl_all]) != 0)[0]     # solved line -> the window's line
@@ -160,7 +164,7 @@ class Problem:
                 pts.append(np.concatenate([ob[0], ob[k]]))
                 where.append((s, s + k, p))
         if P:
-            r, jac = o.projection_factor(np.array(P), np.array(pts), opt.focal_length / 1.5)
+            r, jac = self.ev.projection_factor(np.array(P), np.array(pts), opt.focal_length / 1.5)
             for i, (fi, fj, p) in enumerate(where):
                 out.append(("proj", 1.0, True, r[i],
                             [(15 * fi, jac[i, 0:14].reshape(2, 7)[:, :6]), (15 * fj, jac[i, 14:28].reshape(2, 7)[:, :6]),
@@ -169,8 +173,8 @@ class Problem:
             s = int(w.line_start[l])
             ob = w.line_obs[self.loff[l]:self.loff[l + 1]]
             params = np.array([np.concatenate([pose[s + k], ex, orth[dl]]) for k in range(len(ob))])
-            rl, jl = o.line_factor(params, ob[:, 0:4], opt.line_factor)
-            rv, jv = o.vp_factor(params, ob[:, 4:7], opt.vp_factor)
+            rl, jl = self.ev.line_factor(params, ob[:, 0:4], opt.line_factor)
+            rv, jv = self.ev.vp_factor(params, ob[:, 4:7], opt.vp_factor)
             col = NC + self.nP + 4 * dl
             for k in range(len(ob)):
                 for kind, r, jac in (("line", rl, jl), ("vp", rv, jv)):
