@@ -1100,6 +1100,94 @@ int vpl_pg_optimize_batch(vpl_ctx* ctx, int n_graphs, const vpl_pg_input* in, co
  * node 2, ...  Same refusals as the batch call; VPL_E_NUMERIC when the factorisation fails. */
 int vpl_pg_debug_step(vpl_ctx* ctx, const vpl_pg_input* in, const vpl_pg_options* opt, double* g, double* step, double* model_cost_change);
 
+/* ---- global fusion: GlobalOptimization::optimize (globalOpt.cpp:101-259, functors Factors.h) for a batch of independent pose
+ * chains.  Per chain the nodes 0 .. n-1 are the odometry poses in time order; a node's parameters are its quaternion (w, x, y, z;
+ * ceres' QuaternionParameterization, tangent size 3: q <- [cos|d|, sin|d| / |d| d] (x) q) and t, no node is constant.  Edge
+ * k -> k+1: RelativeRTError, measured on the local poses as iPj = R_i^T (p_j - p_i), iQj = mat2q(R_i^T R_j) with the project's
+ * qmat / mat2q; rows (R(q_i)^T (t_j - t_i) - iPj) / t_var and 2 vec(iQj^-1 (x) q_i^-1 (x) q_j) / q_var, no loss.  GNSS factor of a
+ * node: TError, (t - xyz) / accuracy under HuberLoss(huber_delta).  Minimiser: ceres' trust-region loop with the Levenberg-Marquardt
+ * strategy and Jacobi scaling (the rules of oracle/problem.cpp, SolveWith<LevenbergMarquardt>).  The normal matrix is
+ * block-tridiagonal with 6 x 6 blocks; it is solved directly in f64 by a substructured Cholesky: every `segment`-th node is a
+ * separator, the segments between them are factored side by side, the Schur complement on the separators is again a chain
+ * (csrc/gf_plan.h, DESIGN.md "Global fusion").  All max_iterations + 1 rounds are enqueued at once; nothing is read back between
+ * them.  Then wgps_T_wvio = T_global(n-1) T_local(n-1)^-1, row-major 4 x 4.  Poses are [7] = p, q(w, x, y, z); the returned
+ * quaternions are as Plus leaves them.  A chain with a non-finite input pose comes back with termination VPL_GF_FAILURE, its poses
+ * as given and wgps_T_wvio the identity; its neighbours in the batch run. */
+#define VPL_GF_MAX_NODES 65536
+#define VPL_GF_OK 0
+#define VPL_GF_NO_CONVERGENCE 0   /* termination, ceres' TerminationType as oracle/problem.h numbers it */
+#define VPL_GF_CONVERGENCE 1
+#define VPL_GF_FAILURE 2
+typedef struct vpl_gf_options {
+  int max_iterations;              /* options.max_num_iterations = 5 (globalOpt.cpp:116) */
+  int max_consecutive_invalid_steps; /* 5 */
+  int segment;                     /* S of the substructured solve: 0 = the default (64, the fastest of 32 / 64 / 128 at 16384
+                                      nodes: DESIGN.md), otherwise >= 2; S > n: one segment, the serial chain */
+  int reserved;
+  double t_var, q_var;             /* 0.1, 0.01 (globalOpt.cpp:167) */
+  double huber_delta;              /* HuberLoss(1.0); <= 0: no loss on the GNSS factors */
+  double initial_radius, max_radius, min_radius;   /* 1e4, 1e16, 1e-32 */
+  double min_relative_decrease;    /* 1e-3 */
+  double function_tolerance, gradient_tolerance, parameter_tolerance; /* 1e-6, 1e-10, 1e-8 */
+  double min_lm_diagonal, max_lm_diagonal;         /* 1e-6, 1e32 */
+} vpl_gf_options;
+void vpl_gf_default_options(vpl_gf_options* opt);
+typedef struct vpl_gf_input {
+  int n, n_gps;
+  const double* local;        /* [n][7]: the odometry (VIO) poses */
+  const double* global;       /* [n][7]: the initial global poses (globalPoseMap) */
+  const int* gps_node;        /* [n_gps], strictly ascending, in 0 .. n-1; may be NULL when n_gps = 0, like the next two */
+  const double* gps_xyz;      /* [n_gps][3] */
+  const double* gps_accuracy; /* [n_gps], > 0 */
+} vpl_gf_input;
+typedef struct vpl_gf_result {
+  int status, termination;   /* VPL_GF_OK | VPL_GF_* termination */
+  int iterations;            /* the number of the iteration the minimiser ended in */
+  int successful_steps, unsuccessful_steps;   /* as ceres counts them: iteration 0 is a successful one */
+  int reserved;
+  double initial_cost, final_cost;
+  double wgps_T_wvio[16];
+  double* pose;              /* caller's [n][7], written */
+} vpl_gf_result;
+/* in [n_chains], out [n_chains] with every out[].pose set by the caller.  One copy each way, one synchronisation.
+ * VPL_E_INVALID: null arrays, n < 1, gps_node out of range or not ascending, an accuracy that is not positive, options out of
+ * range, segment other than 0 or >= 2; VPL_E_CAPACITY: n > VPL_GF_MAX_NODES, n_chains > max_windows. */
+int vpl_gf_optimize_batch(vpl_ctx* ctx, int n_chains, const vpl_gf_input* in, const vpl_gf_options* opt, vpl_gf_result* out);
+/* test access: the first linear solve of one chain.  g [6 n] = J^T r in parameter units, step [6 n] = the first trust-region step in
+ * parameter units (Jacobi scale applied), model_cost_change [1]; the order of the unknowns is (dtheta, dt) of node 0, node 1, ...
+ * Same refusals as the batch call; VPL_E_NUMERIC when the factorisation fails. */
+int vpl_gf_debug_step(vpl_ctx* ctx, const vpl_gf_input* in, const vpl_gf_options* opt, double* g, double* step, double* model_cost_change);
+/* host only: the plan of (n, segment): n_sep [1] and sep_node [n / 2] (the first n_sep written), n_seg [1] and seg_bounds
+ * [n / 2 + 1][2] (first and one past the last interior node of the first n_seg segments).  VPL_E_INVALID: null pointers, n < 1,
+ * segment other than 0 or >= 2; VPL_E_CAPACITY: n > VPL_GF_MAX_NODES. */
+int vpl_gf_debug_plan(int n, int segment, int* n_sep, int* sep_node, int* n_seg, int* seg_bounds);
+/* host only, replaces GPS2XYZ: WGS84 geodetic (latitude, longitude in degrees, height in metres) -> ECEF -> east, north, up at the
+ * origin (lat0, lon0, h0), in closed form in f64 (a = 6378137, f = 1 / 298.257223563).  lla [n][3] -> xyz [n][3].
+ * VPL_E_INVALID: null arrays, n < 0. */
+int vpl_gf_local_cartesian(double lat0, double lon0, double h0, int n, const double* lla, double* xyz);
+
+/* The session: the GlobalOptimization object with the trajectory resident on the device.  It runs the batch call's kernels on its
+ * own arrays (sized for max_nodes) and adds none.  The context must outlive it.
+ *   vpl_gf_input_odom   inputOdom + getGlobalOdom: appends the local pose (t strictly increasing) and, on the host, the global pose
+ *                       WGPS_T_WVIO makes of it -- q = mat2q(R qmat(q)), p = R p + t -- which it returns.
+ *   vpl_gf_input_gps    inputGPS with the position already local (vpl_gf_local_cartesian): a fix of the node whose time is t, in
+ *                       place of an earlier one; a t that no node has is stored and never used.
+ *   vpl_gf_optimize     uploads the poses and fixes that came since the last call (and one chain descriptor), runs the solve, and
+ *                       reads back the result head alone (result->pose is not touched); the global poses of every node and
+ *                       WGPS_T_WVIO are the solved ones from then on.  Equal, byte for byte, to vpl_gf_optimize_batch on the
+ *                       same local poses, fixes, and global poses carried forward.
+ *   vpl_gf_get_path     global poses [count][7] of the nodes first .. first + count - 1.
+ * VPL_E_INVALID: null pointers, a time that does not increase, a non-finite pose or fix, an accuracy that is not positive, no node
+ * yet, a path range beyond the last node, options out of range; VPL_E_CAPACITY: max_nodes > VPL_GF_MAX_NODES, a node beyond
+ * max_nodes. */
+typedef struct vpl_gf_session vpl_gf_session;
+int vpl_gf_create(vpl_ctx* ctx, int max_nodes, vpl_gf_session** out);
+void vpl_gf_destroy(vpl_gf_session* h);
+int vpl_gf_input_odom(vpl_gf_session* h, double t, const double* p, const double* q, double* out_p, double* out_q);
+int vpl_gf_input_gps(vpl_gf_session* h, double t, const double* xyz, double accuracy);
+int vpl_gf_optimize(vpl_gf_session* h, const vpl_gf_options* opt, vpl_gf_result* result);
+int vpl_gf_get_path(vpl_gf_session* h, int first, int count, double* out);
+
 #ifdef __cplusplus
 }
 #endif

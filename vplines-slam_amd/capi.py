@@ -393,6 +393,165 @@ class PoseGraphResult:
         return b"".join(a.tobytes() for a in (ints, dbl, self.T, self.R, self.tail_T, self.tail_R))
 
 
+GF_MAX_NODES = 65536   # VPL_GF_MAX_NODES
+GF_NO_CONVERGENCE, GF_CONVERGENCE, GF_FAILURE = 0, 1, 2
+
+
+class GfOptions(C.Structure):   # vpl_gf_options
+    _fields_ = [("max_iterations", C.c_int), ("max_consecutive_invalid_steps", C.c_int), ("segment", C.c_int), ("reserved", C.c_int),
+                ("t_var", C.c_double), ("q_var", C.c_double), ("huber_delta", C.c_double), ("initial_radius", C.c_double),
+                ("max_radius", C.c_double), ("min_radius", C.c_double), ("min_relative_decrease", C.c_double),
+                ("function_tolerance", C.c_double), ("gradient_tolerance", C.c_double), ("parameter_tolerance", C.c_double),
+                ("min_lm_diagonal", C.c_double), ("max_lm_diagonal", C.c_double)]
+
+
+def default_gf_options(**changes):
+    o = GfOptions()
+    load_hip_library().vpl_gf_default_options(C.byref(o))
+    for k, val in changes.items():
+        setattr(o, k, val)
+    return o
+
+
+class CGfInput(C.Structure):   # vpl_gf_input
+    _fields_ = [("n", C.c_int), ("n_gps", C.c_int), ("local", _dp), ("glob", _dp), ("gps_node", _ip), ("gps_xyz", _dp),
+                ("gps_accuracy", _dp)]
+
+
+class CGfResult(C.Structure):   # vpl_gf_result
+    _fields_ = [("status", C.c_int), ("termination", C.c_int), ("iterations", C.c_int), ("successful_steps", C.c_int),
+                ("unsuccessful_steps", C.c_int), ("reserved", C.c_int), ("initial_cost", C.c_double), ("final_cost", C.c_double),
+                ("wgps_T_wvio", C.c_double * 16), ("pose", _dp)]
+
+
+class GlobalFusionInput:
+    """numpy-backed owner of one vpl_gf_input: the odometry poses local [n][7] = p, q(w, x, y, z), the initial global poses
+    global_ [n][7], and the GNSS fixes gps_node [n_gps] (strictly ascending), gps_xyz [n_gps][3], gps_accuracy [n_gps]"""
+
+    def __init__(self, local, global_, gps_node=(), gps_xyz=(), gps_accuracy=()):
+        self.local = _arr(local, np.float64).reshape(-1, 7).copy()
+        n = len(self.local)
+        self.global_ = _arr(global_, np.float64).reshape(n, 7).copy()
+        self.gps_node = _arr(gps_node, np.int32).reshape(-1).copy()
+        m = len(self.gps_node)
+        self.gps_xyz = _arr(gps_xyz, np.float64).reshape(m, 3).copy()
+        self.gps_accuracy = _arr(gps_accuracy, np.float64).reshape(m).copy()
+
+    def to_c(self, ci=None):
+        ci = ci if ci is not None else CGfInput()
+        ci.n, ci.n_gps = len(self.local), len(self.gps_node)
+        ci.local, ci.glob = self.local.ctypes.data_as(_dp), self.global_.ctypes.data_as(_dp)
+        m = len(self.gps_node)
+        ci.gps_node = self.gps_node.ctypes.data_as(_ip) if m else None
+        ci.gps_xyz = self.gps_xyz.ctypes.data_as(_dp) if m else None
+        ci.gps_accuracy = self.gps_accuracy.ctypes.data_as(_dp) if m else None
+        return ci
+
+
+class GlobalFusionResult:
+    """one chain's vpl_gf_result with the array it points to: head (CGfResult), pose [n][7]"""
+
+    def __init__(self, head, pose):
+        self.head, self.pose = head, pose
+
+    def __getattr__(self, name):
+        return getattr(self.head, name)
+
+    @property
+    def T(self):
+        """wgps_T_wvio as a 4 x 4 array"""
+        return np.array(self.head.wgps_T_wvio[:]).reshape(4, 4)
+
+    def data_head(self):
+        """every value of the head, as bytes (the pointer left out)"""
+        h = self.head
+        ints = np.array([h.status, h.termination, h.iterations, h.successful_steps, h.unsuccessful_steps], dtype=np.int32)
+        dbl = np.array([h.initial_cost, h.final_cost] + list(h.wgps_T_wvio))
+        return ints.tobytes() + dbl.tobytes()
+
+    def data(self):
+        """every value the call wrote, as bytes"""
+        return self.data_head() + self.pose.tobytes()
+
+
+def gf_debug_plan(n, segment=0):
+    """vpl_gf_debug_plan (host only): the separators and segments of an n-node chain -> dict sep_node [n_sep], seg_bounds [n_seg][2],
+    or the VPL_E_* code of a refusal"""
+    lib = load_hip_library()
+    cap = max(int(n), 0) // 2 + 1
+    sep, seg = np.zeros(cap, dtype=np.int32), np.zeros((cap, 2), dtype=np.int32)
+    ns, ng = C.c_int(0), C.c_int(0)
+    rc = lib.vpl_gf_debug_plan(int(n), int(segment), C.byref(ns), sep.ctypes.data_as(_ip), C.byref(ng), seg.ctypes.data_as(_ip))
+    return dict(sep_node=sep[:ns.value].copy(), seg_bounds=seg[:ng.value].copy()) if rc == 0 else rc
+
+
+def local_cartesian(lat0, lon0, h0, lla):
+    """vpl_gf_local_cartesian (host only): WGS84 latitude, longitude (degrees), height [n][3] -> east, north, up [n][3] at the origin"""
+    lib = load_hip_library()
+    lla = _arr(lla, np.float64).reshape(-1, 3).copy()
+    xyz = np.zeros_like(lla)
+    rc = lib.vpl_gf_local_cartesian(float(lat0), float(lon0), float(h0), len(lla), lla.ctypes.data_as(_dp), xyz.ctypes.data_as(_dp))
+    if rc != 0:
+        raise RuntimeError("vpl_gf_local_cartesian failed: %d" % rc)
+    return xyz
+
+
+class GlobalFusionSession:
+    """vpl_gf_create .. vpl_gf_destroy: the GlobalOptimization object with the trajectory resident on the device, on a Context that
+    outlives it.  check=False on a method: a refusal comes back as its VPL_E_* code instead of an exception."""
+
+    def __init__(self, ctx, max_nodes):
+        self.ctx, self.lib, self.h = ctx, ctx.lib, C.c_void_p()
+        ctx._settle()
+        rc = self.lib.vpl_gf_create(ctx.h, int(max_nodes), C.byref(self.h))
+        if rc != 0:
+            self.h = None
+            ctx._check(rc, "vpl_gf_create")
+
+    def close(self):
+        if self.h:
+            self.lib.vpl_gf_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _done(self, rc, what, check):
+        if rc != 0 and not check:
+            return rc
+        self.ctx._check(rc, what)
+        return None
+
+    def input_odom(self, t, p, q, check=True):
+        """inputOdom + getGlobalOdom: -> (global p [3], global q [4] = w, x, y, z)"""
+        p, q = _arr(p, np.float64).reshape(3).copy(), _arr(q, np.float64).reshape(4).copy()
+        op, oq = np.zeros(3), np.zeros(4)
+        rc = self.lib.vpl_gf_input_odom(self.h, float(t), p.ctypes.data_as(_dp), q.ctypes.data_as(_dp), op.ctypes.data_as(_dp), oq.ctypes.data_as(_dp))
+        bad = self._done(rc, "vpl_gf_input_odom", check)
+        return bad if bad is not None else (op, oq)
+
+    def input_gps(self, t, xyz, accuracy, check=True):
+        xyz = _arr(xyz, np.float64).reshape(3).copy()
+        return self._done(self.lib.vpl_gf_input_gps(self.h, float(t), xyz.ctypes.data_as(_dp), float(accuracy)), "vpl_gf_input_gps", check)
+
+    def optimize(self, options=None, check=True):
+        """-> GlobalFusionResult with the head only (pose is None): the poses stay on the device, see path()"""
+        opt = options if options is not None else default_gf_options()
+        self.ctx._settle()
+        res = CGfResult()
+        bad = self._done(self.lib.vpl_gf_optimize(self.h, C.byref(opt), C.byref(res)), "vpl_gf_optimize", check)
+        return bad if bad is not None else GlobalFusionResult(res, None)
+
+    def path(self, first, count, check=True):
+        out = np.zeros((max(int(count), 0), 7))
+        self.ctx._settle()
+        bad = self._done(self.lib.vpl_gf_get_path(self.h, int(first), int(count), out.ctypes.data_as(_dp)), "vpl_gf_get_path", check)
+        return bad if bad is not None else out
+
+
 SEL_MAX_FEATURES = 1024   # VPL_SEL_MAX_FEATURES
 
 
@@ -735,6 +894,19 @@ def load_hip_library():
     lib.vpl_pg_default_options.restype = None
     lib.vpl_pg_optimize_batch.argtypes = [vp, C.c_int, C.POINTER(CPgInput), C.POINTER(PgOptions), C.POINTER(CPgResult)]
     lib.vpl_pg_debug_step.argtypes = [vp, C.POINTER(CPgInput), C.POINTER(PgOptions), _dp, _dp, _dp]
+    lib.vpl_gf_default_options.argtypes = [C.POINTER(GfOptions)]
+    lib.vpl_gf_default_options.restype = None
+    lib.vpl_gf_optimize_batch.argtypes = [vp, C.c_int, C.POINTER(CGfInput), C.POINTER(GfOptions), C.POINTER(CGfResult)]
+    lib.vpl_gf_debug_step.argtypes = [vp, C.POINTER(CGfInput), C.POINTER(GfOptions), _dp, _dp, _dp]
+    lib.vpl_gf_debug_plan.argtypes = [C.c_int, C.c_int, _ip, _ip, _ip, _ip]
+    lib.vpl_gf_local_cartesian.argtypes = [C.c_double, C.c_double, C.c_double, C.c_int, _dp, _dp]
+    lib.vpl_gf_create.argtypes = [vp, C.c_int, C.POINTER(vp)]
+    lib.vpl_gf_destroy.argtypes = [vp]
+    lib.vpl_gf_destroy.restype = None
+    lib.vpl_gf_input_odom.argtypes = [vp, C.c_double, _dp, _dp, _dp, _dp]
+    lib.vpl_gf_input_gps.argtypes = [vp, C.c_double, _dp, C.c_double]
+    lib.vpl_gf_optimize.argtypes = [vp, C.POINTER(GfOptions), C.POINTER(CGfResult)]
+    lib.vpl_gf_get_path.argtypes = [vp, C.c_int, C.c_int, _dp]
     lib.vpl_init_visual_batch.argtypes = [vp, C.c_int, C.POINTER(CSfmInput), C.POINTER(C.c_ulonglong), C.POINTER(RelPoseResult),
                                           C.POINTER(SfmResult), _dp, _dp, _ip, _dp]
     lib.vpl_select_features_batch.argtypes = [vp, C.c_int, C.POINTER(SelectParams), C.POINTER(CSelectInput), C.POINTER(SelectResult), _ip, _dp]
@@ -1179,6 +1351,47 @@ class Context:
         rc = self.lib.vpl_pg_debug_step(self.h, ci, C.byref(opt), g.ctypes.data_as(_dp), step.ctypes.data_as(_dp), mc.ctypes.data_as(_dp))
         self._check(rc, "vpl_pg_debug_step")
         return dict(g=g[:m], step=step[:m], model_cost_change=float(mc[0]))
+
+    @staticmethod
+    def _gf_c(inputs):
+        ci = (CGfInput * len(inputs))()
+        for i, q in enumerate(inputs):
+            if isinstance(q, CGfInput):
+                C.memmove(C.byref(ci[i]), C.byref(q), C.sizeof(CGfInput))   # as the caller filled it (tests of the refusals)
+            else:
+                q.to_c(ci[i])
+        return ci
+
+    def global_fusion(self, inputs, options=None, check=True):
+        """vpl_gf_optimize_batch over a list of GlobalFusionInput: GlobalOptimization::optimize per chain -- the global poses and
+        WGPS_T_WVIO -- in one call.  -> list of GlobalFusionResult.  check=False: a refusal comes back as its VPL_E_* code instead of
+        an exception."""
+        self._settle()
+        n = len(inputs)
+        ci = self._gf_c(inputs)
+        opt = options if options is not None else default_gf_options()
+        res = (CGfResult * n)()
+        out = []
+        for i in range(n):
+            pose = np.zeros((max(int(ci[i].n), 0), 7))
+            res[i].pose = pose.ctypes.data_as(_dp)
+            out.append(pose)
+        rc = self.lib.vpl_gf_optimize_batch(self.h, n, ci, C.byref(opt), res)
+        if rc != 0 and not check:
+            return rc
+        self._check(rc, "vpl_gf_optimize_batch")
+        return [GlobalFusionResult(res[i], out[i]) for i in range(n)]
+
+    def global_fusion_debug_step(self, q, options=None):
+        """vpl_gf_debug_step: the first linear solve of one chain -> dict g, step [6 n], model_cost_change"""
+        self._settle()
+        ci = self._gf_c([q])
+        opt = options if options is not None else default_gf_options()
+        m = 6 * max(int(ci[0].n), 1)
+        g, step, mc = np.zeros(m), np.zeros(m), np.zeros(1)
+        rc = self.lib.vpl_gf_debug_step(self.h, ci, C.byref(opt), g.ctypes.data_as(_dp), step.ctypes.data_as(_dp), mc.ctypes.data_as(_dp))
+        self._check(rc, "vpl_gf_debug_step")
+        return dict(g=g, step=step, model_cost_change=float(mc[0]))
 
     @staticmethod
     def _select_c(params, inputs):
