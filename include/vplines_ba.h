@@ -174,7 +174,9 @@ const char* vpl_last_error(const vpl_ctx* ctx);
 /* ---- IMU pre-integration  (replaces IntegrationBase::push_back/propagate/
  *      midPointIntegration, integration_base.h:30-36,54-198) --------------- */
 /* n intervals; interval k has nsamples[k] samples stored at samples + 7*offset[k]
- * as (dt, ax,ay,az, gx,gy,gz); acc0/gyr0/ba/bg are [n][3]. Host in, host out. */
+ * as (dt, ax,ay,az, gx,gy,gz); acc0/gyr0/ba/bg are [n][3]. Host in, host out.
+ * nsamples[k] == 0 is an empty interval: the identity, a zero covariance, sum_dt 0, and no row of `samples` is read for it.
+ * A negative offset[k] or nsamples[k] is VPL_E_INVALID. */
 int vpl_preintegrate_batch(vpl_ctx* ctx, int n, const int* offset, const int* nsamples,
                            const double* samples, const double* acc0, const double* gyr0,
                            const double* lin_ba, const double* lin_bg, const vpl_ba_options* opt,

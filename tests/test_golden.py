@@ -58,8 +58,7 @@ def test_oracle_against_golden():
               lambda p, c: o.vp_factor(p, c, want_jac=False), o.pose_plus, o.line_orth_plus, o.orth_to_plk, imu)
 
 
-@pytest.fixture(scope="module")
-def hostcheck():
+def build_hostcheck():
     """device math header compiled with g++ (test-only; the product library has no CPU path)"""
     src = os.path.join(HERE, "native", "devmath_hostcheck.cpp")
     lib = os.path.join(HERE, "native", "libdevmath_hostcheck.so")
@@ -68,6 +67,11 @@ def hostcheck():
     if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
         subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-o", lib, src])
     return C.CDLL(lib)
+
+
+@pytest.fixture(scope="module")
+def hostcheck():
+    return build_hostcheck()
 
 
 def _P(a):
@@ -118,6 +122,10 @@ def test_device_math_on_host_against_golden_and_oracle(hostcheck):
 
 
 def test_device_preintegration_on_host_matches_oracle(hostcheck):
+    """vpl_preint.h::preint_step (serial, dense F, V and T in memory) against the oracle.  That function is NOT what the device
+    runs: k_preintegrate and k_odo_imu run the lane-spread preint_steps of ba_factors.h, which test_gpu_preint.py holds to the
+    long-double restatement preint_ref.py.  Here it is a third float64 implementation (test_preint_reference.py holds it to long
+    double as well)."""
     opt = v.default_options()
     cfg = v.workload.config(4, 0, False)
     w = v.workload.generate(77, cfg, 0.3)

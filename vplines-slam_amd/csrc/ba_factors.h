@@ -238,9 +238,15 @@ __device__ __forceinline__ void preint_steps(PreintLane& s, int j, const double*
   const int jc = j < 15 ? j : 14, jb = jc / 3, jj = jc % 3;
   for (int k = 0; k < nmax; ++k) {
     const bool on = k < ns;
-    const double* p = sp + 7 * (on ? k : 0);
-    const double dt = on ? p[0] : 0.0;   // a group past its own sample count applies F = I, N = 0 (exact: every term carries dt)
-    const V3 a1{p[1], p[2], p[3]}, g1{p[4], p[5], p[6]};
+    // a group past its own sample count applies F = I, N = 0: every term carries dt = 0, which is exact for FINITE operands only
+    // (0 * NaN is NaN), and with ns == 0 no row at sp is the group's to read -- so it loads nothing and steps on zeros
+    double dt = 0.0;
+    V3 a1{0, 0, 0}, g1{0, 0, 0};
+    if (on) {
+      const double* p = sp + 7 * k;
+      dt = p[0];
+      a1 = V3{p[1], p[2], p[3]}; g1 = V3{p[4], p[5], p[6]};
+    }
     // midPointIntegration (:54-198)
     const V3 un_acc_0 = qrot(s.dq, s.a0 - ba);
     const V3 un_gyr = (s.g0 + g1) * 0.5 - bg;

@@ -2,6 +2,9 @@
 // Reproduces IntegrationBase::{push_back,propagate,midPointIntegration}
 // (vins_estimator/src/factor/integration_base.h:30-36,54-198): per sample
 //   J <- F J,  P <- F P F^T + V Q V^T,  delta_q normalised after every sample.
+// NOT what the device runs: k_preintegrate and k_odo_imu run the lane-spread, block-sparse preint_steps of ba_factors.h.
+// This serial form with dense F, V and T in memory is compiled for the host only (tests/native/devmath_hostcheck.cpp), where
+// it serves as a third float64 implementation held to the long-double restatement (tests/test_preint_reference.py).
 #pragma once
 #include "vpl_math.h"
 

@@ -303,6 +303,9 @@ int vpl_preintegrate_batch(vpl_ctx* c, int n, const int* offset, const int* nsam
                            const vpl_ba_options* opt, vpl_preintegration* out) {
   if (!c || n < 0 || !opt) return VPL_E_INVALID;
   if (n == 0) return VPL_OK;
+  if (!offset || !nsamples) return VPL_E_INVALID;
+  for (int i = 0; i < n; ++i)
+    if (offset[i] < 0 || nsamples[i] < 0) return VPL_E_INVALID;   // before anything is sized by them; nsamples[i] == 0 is an empty interval
   HIPCHK(c, hipSetDevice(c->device));
   size_t total = 0;
   for (int i = 0; i < n; ++i) total = std::max(total, (size_t)offset[i] + nsamples[i]);
