@@ -454,6 +454,80 @@ int vpl_lc_match_batch(vpl_fe_ctx* ctx, int n_pairs, const unsigned long long* w
                        const int* old_counts, float* matched_2d_old, float* matched_2d_old_norm, uint8_t* status, int* best_dist,
                        int* best_index);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Loop detector session: PoseGraph::detectLoop (pose_graph/src/pose_graph.cpp:304-386) and addKeyFrameIntoVoc (:388-401) -- the
+ * DBoW2 vocabulary, the keyframe database and the query that names a loop candidate -- for n_db independent databases (one per
+ * PoseGraph) that share one vocabulary, one call per keyframe; everything stays on the device.  The step between
+ * vpl_lc_keyframe_batch and vpl_lc_match_batch.  The session borrows the context (one per context; vpl_fe_destroy destroys a
+ * session that is still open).
+ *
+ * Vocabulary.  vpl_ld_load_vocabulary reads the reference's binary file (ThirdParty/VocabularyBinary.hpp, loadBin,
+ * TemplatedVocabulary.h:1509-1561): six int32 k, L, scoringType, weightingType, nNodes, nWords; nNodes records of 48 bytes
+ * (int32 nodeId, int32 parentId, double weight, uint64 descriptor[4]); nWords records of 8 bytes (int32 nodeId, int32 wordId).
+ * vpl_ld_set_vocabulary takes the same content from arrays.  The root is node 0 and not listed; a node's children are in list
+ * order; a descriptor has the bit layout vpl_lc_keyframe_batch writes.  The tree need not be regular.  The descent of a
+ * descriptor starts at the root, takes the child of least Hamming distance (the first on a tie) and stops at the first node
+ * without children; its word and weight are that leaf's.  Refused with VPL_E_INVALID, the reason in vpl_fe_last_error, the
+ * session unchanged: a node id outside 1 .. nNodes or given twice, a parent that is not a node, a cycle, a leaf without a word,
+ * a word on an inner node, a node with two words, a word id outside 0 .. nWords - 1 or given twice, a node deeper than 16
+ * levels, a truncated file, a scoring other than L1_NORM (0).  Weighting 0 .. 3 = TF_IDF, TF, IDF, BINARY.  A vocabulary without
+ * nodes is legal and gives empty bags.  Setting a vocabulary empties every database.  The reference's own file
+ * (support_files/brief_k10L6.bin) was never available to this project: the layout is restated from the sources that read it.
+ *
+ * vpl_ld_detect, per database d with counts[d] >= 0 (a negative count leaves the database untouched), in the reference's order:
+ *   transform (TemplatedVocabulary.h:1065-1121): words with a weight > 0; TF_IDF and TF add the weight once per occurrence by
+ *     repeated addition, IDF and BINARY set it once; the L1 norm summed in ascending word id, every value divided by it (left
+ *     as it is when the norm is 0);
+ *   queryL1 (TemplatedDatabase.h:656-723) with max_id = frame_index[d] - recent: entry e takes part if e < max_id || max_id == -1
+ *     || e == n_entries - 1; it is a result if it shares a word with the query; raw score = the sum over the shared words in
+ *     ascending word id of fabs(q - v) - fabs(q) - fabs(v); the max_results smallest by (raw score, entry id) -- the reference
+ *     sorts by the score alone and leaves ties to std::sort -- with score = -raw / 2;
+ *   db.add: the bag becomes entry n_entries (an empty bag too); then loop_index by pose_graph.cpp:348-384: found if
+ *     scores[0] > neighbour_score and some scores[i >= 1] > loop_score, reported only if frame_index[d] > recent, as ids[0]
+ *     replaced by any result of smaller id with a score > loop_score; else -1.
+ *   brief [n_db][max_keypoints][4], counts [n_db], frame_index [n_db], res [n_db] (entry -1, nothing else, for a skipped database)
+ * vpl_ld_add: addKeyFrameIntoVoc, the transform and db.add without the query (res may be NULL).
+ * vpl_ld_detect_fe: vpl_ld_detect on the descriptor rows and counts the last vpl_lc_keyframe_batch on the session's context left on
+ *   the device, image slot i to database i; VPL_E_INVALID unless that call took n_db images with rows of max_keypoints.
+ * vpl_ld_reset empties one database (asynchronous).  vpl_ld_size: its number of entries.  vpl_ld_get_bow (tests): a stored bag,
+ *   words ascending; arrays of max_keypoints entries.
+ * VPL_E_CAPACITY, the database named in vpl_fe_last_error, NO database of the call changed: a count above max_keypoints, entry
+ * max_keyframes + 1, a bag that does not fit into what is left of max_words_total (a stored bag takes its own length; none is
+ * cut short).  VPL_E_INVALID before a vocabulary is set.  One copy down (the rows; frame_index alone for _fe), one copy back,
+ * one synchronisation.  All arithmetic is f64 in the stated order: scores and bag values are the reference's bits.
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct vpl_ld vpl_ld;
+typedef struct vpl_ld_options {
+  int max_keyframes;        /* per database (2048) */
+  int max_keypoints;        /* row length of a descriptor list, <= 8192 (8192) */
+  int max_words_total;      /* per database: the pool of the stored bags (2048 * 3000) */
+  int max_results;          /* 4 (1 .. 4) */
+  int recent;               /* 50 */
+  double neighbour_score;   /* 0.05 */
+  double loop_score;        /* 0.015 */
+} vpl_ld_options;
+typedef struct vpl_ld_result {
+  int loop_index;           /* detectLoop's return value */
+  int n_results;
+  int ids[4];               /* -1 past n_results */
+  double scores[4];         /* 0 past n_results */
+  int n_words;              /* length of the new bag */
+  int entry;                /* the id the keyframe got */
+} vpl_ld_result;
+void vpl_ld_default_options(vpl_ld_options* opt);
+int vpl_ld_create(vpl_ld** out, vpl_fe_ctx* ctx, int n_db, const vpl_ld_options* opt);
+void vpl_ld_destroy(vpl_ld* ld);
+int vpl_ld_set_vocabulary(vpl_ld* ld, int k, int L, int scoring, int weighting, int n_nodes, const int* node_id, const int* parent_id,
+                          const double* weight, const unsigned long long* descriptor, int n_words, const int* word_node,
+                          const int* word_id);
+int vpl_ld_load_vocabulary(vpl_ld* ld, const char* path);
+int vpl_ld_detect(vpl_ld* ld, const unsigned long long* brief, const int* counts, const int* frame_index, vpl_ld_result* res);
+int vpl_ld_detect_fe(vpl_ld* ld, const int* frame_index, vpl_ld_result* res);
+int vpl_ld_add(vpl_ld* ld, const unsigned long long* brief, const int* counts, vpl_ld_result* res);
+int vpl_ld_reset(vpl_ld* ld, int db);
+int vpl_ld_size(vpl_ld* ld, int db);
+int vpl_ld_get_bow(vpl_ld* ld, int db, int entry, int* n, int* words, double* values);
+
 #ifdef __cplusplus
 }
 #endif

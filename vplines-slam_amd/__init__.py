@@ -23,3 +23,4 @@ from . import shard  # noqa: F401
 from . import frontend  # noqa: F401
 from .frontend import TrackerSession, TrackerOptions, TrackerResult, default_tracker_options  # noqa: F401
 from .frontend import PointCamera, PointTrackerSession, PointTrackerOptions, PointTrackerResult, default_point_tracker_options  # noqa: F401
+from .frontend import LoopDetector, LoopDetectorOptions, LoopDetectorResult, Vocabulary, default_loop_detector_options  # noqa: F401

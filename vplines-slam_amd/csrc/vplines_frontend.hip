@@ -16,12 +16,15 @@
 #include "pre_kernels.h"
 #include "pt_kernels.h"
 #include "lc_kernels.h"
+#include "ld_vocab.h"
+#include "ld_kernels.h"
 #include "vp_kernels.h"
 
 using namespace vpl;
 
 struct vpl_trk;
 struct vpl_ptrk;
+struct vpl_ld;
 
 struct vpl_fe_ctx {
   int device = 0;
@@ -75,6 +78,7 @@ struct vpl_fe_ctx {
   unsigned char* d_lcmIn = nullptr;   // vpl_lc_match_batch: the one upload (lc_match_layout)
   unsigned char* d_lcmOut = nullptr;  // its results
   int lcN = 0;                        // frames of the last vpl_lc_keyframe_batch (vpl_lc_debug_frame)
+  bool lcRowsValid = false;           // its descriptor rows and counts stand in d_lcOut (vpl_ld_detect_fe)
   std::vector<DevAlloc> allocs;      // host_common.h: the context's own arrays (owner null, the lazy ones included) and the tracker session's
   bool guards = false;
   std::string err;
@@ -82,6 +86,7 @@ struct vpl_fe_ctx {
   std::vector<std::pair<const char*, double>> ktimes;     // (kernel, ms) of the launches since timing was enabled
   vpl_trk* trk = nullptr;                                 // the tracker session this context lends itself to (trk_session.h)
   vpl_ptrk* ptrk = nullptr;                               // the point tracker session (pt_session.h)
+  vpl_ld* ld = nullptr;                                   // the loop detector session (ld_session.h)
 };
 
 // times one kernel launch with hipEvents on the context's stream when timing is on (bench.py: k_ed_grad GB/s)
@@ -230,6 +235,7 @@ void vpl_fe_destroy(vpl_fe_ctx* c) {
   if (!c) return;
   if (c->trk) vpl_trk_destroy(c->trk);   // a session that is still open goes first (its arrays are the context's)
   if (c->ptrk) vpl_ptrk_destroy(c->ptrk);
+  if (c->ld) vpl_ld_destroy(c->ld);
   // (teardown: a failure has nobody to be reported to)
   (void)hipSetDevice(c->device);
   (void)hipDeviceSynchronize();
@@ -1218,6 +1224,7 @@ int vpl_lc_keyframe_batch(vpl_fe_ctx* c, int n, const uint8_t* images, const flo
   }
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = c->stream;
+  c->lcRowsValid = false;
   if (images) { const int rc = vpl_edlines_upload(c, n, images); if (rc) return rc; }
   const size_t oCnt = (size_t)n * WP * 8;
   std::vector<unsigned char> in(oCnt + (size_t)n * 4);
@@ -1249,6 +1256,7 @@ int vpl_lc_keyframe_batch(vpl_fe_ctx* c, int n, const uint8_t* images, const flo
     if (cnt[i] < 0)
       return fail(c, VPL_E_CAPACITY, "image " + std::to_string(i) + ": " + std::to_string(found[i]) + " FAST corners, max_keypoints is " +
                                          std::to_string(L.capKp));
+  c->lcRowsValid = true;
   for (int i = 0; i < n; ++i) {
     const size_t k = cnt[i], w = window_counts[i];
     kp_counts[i] = cnt[i];
@@ -1368,3 +1376,4 @@ int vpl_line_track_ids(int n_new, const float* ends, int n_prev, const int* id_p
 
 #include "trk_session.h"
 #include "pt_session.h"
+#include "ld_session.h"

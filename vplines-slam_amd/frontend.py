@@ -221,6 +221,8 @@ class FrontendContext:
             self._trk.close()                      # the session goes before the context it borrows
         if self.h and getattr(self, "_ptrk", None) is not None:
             self._ptrk.close()
+        if self.h and getattr(self, "_ld", None) is not None:
+            self._ld.close()
         if self.h:
             bad = self.debug_guards() if os.environ.get("VPL_DEBUG_GUARDS") == "1" else 0
             msg = self.lib.vpl_fe_last_error(self.h).decode() if bad else ""
@@ -856,3 +858,203 @@ class PointTrackerSession:
                                                    usc.ctypes.data_as(fp), C.byref(nid)), "vpl_ptrk_get_frame")
         m = n.value
         return dict(n=m, pts=pts[:m], ids=ids[:m], track_cnt=cnt[:m], scores=sc[:m], un_pts=un[:m], un_scores=usc[:m], next_id=nid.value)
+
+
+# ---- loop detector: the DBoW2 vocabulary, the keyframe database, PoseGraph::detectLoop (pose_graph/src/pose_graph.cpp:304-386) ----
+TF_IDF, TF, IDF, BINARY = 0, 1, 2, 3      # DBoW2::WeightingType
+L1_NORM = 0                               # DBoW2::ScoringType: the only one taken
+
+VOC_NODE_DTYPE = np.dtype([("node_id", "<i4"), ("parent_id", "<i4"), ("weight", "<f8"), ("descriptor", "<u8", 4)])   # 48 bytes
+VOC_WORD_DTYPE = np.dtype([("node_id", "<i4"), ("word_id", "<i4")])
+assert VOC_NODE_DTYPE.itemsize == 48 and VOC_WORD_DTYPE.itemsize == 8
+
+
+class Vocabulary:
+    """The content of the reference's binary vocabulary file (ThirdParty/VocabularyBinary.hpp): k, L, scoring, weighting, the
+    nodes in file order (a node's children are in this order; the root, node 0, is not listed) and the (node, word) pairs.
+    Nothing is validated here: LoopDetector.set_vocabulary / load_vocabulary refuse what the library refuses."""
+
+    def __init__(self, k, L, node_id, parent_id, weight, descriptor, word_node, word_id, scoring=L1_NORM, weighting=TF_IDF):
+        self.k, self.L, self.scoring, self.weighting = int(k), int(L), int(scoring), int(weighting)
+        self.node_id = np.ascontiguousarray(node_id, np.int32).reshape(-1)
+        self.parent_id = np.ascontiguousarray(parent_id, np.int32).reshape(-1)
+        self.weight = np.ascontiguousarray(weight, np.float64).reshape(-1)
+        self.descriptor = np.ascontiguousarray(descriptor, np.uint64).reshape(-1, 4)
+        self.word_node = np.ascontiguousarray(word_node, np.int32).reshape(-1)
+        self.word_id = np.ascontiguousarray(word_id, np.int32).reshape(-1)
+        n = len(self.node_id)
+        if not (len(self.parent_id) == len(self.weight) == len(self.descriptor) == n and len(self.word_node) == len(self.word_id)):
+            raise ValueError("Vocabulary: arrays of different lengths")
+
+    def to_file(self, path):
+        nodes = np.zeros(len(self.node_id), VOC_NODE_DTYPE)
+        nodes["node_id"], nodes["parent_id"], nodes["weight"], nodes["descriptor"] = self.node_id, self.parent_id, self.weight, self.descriptor
+        words = np.zeros(len(self.word_id), VOC_WORD_DTYPE)
+        words["node_id"], words["word_id"] = self.word_node, self.word_id
+        with open(path, "wb") as f:
+            f.write(np.array([self.k, self.L, self.scoring, self.weighting, len(nodes), len(words)], "<i4").tobytes())
+            f.write(nodes.tobytes())
+            f.write(words.tobytes())
+
+    @classmethod
+    def from_file(cls, path):
+        with open(path, "rb") as f:
+            raw = f.read()
+        if len(raw) < 24:
+            raise ValueError("vocabulary file truncated inside its header")
+        k, L, scoring, weighting, n, w = (int(x) for x in np.frombuffer(raw, "<i4", 6))
+        if n < 0 or w < 0 or len(raw) < 24 + 48 * n + 8 * w:
+            raise ValueError("vocabulary file truncated: %d bytes for %d nodes and %d words" % (len(raw), n, w))
+        nodes = np.frombuffer(raw, VOC_NODE_DTYPE, n, 24)
+        words = np.frombuffer(raw, VOC_WORD_DTYPE, w, 24 + 48 * n)
+        return cls(k, L, nodes["node_id"], nodes["parent_id"], nodes["weight"], nodes["descriptor"], words["node_id"], words["word_id"],
+                   scoring, weighting)
+
+
+class LoopDetectorOptions(C.Structure):
+    """vpl_ld_options"""
+    _fields_ = [("max_keyframes", C.c_int), ("max_keypoints", C.c_int), ("max_words_total", C.c_int), ("max_results", C.c_int),
+                ("recent", C.c_int), ("neighbour_score", C.c_double), ("loop_score", C.c_double)]
+
+
+class LoopDetectorResult(C.Structure):
+    """vpl_ld_result"""
+    _fields_ = [("loop_index", C.c_int), ("n_results", C.c_int), ("ids", C.c_int * 4), ("scores", C.c_double * 4),
+                ("n_words", C.c_int), ("entry", C.c_int)]
+
+
+def _bind_ld(lib):
+    if getattr(lib, "_vpl_ld_bound", False):
+        return
+    vp, ip, dp, u64p = C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_ulonglong)
+    rp = C.POINTER(LoopDetectorResult)
+    lib.vpl_ld_default_options.argtypes = [C.POINTER(LoopDetectorOptions)]
+    lib.vpl_ld_default_options.restype = None
+    lib.vpl_ld_create.argtypes = [C.POINTER(vp), vp, C.c_int, C.POINTER(LoopDetectorOptions)]
+    lib.vpl_ld_destroy.argtypes = [vp]
+    lib.vpl_ld_destroy.restype = None
+    lib.vpl_ld_set_vocabulary.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, dp, u64p, C.c_int, ip, ip]
+    lib.vpl_ld_load_vocabulary.argtypes = [vp, C.c_char_p]
+    lib.vpl_ld_detect.argtypes = [vp, u64p, ip, ip, rp]
+    lib.vpl_ld_detect_fe.argtypes = [vp, ip, rp]
+    lib.vpl_ld_add.argtypes = [vp, u64p, ip, rp]
+    lib.vpl_ld_reset.argtypes = [vp, C.c_int]
+    lib.vpl_ld_size.argtypes = [vp, C.c_int]
+    lib.vpl_ld_get_bow.argtypes = [vp, C.c_int, C.c_int, ip, ip, dp]
+    lib._vpl_ld_bound = True
+
+
+def default_loop_detector_options(**kw):
+    """vpl_ld_default_options (detectLoop's constants: 4 results, the 50 most recent keyframes left out, scores 0.05 / 0.015) with
+    any field given by name filled in"""
+    lib = load_hip_library()
+    _bind_ld(lib)
+    o = LoopDetectorOptions()
+    lib.vpl_ld_default_options(C.byref(o))
+    for k, val in kw.items():
+        setattr(o, k, val)
+    return o
+
+
+class LoopDetector:
+    """vpl_ld_*: the vocabulary, n_db keyframe databases and detectLoop on the device.  Borrows a FrontendContext; detect_fe takes
+    the descriptor rows its last lc_keyframe left on the device (lc_reserve with the session's max_keypoints)."""
+
+    def __init__(self, fe, n_db, options=None, **kw):
+        self.fe, self.lib, self.n_db = fe, fe.lib, n_db
+        _bind_ld(self.lib)
+        self.opt = options or default_loop_detector_options(**kw)
+        self.h = C.c_void_p()
+        fe._check(self.lib.vpl_ld_create(C.byref(self.h), fe.h, n_db, C.byref(self.opt)), "vpl_ld_create")
+        fe._ld = self
+        self._res = (LoopDetectorResult * n_db)()
+
+    def close(self):
+        if self.h:
+            self.lib.vpl_ld_destroy(self.h)
+            self.h = C.c_void_p()
+            if getattr(self.fe, "_ld", None) is self:
+                self.fe._ld = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_vocabulary(self, voc):
+        ip, dp, u64 = C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_ulonglong)
+        self.fe._check(self.lib.vpl_ld_set_vocabulary(
+            self.h, voc.k, voc.L, voc.scoring, voc.weighting, len(voc.node_id), voc.node_id.ctypes.data_as(ip),
+            voc.parent_id.ctypes.data_as(ip), voc.weight.ctypes.data_as(dp), voc.descriptor.ctypes.data_as(u64), len(voc.word_id),
+            voc.word_node.ctypes.data_as(ip), voc.word_id.ctypes.data_as(ip)), "vpl_ld_set_vocabulary")
+
+    def load_vocabulary(self, path):
+        self.fe._check(self.lib.vpl_ld_load_vocabulary(self.h, os.fsencode(path)), "vpl_ld_load_vocabulary")
+
+    def _rows(self, briefs):
+        """per database a [m][4] uint64 array, or None to leave the database untouched -> (rows, counts)"""
+        assert len(briefs) == self.n_db
+        MK = self.opt.max_keypoints
+        rows, cnt = np.zeros((self.n_db, MK, 4), np.uint64), np.zeros(self.n_db, np.int32)
+        for d, b in enumerate(briefs):
+            if b is None:
+                cnt[d] = -1
+                continue
+            b = np.asarray(b, np.uint64).reshape(-1, 4)
+            cnt[d] = len(b)
+            if len(b) <= MK:            # otherwise the library reports VPL_E_CAPACITY
+                rows[d, :len(b)] = b
+        return rows, cnt
+
+    def _results(self):
+        out = []
+        for d in range(self.n_db):
+            r = self._res[d]
+            n = r.n_results
+            out.append(dict(loop_index=r.loop_index, ids=np.array(r.ids[:n], np.int32), scores=np.array(r.scores[:n], np.float64),
+                            n_words=r.n_words, entry=r.entry))
+        return out
+
+    def detect(self, briefs, frame_index):
+        """detectLoop for every database: briefs as for _rows, frame_index [n_db] -> per database a dict: loop_index, ids and
+        scores [n_results], n_words of the new bag, entry (the id the keyframe got; -1 for a database left untouched)"""
+        rows, cnt = self._rows(briefs)
+        fi = np.ascontiguousarray(frame_index, np.int32)
+        assert fi.shape == (self.n_db,)
+        ip = C.POINTER(C.c_int)
+        self.fe._check(self.lib.vpl_ld_detect(self.h, rows.ctypes.data_as(C.POINTER(C.c_ulonglong)), cnt.ctypes.data_as(ip),
+                                              fi.ctypes.data_as(ip), self._res), "vpl_ld_detect")
+        return self._results()
+
+    def detect_fe(self, frame_index):
+        """detect on the rows the context's last lc_keyframe left on the device: image slot i goes to database i"""
+        fi = np.ascontiguousarray(frame_index, np.int32)
+        assert fi.shape == (self.n_db,)
+        self.fe._check(self.lib.vpl_ld_detect_fe(self.h, fi.ctypes.data_as(C.POINTER(C.c_int)), self._res), "vpl_ld_detect_fe")
+        return self._results()
+
+    def add(self, briefs):
+        """addKeyFrameIntoVoc: the bags join their databases without a query"""
+        rows, cnt = self._rows(briefs)
+        self.fe._check(self.lib.vpl_ld_add(self.h, rows.ctypes.data_as(C.POINTER(C.c_ulonglong)), cnt.ctypes.data_as(C.POINTER(C.c_int)),
+                                           self._res), "vpl_ld_add")
+        return self._results()
+
+    def reset(self, db):
+        self.fe._check(self.lib.vpl_ld_reset(self.h, db), "vpl_ld_reset")
+
+    def size(self, db):
+        n = self.lib.vpl_ld_size(self.h, db)
+        if n < 0:
+            raise ValueError("LoopDetector.size: no database %d" % db)
+        return n
+
+    def bow(self, db, entry):
+        """test access: (words int32 ascending, values float64) of a stored bag"""
+        MK = self.opt.max_keypoints
+        n = C.c_int(0)
+        w, val = np.zeros(MK, np.int32), np.zeros(MK, np.float64)
+        self.fe._check(self.lib.vpl_ld_get_bow(self.h, db, entry, C.byref(n), w.ctypes.data_as(C.POINTER(C.c_int)),
+                                               val.ctypes.data_as(C.POINTER(C.c_double))), "vpl_ld_get_bow")
+        return w[:n.value].copy(), val[:n.value].copy()
