@@ -1102,6 +1102,94 @@ int vpl_pg_optimize_batch(vpl_ctx* ctx, int n_graphs, const vpl_pg_input* in, co
  * node 2, ...  Same refusals as the batch call; VPL_E_NUMERIC when the factorisation fails. */
 int vpl_pg_debug_step(vpl_ctx* ctx, const vpl_pg_input* in, const vpl_pg_options* opt, double* g, double* step, double* model_cost_change);
 
+/* ---- the same optimisation over several sequences: a graph that holds a loaded base map (sequence 0) or more than one run, as
+ * pose_graph.cpp:447-519 builds it.  Same structs, same limits and refusals as vpl_pg_optimize_batch, which is unchanged; in
+ * addition VPL_E_INVALID for a negative `sequence` value.  sequence == NULL: every node is of sequence 1.
+ *   - A node is constant if it is local node 0 or its sequence is 0 (:473-477).
+ *   - The sequential edge (i, i-j), j = 1..4, exists only if sequence[i] == sequence[i-j] (:482); it is measured on the incoming
+ *     poses.  A loop edge may join two sequences.
+ *   - An edge, sequential or loop, whose two ends are both constant is not part of the problem: it enters no cost, no gradient
+ *     and no tolerance test.  ceres drops it from the reduced program too, but adds its fixed cost back into the costs it
+ *     reports; this call does NOT, so initial_cost / final_cost are the minimiser's own.
+ *   - A free node that no edge of the problem touches is not an unknown (ceres drops the unused parameter block).
+ *   - x_norm, the step norm and the gradient maximum run over the free nodes.  A constant node comes back with its incoming T,
+ *     bit for bit, and R = ypr2R(R2ypr(qmat(mat2q(vio_R)))), as a free node would with a zero step.
+ *   - The drift is taken at node n-1 and applied to the tail, as in vpl_pg_optimize_batch.
+ * On a graph whose sequences are all equal and non-zero the result is, byte for byte, that of vpl_pg_optimize_batch.  No
+ * floating-point atomics, a fixed summation order: a call repeats bit for bit, wherever the graph stands in the batch. */
+int vpl_pg_optimize_seq_batch(vpl_ctx* ctx, int n_graphs, const vpl_pg_input* in, const vpl_pg_options* opt, vpl_pg_result* out);
+/* test access, as vpl_pg_debug_step, with `sequence` honoured: a constant node's entries of g and step are zero */
+int vpl_pg_debug_step_seq(vpl_ctx* ctx, const vpl_pg_input* in, const vpl_pg_options* opt, double* g, double* step, double* model_cost_change);
+
+/* ---- the pose-graph session: one PoseGraph with its keyframe list resident on the device -- per keyframe the shifted VIO pose,
+ * the pose and loop_info; beside them w_r_vio / w_t_vio and the drift.  The host keeps the integers: the index, sequence_cnt,
+ * sequence_loop, earliest_loop_index, the queue, every keyframe's sequence and loop.  Doubles cross the bus only when the caller
+ * asks for them.  Several sessions may share a context; their device arrays go with the context, like those of vpl_gf_*, so a
+ * session is destroyed before its context.  The caller keeps what findConnection needs (descriptors, points) and runs
+ * vpl_ld_detect / vpl_loop_verify_batch first: they work on the original VIO pose, which the shift does not touch.
+ * Not here: savePoseGraph / loadPoseGraph (file formats), the descriptors, visualisation, the 2 s sleep of the optimisation thread. */
+#define VPL_PGS_MAX_KEYFRAMES 65536
+#define VPL_PGS_OK 0
+#define VPL_PGS_NOTHING 2          /* vpl_pgs_optimize: nothing was queued, nothing was launched or changed */
+typedef struct vpl_pgs_session vpl_pgs_session;
+typedef struct vpl_pgs_options {
+  int max_keyframes;               /* 1 .. VPL_PGS_MAX_KEYFRAMES, default 8192 */
+  int fast_relocalization;         /* FAST_RELOCALIZATION, default 0: vpl_pgs_update_loop overwrites the drift */
+  vpl_pg_options pg;
+} vpl_pgs_options;
+typedef struct vpl_pgs_keyframe {
+  int sequence;                    /* add: sequence_cnt or sequence_cnt + 1, >= 1; load: not read (the keyframe is of sequence 0) */
+  int loop_index;                  /* -1, or the index of the old keyframe the caller's findConnection accepted */
+  double vio_T[3], vio_R[9];       /* the VIO pose (row-major R) */
+  double T[3], R[9];               /* load only: the stored pose */
+  double loop_info[8];             /* t, q (w, x, y, z), yaw as vpl_loop_result writes it; read only when there is a loop */
+} vpl_pgs_keyframe;
+typedef struct vpl_pgs_keyframe_out {
+  int index, optimize_pending;
+  double vio_T[3], vio_R[9];       /* the shifted VIO pose */
+  double T[3], R[9];               /* the drift-corrected pose */
+  double w_r_vio[9], w_t_vio[3];
+} vpl_pgs_keyframe_out;
+typedef struct vpl_pgs_result {    /* a vpl_pg_result without the arrays */
+  int status, termination;         /* VPL_PGS_OK / VPL_PGS_NOTHING | VPL_PG_* termination */
+  int iterations, successful_steps, unsuccessful_steps;
+  int n_nodes, first_index, cur_index;   /* the keyframes first_index .. cur_index were the nodes */
+  double initial_cost, final_cost;
+  double yaw_drift, r_drift[9], t_drift[3];
+} vpl_pgs_result;
+void vpl_pgs_default_options(vpl_pgs_options* opt);
+/* VPL_E_INVALID: max_keyframes < 1, pose-graph options out of range; VPL_E_CAPACITY: max_keyframes > VPL_PGS_MAX_KEYFRAMES */
+int vpl_pgs_create(vpl_ctx* ctx, const vpl_pgs_options* opt, vpl_pgs_session** out);
+void vpl_pgs_destroy(vpl_pgs_session* h);
+/* addKeyFrame (pose_graph.cpp:42-136) in one launch: the new-sequence rule (:47-57), the shift by w_r_vio / w_t_vio, the index; on
+ * a loop earliest_loop_index and the queue, and -- when the loop ties the sequence to an older one for the first time -- w_r_vio /
+ * w_t_vio from the old keyframe's VIO pose and the shift of the current and of every stored keyframe of the sequence (:85-124);
+ * then the pose r_drift vio_P + t_drift, r_drift vio_R.  out may be NULL: then nothing is copied back and nothing waited for.
+ * Refused, with the session unchanged -- VPL_E_INVALID: a sequence that is not sequence_cnt or sequence_cnt + 1 or is < 1, a
+ * loop_index outside -1 .. index - 1; VPL_E_CAPACITY: keyframe max_keyframes + 1. */
+int vpl_pgs_add_keyframe(vpl_pgs_session* h, const vpl_pgs_keyframe* kf, vpl_pgs_keyframe_out* out);
+/* loadKeyFrame (:213-287): a keyframe of sequence 0, its VIO pose and pose as given -- no shift, no drift -- with the same loop
+ * bookkeeping and queueing.  out->w_r_vio / w_t_vio are the session's, unchanged. */
+int vpl_pgs_load_keyframe(vpl_pgs_session* h, const vpl_pgs_keyframe* kf, vpl_pgs_keyframe_out* out);
+/* one turn of optimize4DoF's loop body (:407-573).  Nothing queued: status = VPL_PGS_NOTHING, no launch.  Otherwise the LAST queued
+ * index is cur_index, earliest_loop_index is first_index, the queue is emptied; a kernel gathers the nodes and their loop
+ * measurements from the list, the rounds of vpl_pg_optimize_seq_batch run on them (the result is that call's, byte for byte),
+ * a kernel writes the poses back, takes the drift and applies it to every later keyframe in place.  One small upload (the
+ * graph's integers), one copy back (the head), one synchronisation.  VPL_E_CAPACITY: more than VPL_PG_MAX_NODES nodes or
+ * VPL_PG_MAX_LOOPS loops in the range; the queue and the list are then as they were. */
+int vpl_pgs_optimize(vpl_pgs_session* h, vpl_pgs_result* result);
+/* updateKeyFrameLoop (:889-922): behind KeyFrame::updateLoop's gate (|yaw| < 30, |t| < 20; *accepted says whether it held, may be
+ * NULL) the keyframe's loop_info is replaced and, with fast_relocalization, the drift is overwritten from the old keyframe's
+ * pose.  VPL_E_INVALID: no such keyframe, or one without a loop. */
+int vpl_pgs_update_loop(vpl_pgs_session* h, int index, const double* loop_info, int* accepted);
+/* the keyframes first .. first + count - 1: T [count][3], R [count][9], vio_T, vio_R, loop_info [count][8], sequence [count],
+ * loop_index [count]; any pointer may be NULL.  One synchronisation if a double array is asked for. */
+int vpl_pgs_get_path(vpl_pgs_session* h, int first, int count, double* T, double* R, double* vio_T, double* vio_R, double* loop_info,
+                     int* sequence, int* loop_index);
+int vpl_pgs_get_drift(vpl_pgs_session* h, double* yaw_drift, double* r_drift, double* t_drift);
+int vpl_pgs_size(const vpl_pgs_session* h);   /* the number of keyframes */
+int vpl_pgs_reset(vpl_pgs_session* h);        /* an empty PoseGraph again; the capacity and the options stay */
+
 /* ---- global fusion: GlobalOptimization::optimize (globalOpt.cpp:101-259, functors Factors.h) for a batch of independent pose
  * chains.  Per chain the nodes 0 .. n-1 are the odometry poses in time order; a node's parameters are its quaternion (w, x, y, z;
  * ceres' QuaternionParameterization, tangent size 3: q <- [cos|d|, sin|d| / |d| d] (x) q) and t, no node is constant.  Edge

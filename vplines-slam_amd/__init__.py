@@ -14,6 +14,7 @@ from .capi import (  # noqa: F401
     SelectParams, SelectInput, SelectResult, SelectFrame, OdoSelectResult, select_debug_book,
     LoopInput, LoopOptions, LoopResult, default_loop_options, loop_debug_plan,
     PoseGraphInput, PoseGraphResult, PgOptions, default_pg_options,
+    PoseGraphSession, PgsOptions, default_pgs_options,
     GlobalFusionInput, GlobalFusionResult, GfOptions, default_gf_options, gf_debug_plan, local_cartesian,
     GlobalFusionSession,
     MARGIN_OLD, MARGIN_SECOND_NEW, MARGIN_NONE, PRIOR_PIVOTED_CHOLESKY, PRIOR_EIGEN,

@@ -393,6 +393,145 @@ class PoseGraphResult:
         return b"".join(a.tobytes() for a in (ints, dbl, self.T, self.R, self.tail_T, self.tail_R))
 
 
+PGS_MAX_KEYFRAMES = 65536   # VPL_PGS_MAX_KEYFRAMES
+PGS_OK, PGS_NOTHING = 0, 2
+
+
+class PgsOptions(C.Structure):   # vpl_pgs_options
+    _fields_ = [("max_keyframes", C.c_int), ("fast_relocalization", C.c_int), ("pg", PgOptions)]
+
+
+class CPgsKeyframe(C.Structure):   # vpl_pgs_keyframe
+    _fields_ = [("sequence", C.c_int), ("loop_index", C.c_int), ("vio_T", C.c_double * 3), ("vio_R", C.c_double * 9),
+                ("T", C.c_double * 3), ("R", C.c_double * 9), ("loop_info", C.c_double * 8)]
+
+
+class CPgsKeyframeOut(C.Structure):   # vpl_pgs_keyframe_out
+    _fields_ = [("index", C.c_int), ("optimize_pending", C.c_int), ("vio_T", C.c_double * 3), ("vio_R", C.c_double * 9),
+                ("T", C.c_double * 3), ("R", C.c_double * 9), ("w_r_vio", C.c_double * 9), ("w_t_vio", C.c_double * 3)]
+
+
+class CPgsResult(C.Structure):   # vpl_pgs_result
+    _fields_ = [("status", C.c_int), ("termination", C.c_int), ("iterations", C.c_int), ("successful_steps", C.c_int),
+                ("unsuccessful_steps", C.c_int), ("n_nodes", C.c_int), ("first_index", C.c_int), ("cur_index", C.c_int),
+                ("initial_cost", C.c_double), ("final_cost", C.c_double), ("yaw_drift", C.c_double), ("r_drift", C.c_double * 9),
+                ("t_drift", C.c_double * 3)]
+
+
+def default_pgs_options(max_keyframes=None, fast_relocalization=None, **pg_changes):
+    o = PgsOptions()
+    load_hip_library().vpl_pgs_default_options(C.byref(o))
+    if max_keyframes is not None:
+        o.max_keyframes = int(max_keyframes)
+    if fast_relocalization is not None:
+        o.fast_relocalization = int(fast_relocalization)
+    for k, val in pg_changes.items():
+        setattr(o.pg, k, val)
+    return o
+
+
+class PoseGraphSession:
+    """vpl_pgs_create .. vpl_pgs_destroy: one PoseGraph with its keyframe list resident on the device, on a Context that outlives
+    it.  check=False on a method: a refusal comes back as its VPL_E_* code instead of an exception."""
+
+    def __init__(self, ctx, options=None):
+        self.ctx, self.lib, self.h = ctx, ctx.lib, C.c_void_p()
+        opt = options if options is not None else default_pgs_options()
+        ctx._settle()
+        rc = self.lib.vpl_pgs_create(ctx.h, C.byref(opt), C.byref(self.h))
+        if rc != 0:
+            self.h = None
+            ctx._check(rc, "vpl_pgs_create")
+
+    def close(self):
+        if self.h:
+            self.lib.vpl_pgs_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __len__(self):
+        return int(self.lib.vpl_pgs_size(self.h))
+
+    def _done(self, rc, what, check):
+        if rc != 0 and not check:
+            return rc
+        self.ctx._check(rc, what)
+        return None
+
+    @staticmethod
+    def _kf(sequence, vio_T, vio_R, loop_index, loop_info, T=None, R=None):
+        kf = CPgsKeyframe()
+        kf.sequence, kf.loop_index = int(sequence), int(loop_index)
+        kf.vio_T[:] = _arr(vio_T, np.float64).reshape(3)
+        kf.vio_R[:] = _arr(vio_R, np.float64).reshape(9)
+        if T is not None:
+            kf.T[:] = _arr(T, np.float64).reshape(3)
+            kf.R[:] = _arr(R, np.float64).reshape(9)
+        if loop_info is not None:
+            kf.loop_info[:] = _arr(loop_info, np.float64).reshape(8)
+        return kf
+
+    def _put(self, call, kf, want_out, check):
+        out = CPgsKeyframeOut() if want_out else None
+        bad = self._done(getattr(self.lib, call)(self.h, C.byref(kf), C.byref(out) if want_out else None), call, check)
+        if bad is not None:
+            return bad
+        if not want_out:
+            return None
+        return dict(index=out.index, optimize_pending=bool(out.optimize_pending), vio_T=np.array(out.vio_T[:]),
+                    vio_R=np.array(out.vio_R[:]).reshape(3, 3), T=np.array(out.T[:]), R=np.array(out.R[:]).reshape(3, 3),
+                    w_r_vio=np.array(out.w_r_vio[:]).reshape(3, 3), w_t_vio=np.array(out.w_t_vio[:]))
+
+    def add(self, sequence, vio_T, vio_R, loop_index=-1, loop_info=None, out=True, check=True):
+        """addKeyFrame -> dict index, optimize_pending, vio_T, vio_R (shifted), T, R (drift-corrected), w_r_vio, w_t_vio; out=False:
+        nothing is copied back or waited for, -> None"""
+        return self._put("vpl_pgs_add_keyframe", self._kf(sequence, vio_T, vio_R, loop_index, loop_info), out, check)
+
+    def load(self, vio_T, vio_R, T, R, loop_index=-1, loop_info=None, out=True, check=True):
+        """loadKeyFrame: a keyframe of sequence 0 with its stored poses"""
+        return self._put("vpl_pgs_load_keyframe", self._kf(0, vio_T, vio_R, loop_index, loop_info, T, R), out, check)
+
+    def optimize(self, check=True):
+        """one turn of optimize4DoF -> CPgsResult (status PGS_NOTHING when nothing was queued)"""
+        self.ctx._settle()
+        res = CPgsResult()
+        bad = self._done(self.lib.vpl_pgs_optimize(self.h, C.byref(res)), "vpl_pgs_optimize", check)
+        return bad if bad is not None else res
+
+    def update_loop(self, index, loop_info, check=True):
+        """updateKeyFrameLoop -> whether the gate let the new loop_info in"""
+        li = _arr(loop_info, np.float64).reshape(8).copy()
+        ok = C.c_int(0)
+        bad = self._done(self.lib.vpl_pgs_update_loop(self.h, int(index), li.ctypes.data_as(_dp), C.byref(ok)), "vpl_pgs_update_loop", check)
+        return bad if bad is not None else bool(ok.value)
+
+    def path(self, first=0, count=None, check=True):
+        """-> dict T [count][3], R [count][3][3], vio_T, vio_R, loop_info [count][8], sequence, loop_index [count]"""
+        count = len(self) - int(first) if count is None else int(count)
+        n = max(count, 0)
+        d = dict(T=np.zeros((n, 3)), R=np.zeros((n, 3, 3)), vio_T=np.zeros((n, 3)), vio_R=np.zeros((n, 3, 3)), loop_info=np.zeros((n, 8)),
+                 sequence=np.zeros(n, dtype=np.int32), loop_index=np.zeros(n, dtype=np.int32))
+        self.ctx._settle()
+        rc = self.lib.vpl_pgs_get_path(self.h, int(first), count, *(d[k].ctypes.data_as(_dp) for k in ("T", "R", "vio_T", "vio_R", "loop_info")),
+                                       d["sequence"].ctypes.data_as(_ip), d["loop_index"].ctypes.data_as(_ip))
+        bad = self._done(rc, "vpl_pgs_get_path", check)
+        return bad if bad is not None else d
+
+    def drift(self):
+        """-> (yaw_drift, r_drift [3][3], t_drift [3])"""
+        yaw, r, t = C.c_double(0), np.zeros((3, 3)), np.zeros(3)
+        self._done(self.lib.vpl_pgs_get_drift(self.h, C.byref(yaw), r.ctypes.data_as(_dp), t.ctypes.data_as(_dp)), "vpl_pgs_get_drift", True)
+        return float(yaw.value), r, t
+
+    def reset(self):
+        self._done(self.lib.vpl_pgs_reset(self.h), "vpl_pgs_reset", True)
+
+
 GF_MAX_NODES = 65536   # VPL_GF_MAX_NODES
 GF_NO_CONVERGENCE, GF_CONVERGENCE, GF_FAILURE = 0, 1, 2
 
@@ -894,6 +1033,21 @@ def load_hip_library():
     lib.vpl_pg_default_options.restype = None
     lib.vpl_pg_optimize_batch.argtypes = [vp, C.c_int, C.POINTER(CPgInput), C.POINTER(PgOptions), C.POINTER(CPgResult)]
     lib.vpl_pg_debug_step.argtypes = [vp, C.POINTER(CPgInput), C.POINTER(PgOptions), _dp, _dp, _dp]
+    lib.vpl_pg_optimize_seq_batch.argtypes = lib.vpl_pg_optimize_batch.argtypes
+    lib.vpl_pg_debug_step_seq.argtypes = lib.vpl_pg_debug_step.argtypes
+    lib.vpl_pgs_default_options.argtypes = [C.POINTER(PgsOptions)]
+    lib.vpl_pgs_default_options.restype = None
+    lib.vpl_pgs_create.argtypes = [vp, C.POINTER(PgsOptions), C.POINTER(vp)]
+    lib.vpl_pgs_destroy.argtypes = [vp]
+    lib.vpl_pgs_destroy.restype = None
+    lib.vpl_pgs_add_keyframe.argtypes = [vp, C.POINTER(CPgsKeyframe), C.POINTER(CPgsKeyframeOut)]
+    lib.vpl_pgs_load_keyframe.argtypes = [vp, C.POINTER(CPgsKeyframe), C.POINTER(CPgsKeyframeOut)]
+    lib.vpl_pgs_optimize.argtypes = [vp, C.POINTER(CPgsResult)]
+    lib.vpl_pgs_update_loop.argtypes = [vp, C.c_int, _dp, C.POINTER(C.c_int)]
+    lib.vpl_pgs_get_path.argtypes = [vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _ip, _ip]
+    lib.vpl_pgs_get_drift.argtypes = [vp, C.POINTER(C.c_double), _dp, _dp]
+    lib.vpl_pgs_size.argtypes = [vp]
+    lib.vpl_pgs_reset.argtypes = [vp]
     lib.vpl_gf_default_options.argtypes = [C.POINTER(GfOptions)]
     lib.vpl_gf_default_options.restype = None
     lib.vpl_gf_optimize_batch.argtypes = [vp, C.c_int, C.POINTER(CGfInput), C.POINTER(GfOptions), C.POINTER(CGfResult)]
@@ -1320,7 +1474,7 @@ class Context:
                 q.to_c(ci[i])
         return ci
 
-    def pose_graph_optimize(self, inputs, opt=None, check=True):
+    def pose_graph_optimize(self, inputs, opt=None, check=True, _call="vpl_pg_optimize_batch"):
         """vpl_pg_optimize_batch over a list of PoseGraphInput: PoseGraph::optimize4DoF per graph -- the corrected poses, the drift
         and the drift-corrected tail -- in one call.  -> list of PoseGraphResult.  check=False: a refusal comes back as its
         VPL_E_* code instead of an exception."""
@@ -1335,22 +1489,31 @@ class Context:
             arrs = (np.zeros((nn, 3)), np.zeros((nn, 3, 3)), np.zeros((nt, 3)), np.zeros((nt, 3, 3)))
             res[i].T, res[i].R, res[i].tail_T, res[i].tail_R = (a.ctypes.data_as(_dp) for a in arrs)
             out.append(arrs)
-        rc = self.lib.vpl_pg_optimize_batch(self.h, n, ci, C.byref(opt), res)
+        rc = getattr(self.lib, _call)(self.h, n, ci, C.byref(opt), res)
         if rc != 0 and not check:
             return rc
-        self._check(rc, "vpl_pg_optimize_batch")
+        self._check(rc, _call)
         return [PoseGraphResult(res[i], *out[i]) for i in range(n)]
 
-    def pose_graph_debug_step(self, q, opt=None):
+    def pose_graph_optimize_seq(self, inputs, opt=None, check=True):
+        """vpl_pg_optimize_seq_batch: pose_graph_optimize with every graph's `sequence` honoured -- nodes of sequence 0 are
+        constant, sequential edges stay inside a sequence, loop edges may join two.  Same arguments, same result."""
+        return self.pose_graph_optimize(inputs, opt, check, "vpl_pg_optimize_seq_batch")
+
+    def pose_graph_debug_step(self, q, opt=None, _call="vpl_pg_debug_step"):
         """vpl_pg_debug_step: the first linear solve of one graph -> dict g, step [4 (n - 1)], model_cost_change"""
         self._settle()
         ci = self._pg_c([q])
         opt = opt if opt is not None else default_pg_options()
         m = 4 * (int(ci[0].n) - 1)
         g, step, mc = np.zeros(max(m, 1)), np.zeros(max(m, 1)), np.zeros(1)
-        rc = self.lib.vpl_pg_debug_step(self.h, ci, C.byref(opt), g.ctypes.data_as(_dp), step.ctypes.data_as(_dp), mc.ctypes.data_as(_dp))
-        self._check(rc, "vpl_pg_debug_step")
+        rc = getattr(self.lib, _call)(self.h, ci, C.byref(opt), g.ctypes.data_as(_dp), step.ctypes.data_as(_dp), mc.ctypes.data_as(_dp))
+        self._check(rc, _call)
         return dict(g=g[:m], step=step[:m], model_cost_change=float(mc[0]))
+
+    def pose_graph_debug_step_seq(self, q, opt=None):
+        """vpl_pg_debug_step_seq: pose_graph_debug_step with the graph's `sequence` honoured"""
+        return self.pose_graph_debug_step(q, opt, "vpl_pg_debug_step_seq")
 
     @staticmethod
     def _gf_c(inputs):

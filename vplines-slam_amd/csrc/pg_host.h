@@ -1,4 +1,4 @@
-// Host side of the pose-graph optimisation (vpl_pg_optimize_batch, vpl_pg_debug_step): the refusals, one plan per graph
+// Host side of the pose-graph optimisation (vpl_pg_optimize_batch, vpl_pg_optimize_seq_batch, vpl_pg_debug_step[_seq]): the refusals, one plan per graph
 // (pg_plan.h), the one packed upload, the rounds enqueued without a look at the device, the one read-back.  Included once by
 // vplines_ba.hip, behind loop_host.h.
 #pragma once
@@ -22,21 +22,55 @@ namespace vpl {
 
 struct PgDebugOut { double *g, *step, *model; };
 
-// the whole call; dbg: stop after the first linear solve of graph 0 and hand out g, step and the model cost change
-static int pg_run(vpl_ctx* c, int n, const vpl_pg_input* in, const vpl_pg_options* opt, vpl_pg_result* out, const PgDebugOut* dbg) {
+static bool pg_options_ok(const vpl_pg_options* opt) {
+  auto pos = [](double v) { return v > 0.0 && std::isfinite(v); };
+  return !(opt->max_iterations < 0 || opt->max_iterations > 1000 || opt->max_consecutive_invalid_steps < 1 || !std::isfinite(opt->huber_delta) ||
+           !pos(opt->loop_yaw_scale) || !pos(opt->initial_radius) || !pos(opt->max_radius) || !(opt->min_radius >= 0.0) ||
+           !std::isfinite(opt->min_relative_decrease) || !(opt->function_tolerance >= 0.0) || !(opt->gradient_tolerance >= 0.0) ||
+           !(opt->parameter_tolerance >= 0.0) || !pos(opt->min_lm_diagonal) || !(opt->max_lm_diagonal >= opt->min_lm_diagonal));
+}
+
+// the largest graph of a batch: what the grids are sized by
+struct PgDims { int n_graphs = 0, maxE = 1, maxn = 1, maxnb = 1, maxLP = 0; };
+
+// k_pg_init and the rounds, enqueued on the context's stream over an input block, graphs and integer blocks that are on the device
+// (A); nothing is read back.  SEQ: the graphs carry node flags (vpl_pg_optimize_seq_batch).  first_only: one round, up to k_pg_back
+template <bool SEQ>
+static void pg_enqueue_rounds(vpl_ctx* c, const PgArgs& A, const PgDims& d, bool first_only) {
+  const int n = d.n_graphs;
+  const dim3 one(1, n), per_edge((d.maxE + PG_THREADS - 1) / PG_THREADS, n), per_node((16 * d.maxnb + PG_THREADS - 1) / PG_THREADS, n);
+  const int tiles = d.maxLP / 16;
+  { KTimer t(c, "k_pg_init"); hipLaunchKernelGGL(k_pg_init, dim3((std::max(d.maxE, d.maxn) + PG_THREADS - 1) / PG_THREADS, n), dim3(PG_THREADS), 0, c->stream, A); }
+  const int rounds = first_only ? 1 : A.opt.max_iterations + 1;
+  for (int it = 0; it < rounds; ++it) {
+    { KTimer t(c, "k_pg_lin"); hipLaunchKernelGGL((k_pg_edges<0, SEQ>), per_edge, dim3(PG_THREADS), 0, c->stream, A);
+      hipLaunchKernelGGL(k_pg_asm, per_node, dim3(PG_THREADS), 0, c->stream, A); }
+    { KTimer t(c, "k_pg_factor"); hipLaunchKernelGGL(k_pg_factor<SEQ>, one, dim3(64), 0, c->stream, A); }
+    { KTimer t(c, "k_pg_cols"); hipLaunchKernelGGL(k_pg_cols, dim3(d.maxLP / 64 + 1, n), dim3(64), 0, c->stream, A); }
+    if (tiles) {
+      KTimer t(c, "k_pg_cap");
+      hipLaunchKernelGGL(k_pg_cap, dim3(tiles * tiles, n), dim3(64), 0, c->stream, A, tiles);
+      hipLaunchKernelGGL(k_pg_capsolve, one, dim3(PG_THREADS), 0, c->stream, A);
+    }
+    { KTimer t(c, "k_pg_back"); hipLaunchKernelGGL(k_pg_back, one, dim3(PG_THREADS), 0, c->stream, A); }
+    if (first_only) break;
+    { KTimer t(c, "k_pg_decide"); hipLaunchKernelGGL((k_pg_edges<1, SEQ>), per_edge, dim3(PG_THREADS), 0, c->stream, A);
+      hipLaunchKernelGGL(k_pg_decide<SEQ>, one, dim3(PG_THREADS), 0, c->stream, A); }
+  }
+}
+
+// the whole call; dbg: stop after the first linear solve of graph 0 and hand out g, step and the model cost change.  seq: honour
+// `sequence` (vpl_pg_optimize_seq_batch) instead of refusing a graph whose sequences differ
+static int pg_run(vpl_ctx* c, int n, const vpl_pg_input* in, const vpl_pg_options* opt, vpl_pg_result* out, const PgDebugOut* dbg, bool seq) {
   if (!c || n < 0 || !in || !opt || (!out && !dbg)) return VPL_E_INVALID;
   if (n == 0) return VPL_OK;
   if (n > c->maxW) return fail(c, VPL_E_CAPACITY, "pose graph: more graphs than max_windows");
-  auto pos = [](double v) { return v > 0.0 && std::isfinite(v); };
-  if (opt->max_iterations < 0 || opt->max_iterations > 1000 || opt->max_consecutive_invalid_steps < 1 || !std::isfinite(opt->huber_delta) ||
-      !pos(opt->loop_yaw_scale) || !pos(opt->initial_radius) || !pos(opt->max_radius) || !(opt->min_radius >= 0.0) ||
-      !std::isfinite(opt->min_relative_decrease) || !(opt->function_tolerance >= 0.0) || !(opt->gradient_tolerance >= 0.0) ||
-      !(opt->parameter_tolerance >= 0.0) || !pos(opt->min_lm_diagonal) || !(opt->max_lm_diagonal >= opt->min_lm_diagonal))
-    return fail(c, VPL_E_INVALID, "pose graph: options out of range");
+  if (!pg_options_ok(opt)) return fail(c, VPL_E_INVALID, "pose graph: options out of range");
   std::vector<PgGraph> gr(n);
   std::vector<std::vector<int>> li(n), la(n);
   size_t ws = 0, is = 0, ins = 0, outs = 0;
-  int maxE = 1, maxn = 1, maxnb = 1, maxLP = 0;
+  PgDims dims;
+  dims.n_graphs = n;
   for (int s = 0; s < n; ++s) {
     const vpl_pg_input& q = in[s];
     const std::string at = " (graph " + std::to_string(s) + ")";
@@ -49,7 +83,8 @@ static int pg_run(vpl_ctx* c, int n, const vpl_pg_input* in, const vpl_pg_option
     for (int k = 0; k < q.n; ++k) {
       if (q.loop_local[k] >= k) return fail(c, VPL_E_INVALID, "pose graph: loop_local not smaller than the node's own index" + at);
       if (q.loop_local[k] >= 0) { li[s].push_back(k); la[s].push_back(q.loop_local[k]); }
-      if (q.sequence && q.sequence[k] != q.sequence[0]) run = false;
+      if (seq && q.sequence && q.sequence[k] < 0) return fail(c, VPL_E_INVALID, "pose graph: negative sequence" + at);
+      if (!seq && q.sequence && q.sequence[k] != q.sequence[0]) run = false;
     }
     if ((int)li[s].size() > VPL_PG_MAX_LOOPS) return fail(c, VPL_E_CAPACITY, "pose graph: more than VPL_PG_MAX_LOOPS loops" + at);
     PgGraph& G = gr[s];
@@ -58,10 +93,11 @@ static int pg_run(vpl_ctx* c, int n, const vpl_pg_input* in, const vpl_pg_option
     G.p = run ? pg_layout(q.n, (int)li[s].size()) : pg_layout(1, 0);
     G.n_tail = run ? q.n_tail : 0;
     G.w = ws; G.iw = is; G.in = ins; G.out = outs;
-    ws += G.p.total; is += G.p.itotal;
+    ws += G.p.total; is += G.p.itotal + (seq ? pg_up8((size_t)G.p.n) : 0);   // (seq: the node flags behind the integer block)
     ins += pg_up8(12 * (size_t)G.p.n + 4 * (size_t)G.p.L + 12 * (size_t)G.n_tail);
     outs += pg_up8(PG_HEAD + 12 * (size_t)G.p.n + 12 * (size_t)G.n_tail);
-    maxE = std::max(maxE, G.p.E); maxn = std::max(maxn, G.p.n); maxnb = std::max(maxnb, G.p.nb); maxLP = std::max(maxLP, G.p.LP);
+    dims.maxE = std::max(dims.maxE, G.p.E); dims.maxn = std::max(dims.maxn, G.p.n);
+    dims.maxnb = std::max(dims.maxnb, G.p.nb); dims.maxLP = std::max(dims.maxLP, G.p.LP);
   }
   const int rs = settle(c);
   if (rs) return rs;
@@ -87,6 +123,7 @@ static int pg_run(vpl_ctx* c, int n, const vpl_pg_input* in, const vpl_pg_option
       }
     }
     pg_fill_ints(G.p, li[s].data(), la[s].data(), (int*)(buf.data() + b_int) + G.iw);
+    if (seq) pg_node_flags(G.p.n, q.sequence, G.p.L, li[s].data(), la[s].data(), (int*)(buf.data() + b_int) + G.iw + G.p.itotal);
   }
   std::memcpy(buf.data() + b_gr, gr.data(), (size_t)n * sizeof(PgGraph));
   const void* owner = &gr;
@@ -105,25 +142,9 @@ static int pg_run(vpl_ctx* c, int n, const vpl_pg_input* in, const vpl_pg_option
     PgArgs A;
     A.gr = (const PgGraph*)(d_in + b_gr); A.ws = d_ws; A.ints = (const int*)(d_in + b_int); A.in = (const double*)d_in; A.out = d_out;
     A.opt = *opt;
-    const dim3 one(1, n), per_edge((maxE + PG_THREADS - 1) / PG_THREADS, n), per_node((16 * maxnb + PG_THREADS - 1) / PG_THREADS, n);
-    const int tiles = maxLP / 16;
-    { KTimer t(c, "k_pg_init"); hipLaunchKernelGGL(k_pg_init, dim3((std::max(maxE, maxn) + PG_THREADS - 1) / PG_THREADS, n), dim3(PG_THREADS), 0, c->stream, A); }
-    const int rounds = dbg ? 1 : opt->max_iterations + 1;
-    for (int it = 0; it < rounds; ++it) {
-      { KTimer t(c, "k_pg_lin"); hipLaunchKernelGGL(k_pg_edges<0>, per_edge, dim3(PG_THREADS), 0, c->stream, A);
-        hipLaunchKernelGGL(k_pg_asm, per_node, dim3(PG_THREADS), 0, c->stream, A); }
-      { KTimer t(c, "k_pg_factor"); hipLaunchKernelGGL(k_pg_factor, one, dim3(64), 0, c->stream, A); }
-      { KTimer t(c, "k_pg_cols"); hipLaunchKernelGGL(k_pg_cols, dim3(maxLP / 64 + 1, n), dim3(64), 0, c->stream, A); }
-      if (tiles) {
-        KTimer t(c, "k_pg_cap");
-        hipLaunchKernelGGL(k_pg_cap, dim3(tiles * tiles, n), dim3(64), 0, c->stream, A, tiles);
-        hipLaunchKernelGGL(k_pg_capsolve, one, dim3(PG_THREADS), 0, c->stream, A);
-      }
-      { KTimer t(c, "k_pg_back"); hipLaunchKernelGGL(k_pg_back, one, dim3(PG_THREADS), 0, c->stream, A); }
-      if (dbg) break;
-      { KTimer t(c, "k_pg_decide"); hipLaunchKernelGGL(k_pg_edges<1>, per_edge, dim3(PG_THREADS), 0, c->stream, A);
-        hipLaunchKernelGGL(k_pg_decide, one, dim3(PG_THREADS), 0, c->stream, A); }
-    }
+    const dim3 one(1, n);
+    if (seq) pg_enqueue_rounds<true>(c, A, dims, dbg != nullptr);
+    else pg_enqueue_rounds<false>(c, A, dims, dbg != nullptr);
     HIPCHK(c, hipGetLastError());
     if (dbg) {
       const PgLayout& p = gr[0].p;
@@ -170,14 +191,26 @@ extern "C" {
 
 int vpl_pg_optimize_batch(vpl_ctx* c, int n, const vpl_pg_input* in, const vpl_pg_options* opt, vpl_pg_result* out) {
   if (!out) return VPL_E_INVALID;
-  return vpl::pg_run(c, n, in, opt, out, nullptr);
+  return vpl::pg_run(c, n, in, opt, out, nullptr, false);
+}
+
+int vpl_pg_optimize_seq_batch(vpl_ctx* c, int n, const vpl_pg_input* in, const vpl_pg_options* opt, vpl_pg_result* out) {
+  if (!out) return VPL_E_INVALID;
+  return vpl::pg_run(c, n, in, opt, out, nullptr, true);
 }
 
 int vpl_pg_debug_step(vpl_ctx* c, const vpl_pg_input* in, const vpl_pg_options* opt, double* g, double* step, double* model_cost_change) {
   if (!in || !g || !step || !model_cost_change) return VPL_E_INVALID;
   if (in->n < 2) return VPL_E_INVALID;
   const vpl::PgDebugOut dbg{g, step, model_cost_change};
-  return vpl::pg_run(c, 1, in, opt, nullptr, &dbg);
+  return vpl::pg_run(c, 1, in, opt, nullptr, &dbg, false);
+}
+
+int vpl_pg_debug_step_seq(vpl_ctx* c, const vpl_pg_input* in, const vpl_pg_options* opt, double* g, double* step, double* model_cost_change) {
+  if (!in || !g || !step || !model_cost_change) return VPL_E_INVALID;
+  if (in->n < 2) return VPL_E_INVALID;
+  const vpl::PgDebugOut dbg{g, step, model_cost_change};
+  return vpl::pg_run(c, 1, in, opt, nullptr, &dbg, true);
 }
 
 }  // extern "C"

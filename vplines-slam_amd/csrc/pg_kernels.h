@@ -4,6 +4,11 @@
 // One round = k_pg_edges<0>, k_pg_asm, k_pg_factor, k_pg_cols, k_pg_cap, k_pg_capsolve, k_pg_back, k_pg_edges<1>, k_pg_decide;
 // the host enqueues max_iterations + 1 rounds and k_pg_finish.  blockIdx.y is the graph; a graph that has ended has PG_DONE set
 // and its work-groups leave at once.  f64 throughout, no atomics: every sum has the order pg_plan.h fixes.
+// SEQ (vpl_pg_optimize_seq_batch): the graph spans several sequences.  Every node keeps its slot; pg_node_flags (pg_plan.h) marks the
+// constant nodes and the sequential edges that exist.  A masked edge writes nothing, so its residual, Jacobians and costs stay the
+// zeros the workspace starts with; a constant end's Jacobian is stored as zero, which leaves its block of B, its g and its column
+// norms zero and its Jacobi scale 1; k_pg_factor gives it a unit diagonal, so its step is zero; the norms skip it.  With SEQ
+// false the kernels are what they were, and on a graph of one non-zero sequence SEQ changes no operation.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -106,6 +111,12 @@ __device__ __forceinline__ double pg_block_sum(const double* v, int count, doubl
   return red[0];
 }
 
+// SEQ: is edge slot s with the ends a < b part of the problem
+__device__ __forceinline__ bool pg_edge_active(const int* fl, int a, int b, bool loop) {
+  if (loop) return !((fl[a] & PG_NODE_CONST0) && (fl[b] & PG_NODE_CONST0));
+  return (fl[b] >> (b - a)) & 1;
+}
+
 #define PG_GRAPH(A)                                 \
   const PgGraph& G = (A).gr[blockIdx.y];            \
   const PgLayout& p = G.p;                          \
@@ -150,7 +161,7 @@ __global__ __launch_bounds__(PG_THREADS) void k_pg_init(PgArgs A) {
 }
 
 // ---- one lane per edge.  MODE 0: residual, Jacobians, corrector and cost at x; MODE 1: the cost at the candidate
-template <int MODE>
+template <int MODE, bool SEQ>
 __global__ __launch_bounds__(PG_THREADS) void k_pg_edges(PgArgs A) {
   PG_GRAPH(A);
   if (ctl[PG_DONE] != 0.0) return;
@@ -159,6 +170,8 @@ __global__ __launch_bounds__(PG_THREADS) void k_pg_edges(PgArgs A) {
   if (t >= p.E) return;
   int a, b; bool loop;
   if (!pg_ends(p, ints, t, a, b, loop)) return;
+  const int* fl = ints + p.itotal;   // SEQ: the node flags stand behind the graph's integer block
+  if (SEQ && !pg_edge_active(fl, a, b, loop)) return;
   const double* xs = w + (MODE == 0 ? p.x : p.cand);
   double r[4], Ja[16], Jb[16];
   pg_eval(xs + 4 * a, xs + 4 * b, w + p.pr + 2 * a, w + p.meas + 4 * (size_t)t, loop ? A.opt.loop_yaw_scale : 1.0, r,
@@ -170,7 +183,11 @@ __global__ __launch_bounds__(PG_THREADS) void k_pg_edges(PgArgs A) {
   w[p.ecost + t] = 0.5 * rho0;
   const double sc = sqrt(rho1);   // the corrector with rho'' <= 0: a plain scaling
   for (int i = 0; i < 4; ++i) w[p.er + 4 * (size_t)t + i] = r[i] * sc;
-  for (int i = 0; i < 16; ++i) { w[p.eJa + 16 * (size_t)t + i] = Ja[i] * sc; w[p.eJb + 16 * (size_t)t + i] = Jb[i] * sc; }
+  const bool ca = SEQ && (fl[a] & PG_NODE_CONST), cb = SEQ && (fl[b] & PG_NODE_CONST);
+  for (int i = 0; i < 16; ++i) {
+    w[p.eJa + 16 * (size_t)t + i] = ca ? 0.0 : Ja[i] * sc;
+    w[p.eJb + 16 * (size_t)t + i] = cb ? 0.0 : Jb[i] * sc;
+  }
 }
 
 // ---- sixteen lanes per unknown node: its block column of B (unscaled, without the LM diagonal), its g and column norms, and in
@@ -220,6 +237,7 @@ __global__ __launch_bounds__(PG_THREADS) void k_pg_asm(PgArgs A) {
 // ---- one work-group (one wave) per graph: the head of the iteration (ceres' FinalizeIterationAndCheckIfMinimizerCanContinue), then
 //      the band Cholesky B = L L^T walking the chain, the 20 x 20 window of the current and the next four block columns in LDS
 constexpr int PG_WIN = 4 * (PG_BW + 1);
+template <bool SEQ>
 __global__ __launch_bounds__(64) void k_pg_factor(PgArgs A) {
   PG_GRAPH(A);
   if (ctl[PG_DONE] != 0.0) return;
@@ -228,11 +246,14 @@ __global__ __launch_bounds__(64) void k_pg_factor(PgArgs A) {
   __shared__ double red[64];
   const int l = threadIdx.x;
   const double* x = w + p.x;
+  const int* fl = ints + p.itotal;   // SEQ: the node flags stand behind the graph's integer block
+  auto is_const = [&](int k) { return SEQ && (fl[k] & PG_NODE_CONST); };   // node k
   if (ctl[PG_NEED_LIN] != 0.0) {
     if (ctl[PG_ITER] == 0.0) {
       const double cost = pg_block_sum<64>(w + p.ecost, p.E, red);
       double s = 0.0;
-      for (int i = l; i < p.m; i += 64) s += x[4 + i] * x[4 + i];
+      for (int i = l; i < p.m; i += 64)
+        if (!is_const(1 + (i >> 2))) s += x[4 + i] * x[4 + i];
       __syncthreads();
       red[l] = s;
       __syncthreads();
@@ -242,6 +263,7 @@ __global__ __launch_bounds__(64) void k_pg_factor(PgArgs A) {
     }
     double gm = 0.0;   // max |x - Plus(x, -g)|
     for (int i = l; i < p.m; i += 64) {
+      if (is_const(1 + (i >> 2))) continue;
       const double xi = x[4 + i], gi = w[p.g + i];
       const double moved = (i & 3) == 0 ? pg_norm_angle(xi - gi) : xi - gi;
       gm = fmax(gm, fabs(xi - moved));
@@ -270,6 +292,7 @@ __global__ __launch_bounds__(64) void k_pg_factor(PgArgs A) {
   // element (r, c) of block (Pb, Qb), Qb <= Pb <= Qb + 4, scaled, the LM diagonal added; 0 outside the matrix
   auto elem = [&](int Pb, int Qb, int r, int c) -> double {
     if (Pb >= nb) return 0.0;
+    if (is_const(Qb + 1) && Pb == Qb) return r == c ? 1.0 : 0.0;
     const double sr = scale[4 * Pb + r], sc = scale[4 * Qb + c];
     double v = Bu[((size_t)Qb * (PG_BW + 1) + (Pb - Qb)) * 16 + 4 * r + c] * sr * sc;
     if (Pb == Qb && r == c) v += fmin(fmax(sc * sc * cn[4 * Qb + c], A.opt.min_lm_diagonal), A.opt.max_lm_diagonal) / radius;
@@ -566,6 +589,7 @@ __global__ __launch_bounds__(PG_THREADS) void k_pg_back(PgArgs A) {
 }
 
 // ---- one work-group per graph: the candidate's cost in fixed order, the tolerance tests, rho, the radius, accept or keep x
+template <bool SEQ>
 __global__ __launch_bounds__(PG_THREADS) void k_pg_decide(PgArgs A) {
   PG_GRAPH(A);
   if (ctl[PG_DONE] != 0.0) return;
@@ -579,9 +603,12 @@ __global__ __launch_bounds__(PG_THREADS) void k_pg_decide(PgArgs A) {
     }
     return;
   }
+  const int* fl = ints + p.itotal;   // SEQ: the node flags stand behind the graph's integer block
+  auto is_const = [&](int k) { return SEQ && (fl[k] & PG_NODE_CONST); };   // node k
   double cand_cost = pg_block_sum<PG_THREADS>(w + p.ecand, p.E, red);
   double s = 0.0, bad = 0.0;
   for (int i = tid; i < p.m; i += PG_THREADS) {
+    if (is_const(1 + (i >> 2))) continue;
     const double c = w[p.cand + 4 + i], d = w[p.x + 4 + i] - c;
     s += d * d;
     if (!(fabs(c) <= DBL_MAX)) bad = 1.0;
@@ -606,7 +633,10 @@ __global__ __launch_bounds__(PG_THREADS) void k_pg_decide(PgArgs A) {
   double xn = 0.0;
   if (verdict == 3) {
     double s2 = 0.0;
-    for (int i = tid; i < p.m; i += PG_THREADS) { const double c = w[p.cand + 4 + i]; w[p.x + 4 + i] = c; s2 += c * c; }
+    for (int i = tid; i < p.m; i += PG_THREADS) {
+      if (is_const(1 + (i >> 2))) continue;
+      const double c = w[p.cand + 4 + i]; w[p.x + 4 + i] = c; s2 += c * c;
+    }
     __syncthreads();
     red[tid] = s2;
     __syncthreads();

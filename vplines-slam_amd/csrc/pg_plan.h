@@ -82,4 +82,28 @@ inline void pg_fill_ints(const PgLayout& p, const int* loop_i, const int* loop_a
   }
 }
 
+// ---- several sequences (vpl_pg_optimize_seq_batch; pose_graph.cpp:447-519).  One int per node:
+// PG_NODE_CONST0: the node is local node 0 or of sequence 0 (:473-477).  Bit j = 1..4: the sequential edge (k, k-j) is part of the
+// problem -- both ends of one sequence (:482) and not both PG_NODE_CONST0.  A loop edge is part of the problem unless both its
+// ends are PG_NODE_CONST0.  PG_NODE_CONST: the node is not an unknown -- it is PG_NODE_CONST0, or no edge of the problem touches it
+// (ceres drops an unused parameter block from the reduced program).  sequence == nullptr: every node is of sequence 1.
+constexpr int PG_NODE_CONST = 1, PG_NODE_CONST0 = 1 << 5;
+
+inline void pg_node_flags(int n, const int* sequence, int L, const int* loop_i, const int* loop_a, int* flags) {
+  auto seq = [sequence](int k) { return sequence ? sequence[k] : 1; };
+  auto const0 = [&seq](int k) { return k == 0 || seq(k) == 0; };
+  for (int k = 0; k < n; ++k) flags[k] = const0(k) ? PG_NODE_CONST0 : 0;
+  // (bit 6 marks a node some edge of the problem touches; it is cleared again below)
+  constexpr int touched = 1 << 6;
+  for (int k = 1; k < n; ++k)
+    for (int j = 1; j <= PG_BW && k - j >= 0; ++j)
+      if (seq(k) == seq(k - j) && !(const0(k) && const0(k - j))) { flags[k] |= (1 << j) | touched; flags[k - j] |= touched; }
+  for (int e = 0; e < L; ++e)
+    if (!(const0(loop_i[e]) && const0(loop_a[e]))) { flags[loop_i[e]] |= touched; flags[loop_a[e]] |= touched; }
+  for (int k = 0; k < n; ++k) {
+    if ((flags[k] & PG_NODE_CONST0) || !(flags[k] & touched)) flags[k] |= PG_NODE_CONST;
+    flags[k] &= ~touched;
+  }
+}
+
 }  // namespace vpl

@@ -4,7 +4,7 @@
 // One translation unit.  This file: context create / destroy and the setters, pre-integration and the single-factor evaluators,
 // the launch sequences, the window entry points, download and prior fetch, the debug entry points.  Included once each, like the
 // kernel headers: ba_stage.h (staging arena), ba_ctx.h (vpl_ctx), ba_upload.h (the upload), init_align_host.h, init_sfm_host.h and
-// init_relpose_host.h (vpl_init_*), loop_host.h, pg_host.h and gf_host.h (vpl_loop_*, vpl_pg_*, vpl_gf_*), sel_host.h (vpl_select_*,
+// init_relpose_host.h (vpl_init_*), loop_host.h, pg_host.h, pgs_host.h and gf_host.h (vpl_loop_*, vpl_pg_*, vpl_pgs_*, vpl_gf_*), sel_host.h (vpl_select_*,
 // vpl_sel_*), ba_session.h (vpl_odo_*).
 // There is no CPU compute path in this library: every entry point that computes launches
 // HIP kernels and reports VPL_E_NODEVICE / VPL_E_HIP when that is impossible.
@@ -44,6 +44,7 @@ using namespace vpl;
 #include "init_relpose_host.h"
 #include "loop_host.h"
 #include "pg_host.h"
+#include "pgs_host.h"
 #include "gf_host.h"
 #include "sel_host.h"
 
