@@ -9,7 +9,8 @@ the prior, the IMU factors 1..10, every point track's observation 0 against k >=
 and are promoted; everything after that (Huber scaling, J^T J, the scaling, the Cholesky solve, the dogleg step, the model
 cost change) is long double.  Columns are local coordinates: the evaluators' zero seventh pose column is dropped.
 Problem(w, opt, evaluators=vis_ref.Evaluators) takes the point, line and VP rows from vis_ref.py instead, in true long double
-(test_gpu_vis_factors.py); the IMU rows have their long-double form in imu_ref.py; the prior rows stay the oracle's.
+(test_gpu_vis_factors.py); the IMU rows have their long-double form in imu_ref.py; Problem(w, opt, prior_rows=prior_ref.prior_rows)
+takes the prior's row from prior_ref.py, in long double from dx on (test_gpu_prior_factor.py) -- the cases below keep the oracle's.
 
 Index of a window with nP points and nL triangulated lines (n = 171 + nP + 4 nL): frame f pose 15 f + 0..5, speed/bias
 15 f + 6..14, extrinsic 165..170, inverse depth of point p 171 + p, line l 171 + nP + 4 l + 0..3.
@@ -87,10 +88,11 @@ def plk_from_pose(plk, Rcw, tcw):
 
 # ---- the problem of one window -----------------------------------------------------------------------------------------
 class Problem:
-    def __init__(self, w, opt, evaluators=o):
+    def __init__(self, w, opt, evaluators=o, prior_rows=None):
         """evaluators: what has projection_factor, line_factor and vp_factor(params, observations, sqrt_info) -> r, jac for the
-        point, line and VP rows: the oracle's (float64) by default; vis_ref.Evaluators gives long-double rows"""
-        self.w, self.opt, self.ev = w, opt, evaluators
+        point, line and VP rows: the oracle's (float64) by default; vis_ref.Evaluators gives long-double rows.
+        prior_rows: (problem, x) -> the prior's entry of rows(); None: the oracle's prior_factor (float64)"""
+        self.w, self.opt, self.ev, self.prior_rows = w, opt, evaluators, prior_rows
         self.nP = len(w.point_start)
         nl_all = len(w.line_start)
         self.lines = np.nonzero(np.asarray(w.line_triangulated[:nl_all]) != 0)[0]     # solved line -> the window's line
@@ -133,7 +135,9 @@ class Problem:
         pose, sb, ex, invd, orth = x["pose"], x["sb"], x["ex"], x["invd"], x["orth"]
         out = []
         pr = w.prior
-        if pr is not None and pr.n > 0:
+        if pr is not None and pr.n > 0 and self.prior_rows is not None:
+            out.append(self.prior_rows(self, x))
+        elif pr is not None and pr.n > 0:
             params, meta = [], []
             for b in range(pr.n_blocks):
                 kind, fr = pr.block_kind[b], pr.block_frame[b]
